@@ -10,11 +10,20 @@ rounds against the K resident keyframe trees -> X, H, b, matched flags and their
 scan every step (8 distinct scans, cycled).  The library streams: the leaves of scan i+1 are fed on its copy stream
 while scan i registers, results are written by the last kernel into pinned host memory (madicp_stream_submit /
 madicp_stream_collect), so upload and read-back are INSIDE the timed region and overlap the device work.  The keyframe
-trees are resident before the timed region starts (they are the local map).  The device-resident loop of round 1
-(same pre-uploaded scan re-registered, nothing read back) is kept as the secondary key `resident_loop`.
+trees are resident before the timed region starts (they are the local map).  The timed region is exactly K steps between
+two fences, preceded by max(W, 40) untimed steps (and at least a second of them); `value` is K / its duration and
+`ms_per_step` its duration / K.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain single-GPU run does only that: set up, warm up, time the K steps, write the last step's results if --dump-outputs
+DIR is given (DIR/X.npy, H.npy, b.npy, n_matched.npy, matched.npy; the inputs are seeded, so two builds can be compared
+output for output), print the line.  --full also measures, before the headline, everything else the line can carry — the
+device-resident loop of round 1 (same pre-uploaded scan re-registered, nothing read back: `resident_loop`), the roofline of
+icp_round with its PMC sub-runs, BASELINE configs[4] (`stress_k64_b8`), `nn_descend`, the device front-end and
+Pipeline.compute end to end — and after it the spread over repeated timed regions, the single-registration latency and the
+CPU baseline; it force-rebuilds the HIP libraries first (--no-rebuild: only if a source changed).
 
 N > 1 (one rank per GPU) — `value` is BASELINE configs[3], the north-star's multi-GPU configuration:
   shard     (value) the 16 keyframe trees are dealt over the ranks (16/N per GPU, sharded.keyframe_owner); every rank holds the
@@ -26,8 +35,8 @@ N > 1 (one rank per GPU) — `value` is BASELINE configs[3], the north-star's mu
             registration is ~15 us of work per round, so this is latency-bound by the all-reduce) and `replica`
             (every rank holds the whole map and streams its own scans, no collective).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (icp_round: one Gauss-Newton round); see DESIGN.md
-section 6 for every figure in it.  `cpu_baseline` is the CPU restatement of the reference's OpenMP path (oracle/, kind
+Rank 0 prints ONE JSON line.  `roofline` (--full) is for the dominant kernel (icp_round: one Gauss-Newton round); see DESIGN.md
+section 6 for every figure in it.  `cpu_baseline` (--full) is the CPU restatement of the reference's OpenMP path (oracle/, kind
 "port") timed on this box's host cores on a bounded sample.
 """
 import argparse
@@ -72,6 +81,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 L2_PEAK_GBS = 34500.0  # aggregate L2 bandwidth, same guide
 N_DISTINCT = 8         # distinct query scans cycled through the timed region
 MIN_WARMUP = 40        # untimed steps really run before the timed region (whatever --warmup says, never fewer): "warmup_run"
+MIN_WARMUP_S = 1.0     # ... and for at least this many seconds
+DUMP_LIMIT = 64 << 20  # --dump-outputs writes at most this many bytes
 
 
 def parse():
@@ -84,11 +95,17 @@ def parse():
     ap.add_argument("--mode", choices=["auto", "shard", "replica"], default="auto",
                     help="N > 1 only; auto = shard (BASELINE configs[3]) with the replica figure as a second key")
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU time budget of the baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else the line can report (single GPU: spread over repeated "
+                         "timed regions, resident loops, roofline, BASELINE configs[4], nn_descend, front-end, Pipeline.compute, "
+                         "CPU baseline) and force-rebuild the HIP libraries first")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (single GPU)")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto", help="(--full)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU time budget of the baseline sample (--full)")
     ap.add_argument("--pmc", choices=["auto", "off"], default="auto",
-                    help="measure HBM traffic of icp_round in this run (rocprofv3 --pmc sub-runs of this script)")
-    ap.add_argument("--no-rebuild", action="store_true", help="do not force-rebuild the HIP library first")
+                    help="measure HBM traffic of icp_round in this run (rocprofv3 --pmc sub-runs of this script; --full)")
+    ap.add_argument("--no-rebuild", action="store_true", help="with --full: do not force-rebuild the HIP library first")
     ap.add_argument("--option", action="append", default=[], help="library option key=value (tuning)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--build-child", default=None, help=argparse.SUPPRESS)
@@ -143,6 +160,18 @@ def streamed_loop(ctx, capi, leaves, guesses, tids, n, results=None, stamps=None
         r = ctx.stream_collect(prev[0], leaves[prev[1]].shape[0])
         if results is not None:
             results.append((prev[1], r))
+
+
+def dump_outputs(d, r):
+    """--dump-outputs: what the caller of the timed path (madicp_stream_collect) received for the last timed step — pose X
+    (12 = R row-major + t), H (6x6), b (6), the count of matched leaves and the per-leaf matched flags — as float64 / float32
+    .npy files.  The node-visit count it also returns is a work statistic, not a result, and is left out."""
+    arrays = {"X": np.asarray(r["X"], np.float64), "H": np.asarray(r["H"], np.float64), "b": np.asarray(r["b"], np.float64),
+              "n_matched": np.array([r["n_matched"]], np.float64), "matched": np.asarray(r["matched"], np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -395,6 +424,10 @@ def main():
             print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; launch with torch.distributed.run",
                   file=sys.stderr)
         sys.exit(2)
+    if args.dump_outputs and (world > 1 or os.environ.get("MADICP_BENCH_FORCE_MULTI") == "1"):
+        if rank == 0:
+            print("bench.py: --dump-outputs is implemented for the single-GPU run", file=sys.stderr)
+        sys.exit(2)
 
     import torch
     import torch.distributed as dist
@@ -424,12 +457,14 @@ def main():
 
     from mad_icp_amd import _build, capi, synth
 
-    # the libraries this run measures are built from the sources in this tree, in this run
+    # the libraries this run measures are built from the sources in this tree: rebuilt if a source changed since they were
+    # built (content hash), and with --full rebuilt in this run whatever the hash says
+    force = args.full and not args.no_rebuild
     if rank == 0:
-        _build.build_hip(force=not args.no_rebuild)
+        _build.build_hip(force=force)
         _build.build_host()
-        if world == 1:  # (the measurement build of the same sources: the roofline's launch times and the counter sub-runs)
-            _build.build_measure(force=not args.no_rebuild)
+        if world == 1 and args.full:  # (the measurement build of the same sources: the roofline's launch times and the counter sub-runs)
+            _build.build_measure(force=force)
     if world > 1:
         dist.barrier()
 
@@ -471,7 +506,7 @@ def main():
         out = multi_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, fence, max_over_ranks, dist, torch, rank, world,
                         small, backend)
     if rank == 0:
-        out["built_in_this_run"] = {"forced_rebuild": not args.no_rebuild, "hip_source_sha256": _build.hip_source_hash()}
+        out["built_in_this_run"] = {"forced_rebuild": force, "hip_source_sha256": _build.hip_source_hash()}
         print(json.dumps(out), flush=True)
     if world > 1 or force_multi:
         dist.barrier()
@@ -702,18 +737,11 @@ def set_counter_roofline(roofline, traffic, detail, l2, avg_us, hbm_copy):
 
 
 # ---------------------------------------------------------------------------------------------------------
-def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, t_build):
+def secondary_figures(args, ctx, capi, synth, pb, leaves, Ls, guesses, kf_trees, tids, n_nodes, fence, t_build):
+    """Everything the single-GPU line reports beside its headline (--full): the resident loops, the roofline of icp_round
+    (measurement build, PMC sub-runs), BASELINE configs[4], nn_descend, the device front-end and Pipeline.compute end to end."""
     K = args.keyframes
     B = max(1, args.scans)
-    kf_trees = []
-    tids, n_nodes = [], 0
-    for k in range(K):
-        T = pb["keyframe_poses"][k]
-        ht = capi.HostTree(pb["keyframe_scans"][k], B_MAX, B_MIN, 3)
-        ht.transform(T[:3, :3], T[:3, 3])
-        kf_trees.append(ht)
-        tids.append(ctx.upload(ht))
-        n_nodes += ht.num_nodes
 
     # ---- secondary: device-resident loops (round 1's definition), 1 and 8 scans in flight -------------------
     mids = [ctx.moving_upload(lm) for lm in leaves]
@@ -982,12 +1010,39 @@ def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, 
     except Exception as e:  # noqa: BLE001
         pipe = {"error": str(e)[:200]}
 
-    # ---- the headline: streamed registrations, a different scan every step (measured after the secondary figures:
-    # the W warm-up steps below are then the only thing between a busy device and the timed region) --------------
+    return {"resident_loop": {"registrations_per_s": round(resident1, 1), "scans8_in_flight_registrations_per_s": round(resident8, 1),
+                              "batch_registrations_per_s": None if batch_value is None else round(batch_value, 1),
+                              "note": "round-1 definition: same pre-uploaded scans re-registered, nothing read back"},
+            "stress_k64_b8": stress,
+            "front_end": front,
+            "pipeline_end_to_end": pipe,
+            "nn_descend": nn,
+            "roofline": roofline}
+
+
+# ---------------------------------------------------------------------------------------------------------
+def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, t_build):
+    K = args.keyframes
+    kf_trees = []
+    tids, n_nodes = [], 0
+    for k in range(K):
+        T = pb["keyframe_poses"][k]
+        ht = capi.HostTree(pb["keyframe_scans"][k], B_MAX, B_MIN, 3)
+        ht.transform(T[:3, :3], T[:3, 3])
+        kf_trees.append(ht)
+        tids.append(ctx.upload(ht))
+        n_nodes += ht.num_nodes
+
+    # ---- everything else the line reports (--full only): measured BEFORE the headline, so that the warm-up below is the only
+    # thing between a busy device and the timed region
+    extra = secondary_figures(args, ctx, capi, synth, pb, leaves, Ls, guesses, kf_trees, tids, n_nodes, fence, t_build) if args.full else {}
+
+    # ---- the headline: streamed registrations, a different scan every step --------------------------------------------------
     # (at least 40 untimed steps — 9 ms — whatever W says: every stream slot's graph, the kernel-by-kernel route a busy stream
     # takes, the pinned staging of all four slots have then been used, and the device clocks are where a long run keeps them:
     # the driver's --steps 20 --warmup 5 then reports 4 420 against 4 540 for 400 steps — what is left is the one registration
     # of pipeline drain in twenty — instead of 4 150)
+    # (and at least MIN_WARMUP_S of them: without --full nothing has kept the device busy before the warm-up)
     # the host is only one submission ahead of the device here, so a generational garbage collection over the
     # interpreter's (torch-sized) heap would stall the device for tens of milliseconds: keep it out of the timed region,
     # like timeit does — and collect BEFORE the warm-up, so that nothing but the fence separates the warm-up's last
@@ -995,7 +1050,12 @@ def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, 
     # 20-step run)
     gc.collect()
     gc.disable()
-    streamed_loop(ctx, capi, leaves, guesses, tids, max(args.warmup, MIN_WARMUP))
+    warmup_run = max(args.warmup, MIN_WARMUP)
+    t_warm = time.perf_counter()
+    streamed_loop(ctx, capi, leaves, guesses, tids, warmup_run)
+    while time.perf_counter() - t_warm < MIN_WARMUP_S:
+        streamed_loop(ctx, capi, leaves, guesses, tids, MIN_WARMUP)
+        warmup_run += MIN_WARMUP
     fence()
     results = []
     stamps = [] if os.environ.get("MADICP_BENCH_DEBUG") else None
@@ -1007,35 +1067,38 @@ def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, 
         fence()
         return time.perf_counter() - t0
 
-    # The timed region — exactly K steps between two fences — is repeated, back to back, and the line carries the spread:
-    # `value` / `ms_per_step` are the MEDIAN repetition, p10 / p90 beside it.  (One repetition of the driver's K = 20 is 4.5 ms:
-    # a single sample of that says little; rounds 4-5 reported 4 492 .. 4 547 from it against 4 665 .. 4 684 from 400 steps.)
-    reps = 5 if args.steps >= 400 else int(min(25, max(5, 2000 // max(1, args.steps))))
-    laps = []
-    for r_ in range(reps):
-        laps.append(timed(args.steps, results if r_ == 0 else None, stamps if r_ == 0 else None))
-    rates = np.array([args.steps / t for t in laps])
-    elapsed = float(np.median(laps))
+    # The timed region: exactly --steps steps between two fences.  `value` / `ms_per_step` are this one repetition.
+    elapsed = timed(args.steps, results, stamps)
     value = args.steps / elapsed
-    spread = {"repetitions": reps, "steps_each": args.steps, "median": round(float(np.median(rates)), 1),
-              "p10": round(float(np.percentile(rates, 10)), 1), "p90": round(float(np.percentile(rates, 90)), 1),
-              "min": round(float(rates.min()), 1), "max": round(float(rates.max()), 1),
-              "note": "registrations/s of each repetition of the timed region (exactly --steps steps between two fences, "
-                      "repeated back to back); `value` is the median repetition"}
-    # ... and the long-run interval beside it, so that a short run can be read against it
-    if args.steps != 400:
-        long_rates = np.array([400 / timed(400) for _ in range(5)])
-        spread["steps400"] = {"repetitions": 5, "median": round(float(np.median(long_rates)), 1),
-                              "p10": round(float(np.percentile(long_rates, 10)), 1), "p90": round(float(np.percentile(long_rates, 90)), 1)}
-        lo, hi = float(long_rates.min()), float(long_rates.max())
-        spread["stability"] = ("this run's %d-step median %.0f is %s the 400-step interval [%.0f, %.0f] measured in the same process "
-                               "(a short run ends with one registration of pipeline drain in %d)" % (
-                                   args.steps, value, "INSIDE" if lo <= value <= hi else ("%.1f %% below" % (100 * (lo - value) / lo) if value < lo
-                                                                                          else "%.1f %% above" % (100 * (value - hi) / hi)),
-                                   lo, hi, args.steps))
-    else:
-        spread["stability"] = "400-step repetitions: p10 .. p90 = %.0f .. %.0f (%.1f %% of the median)" % (
-            spread["p10"], spread["p90"], 100 * (spread["p90"] - spread["p10"]) / spread["median"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, results[-1][1])
+    spread = None
+    if args.full:
+        # --full repeats the timed region back to back and the line carries the spread.  (One repetition of the driver's
+        # K = 20 is 4.5 ms: a single sample of that says little; rounds 4-5 reported 4 492 .. 4 547 from it against 4 665 .. 4 684
+        # from 400 steps.)
+        reps = 5 if args.steps >= 400 else int(min(25, max(5, 2000 // max(1, args.steps))))
+        laps = [elapsed] + [timed(args.steps) for _ in range(reps - 1)]
+        rates = np.array([args.steps / t for t in laps])
+        spread = {"repetitions": reps, "steps_each": args.steps, "median": round(float(np.median(rates)), 1),
+                  "p10": round(float(np.percentile(rates, 10)), 1), "p90": round(float(np.percentile(rates, 90)), 1),
+                  "min": round(float(rates.min()), 1), "max": round(float(rates.max()), 1),
+                  "note": "registrations/s of each repetition of the timed region (exactly --steps steps between two fences, "
+                          "repeated back to back); `value` is the first repetition"}
+        # ... and the long-run interval beside it, so that a short run can be read against it
+        if args.steps != 400:
+            long_rates = np.array([400 / timed(400) for _ in range(5)])
+            spread["steps400"] = {"repetitions": 5, "median": round(float(np.median(long_rates)), 1),
+                                  "p10": round(float(np.percentile(long_rates, 10)), 1), "p90": round(float(np.percentile(long_rates, 90)), 1)}
+            lo, hi = float(long_rates.min()), float(long_rates.max())
+            spread["stability"] = ("this run's %d-step figure %.0f is %s the 400-step interval [%.0f, %.0f] measured in the same process "
+                                   "(a short run ends with one registration of pipeline drain in %d)" % (
+                                       args.steps, value, "INSIDE" if lo <= value <= hi else ("%.1f %% below" % (100 * (lo - value) / lo) if value < lo
+                                                                                              else "%.1f %% above" % (100 * (value - hi) / hi)),
+                                       lo, hi, args.steps))
+        else:
+            spread["stability"] = "400-step repetitions: p10 .. p90 = %.0f .. %.0f (%.1f %% of the median)" % (
+                spread["p10"], spread["p90"], 100 * (spread["p90"] - spread["p10"]) / spread["median"])
     gc.enable()
     if stamps:
         d = np.diff(np.array(stamps)) * 1e6
@@ -1045,6 +1108,24 @@ def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, 
     # what was timed is a real registration: every collected result sits at its scan's ground-truth pose
     terr = max(pose_error(pb["query_gt"][q], r["T"]) for q, r in results)
     matched = [int(r["n_matched"]) for _, r in results[:N_DISTINCT]]
+
+    out = base_line(args, 1, value, elapsed,
+                    "BASELINE configs[2]: %d-pt KITTI-shaped synthetic scans vs %d keyframe MAD-trees, %d GN rounds, b_max=0.2 "
+                    "b_min=0.1 rho_ker=0.1 b_ratio=0.02; a step = new scan's leaves in (host) -> registration -> X,H,b,flags out "
+                    "(host), %d distinct scans cycled, upload/read-back streamed inside the timed region"
+                    % (len(pb["query_scans"][0]), K, N_ITERS, N_DISTINCT),
+                    {"keyframes": K, "scans_in_flight": 1, "moving_leaves": Ls, "map_nodes_this_rank": n_nodes,
+                     "parallelism": "single GPU"}, warmup_run=warmup_run)
+    out.update({
+        "nn_mqueries_per_s": round(value * float(np.mean(Ls)) * K * N_ITERS / 1e6, 1),
+        "nn_mqueries_note": "(leaf, tree, round) pairs resolved per second = value x L x K x 15; pairs whose descent is "
+                            "provably unchanged are resolved without a walk — nodes really walked are in roofline (--full)",
+        "max_translation_error_m": round(terr, 5),
+        "matched_leaves_first_scans": matched,
+        "host_tree_build_ms_per_scan": round(t_build * 1e3, 2),
+    })
+    if not args.full:
+        return out
 
     # PCIe-inclusive SINGLE registration with nothing overlapped (submit, then collect at once): the latency a caller
     # sees for one scan — reported, never `value`
@@ -1060,30 +1141,15 @@ def single_gpu(args, ctx, capi, synth, pb, leaves, Ls, guesses, q_trees, fence, 
     if args.cpu_baseline == "auto":
         cpu = cpu_baseline(pb, K, args.cpu_seconds)
 
-    out = base_line(args, 1, value, elapsed,
-                    "BASELINE configs[2]: %d-pt KITTI-shaped synthetic scans vs %d keyframe MAD-trees, %d GN rounds, b_max=0.2 "
-                    "b_min=0.1 rho_ker=0.1 b_ratio=0.02; a step = new scan's leaves in (host) -> registration -> X,H,b,flags out "
-                    "(host), %d distinct scans cycled, upload/read-back streamed inside the timed region"
-                    % (len(pb["query_scans"][0]), K, N_ITERS, N_DISTINCT),
-                    {"keyframes": K, "scans_in_flight": 1, "moving_leaves": Ls, "map_nodes_this_rank": n_nodes,
-                     "parallelism": "single GPU"}, warmup_run=max(args.warmup, MIN_WARMUP))
     out.update({
-        "nn_mqueries_per_s": round(value * float(np.mean(Ls)) * K * N_ITERS / 1e6, 1),
-        "nn_mqueries_note": "(leaf, tree, round) pairs resolved per second = value x L x K x 15; pairs whose descent is "
-                            "provably unchanged are resolved without a walk — nodes really walked are in roofline",
-        "max_translation_error_m": round(terr, 5),
-        "matched_leaves_first_scans": matched,
         "spread": spread,
-        "resident_loop": {"registrations_per_s": round(resident1, 1), "scans8_in_flight_registrations_per_s": round(resident8, 1),
-                          "batch_registrations_per_s": None if batch_value is None else round(batch_value, 1),
-                          "note": "round-1 definition: same pre-uploaded scans re-registered, nothing read back"},
+        "resident_loop": extra["resident_loop"],
         "single_registration_latency_ms": round(lat_ms, 3),
-        "host_tree_build_ms_per_scan": round(t_build * 1e3, 2),
-        "stress_k64_b8": stress,
-        "front_end": front,
-        "pipeline_end_to_end": pipe,
-        "nn_descend": nn,
-        "roofline": roofline,
+        "stress_k64_b8": extra["stress_k64_b8"],
+        "front_end": extra["front_end"],
+        "pipeline_end_to_end": extra["pipeline_end_to_end"],
+        "nn_descend": extra["nn_descend"],
+        "roofline": extra["roofline"],
         "cpu_baseline": cpu,
     })
     return out

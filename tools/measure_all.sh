@@ -7,10 +7,10 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 (python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|rror" | tail -5) > $OUT/tests.log 2>&1
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench.err
-python bench.py --scans 8 --cpu-baseline off > $OUT/bench_n1_scans8.json 2>> $OUT/bench.err
-python bench.py --keyframes 64 --scans 8 --steps 30 --warmup 5 --cpu-baseline off > $OUT/bench_n1_k64_scans8.json 2>> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o t -- python bench.py --steps 30 --warmup 5 --cpu-baseline off > $OUT/bench_prof.json 2> $OUT/prof.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench.err
+python bench.py --full --scans 8 --cpu-baseline off > $OUT/bench_n1_scans8.json 2>> $OUT/bench.err
+python bench.py --full --keyframes 64 --scans 8 --steps 30 --warmup 5 --cpu-baseline off > $OUT/bench_n1_k64_scans8.json 2>> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o t -- python bench.py --full --steps 30 --warmup 5 --cpu-baseline off > $OUT/bench_prof.json 2> $OUT/prof.err
 python tools/trace_split.py $OUT/prof/t_kernel_trace.csv 35 > $OUT/kernel_trace_summary.md
 tools/pmc.sh $OUT/pmc > $OUT/pmc.log 2>&1
 python tools/stamps.py 16 > $OUT/stamps.md 2>&1

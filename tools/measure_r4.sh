@@ -22,8 +22,8 @@ if has big; then
   timeout 600 python tools/big_probe.py > $OUT/big_probe.log 2>&1; tail -12 $OUT/big_probe.log
 fi
 if has bench; then
-  timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench.err
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-rebuild > $OUT/bench_steps20.json 2>> $OUT/bench.err
+  timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-rebuild > $OUT/bench_steps20.json 2>> $OUT/bench.err
   python tools/show_bench.py $OUT/bench_n1.json
 fi
 if has trace; then

@@ -25,7 +25,7 @@ if has k64; then
   python tools/k64_trace.py $(find $OUT/k64trace -name "t_kernel_trace.csv" | head -1) > $OUT/k64_round_trace.md; rm -rf $OUT/k64trace; cat $OUT/k64_round_trace.md
 fi
 if has bench; then
-  timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench.err; python tools/show_bench.py $OUT/bench_n1.json | head -40
+  timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench.err; python tools/show_bench.py $OUT/bench_n1.json | head -40
 fi
 if has pmc; then
   timeout 600 tools/k64_pmc.sh $OUT/k64_pmc > $OUT/k64_pmc.log 2>&1; cp $OUT/k64_pmc/summary.md $OUT/k64_pmc_summary.md 2>/dev/null; rm -rf $OUT/k64_pmc; grep -A 24 "icp_round" $OUT/k64_pmc_summary.md | head -30

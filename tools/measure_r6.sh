@@ -45,8 +45,8 @@ if has final; then
   F='^\[mad_icp_amd build\]\|^madicp: MADICP_CU_MASK\|RCCL version\|HIP version\|ROCm version\|Hostname\|Librccl\|amdgpu.ids\|socket.cpp\|\[Gloo\]\|Loading frame\|Time for'
   timeout 1800 python -m pytest tests -m gpu -q -s 2>&1 | grep -v "$F" > $OUT/pytest_gpu_full.log; grep -E "passed|failed" $OUT/pytest_gpu_full.log | tail -2
   grep -E "^\[(configs3|lost peer|deskew = true|default Pipeline|pipeline,)|python launcher|bin_runner|passed|failed" $OUT/pytest_gpu_full.log > $OUT/pytest_gpu_summary.log
-  timeout 900 python bench.py > $OUT/bench_n1.json 2> $OUT/bench.err; python tools/show_bench.py $OUT/bench_n1.json | head -3
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-rebuild > $OUT/bench_steps20.json 2>> $OUT/bench.err
+  timeout 900 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench.err; python tools/show_bench.py $OUT/bench_n1.json | head -3
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-rebuild > $OUT/bench_steps20.json 2>> $OUT/bench.err
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python tools/round_trace.py run 200 > /dev/null 2> $OUT/trace.err
   python tools/round_trace.py split $(find $OUT/trace -name "t_kernel_trace.csv" | head -1) > $OUT/round_trace.md
   cp $(find $OUT/trace -name "t_kernel_stats.csv" | head -1) $OUT/round_trace_kernel_stats.csv; rm -rf $OUT/trace; head -12 $OUT/round_trace.md

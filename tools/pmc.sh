@@ -5,7 +5,7 @@ set -u
 OUT=$1; shift
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps 6 --warmup 2 --cpu-baseline off $*"
+ARGS="--full --steps 6 --warmup 2 --cpu-baseline off $*"
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM" \
