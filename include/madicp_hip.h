@@ -273,7 +273,14 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
  * for the nodes of at most 32 points its summation order: same topology and leaf representatives as the host builder on
  * every scan tried, centroids and covariances of small nodes bit for bit.  Not the same bits everywhere: larger nodes add in
  * a parallel shape and the eigen-solver's trigonometry comes from the device library (mad_icp_amd/csrc/hip/tree_build.hip.h);
- * bit-reproducible run to run.  The cloud is left untouched.  Synchronises the copy stream once (the leaf count sizes the tree). */
+ * bit-reproducible run to run.  The cloud is left untouched.  Synchronises the copy stream once (the leaf count sizes the tree).
+ * The contract (tests/test_gpu_default_path_parity.py): the kernels' decisions are bit-exact on any
+ * tree; host-built trees are the reference's; against device-built trees N of D decisions per registration differ from the
+ * reference's, all at nodes within S of their split plane — measured N = 0 of D = 324 832 decisions (16 keyframes) and 0 of
+ * 1 516 352 (64 keyframes) at four poses each, so S has no value: no pair of those problems passes within 1e-7 m of a plane
+ * and the device-built planes lie within ~1e-12 m of the reference's.  Every internal node is held to its members'
+ * centroid within the float64 summation bound and to their principal axis with at most 4 x the reference's own residual
+ * (measured 2.34 x); nodes of at most 32 points have the reference's centroid bit for bit. */
 int madicp_tree_build(madicp_ctx* ctx, int cloud_id, double b_max, double b_min, int* out_tree_id, int32_t* out_n_leaves);
 /* The same construction as a look-ahead, for a caller that has the NEXT scan in hand while the current one registers
  * (what Pipeline::prefetch does with the device front-end on).  _begin copies the (n,3) float64 scan to the device and

@@ -52,6 +52,10 @@ int madicp_debug_gather16(madicp_ctx* ctx, int64_t region_bytes, int64_t n_gathe
  * MADtree::build (mad_tree.cpp:95-97 with utils.h:37-52; the reference additionally overwrites a leaf's first member with
  * the leaf's representative, mad_tree.cpp:76-84).  Valid until the next build, ingest or deskew on the context. */
 int madicp_debug_tree_build_points(madicp_ctx* ctx, double* out_xyz, int64_t n);
+/* diagnostics (tests): the rho the screening test of a resident tree runs with (it must be >= |m - o|_1 for every internal
+ * node m of the tree, o = the root's centroid: sqrt(3) x the largest |m - o|_2, rounded up) — host-validated, device-built
+ * or transformed, the kernels read this one number. */
+int madicp_debug_tree_rho(madicp_ctx* ctx, int tree_id, double* out_rho);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,8 @@ def hip_lib():
             L.madicp_icp_time_registration.argtypes = [C.c_void_p, C.c_int, _ip, _ip, C.c_int, _dp, C.POINTER(IcpParams), C.c_int,
                                                        C.c_int, _dp, _dp, _u64p, _u64p]
             L.madicp_debug_tree_build_points.argtypes = [C.c_void_p, _dp, C.c_int64]
+        if hasattr(L, "madicp_debug_tree_rho"):
+            L.madicp_debug_tree_rho.argtypes = [C.c_void_p, C.c_int, _dp]
         if hasattr(L, "madicp_debug_gather16"):  # (absent from an older build loaded through MADICP_HIP_LIB for an A/B)
             L.madicp_debug_gather16.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int, _dp]
         L.madicp_icp_linearize.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, _dp, C.POINTER(IcpParams), _dp, _dp,
@@ -460,6 +462,12 @@ class Context:
         out = np.empty((int(n), 3))
         _check(_aid("madicp_debug_tree_build_points")(self._h, out.ctypes.data_as(_dp), int(n)))
         return out
+
+    def tree_rho(self, tid):
+        """the rho the screening test of this tree runs with (diagnostics: the measurement build only)"""
+        rho = C.c_double(0.0)
+        _check(_aid("madicp_debug_tree_rho")(self._h, int(tid), C.byref(rho)))
+        return rho.value
 
     # ---- moving ----
     def moving_upload(self, leaf_means):

@@ -1035,6 +1035,16 @@ int madicp_debug_tree_build_points(madicp_ctx* ctx, double* out_xyz, int64_t n) 
     return fail(MADICP_ERR_DEVICE, std::string("tree build points: ") + hipGetErrorString(e != hipSuccess ? e : e2));
   return MADICP_OK;
 }
+
+// Diagnostics (tests): the rho a tree's screening test runs with (TreeDesc::rho, kernels.hip.h: it has to bound |m - o|_1 of
+// every internal node, whoever made it — validate_nodes on the host, the builder's atomicMax, a chain of transforms).
+int madicp_debug_tree_rho(madicp_ctx* ctx, int tree_id, double* out_rho) {
+  if (!ctx || !out_rho) return fail(MADICP_ERR_INVALID, "null argument");
+  auto it = ctx->trees.find(tree_id);
+  if (it == ctx->trees.end()) return fail(MADICP_ERR_INVALID, "unknown tree id");
+  *out_rho = it->second.desc.rho;
+  return MADICP_OK;
+}
 #endif  // MADICP_MEASURE
 
 // per-level node counts of the last build on this context (diagnostics for tests / tools): out[0] = levels reached,

@@ -23,6 +23,11 @@ What "parity" means here, stated per piece:
                     leaf ordinals in getLeafs() order, a leaf mean queried against its own tree returns itself at
                     distance exactly 0 (the reference's nn_search.py property), bit-reproducible run to run, and the
                     device-made LDS-top layout equals the host-made one (identical registration results either way).
+                    HOW FAR those last bits may go, and what they do to correspondences, is held elsewhere:
+                    tests/test_gpu_default_path_parity.py audits every internal node of a device-built tree against its
+                    members' centroid and principal axis in extended precision (what bounds the internal nodes this file
+                    only counts as "bitwise equal on >= 0.6"), holds the kernels on device-built trees to a plain
+                    reference of the descent exactly, and counts the decisions that differ from the oracle's.
 """
 import numpy as np
 import pytest
