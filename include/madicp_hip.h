@@ -330,7 +330,8 @@ int madicp_p2p_detach(madicp_ctx* ctx);
  * torch.distributed broadcast).  After this call every registration on the context all-reduces
  * [H(21) b(6) n] over the communicator after each round and ORs the matched flags after the last.  With a
  * communicator a registration may be given K = 0 trees (a rank that owns no keyframe still joins every collective,
- * contributing zeros). */
+ * contributing zeros).  get_option "comm_ranks" (read-only) says how many ranks the installed communicator — this one or
+ * madicp_comm_init_host's — has, 0 without one; "comm_rank" this context's rank in it, -1 without one. */
 int madicp_comm_unique_id(uint8_t out_id[128]);
 int madicp_comm_init(madicp_ctx* ctx, const uint8_t unique_id[128], int n_ranks, int rank);
 int madicp_comm_destroy(madicp_ctx* ctx);

@@ -62,6 +62,31 @@ int64_t madicp_host_debug_tree_points(double* points, int64_t n, double b_max, d
 int madicp_host_debug_deskew(double* points, int64_t n, const double T_prev[12], const double T_now[12], double sensor_hz, int route,
                              double* out_velocity6);
 
+/* ---- the keyframe map sharded over the ranks of a node (Pipeline::setShard, csrc/host/pipeline.h) ---- */
+/* The rank that owns the keyframe of ORDINAL k — promotion order: the first scan is 0, every promotion adds 1; not the frame
+ * id, which has gaps — among `world` ranks: rows of `world`, alternate rows reversed (csrc/common/keyframe_owner.h; the same
+ * function as mad_icp_amd.sharded.keyframe_owner).  -1 on bad arguments (k < 0, world < 1). */
+int madicp_host_keyframe_owner(int64_t k, int world);
+/* The process-wide device context every host class (MADtree, MADicp, Pipeline) works on, created on first use; NULL when no
+ * device is usable (madicp_last_error()).  Owned by the library: never pass it to madicp_ctx_destroy.  What a caller installs
+ * the communicator of a sharded Pipeline in — madicp_comm_init / madicp_comm_init_host, madicp_p2p_export / _attach, option
+ * "shard_p2p" — before Pipeline::setShard and the first compute().  Calls on it from other threads than the Pipeline's must
+ * not overlap a compute() (the C ABI is not re-entrant). */
+madicp_ctx* madicp_host_device_ctx(void);
+
+/* Test hooks: the window bookkeeping of a (sharded) Pipeline on its own, no device involved (csrc/host/keyframe_ledger.h —
+ * the class Pipeline pushes and evicts its keyframes by).  _create: NULL unless 0 <= rank < world and num_keyframes >= 1.
+ * _promote: one keyframe promotion; *out_ordinal its ordinal, *out_evicted the ordinal the overflowing window dropped or -1;
+ * returns 1 when this rank owns the promoted keyframe, 0 when not, -1 on a null ledger.  _window: the ordinals in the window,
+ * oldest first, and whether this rank holds each one's tree (up to `capacity` entries written; returns the window's size).
+ * _num_local: how many of them this rank holds. */
+typedef struct madicp_host_ledger madicp_host_ledger;
+madicp_host_ledger* madicp_host_debug_ledger_create(int rank, int world, int num_keyframes);
+void madicp_host_debug_ledger_free(madicp_host_ledger* l);
+int madicp_host_debug_ledger_promote(madicp_host_ledger* l, int64_t* out_ordinal, int64_t* out_evicted);
+int64_t madicp_host_debug_ledger_window(const madicp_host_ledger* l, int64_t* out_ordinals, uint8_t* out_local, int64_t capacity);
+int64_t madicp_host_debug_ledger_num_local(const madicp_host_ledger* l);
+
 #ifdef __cplusplus
 }
 #endif

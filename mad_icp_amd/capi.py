@@ -187,6 +187,17 @@ def host_lib():
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
         L.madicp_host_debug_partition.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_int]
+        L.madicp_host_keyframe_owner.argtypes = [C.c_int64, C.c_int]
+        L.madicp_host_device_ctx.restype = C.c_void_p
+        L.madicp_host_device_ctx.argtypes = []
+        L.madicp_host_debug_ledger_create.restype = C.c_void_p
+        L.madicp_host_debug_ledger_create.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.madicp_host_debug_ledger_free.argtypes = [C.c_void_p]
+        L.madicp_host_debug_ledger_promote.argtypes = [C.c_void_p, _i64p, _i64p]
+        L.madicp_host_debug_ledger_window.restype = C.c_int64
+        L.madicp_host_debug_ledger_window.argtypes = [C.c_void_p, _i64p, _u8p, C.c_int64]
+        L.madicp_host_debug_ledger_num_local.restype = C.c_int64
+        L.madicp_host_debug_ledger_num_local.argtypes = [C.c_void_p]
         _host = L
     return _host
 
@@ -295,6 +306,47 @@ def host_tree_points(points, b_max, b_min, max_parallel_level=0):
     return pts, int(nl)
 
 
+def host_keyframe_owner(k, world):
+    """madicp_host_keyframe_owner: the C++ restatement of sharded.keyframe_owner (-1 on bad arguments)."""
+    return int(host_lib().madicp_host_keyframe_owner(int(k), int(world)))
+
+
+class KeyframeLedger:
+    """The window bookkeeping of a (sharded) Pipeline on its own (csrc/host/keyframe_ledger.h), through the host library's test
+    hooks: no device involved."""
+
+    def __init__(self, rank, world, num_keyframes):
+        self._h = host_lib().madicp_host_debug_ledger_create(int(rank), int(world), int(num_keyframes))
+        if not self._h:
+            raise ValueError("need 0 <= rank < world and num_keyframes >= 1")
+        self.num_keyframes = int(num_keyframes)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            host_lib().madicp_host_debug_ledger_free(self._h)
+            self._h = None
+
+    def promote(self):
+        """One promotion: (ordinal, this rank owns it, evicted ordinal or None)."""
+        o, e = C.c_int64(-1), C.c_int64(-1)
+        rc = host_lib().madicp_host_debug_ledger_promote(self._h, C.byref(o), C.byref(e))
+        if rc < 0:
+            raise MadIcpError("madicp_host_debug_ledger_promote: bad arguments")
+        return o.value, bool(rc), (e.value if e.value >= 0 else None)
+
+    def window(self):
+        """(ordinals in the window, oldest first; whether this rank holds each one's tree)."""
+        cap = self.num_keyframes + 1
+        o, l = np.empty(cap, np.int64), np.empty(cap, np.uint8)
+        n = host_lib().madicp_host_debug_ledger_window(self._h, o.ctypes.data_as(_i64p), l.ctypes.data_as(_u8p), cap)
+        if n < 0 or n > cap:
+            raise MadIcpError("madicp_host_debug_ledger_window: %d entries" % n)
+        return o[:n].copy(), l[:n].astype(bool)
+
+    def num_local(self):
+        return int(host_lib().madicp_host_debug_ledger_num_local(self._h))
+
+
 def host_deskew(points, T_prev, T_now, sensor_hz, route=0):
     """Pipeline::deskew on the host (csrc/host/deskew.h).  Returns (cloud in azimuth order, naive velocity (6,), used_parallel_order)."""
     pts = np.ascontiguousarray(points, dtype=np.float64).copy()
@@ -316,9 +368,24 @@ class Context:
         self._h = h
         self.device = device
 
+    @classmethod
+    def borrowed(cls):
+        """The process-wide context the host classes (pymadtree, pymadicp, pypeline.Pipeline) work on —
+        madicp_host_device_ctx(), created on first use — wrapped without owning it: close() and __del__ let go of the handle
+        and never destroy it.  What sharded.shard_pipeline installs a Pipeline's communicator in."""
+        h = host_lib().madicp_host_device_ctx()
+        if not h:
+            raise MadIcpError("madicp_host_device_ctx: " + hip_lib().madicp_last_error().decode())
+        self = cls.__new__(cls)
+        self._h = C.c_void_p(h)
+        self._borrowed = True
+        self.device = int(os.environ.get("MAD_ICP_DEVICE", "0"))
+        return self
+
     def close(self):
         if getattr(self, "_h", None):
-            hip_lib().madicp_ctx_destroy(self._h)
+            if not getattr(self, "_borrowed", False):
+                hip_lib().madicp_ctx_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1435,6 +1435,8 @@ int madicp_ctx_get_option(madicp_ctx* ctx, const char* key, int64_t* out_value) 
   else if (k == "p2p_fine_grained") v = (ctx->p2p_box && ctx->p2p_fine) ? 1 : 0;  // (read-only: what madicp_p2p_export obtained)
   else if (k == "nn_lds_top") v = ctx->nn_lds_top;
   else if (k == "queries_per_lane") v = ctx->qpt_override;
+  else if (k == "comm_ranks") v = ctx->sharded() ? ctx->n_ranks : 0;  // (read-only: ranks of the installed communicator, 0: none)
+  else if (k == "comm_rank") v = ctx->sharded() ? ctx->rank : -1;     // (read-only: this context's rank in it, -1: none)
   else return fail(MADICP_ERR_INVALID, "unknown option: " + k);
   *out_value = v;
   return MADICP_OK;

@@ -2,6 +2,9 @@
 #include <cstring>
 #include <vector>
 
+#include "../common/keyframe_owner.h"
+#include "device.h"
+#include "keyframe_ledger.h"
 #include "linalg.h"
 #include "madicp_host.h"
 #include "task_pool.h"
@@ -10,6 +13,9 @@
 
 struct madicp_host_tree {
   madicp_host::LinearTree tree;
+};
+struct madicp_host_ledger {
+  madicp_host::KeyframeLedger ledger;
 };
 
 extern "C" {
@@ -85,5 +91,44 @@ int madicp_host_debug_deskew(double* points, int64_t n, const double T_prev[12],
   if (n) std::memcpy(points, static_cast<const void*>(cloud.data()), sizeof(double) * 3 * static_cast<size_t>(n));
   return fast;
 }
+
+int madicp_host_keyframe_owner(int64_t k, int world) { return madicp::keyframe_owner(k, world); }
+
+madicp_ctx* madicp_host_device_ctx(void) {
+  try {
+    return madicp_host::Device::ctx();
+  } catch (...) {  // (no usable device: madicp_last_error() of libmadicp_hip.so says why)
+    return nullptr;
+  }
+}
+
+// KeyframeLedger on its own (csrc/host/keyframe_ledger.h): the window bookkeeping of a sharded Pipeline, no device involved
+madicp_host_ledger* madicp_host_debug_ledger_create(int rank, int world, int num_keyframes) {
+  if (world < 1 || rank < 0 || rank >= world || num_keyframes < 1) return nullptr;
+  madicp_host_ledger* l = new madicp_host_ledger;
+  l->ledger.configure(rank, world, num_keyframes);
+  return l;
+}
+void madicp_host_debug_ledger_free(madicp_host_ledger* l) { delete l; }
+int madicp_host_debug_ledger_promote(madicp_host_ledger* l, int64_t* out_ordinal, int64_t* out_evicted) {
+  if (!l) return -1;
+  const madicp_host::KeyframeLedger::Step s = l->ledger.promote();
+  if (out_ordinal) *out_ordinal = s.promoted.ordinal;
+  if (out_evicted) *out_evicted = s.evicted ? s.evicted_entry.ordinal : -1;
+  return s.promoted.local ? 1 : 0;
+}
+int64_t madicp_host_debug_ledger_window(const madicp_host_ledger* l, int64_t* out_ordinals, uint8_t* out_local, int64_t capacity) {
+  if (!l || capacity < 0) return -1;
+  int64_t n = 0;
+  for (const auto& e : l->ledger.window()) {
+    if (n < capacity) {
+      if (out_ordinals) out_ordinals[n] = e.ordinal;
+      if (out_local) out_local[n] = e.local ? 1 : 0;
+    }
+    ++n;
+  }
+  return n;
+}
+int64_t madicp_host_debug_ledger_num_local(const madicp_host_ledger* l) { return l ? int64_t(l->ledger.numLocal()) : -1; }
 
 }  // extern "C"

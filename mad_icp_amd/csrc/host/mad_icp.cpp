@@ -35,9 +35,17 @@ void MADicp::setMoving(MADtree& scan_tree) {
 void MADicp::compute(const std::vector<MADtree*>& fixed, int n_iters, bool truncated, const std::function<void()>& while_in_flight,
                      bool eager) {
   if (L_ <= 0) throw std::runtime_error("MADicp::compute: setMoving was not called");
-  if (fixed.empty()) throw std::runtime_error("MADicp::compute: no fixed tree");
-  if (n_iters < 1) return;
+  if (n_iters < 1 && !fixed.empty()) return;
   DeviceLock lock(Device::mutex());
+  if (fixed.empty()) {
+    // A rank of a sharded registration that owns no keyframe still joins every round (with zero adders: include/madicp_hip.h,
+    // madicp_comm_init) — legal if and only if the context holds a communicator of more than one rank
+    int64_t ranks = 0;
+    if (madicp_ctx* live = Device::current(Device::generation()))
+      check(madicp_ctx_get_option(live, "comm_ranks", &ranks), "madicp_ctx_get_option");
+    if (ranks <= 1) throw std::runtime_error("MADicp::compute: no fixed tree");
+    if (n_iters < 1) return;
+  }
   madicp_ctx* ctx = Device::ctx();
   // A loop the caller cut short (Pipeline's realtime budget): the reference only resets matched_ in iteration
   // MAX_ICP_ITS - 1, so after an early break the flags are the OR of every round that ran (pipeline.cpp:167-176); and a

@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <stdexcept>
+#include <string>
 #include <utility>
 
 namespace madicp_host {
@@ -44,6 +46,7 @@ Pipeline::Pipeline(double sensor_hz, bool deskew, double b_max, double rho_ker, 
     b_max_(b_max),
     p_th_(p_th),
     b_min_(b_min) {
+  ledger_.configure(0, 1, num_keyframes);
   frame_to_map_ = Pose::identity();
   keyframe_to_map_ = Pose::identity();
   std::memset(current_velocity_, 0, sizeof(current_velocity_));
@@ -164,8 +167,11 @@ void Pipeline::initialize(const double& curr_stamp, ContainerType& cloud) {
   frame->frame_to_map_ = frame_to_map_;
   frame->stamp_ = curr_stamp;
   frame->tree_ = std::make_unique<MADtree>(std::move(cloud), b_max_, b_min_, max_parallel_levels_);
-  frame->tree_->deviceId();  // first keyframe: resident from now on
-  keyframes_.push_back(std::move(frame));
+  current_num_leaves_ = size_t(frame->tree_->numLeaves());
+  current_tree_view_ = frame->tree_.get();
+  if (ledger_.world() == 1 || madicp::keyframe_owner(0, ledger_.world()) == ledger_.rank())
+    frame->tree_->deviceId();  // first keyframe: resident from now on (sharded: on its owner)
+  pushKeyframe(std::move(frame));
   trajectory_.push_back(Pose::identity());
   is_initialized_ = true;
   is_map_updated_ = true;
@@ -333,6 +339,7 @@ void Pipeline::compute(const double& curr_stamp, ContainerType curr_cloud) {
 // the frame step once the scan's tree exists (or, host path, is still to be built from *cloud)
 void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree> current_tree, ContainerType* cloud,
                                double t_pre) {
+  current_leaves_host_ = nullptr;
   if (!is_initialized_) {
     if (current_tree) {
       auto frame = std::make_unique<Frame>();
@@ -341,7 +348,9 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
       frame->stamp_ = curr_stamp;
       frame->tree_ = std::move(current_tree);
       frame->tree_->deviceId();
-      keyframes_.push_back(std::move(frame));
+      current_num_leaves_ = size_t(frame->tree_->numLeaves());
+      current_tree_view_ = frame->tree_.get();
+      pushKeyframe(std::move(frame));
       trajectory_.push_back(Pose::identity());
       is_initialized_ = true;
       is_map_updated_ = true;
@@ -349,8 +358,6 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
     } else {
       initialize(curr_stamp, *cloud);
     }
-    current_tree_view_ = keyframes_.back()->tree_.get();
-    current_num_leaves_ = size_t(current_tree_view_->numLeaves());
     return;
   }
 
@@ -407,7 +414,9 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
   if (rounds > 0) {
     std::vector<MADtree*> fixed;
     fixed.reserve(keyframes_.size());
-    for (auto& f : keyframes_) fixed.push_back(f->tree_.get());
+    for (auto& f : keyframes_)
+      if (f->tree_) fixed.push_back(f->tree_.get());  // (sharded: this rank's keyframes — none at all is legal there)
+    if (ledger_.world() > 1) checkShardCommunicator();
     // (cut short: the matched flags are the OR over the rounds that ran — the reference resets them in iteration
     // MAX_ICP_ITS - 1 only — and the launch goes kernel by kernel, no graph is instantiated for an odd round count)
     const bool looking_ahead = device_frontend_ && (dev_pending_ || dev_next_staged_);
@@ -465,8 +474,7 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
       }
       // promotion is a pointer move: the tree has been resident, in the map frame, since its own frame
       keyframe_to_map_ = best_frame->frame_to_map_;
-      keyframes_.push_back(std::move(best_frame));
-      if (keyframes_.size() > size_t(num_keyframes_)) keyframes_.pop_front();  // eviction: buffers back to the pool
+      pushKeyframe(std::move(best_frame));  // (and the eviction: buffers back to the pool)
       is_map_updated_ = true;
       seq_keyframe_ = new_seq;
     }
@@ -479,16 +487,62 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
 // pipeline.cpp:290-297: `current_leaves_` is filled by the first REGISTERED frame (pipeline.cpp:143-144); initialize() (:267-283)
 // leaves it empty, so the reference returns nothing after the first scan — mirrored
 const ContainerType Pipeline::currentLeaves() {
-  return (current_tree_view_ && trajectory_.size() > 1) ? current_tree_view_->leafMeans() : ContainerType{};
+  if (trajectory_.size() <= 1) return ContainerType{};
+  if (current_leaves_host_) return *current_leaves_host_;  // (sharded: the scan was promoted and its tree is another rank's)
+  return current_tree_view_ ? current_tree_view_->leafMeans() : ContainerType{};
 }
 
+// (sharded: every rank returns the FULL map — the device tree's leaves where this rank owns the keyframe, the host copy taken
+// at promotion elsewhere)
 const ContainerType Pipeline::modelLeaves() {  // pipeline.cpp:299-308
   ContainerType leaves;
   for (auto& frame : keyframes_) {
+    if (!frame->tree_) {
+      leaves.insert(leaves.end(), frame->host_leaves_.begin(), frame->host_leaves_.end());
+      continue;
+    }
     const ContainerType l = frame->tree_->leafMeans();
     leaves.insert(leaves.end(), l.begin(), l.end());
   }
   return leaves;
+}
+
+void Pipeline::setShard(int rank, int world) {
+  if (is_initialized_ || seq_ != 0) throw std::logic_error("Pipeline::setShard: only before the first compute()");
+  if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("Pipeline::setShard: need 0 <= rank < world");
+  if (realtime_ && world > 1)
+    throw std::invalid_argument("Pipeline::setShard: realtime = true cannot be sharded (the round count comes from each rank's "
+                                "own wall clock and would differ between the ranks)");
+  ledger_.configure(rank, world, num_keyframes_);
+}
+
+// pipeline.cpp:252-257 through the ledger: the new keyframe enters the (global) window on every rank, its tree stays on the
+// rank that owns its ordinal; the oldest one leaves on every rank, its tree is freed where it was
+void Pipeline::pushKeyframe(std::unique_ptr<Frame> frame) {
+  const KeyframeLedger::Step step = ledger_.promote();
+  if (!step.promoted.local && frame->tree_) {
+    frame->host_leaves_ = frame->tree_->leafMeans();  // (already in the map frame: transformed in its own frame's compute())
+    if (frame->tree_.get() == current_tree_view_) {
+      current_tree_view_ = nullptr;
+      current_leaves_host_ = &frame->host_leaves_;  // (the Frame is heap-allocated: the address survives the deque)
+    }
+    frame->tree_.reset();  // the HBM goes back to the library's pool
+  }
+  keyframes_.push_back(std::move(frame));
+  if (step.evicted) keyframes_.pop_front();
+}
+
+// a sharded registration against a context without the communicator would silently register against this rank's part of the
+// map alone: refuse it
+void Pipeline::checkShardCommunicator() {
+  DeviceLock lock(Device::mutex());
+  int64_t ranks = 0, rank = -1;
+  check(madicp_ctx_get_option(Device::ctx(), "comm_ranks", &ranks), "madicp_ctx_get_option");
+  check(madicp_ctx_get_option(Device::ctx(), "comm_rank", &rank), "madicp_ctx_get_option");
+  if (ranks != ledger_.world() || rank != ledger_.rank())
+    throw std::runtime_error("Pipeline: setShard(" + std::to_string(ledger_.rank()) + ", " + std::to_string(ledger_.world()) +
+                             ") but the device context's communicator has " + std::to_string(ranks) + " ranks, this one rank " +
+                             std::to_string(rank) + " (install it on madicp_host_device_ctx() before the first compute())");
 }
 
 }  // namespace madicp_host

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "deskew.h"
+#include "keyframe_ledger.h"
 #include "linalg.h"
 #include "mad_icp.h"
 #include "mad_tree.h"
@@ -50,7 +51,8 @@ static constexpr int FRAME_WINDOW = 10;
 
 struct Frame {  // tools/frame.h:37-52; the tree is owned here
   Pose frame_to_map_ = Pose::identity();
-  std::unique_ptr<MADtree> tree_;
+  std::unique_ptr<MADtree> tree_;  // (a keyframe of a sharded Pipeline: on the rank that owns it only)
+  ContainerType host_leaves_;      // sharded, keyframe owned by another rank: its leaf means, map frame (modelLeaves())
   double stamp_ = 0.;
   double weight_ = 0.;
   int frame_ = 0;
@@ -101,6 +103,28 @@ class Pipeline {
   void computeRecords(const double& curr_stamp, const float* records, size_t n_records, int stride_floats, double min_range,
                       double max_range, bool kitti_correction);
 
+  // additive: the keyframe map sharded over the ranks of a node.  Every rank runs ONE Pipeline and is
+  // fed the same scans in the same order; setShard(rank, world) makes this one keep the tree of a keyframe only when
+  // keyframe_owner(ordinal, world) == rank (csrc/common/keyframe_owner.h; ordinal: promotion order, the first scan is 0) and
+  // register against its own trees alone — the library joins the ranks' adders round by round, because the process-wide
+  // context (madicp_host_device_ctx()) holds a communicator of `world` ranks, which the CALLER installs before the first
+  // compute() (madicp_comm_init / madicp_comm_init_host, optionally the peer mailboxes; Python: sharded.shard_pipeline does all
+  // of it).  Every rank ends each registration with the same X, H, b and matched count bit for bit, so every rank takes the
+  // same promotion decision without any further exchange: keyframeID(), keyframePose(), isMapUpdated(), currentID(),
+  // numKeyframes() and modelLeaves() answer on every rank as on one GPU (a non-owner keeps a promoted tree's leaf means as a
+  // host copy and gives the tree's HBM back).  Each rank still builds / deskews every scan itself and keeps the whole frame
+  // window resident: any frame may be promoted.
+  // Only legal before the first compute() (std::logic_error after it); std::invalid_argument unless 0 <= rank < world, and for
+  // realtime = true with world > 1 (the round count comes from each rank's own wall clock and would differ between ranks,
+  // which a collective does not survive).  world == 1: exactly the unsharded Pipeline.  prefetch() stays legal.
+  // A communicator failure (MADICP_ERR_COMM from the submission or the collect: a rank that never joined, a broken transport)
+  // surfaces from compute() as the std::runtime_error of every device failure; the ranks' states may have parted by then, so
+  // the Pipeline — on every rank — is unusable from there on: destroy it, re-create the communicator, start a new one.
+  void setShard(int rank, int world);
+  int shardRank() const { return ledger_.rank(); }
+  int shardWorld() const { return ledger_.world(); }
+  size_t numLocalKeyframes() const { return ledger_.numLocal(); }  // keyframes whose tree THIS rank holds
+
   // instrumentation (not in the reference)
   double lastInliersRatio() const { return last_inliers_ratio_; }
   int lastRounds() const { return last_rounds_; }  // GN rounds the last frame ran (realtime = true can cut them short)
@@ -133,6 +157,10 @@ class Pipeline {
   std::deque<std::unique_ptr<Frame>> frames_;
   std::vector<Pose> trajectory_;
   MADtree* current_tree_view_ = nullptr;  // the last scan's tree (owned by a Frame in frames_ / keyframes_)
+  const ContainerType* current_leaves_host_ = nullptr;  // ... or, sharded, its leaf means where the tree was promoted and released
+  KeyframeLedger ledger_;                 // which keyframe ordinals are in the window, which of them this rank owns
+  void checkShardCommunicator();          // sharded: the context's communicator is the one setShard() was told about
+  void pushKeyframe(std::unique_ptr<Frame> frame);  // keyframes_ push + eviction by the ledger; a non-owner releases the tree
   size_t current_num_leaves_ = 0;
   // what a look-ahead result is matched to its scan by: size, end points and a digest of a strided sample of the points
   struct DevKey {

@@ -52,6 +52,12 @@ PYBIND11_MODULE(pypeline, m) {
                                max_range, kitti);
          },
          py::arg("stamp"), py::arg("records"), py::arg("min_range"), py::arg("max_range"), py::arg("kitti_correction") = false)
+    // additive: the keyframe map sharded over the ranks of a node (csrc/host/pipeline.h; mad_icp_amd.sharded.shard_pipeline
+    // installs the communicator and calls this)
+    .def("setShard", &Pipeline::setShard, py::arg("rank"), py::arg("world"))
+    .def("shardRank", &Pipeline::shardRank)
+    .def("shardWorld", &Pipeline::shardWorld)
+    .def("numLocalKeyframes", &Pipeline::numLocalKeyframes)
     // instrumentation, not in the reference
     .def("lastInliersRatio", &Pipeline::lastInliersRatio)
     .def("lastRounds", &Pipeline::lastRounds)

@@ -112,6 +112,60 @@ def attach_peer_mailboxes(ctx, group=None, allow_coarse=False):
     return rank, world
 
 
+# the callbacks / handles a borrowed context's communicator needs for as long as it is installed (the wrapper objects come and
+# go; the process-wide context stays)
+_installed = {}
+
+
+def shard_pipeline(pipe, group=None, transport="native", allow_coarse=False):
+    """Shard the keyframe map behind `pipe` (a pypeline.Pipeline that has not computed yet) over the ranks of `group`: every
+    rank runs this with its own Pipeline and then feeds it the same scans in the same order.
+
+    Installs the communicator in the process-wide device context the Pipeline works on (capi.Context.borrowed()) and calls
+    pipe.setShard(rank, world):
+      "native"  init_native_comm: RCCL, one GPU per rank
+      "host"    init_host_comm: the all-reduce goes through torch.distributed on host memory (any backend, ranks may share a GPU)
+      "p2p"     a communicator as above — native where the ranks have a GPU each (nccl backend), host-staged otherwise — then
+                attach_peer_mailboxes and option shard_p2p = 1: the per-round join inside the registration's own kernels
+    `allow_coarse`: see attach_peer_mailboxes (ranks that share ONE device).  Returns the borrowed context — hand it to
+    unshard() when the Pipeline is done.  One sharded Pipeline per process at a time: the context is process-wide."""
+    import torch.distributed as dist
+
+    if transport not in ("native", "host", "p2p"):
+        raise ValueError("transport must be 'native', 'host' or 'p2p'")
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if pipe.isInitialized():
+        raise RuntimeError("shard_pipeline: the Pipeline has computed already (setShard is only legal before the first compute)")
+    ctx = capi.Context.borrowed()
+    if ctx.get_option("comm_ranks"):
+        raise capi.MadIcpError("shard_pipeline: the process-wide context already holds a communicator (sharded.unshard first)")
+    native = transport == "native" or (transport == "p2p" and dist.get_backend(group) == "nccl")
+    if native:
+        init_native_comm(ctx, group)
+    else:
+        init_host_comm(ctx, group)
+    _installed[ctx._h.value] = ctx  # (keeps the host transport's callback alive)
+    try:
+        if transport == "p2p":
+            attach_peer_mailboxes(ctx, group, allow_coarse=allow_coarse)
+            ctx.set_option("shard_p2p", 1)
+        pipe.setShard(rank, world)
+    except Exception:
+        unshard(ctx)
+        raise
+    return ctx
+
+
+def unshard(pipe_ctx):
+    """Undo shard_pipeline on the context it returned: option shard_p2p back to 0, the communicator (and the peers' mailbox
+    mappings) destroyed.  Pipelines created afterwards in this process are unsharded again; the sharded one is finished."""
+    pipe_ctx.set_option("shard_p2p", 0)
+    pipe_ctx.comm_destroy()
+    held = _installed.pop(pipe_ctx._h.value, None)
+    if held is not None and held is not pipe_ctx:
+        held.close()
+
+
 class StagedShardedRegistration:
     """GN loop with the (H,b) join done by torch.distributed.
 
