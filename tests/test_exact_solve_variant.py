@@ -2,8 +2,8 @@
 default kernels use fused multiply-adds, refined reciprocals and a lane-parallel Gauss-Jordan solve (DESIGN.md section 5);
 with the flag e, J, the weights, the 27 accumulations and the 6x6 LDLT run in the reference's operation order with correctly
 rounded divisions (mad_icp.cpp:59-72, 92-101, 111).  This test builds the HIP library a second time with the flag, into a
-scratch directory, and runs the registration parity tests against it: the leg stays buildable and green, and the default
-build is shown to differ from it only in the last bits."""
+scratch directory, and runs the registration parity tests and the update-step tests (tests/test_gpu_gn_step.py) against it: the
+leg stays buildable and green, and the default build is shown to differ from it only in the last bits."""
 import os
 import subprocess
 import sys
@@ -28,6 +28,12 @@ def test_exact_solve_build_passes_the_registration_parity_tests(tmp_path):
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
+    # the update step at its edges (tests/test_gpu_gn_step.py): the restated LDLT, its zero_matrix path and its DBL_MIN guard meet
+    # H with rows of zeros and H = 0, held to the exact solve at the same bound as the default build's Gauss-Jordan
+    r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "tests/test_gpu_gn_step.py", "-p",
+                        "no:cacheprovider"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert " passed" in r.stdout and "skipped" not in r.stdout and "deselected" not in r.stdout
     # and the two builds agree to the last bits on a registration (same decisions, arithmetic after the gate differs)
     code = r"""
 import numpy as np
