@@ -267,6 +267,20 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
  * reference's up to the order of such ties.  out_chunks (n, optional): the time chunk of every point in walk order
  * (largest azimuth first) — synchronises when given. */
 int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks);
+/* Motion compensation from PER-POINT TIMESTAMPS, for callers whose driver delivers them (a PointCloud2 `t` / `timestamp` /
+ * `time` field): additive, the reference has no such path — its azimuth guess above fits a single 360-degree head that starts
+ * at +pi and turns clockwise, and nothing else.  stamps01[i] is the acquisition time of point i normalised over the scan, 0 =
+ * start, 1 = end.  Same time model as madicp_cloud_deskew: 1024 chunk times t_0 = -1/hz, t_{k+1} = t_k + (1/hz)/1023, one pose
+ * [expMapSO3(omega t_k), v t_k] per chunk from the same host table.  Chunk of a point, in fp64 without contraction: NaN -> 1023
+ * (time unknown: taken as the scan's end, the frame the pose refers to); else q = floor(s * 1023 + 0.5), q <= 0 -> 0,
+ * q >= 1023 -> 1023 (covers +-inf and out-of-range stamps), otherwise (int)q.  out[i] = pose[k_i] * p[i]: the cloud KEEPS ITS
+ * INPUT ORDER (nothing is sorted), written to a fresh buffer like the azimuth path's.  One streaming kernel on the copy
+ * stream; the stamps cross PCIe through the context's pinned staging.  MADICP_ERR_INVALID — before anything is launched or
+ * allocated — for a null argument, an unknown cloud, n != the cloud's size, sensor_hz <= 0; MADICP_ERR_CAPACITY while a
+ * look-ahead build is in flight; the cloud is unchanged after either.  out_chunks (n, optional): the chunk of every point in
+ * input order — synchronises when given.  Bit-equal to madicp_host_deskew_stamped (madicp_host.h) for the same velocity. */
+int madicp_cloud_deskew_stamped(madicp_ctx* ctx, int cloud_id, const double* stamps01, int64_t n, const double velocity[6],
+                                double sensor_hz, int32_t* out_chunks);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes
  * a resident tree exactly like one given to madicp_tree_upload (same node format, madicp_tree_download returns it).
  * Same decisions as the reference node by node, the reference's member order (the permutation utils.h:37-52 leaves), and
@@ -287,7 +301,8 @@ int madicp_tree_build(madicp_ctx* ctx, int cloud_id, double b_max, double b_min,
  * enqueues the whole level loop on a stream of its own — the library's BUILD stream, so that neither the registration on
  * the compute stream nor its feed on the copy stream queues behind it — and returns without waiting; _end waits for the
  * leaf count, sizes and emits the tree and returns its id.  One look-ahead per context: a second _begin, or
- * madicp_tree_build / madicp_cloud_ingest_f32 / madicp_cloud_deskew / madicp_tree_build_stats before the _end, return
+ * madicp_tree_build / madicp_cloud_ingest_f32 / madicp_cloud_deskew / madicp_cloud_deskew_stamped / madicp_tree_build_stats
+ * before the _end, return
  * MADICP_ERR_CAPACITY (they share the builder's scratch).  Registrations, uploads, transforms, searches and releases are
  * free to run in between.  The tree is the one madicp_cloud_upload + madicp_tree_build give for the same scan, bit for bit. */
 int madicp_tree_build_begin(madicp_ctx* ctx, const double* xyz, int64_t n, double b_max, double b_min);

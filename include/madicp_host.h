@@ -61,6 +61,14 @@ int64_t madicp_host_debug_tree_points(double* points, int64_t n, double b_max, d
  * naive_vel of pipeline.cpp:82-86. */
 int madicp_host_debug_deskew(double* points, int64_t n, const double T_prev[12], const double T_now[12], double sensor_hz, int route,
                              double* out_velocity6);
+/* Motion compensation from per-point timestamps on the host (csrc/host/deskew.h: deskew_cloud_stamped — what a Pipeline
+ * with the host front-end runs for computeStamped), in place, INPUT order kept: the host twin of madicp_cloud_deskew_stamped
+ * (madicp_hip.h: same chunk rule, same pose table, same evaluation order — bit-equal for the same velocity).  stamps01 (n):
+ * acquisition time of every point, 0 = scan start, 1 = scan end; the velocity is naive_vel of pipeline.cpp:82-86 from the two
+ * poses (12 doubles each: R row-major, t).  out_velocity6, out_chunks (n, the chunk of every point): optional.  Returns 0,
+ * < 0 on bad arguments (a null pointer, n < 0, sensor_hz <= 0), the buffer untouched. */
+int madicp_host_deskew_stamped(double* points, const double* stamps01, int64_t n, const double T_prev[12], const double T_now[12],
+                               double sensor_hz, double* out_velocity6, int32_t* out_chunks);
 
 /* ---- the keyframe map sharded over the ranks of a node (Pipeline::setShard, csrc/host/pipeline.h) ---- */
 /* The rank that owns the keyframe of ORDINAL k — promotion order: the first scan is 0, every promotion adds 1; not the frame

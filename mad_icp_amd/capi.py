@@ -141,6 +141,7 @@ def hip_lib():
         L.madicp_cloud_ingest_f32.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int, C.c_double, C.c_double,
                                               C.c_int, _ip, _i64p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
+        L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
         L.madicp_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, _ip, _i32p]
         L.madicp_tree_build_begin.argtypes = [C.c_void_p, _dp, C.c_int64, C.c_double, C.c_double]
         L.madicp_tree_build_end.argtypes = [C.c_void_p, _ip, _i32p]
@@ -183,6 +184,7 @@ def host_lib():
         L.madicp_host_tree_rho2.restype = C.c_double
         L.madicp_host_tree_rho2.argtypes = [C.c_void_p]
         L.madicp_host_debug_deskew.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_double, C.c_int, _dp]
+        L.madicp_host_deskew_stamped.argtypes = [_dp, _dp, C.c_int64, _dp, _dp, C.c_double, _dp, _i32p]
         L.madicp_host_debug_tree_points.restype = C.c_int64
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
@@ -359,6 +361,24 @@ def host_deskew(points, T_prev, T_now, sensor_hz, route=0):
     return pts, vel, bool(rc)
 
 
+def host_deskew_stamped(points, stamps, T_prev, T_now, sensor_hz):
+    """deskew_cloud_stamped on the host (csrc/host/deskew.h): motion compensation from per-point timestamps in [0, 1].
+    Returns (cloud in input order, naive velocity (6,), chunk of every point (n,) int32)."""
+    pts = np.ascontiguousarray(points, dtype=np.float64).copy()
+    st = np.ascontiguousarray(stamps, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or st.shape != (pts.shape[0],):
+        raise ValueError("points must be (n, 3) and stamps (n,)")
+    vel = np.empty(6)
+    chunks = np.empty(pts.shape[0], np.int32)
+    a, b = pose12(T_prev), pose12(T_now)
+    rc = host_lib().madicp_host_deskew_stamped(pts.ctypes.data_as(_dp), st.ctypes.data_as(_dp), pts.shape[0], a.ctypes.data_as(_dp),
+                                               b.ctypes.data_as(_dp), float(sensor_hz), vel.ctypes.data_as(_dp),
+                                               chunks.ctypes.data_as(_i32p))
+    if rc < 0:
+        raise MadIcpError("madicp_host_deskew_stamped: bad arguments")
+    return pts, vel, chunks
+
+
 class Context:
     """One device + one stream (include/madicp_hip.h)."""
 
@@ -492,6 +512,16 @@ class Context:
         chunks = np.empty(self.cloud_size(cid), np.int32) if want_chunks else None
         _check(hip_lib().madicp_cloud_deskew(self._h, cid, v.ctypes.data_as(_dp), float(sensor_hz),
                                              chunks.ctypes.data_as(_i32p) if want_chunks else None))
+        return chunks
+
+    def cloud_deskew_stamped(self, cid, stamps, velocity, sensor_hz, want_chunks=False):
+        """Motion compensation from per-point timestamps in [0, 1] (one per point, input order kept).  Returns the chunk of
+        every point (n,) int32 when asked for, else None."""
+        st = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1)
+        v = _f64(velocity, (6,))
+        chunks = np.empty(st.shape[0], np.int32) if want_chunks else None
+        _check(hip_lib().madicp_cloud_deskew_stamped(self._h, cid, st.ctypes.data_as(_dp), st.shape[0], v.ctypes.data_as(_dp),
+                                                     float(sensor_hz), chunks.ctypes.data_as(_i32p) if want_chunks else None))
         return chunks
 
     def tree_build(self, cid, b_max, b_min):

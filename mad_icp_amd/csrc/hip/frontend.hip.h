@@ -4,6 +4,8 @@
 //            angle correction — apps/cpp_runners/bin_runner.cpp:126-166 of the reference
 //   deskew : Pipeline::deskew, mad_icp/src/odometry/pipeline.cpp:79-123 — azimuth sort + per-chunk constant-velocity
 //            compensation
+//   deskew from per-point timestamps (additive, the reference has none): the same time model with the chunk read off the
+//            acquisition time the sensor driver delivers for every point — one streaming kernel, input order kept
 // All of it is HBM-bound streaming work (24-32 bytes per point per pass); the kernels are coalesced grid-stride
 // passes, the sort is rocPRIM's radix sort, scans are the three-kernel tile scans of tree_build.hip.h.
 #pragma once
@@ -196,6 +198,43 @@ __global__ __launch_bounds__(256) void deskew_apply(const double* __restrict__ x
     out[3 * j + 2] = P[11] + madicp_host::sum3s(P[6] * x, P[7] * y, P[8] * z);
 #endif
     if (chunk_of) chunk_of[d] = kd;
+  }
+}
+
+// ---- deskew from per-point timestamps ---------------------------------------------------------------------------------
+// For sensors whose driver delivers the acquisition time of every point (a PointCloud2 `t` / `timestamp` / `time` field,
+// normalised to [0, 1] over the scan): the chunk of a point is a function of that point alone — no azimuth, no sort, no
+// prefix minimum.  s in [0, 1] -> k = floor(s * 1023 + 0.5) clamped to [0, 1023] (round half up: a stamp on the boundary
+// (k + 0.5) / 1023 belongs to chunk k + 1); NaN — time unknown — is the scan's end, the frame the pose refers to.  Evaluated in
+// fp64 WITHOUT contraction (the pragma above): a fused s * 1023 + 0.5 rounds the other way on some boundaries, and the host
+// twin (csrc/host/deskew.cpp: deskew_cloud_stamped) must take the same side.  +-inf and out-of-range stamps are clamped
+// before the conversion to int.  out[i] = pose[k_i] * p[i], in INPUT order; poses: (1024, 12) as for deskew_apply, gathered
+// through L2 (neighbouring points carry neighbouring stamps: a wavefront reads one or two poses).
+constexpr int kStampChunks = 1024;  // CHUNKS, tools/constants.h:31
+__device__ __host__ inline int stamp_chunk(double s) {
+  if (s != s) return kStampChunks - 1;
+  const double q = floor(s * double(kStampChunks - 1) + 0.5);
+  if (q <= 0.0) return 0;
+  if (q >= double(kStampChunks - 1)) return kStampChunks - 1;
+  return (int)q;
+}
+__global__ __launch_bounds__(256) void deskew_stamped(const double* __restrict__ xyz, const double* __restrict__ stamps, long n,
+                                                      const double* __restrict__ poses, double* __restrict__ out,
+                                                      int32_t* __restrict__ chunk_of /* optional, input order */) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int k = stamp_chunk(stamps[i]);
+    const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    const double* P = poses + 12 * (long)k;
+#ifdef MADICP_XFORM_HOMOGENEOUS
+    out[3 * i] = ((P[0] * x + P[1] * y) + P[2] * z) + P[9];
+    out[3 * i + 1] = ((P[3] * x + P[4] * y) + P[5] * z) + P[10];
+    out[3 * i + 2] = ((P[6] * x + P[7] * y) + P[8] * z) + P[11];
+#else
+    out[3 * i] = P[9] + madicp_host::sum3s(P[0] * x, P[1] * y, P[2] * z);
+    out[3 * i + 1] = P[10] + madicp_host::sum3s(P[3] * x, P[4] * y, P[5] * z);
+    out[3 * i + 2] = P[11] + madicp_host::sum3s(P[6] * x, P[7] * y, P[8] * z);
+#endif
+    if (chunk_of) chunk_of[i] = k;
   }
 }
 

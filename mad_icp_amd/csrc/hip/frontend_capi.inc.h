@@ -492,33 +492,21 @@ size_t sort_temp_bytes(int64_t n) {
   (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)n, 0, 64, (hipStream_t) nullptr);
   return bytes + 256;
 }
-}  // namespace
 
-extern "C" {
-
-int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks) {
-  if (!ctx || !velocity) return fail(MADICP_ERR_INVALID, "null argument");
-  DevCloud* c = find_cloud(ctx, cloud_id);
-  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
-  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
-  FrontScratch* fs = nullptr;
-  RC_TRY(ensure_scratch(ctx, c->n, &fs));
-  const int64_t n = c->n;
-  // The reference's running threshold and time (pipeline.cpp:99-106,109-117), tabulated with its own arithmetic
-  // (repeated subtraction / addition), and the pose of every chunk by the host's expSO3 (libm, like the reference).
-  constexpr int CHUNKS = 1024;  // tools/constants.h:31
+// The reference's running threshold and time (pipeline.cpp:99-106,109-117), tabulated with its own arithmetic (repeated
+// subtraction / addition), and the pose of every chunk by the host's expSO3 (libm, like the reference): poses[12 k] =
+// [expMapSO3(omega t_k) row-major | v t_k], t_0 = -1/hz, t_{k+1} = t_k + (1/hz) / 1023.  One table for both deskews: the azimuth
+// walk reads thresholds and poses (`count` = kDeskewTableMax), the stamped path the first CHUNKS poses (thr = nullptr).
+// Returns the number of thresholds that can still be undercut.
+int deskew_table(const double velocity[6], double sensor_hz, int count, double* thr, double* poses) {
+  constexpr int CHUNKS = fe::kStampChunks;  // tools/constants.h:31
   const double ts = 1. / sensor_hz;
   const double resolution = 2 * M_PI / double(CHUNKS);
   const double delta = ts / double(CHUNKS - 1);
-  HIP_TRY(hipEventSynchronize(fs->h_table_read));
-  double* thr = fs->h_table;
-  double* poses = fs->h_table + kDeskewTableMax;
   double angle = M_PI - resolution;
   double t = -ts;
   int n_thr = 0;
-  for (int k = 0; k < kDeskewTableMax; ++k) {
+  for (int k = 0; k < count; ++k) {
     double dx[6];
     for (int i = 0; i < 6; ++i) dx[i] = velocity[i] * t;
     double* Pk = poses + 12 * k;
@@ -545,11 +533,29 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
       }
       Pk[9] = dx[0]; Pk[10] = dx[1]; Pk[11] = dx[2];
     }
-    thr[k] = angle;
+    if (thr) thr[k] = angle;
     if (angle >= -M_PI - resolution) n_thr = k + 1;  // thresholds at or below -pi can never be undercut again
     angle -= resolution;
     t += delta;
   }
+  return n_thr;
+}
+}  // namespace
+
+extern "C" {
+
+int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks) {
+  if (!ctx || !velocity) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, c->n, &fs));
+  const int64_t n = c->n;
+  HIP_TRY(hipEventSynchronize(fs->h_table_read));
+  const int n_thr = deskew_table(velocity, sensor_hz, kDeskewTableMax, fs->h_table, fs->h_table + kDeskewTableMax);
   const int n_poses = std::min(n_thr + 1, kDeskewTableMax);
   HIP_TRY(hipMemcpyAsync(fs->table, fs->h_table, sizeof(double) * kDeskewTableMax * 13, hipMemcpyHostToDevice, ctx->copy));
   HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
@@ -585,6 +591,70 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   c->xyz = static_cast<double*>(fresh);
   HIP_TRY(hipEventRecord(c->ready, ctx->copy));
   if (out_chunks) {  // debugging / parity aid: the time chunk of every point, in walk order (largest azimuth first)
+    HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
+    HIP_TRY(hipStreamSynchronize(ctx->copy));
+  }
+  return MADICP_OK;
+}
+
+// Motion compensation from the acquisition time of every point (fe::deskew_stamped): the same time model and pose table as
+// above, the chunk taken from the point's own stamp.  One kernel; the cloud keeps its input order.
+int madicp_cloud_deskew_stamped(madicp_ctx* ctx, int cloud_id, const double* stamps01, int64_t n, const double velocity[6],
+                                double sensor_hz, int32_t* out_chunks) {
+  if (!ctx || !stamps01 || !velocity) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (n != c->n) return fail(MADICP_ERR_INVALID, "n mismatch: one stamp per point of the cloud");
+  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, n, &fs));
+  // the stamps: pinned staging shared with the cloud and tree uploads (two buffers, alternating) -> key[0] of the scratch
+  const size_t bytes = sizeof(double) * (size_t)n;
+  const int hb = ctx->h_tree_next;
+  ctx->h_tree_next ^= 1;
+  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
+  if (ctx->h_tree_cap[hb] < bytes) {
+    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
+    ctx->h_tree[hb] = nullptr;
+    ctx->h_tree_cap[hb] = 0;
+    const size_t cap = bytes + bytes / 4;
+    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
+    ctx->h_tree_cap[hb] = cap;
+  }
+  std::memcpy(ctx->h_tree[hb], stamps01, bytes);
+  double* d_stamps = fs->key[0];
+  HIP_TRY(hipMemcpyAsync(d_stamps, ctx->h_tree[hb], bytes, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], ctx->copy));
+  // the chunk poses, where the azimuth path keeps them (behind the thresholds, which this path does not read)
+  HIP_TRY(hipEventSynchronize(fs->h_table_read));
+  double* h_poses = fs->h_table + kDeskewTableMax;
+  double* d_poses = fs->table + kDeskewTableMax;
+  (void)deskew_table(velocity, sensor_hz, fe::kStampChunks, nullptr, h_poses);
+  HIP_TRY(hipMemcpyAsync(d_poses, h_poses, sizeof(double) * 12 * fe::kStampChunks, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
+  // the compensated cloud replaces the input: written to a fresh buffer, the old one goes back to the pool
+  void* fresh = nullptr;
+  RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)n, ctx->copy, &fresh));
+  int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;
+  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+  hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (const double*)d_stamps, (long)n,
+                     (const double*)d_poses, static_cast<double*>(fresh), d_chunks);
+  EventRef after;
+  {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
+    const hipError_t le = hipGetLastError();
+    const int frc = le == hipSuccess ? fence_event(ctx, &after) : MADICP_OK;
+    if (le != hipSuccess || frc != MADICP_OK) {
+      hipStreamSynchronize(ctx->copy);
+      pool_free(ctx, fresh, nullptr);
+      return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string("deskew_stamped: ") + hipGetErrorString(le)) : frc;
+    }
+  }
+  pool_free(ctx, c->xyz, after);
+  c->xyz = static_cast<double*>(fresh);
+  HIP_TRY(hipEventRecord(c->ready, ctx->copy));
+  if (out_chunks) {  // the time chunk of every point, in input order
     HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
     HIP_TRY(hipStreamSynchronize(ctx->copy));
   }

@@ -201,4 +201,56 @@ void deskew_cloud(ContainerType& cloud, const Pose& T_prev, const Pose& T_now, d
   });
 }
 
+// The chunk of a stamp: round half up to the nearest of the CHUNKS chunk times, clamped; NaN (time unknown) is the scan's end.
+// The comparisons come before the conversion, so +-inf and out-of-range stamps never reach an undefined float-to-int
+// conversion.  This file is compiled with -ffp-contract=off like the device kernel (fe::deskew_stamped): a fused
+// s * 1023 + 0.5 rounds the other way on some of the boundaries (k + 0.5) / 1023.
+int stamp_chunk(double s) {
+  if (s != s) return CHUNKS - 1;
+  const double q = std::floor(s * double(CHUNKS - 1) + 0.5);
+  if (q <= 0.0) return 0;
+  if (q >= double(CHUNKS - 1)) return CHUNKS - 1;
+  return static_cast<int>(q);
+}
+
+void deskew_cloud_stamped(ContainerType& cloud, const double* stamps, const Pose& T_prev, const Pose& T_now, double sensor_hz,
+                          double* out_velocity6, int32_t* out_chunks) {
+  const double ts = 1. / sensor_hz;
+  double vel[6];
+  naive_velocity(T_prev, T_now, sensor_hz, vel);
+  if (out_velocity6)
+    for (int i = 0; i < 6; ++i) out_velocity6[i] = vel[i];
+  // the reference's running time (pipeline.cpp:103-106,112-117) and the pose of every chunk — the table madicp_cloud_deskew and
+  // madicp_cloud_deskew_stamped make on the host for the device
+  const double delta = ts / double(CHUNKS - 1);
+  std::vector<Pose> poses(CHUNKS);
+  double t = -ts;
+  for (int k = 0; k < CHUNKS; ++k) {
+    const double dx[6] = {vel[0] * t, vel[1] * t, vel[2] * t, vel[3] * t, vel[4] * t, vel[5] * t};
+    poses[static_cast<size_t>(k)] = motion_from_twist(dx);
+    t += delta;
+  }
+  const size_t n = cloud.size();
+  auto body = [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      const int k = stamp_chunk(stamps[i]);
+      const Vector3d p = cloud[i];
+      apply(poses[static_cast<size_t>(k)], p.data(), cloud[i].data());
+      if (out_chunks) out_chunks[i] = k;
+    }
+  };
+  const int pieces = static_cast<int>(std::max<size_t>(1, std::min<size_t>(16, n / 8192)));
+  if (pieces == 1) {
+    body(0, n);
+    return;
+  }
+  std::vector<std::function<void()>> fns;
+  for (int p = 0; p < pieces; ++p) {
+    const size_t lo = n * static_cast<size_t>(p) / static_cast<size_t>(pieces), hi = n * static_cast<size_t>(p + 1) / static_cast<size_t>(pieces);
+    fns.emplace_back([&body, lo, hi] { body(lo, hi); });
+  }
+  TaskPool& pool = TaskPool::instance();
+  for (const TaskPool::Handle& j : pool.submit_batch(std::move(fns))) pool.wait(j);
+}
+
 }  // namespace madicp_host

@@ -29,6 +29,16 @@ DeskewOrder deskew_order(const ContainerType& cloud);  // parallel (task pool)
 void deskew_cloud(ContainerType& cloud, const Pose& T_prev, const Pose& T_now, double sensor_hz, const DeskewOrder* prep,
                   double* out_velocity6 /* optional */);
 
+// Additive (the reference has no such path): motion compensation from the acquisition time of every point, for sensors the
+// azimuth guess does not fit (solid-state, multi-head, limited field of view) and drivers that deliver the time anyway.
+// stamps[i] in [0, 1]: 0 = scan start, 1 = scan end.  The reference's time model — CHUNKS chunk times from -1/hz by repeated
+// addition, one pose [expMapSO3(omega t_k), v t_k] each — with the chunk read off the stamp: stamp_chunk().  In place, input
+// order kept, independent per point (task pool).  The host twin of fe::deskew_stamped (csrc/hip/frontend.hip.h): same table,
+// same rule, same evaluation order, bit-equal by construction.  out_chunks (optional): the chunk of every point.
+int stamp_chunk(double stamp01);  // NaN -> CHUNKS-1; else floor(s * (CHUNKS-1) + 0.5) clamped to [0, CHUNKS-1]
+void deskew_cloud_stamped(ContainerType& cloud, const double* stamps, const Pose& T_prev, const Pose& T_now, double sensor_hz,
+                          double* out_velocity6 /* optional */, int32_t* out_chunks = nullptr);
+
 // pipeline.cpp:82-86: [translation; logMapSO3(rotation)] of T_prev^-1 T_now over one scan period
 void naive_velocity(const Pose& T_prev, const Pose& T_now, double sensor_hz, double* vel6);
 

@@ -92,6 +92,22 @@ int madicp_host_debug_deskew(double* points, int64_t n, const double T_prev[12],
   return fast;
 }
 
+// deskew_cloud_stamped on its own (csrc/host/deskew.h): in place, input order kept
+int madicp_host_deskew_stamped(double* points, const double* stamps01, int64_t n, const double T_prev[12], const double T_now[12],
+                               double sensor_hz, double* out_velocity6, int32_t* out_chunks) {
+  if (!points || !stamps01 || n < 0 || !T_prev || !T_now || !(sensor_hz > 0.0)) return -1;
+  madicp_host::ContainerType cloud(static_cast<size_t>(n));
+  if (n) std::memcpy(static_cast<void*>(cloud.data()), points, sizeof(double) * 3 * static_cast<size_t>(n));
+  madicp_host::Pose a, b;
+  std::memcpy(a.R, T_prev, sizeof(a.R));
+  std::memcpy(a.t, T_prev + 9, sizeof(a.t));
+  std::memcpy(b.R, T_now, sizeof(b.R));
+  std::memcpy(b.t, T_now + 9, sizeof(b.t));
+  madicp_host::deskew_cloud_stamped(cloud, stamps01, a, b, sensor_hz, out_velocity6, out_chunks);
+  if (n) std::memcpy(points, static_cast<const void*>(cloud.data()), sizeof(double) * 3 * static_cast<size_t>(n));
+  return 0;
+}
+
 int madicp_host_keyframe_owner(int64_t k, int world) { return madicp::keyframe_owner(k, world); }
 
 madicp_ctx* madicp_host_device_ctx(void) {

@@ -232,7 +232,7 @@ void Pipeline::prefetch(ContainerType next_cloud) {
 
 // the device front-end for one frame: the cloud is resident; deskew when the reference would (pipeline.cpp:138-139),
 // build, hand the cloud's buffer back
-std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id) {
+std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* stamps, size_t n_stamps) {
   DeviceLock lock(Device::mutex());
   madicp_ctx* ctx = Device::ctx();
   MADtree::cancelDeviceBuild(0);  // deskew and build need the builder's scratch: a look-ahead of another Pipeline gives way
@@ -241,7 +241,11 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id) {
     if (is_initialized_ && deskew_ && trajectory_.size() > 1) {
       double vel[6];
       naiveVelocity(trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], vel);
-      check(madicp_cloud_deskew(ctx, cloud_id, vel, sensor_hz_, nullptr), "madicp_cloud_deskew");
+      if (stamps)
+        check(madicp_cloud_deskew_stamped(ctx, cloud_id, stamps, static_cast<int64_t>(n_stamps), vel, sensor_hz_, nullptr),
+              "madicp_cloud_deskew_stamped");
+      else
+        check(madicp_cloud_deskew(ctx, cloud_id, vel, sensor_hz_, nullptr), "madicp_cloud_deskew");
     }
     tree = std::make_unique<MADtree>(MADtree::DeviceCloud{cloud_id}, b_max_, b_min_);
   } catch (...) {
@@ -303,6 +307,53 @@ void Pipeline::computeView(const double& curr_stamp, const Vector3d* curr_cloud,
     current_tree = buildOnDevice(cloud_id);
   }
   computeWithTree(curr_stamp, std::move(current_tree), nullptr, t_pre);
+}
+
+// A scan with per-point acquisition times (pipeline.h).  The stamps matter under exactly the condition the reference deskews;
+// everywhere else this is compute().
+void Pipeline::computeStampedView(const double& curr_stamp, const Vector3d* curr_cloud, const double* stamps, size_t n) {
+  if (!curr_cloud || !stamps || n == 0) throw std::invalid_argument("Pipeline::computeStamped: empty cloud or no timestamps");
+  if (!(deskew_ && trajectory_.size() > 1)) {
+    computeView(curr_stamp, curr_cloud, n);
+    return;
+  }
+  is_map_updated_ = false;
+  const double t_pre = now_ms();
+  waitPrefetched();
+  std::unique_ptr<MADtree> current_tree;
+  if (device_frontend_) {
+    collectDeviceLookAhead();  // (the synchronous build needs the builder's scratch: as in computeView)
+    int cloud_id = -1;
+    {
+      DeviceLock lock(Device::mutex());
+      check(madicp_cloud_upload(Device::ctx(), curr_cloud[0].data(), static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
+    }
+    current_tree = buildOnDevice(cloud_id, stamps, n);
+  } else {
+    // the azimuth order prefetch() computed ahead for this scan (and older ones: scans that never came) is not needed
+    for (size_t q = 0; q < deskew_ahead_.size(); ++q) {
+      if (!deskew_ahead_[q].key.matches(curr_cloud, n)) continue;
+      for (size_t d = 0; d <= q; ++d) {
+        if (deskew_ahead_.front().order.valid()) deskew_ahead_.front().order.wait();
+        deskew_ahead_.pop_front();
+      }
+      break;
+    }
+    ContainerType cloud(curr_cloud, curr_cloud + n);  // (the host builder takes the points over)
+    deskew_cloud_stamped(cloud, stamps, trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], sensor_hz_, nullptr);
+    current_tree = std::make_unique<MADtree>(std::move(cloud), b_max_, b_min_, max_parallel_levels_);
+  }
+  computeWithTree(curr_stamp, std::move(current_tree), nullptr, t_pre);
+}
+
+void Pipeline::computeStamped(const double& curr_stamp, ContainerType curr_cloud, const std::vector<double>& stamps) {
+  if (curr_cloud.empty()) throw std::invalid_argument("Pipeline::computeStamped: empty cloud");
+  if (stamps.size() != curr_cloud.size()) throw std::invalid_argument("Pipeline::computeStamped: one timestamp per point");
+  if (!(deskew_ && trajectory_.size() > 1)) {
+    compute(curr_stamp, std::move(curr_cloud));
+    return;
+  }
+  computeStampedView(curr_stamp, curr_cloud.data(), stamps.data(), curr_cloud.size());
 }
 
 // pipeline.cpp:125-265

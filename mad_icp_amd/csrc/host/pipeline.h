@@ -25,6 +25,9 @@
 // (0.90 -> 0.64 ms; the kernels of the two streams interleave, profiles/r3_o_lookahead_overlap.md); one look-ahead there.  For
 // deskewed datasets the tree needs the previous poses: prefetch() then computes the pose-independent half of deskew ahead —
 // the azimuth of every point and their order (deskew.h).
+//
+// Additive: computeStamped(stamp, cloud, stamps) — a scan with the acquisition time of every point (what a PointCloud2 carries)
+// is motion-compensated from those times instead of the reference's azimuth guess, on the device or on the host (deskew.h).
 #pragma once
 #include <array>
 #include <cstddef>
@@ -81,6 +84,17 @@ class Pipeline {
   // Python bindings use, so that a frame does not begin with a 3 MB allocation + copy of its by-value argument
   void computeView(const double& curr_stamp, const Vector3d* curr_cloud, size_t n);
   void prefetchView(const Vector3d* next_cloud, size_t n);
+
+  // additive (not in the reference): a scan WITH the acquisition time of every point — stamps[i] in [0, 1], 0 = scan start,
+  // 1 = scan end, what a PointCloud2 reader extracts from the `t` / `timestamp` / `time` field.  Where the reference deskews
+  // (deskew = true and two poses exist: pipeline.cpp:138-139) the scan is motion-compensated from the stamps instead of the
+  // azimuth guess of pipeline.cpp:79-123 — same time model, same pose table, the chunk read off the stamp (deskew.h) — on the
+  // device (madicp_cloud_deskew_stamped) or, host front-end, by deskew_cloud_stamped; the points keep their input order.
+  // With deskew = false, and on the first two frames, the stamps are not used: the call IS compute() / computeView(), look-ahead
+  // hits included.  An azimuth order prefetch() computed ahead for this scan is dropped unused; there is no look-ahead for
+  // stamped frames.  std::invalid_argument for a null pointer, an empty cloud or stamps.size() != cloud.size().
+  void computeStamped(const double& curr_stamp, ContainerType curr_cloud, const std::vector<double>& stamps);
+  void computeStampedView(const double& curr_stamp, const Vector3d* curr_cloud, const double* stamps, size_t n);
 
   // additive: the device front-end.  When on, compute() uploads the scan once and deskew
   // (pipeline.cpp:79-123) and MADtree::build (mad_tree.cpp:47-130) run on the MI355X; the tree never exists on the host
@@ -145,7 +159,8 @@ class Pipeline {
   void initialize(const double& curr_stamp, ContainerType& curr_cloud);
   void deskew(ContainerType& curr_cloud, const Pose& T_prev, const Pose& T_now, const DeskewOrder* prep = nullptr);
   void naiveVelocity(const Pose& T_prev, const Pose& T_now, double* vel6) const;  // pipeline.cpp:82-86
-  std::unique_ptr<MADtree> buildOnDevice(int cloud_id);  // deskew (if due) + build + release of the cloud
+  // deskew (if due; from `stamps`, one per point, when given) + build + release of the cloud
+  std::unique_ptr<MADtree> buildOnDevice(int cloud_id, const double* stamps = nullptr, size_t n_stamps = 0);
   void computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree> current_tree, ContainerType* curr_cloud, double t_pre);
 
   MADicp icp_;

@@ -29,6 +29,26 @@ PYBIND11_MODULE(pypeline, m) {
            const Vector3d* pts = points_of_array(cloud);
            self.computeView(stamp, pts, static_cast<size_t>(cloud.shape(0)));
          })
+    // additive: compute(stamp, cloud, timestamps) — the acquisition time of every point, normalised to [0, 1] over the scan
+    // (what a PointCloud2 reader returns beside the points): with deskew = True the scan is motion-compensated from them
+    // instead of the azimuth guess (Pipeline::computeStamped); otherwise exactly compute(stamp, cloud).  A 1-D float64 array
+    // (forcecast) of one value per point, ValueError otherwise; the points are read as a view.
+    .def("compute",
+         [](Pipeline& self, double stamp, const ContainerType& cloud, py::array_t<double, py::array::c_style | py::array::forcecast> ts) {
+           if (ts.ndim() != 1 || static_cast<size_t>(ts.shape(0)) != cloud.size())
+             throw py::value_error("timestamps must be a 1-D array with one value per point");
+           self.computeStampedView(stamp, cloud.data(), ts.data(), cloud.size());
+         },
+         py::arg("stamp"), py::arg("cloud"), py::arg("timestamps"))
+    .def("compute",
+         [](Pipeline& self, double stamp, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> ts) {
+           const Vector3d* pts = points_of_array(cloud);
+           if (ts.ndim() != 1 || ts.shape(0) != cloud.shape(0))
+             throw py::value_error("timestamps must be a 1-D array with one value per point");
+           self.computeStampedView(stamp, pts, ts.data(), static_cast<size_t>(cloud.shape(0)));
+         },
+         py::arg("stamp"), py::arg("cloud"), py::arg("timestamps"))
     // additive look-ahead: start building the next scan's MAD-tree while this frame is registered
     .def("lookAheadHits", &Pipeline::lookAheadHits)
     .def("prefetch", [](Pipeline& self, const ContainerType& cloud) { self.prefetchView(cloud.data(), cloud.size()); },
