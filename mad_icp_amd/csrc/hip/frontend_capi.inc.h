@@ -330,7 +330,7 @@ int stage_and_send_cloud(madicp_ctx* ctx, const double* xyz, int64_t n, double* 
   char* stage = ctx->h_tree[hb];
   size_t done3 = 0;  // values already on their way as floats
   void* d_f32 = nullptr;
-  if (ctx->upload_f32 && n3 >= 4096) {
+  if (ctx->opt.upload_f32 && n3 >= 4096) {
     float* hf = reinterpret_cast<float*>(stage);
     const size_t piece3 = std::max<size_t>((n3 / 2 + 3) / 4 * 4, (size_t)64 << 10);  // two pieces (half the bytes: half the pieces)
     for (size_t off = 0; off < n3; off += piece3) {
@@ -731,7 +731,7 @@ int tb_summary_wait(madicp_ctx* ctx, FrontScratch& fs, int next_step) {
   tb::HostLine& hl = *fs.h_line;
   if (f.n_tiles <= tb::kScanDirectMax) {
     const int seq = f.seq;
-    const unsigned check_mask = ctx->wait_mode == 0 ? 0x3ffu : 0xfu;  // (option "wait_mode": spin / yield / sleep)
+    const unsigned check_mask = ctx->opt.wait_mode == 0 ? 0x3ffu : 0xfu;  // (option "wait_mode": spin / yield / sleep)
     for (unsigned spins = 1; __atomic_load_n(&hl.seq, __ATOMIC_ACQUIRE) != seq; ++spins) {
       if ((spins & check_mask) == 0) {  // every few tens of microseconds: is the stream still alive?
         const hipError_t q = hipStreamQuery(f.s);
@@ -1026,7 +1026,7 @@ int madicp_tree_build_begin(madicp_ctx* ctx, const double* xyz, int64_t n, doubl
   // cliff (0.67 ms per frame in one process configuration, 1.5 in the others) is the two kernel sets fighting for the CUs;
   // measured: it is not — with the construction strictly behind the registration the other configurations stay at 1.5-2.1 ms
   // (profiles/r5_lookahead_matrix.md).
-  if (ctx->build_after_registration) {
+  if (ctx->opt.build_after_registration) {
     if (!ctx->ev_build_gate) CLOUD_TRY(hipEventCreateWithFlags(&ctx->ev_build_gate, hipEventDisableTiming));
     CLOUD_TRY(hipEventRecord(ctx->ev_build_gate, ctx->stream));
     CLOUD_TRY(hipStreamWaitEvent(s, ctx->ev_build_gate, 0));

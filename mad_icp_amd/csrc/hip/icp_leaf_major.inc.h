@@ -9,7 +9,7 @@
 // which 0.1-10 % of the pairs walk costs 150-300 us, because a wavefront that holds ONE walker waits out a whole descent.
 //
 // Here the launch geometry gives every workgroup ONE range of the scan's leaves and ALL the trees of its XCD piece
-// (ranges_per_tree = workgroups per piece, pick_geometry), and the loops are turned inside out:
+// (ranges_per_tree = workgroups per piece, make_plan), and the loops are turned inside out:
 //     for every pass of 768 leaves:  p, |p|, q = X p ONCE;  for every tree of the piece:  cached correspondence (12 B, the
 //     loads of four trees in flight together) -> reuse test -> gate reuse or leaf record, gate, e, J, accumulation
 // so the moving leaf is read and transformed once per 8 trees (32 + 18 flops -> 4 B + 2 flops per pair at 64 keyframes), and

@@ -31,16 +31,11 @@
 #include <stdint.h>
 
 #include "madicp_hip.h"
+#include "../common/launch_plan.h"  // kBlock, kAcc, the join / exchange-row / DEEP constants: what the host's planning shares
 
 #pragma clang fp contract(off)
 
 namespace madicp {
-
-constexpr int kBlock = 768;          // threads per icp_round workgroup = 12 wave64 = 3 per SIMD: ONE workgroup per CU
-constexpr int kWaves = kBlock / 64;
-constexpr int kAcc = 30;             // 21 (lower triangle of H, column by column) + 6 (b) + accepted pairs + nodes visited
-                                     // (the reference's count: cached depths included) + nodes actually walked this round;
-                                     // 30 doubles = 240 B: partial rows are 16-byte aligned
 
 
 // 16-byte screening record of one node, same index as the exact 64-byte madicp_node.
@@ -119,9 +114,7 @@ struct TreeDesc {
 // right child's is x + 2y - 1), y = leaves of the left sub-tree, z = leaf ordinal of the entry's left-most leaf (so the
 // running ordinal is not carried through these levels: it is z, plus y when the walk leaves to the right), w = the
 // entry's level (the depth is not counted either: it is w + 1).
-constexpr int kTopLevels = 11;
-constexpr int kTopMax = 2048;
-constexpr int kTopLdsBytes = kTopMax * (16 + 16);
+constexpr int kTopLevels = 11;  // (kTopMax, kTopLdsBytes: launch_plan.h)
 constexpr unsigned int kTopNone = 0x7ffu, kTopLeftLeaf = 1u << 22, kTopRightLeaf = 1u << 23;
 __host__ __device__ __forceinline__ unsigned int top_link_word(int left_entry, int right_entry, bool l_leaf, bool r_leaf) {
   return (left_entry < 0 ? kTopNone : (unsigned int)left_entry) | ((right_entry < 0 ? kTopNone : (unsigned int)right_entry) << 11) |
@@ -368,8 +361,7 @@ constexpr int kCacheMaxDepth = 63;
 // DEEP launches (a batch shares the chip) and their leaf-major rounds (icp_leaf_major.inc.h): ranges of at least
 // kQueueMinPasses passes; at most kDeepTrees trees per workgroup and 64 passes per range (a queue entry is pass | tree | lane in
 // 16 bits); kQueueCap queued walkers per wavefront before the queue is walked
-constexpr int kQueueMinPasses = 2;
-constexpr int kDeepTreesLog2 = 4, kDeepTrees = 1 << kDeepTreesLog2;
+// (kQueueMinPasses, kDeepTrees: launch_plan.h)
 constexpr int kDeepPasses = 64;
 constexpr int kQueueCap = 1024;
 constexpr int kEvalCap = 128;  // queued evaluations per wavefront: flushed 64 at a time as soon as 64 are there, a (pass, tree) adds at most 64
@@ -1228,11 +1220,7 @@ __device__ __forceinline__ void solve_pose(const double* total, const double (&X
 // Split in issue (loads in flight) / stage 1 (ends with the workgroup barrier) / stage 2 (wave 0), so that the
 // caller can overlap the memory round trip with other work.  Readable one double past the last row (c = 14 loads
 // columns 28 and "29"): the host pads.
-constexpr int kJoinGroups = 4 * kWaves;  // 48
-constexpr int kJoinRows = 6;             // rows per lane held in registers (nblocks <= 288); longer ones stream
-__host__ __device__ constexpr int join_rows(int nblocks) {
-  return (nblocks <= kJoinGroups * kJoinRows) ? kJoinGroups * kJoinRows : (nblocks + kJoinGroups - 1) / kJoinGroups * kJoinGroups;
-}
+// (kJoinGroups = 48, kJoinRows = 6 rows per lane held in registers, join_rows: launch_plan.h)
 typedef double vd2u __attribute__((ext_vector_type(2), aligned(8)));
 typedef const __attribute__((address_space(1))) vd2u* gptr_d2u;
 typedef double JoinSeg[kJoinGroups][30];
@@ -1276,7 +1264,7 @@ __device__ __forceinline__ void join_stage1(const double* __restrict__ partials,
 //     F[x]    = seg[x] + seg[x + 8] + ... + seg[x + 40]           x = 0..7           (the fold of one XCD's rows)
 //     total   = F[0] + F[1] + ... + F[7]
 // — 14 dependent additions here instead of 47, and the two levels are what icp_persist's XCD leaders / consumers compute.
-constexpr int kFoldGroups = 8;                          // row & 7
+// (kFoldGroups = 8, row & 7: launch_plan.h)
 constexpr int kFoldChains = kJoinGroups / kFoldGroups;  // 6 interleaved chains per group
 __device__ __forceinline__ void join_stage2_wave0(const JoinSeg& seg, double* total /*LDS kAcc*/) {
   if (threadIdx.x < kAcc) {
@@ -1323,11 +1311,7 @@ __device__ unsigned long long g_stamps[16 * 256 * 16];
 
 // exchange granules (icp_persist, and icp_round's FOLD variant): see icp_persist for the protocol
 typedef __attribute__((address_space(1))) unsigned long long* gptr_g64;
-constexpr int kRowGranules = 2 * kAcc;  // 480 bytes per row
-__host__ __device__ constexpr size_t xch_level1(int n_scans, int grid) { return (size_t)2 * n_scans * grid * kRowGranules; }
-__host__ __device__ constexpr size_t xch_granules(int n_scans, int grid) {
-  return xch_level1(n_scans, grid) + (size_t)2 * n_scans * kFoldGroups * kRowGranules;
-}
+// (kRowGranules, xch_level1, xch_granules: launch_plan.h)
 __device__ __forceinline__ void granule_store(gptr_g64 g, unsigned tag, double v) {
   const unsigned long long t = (unsigned long long)tag << 32;
   __hip_atomic_store(g, t | (unsigned)__double2loint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1371,7 +1355,7 @@ __host__ __device__ constexpr size_t p2p_row(int slot, int scan, int q) {
 // rank matched it, pipeline.cpp:197-204), 32 flags per tagged 8-byte word, one row per (registration parity, scan, sending
 // rank).  Two parities are enough: no rank can finish registration e + 1 before every rank has started its icp_final — i.e.
 // has left registration e's behind, flags read — so a row of parity e & 1 is never rewritten (by e + 2) while it is still unread.
-constexpr int kP2pFlagLeaves = 131072;  // moving sets beyond this OR their flags through the communicator, as before
+// (kP2pFlagLeaves, beyond which moving sets OR their flags through the communicator as before: launch_plan.h)
 constexpr int kP2pFlagWords = kP2pFlagLeaves / 32;
 __host__ __device__ constexpr size_t p2p_flag_row(int parity, int scan, int q) {
   return kP2pSumWords + (((size_t)parity * MADICP_MAX_BATCH + (size_t)scan) * kMaxRanks + (size_t)q) * kP2pFlagWords;
@@ -1512,7 +1496,7 @@ __device__ __forceinline__ bool p2p_flags_join(const PeerBox& pb, unsigned epoch
 // all its threads, stage 2 by wave 0: the bits of icp_reduce) and resets the ticket.  `totals` (the reduced sums of the
 // PREVIOUS round, read in the prologue) and `totals_out` are the two parity halves of one buffer, never the same memory.
 // QUEUE (= DEEP): the variant with the leaf-major rounds compiled in (icp_leaf_major.inc.h) — launched only for the geometry
-// they are for (a batch sharing the chip: pick_geometry); code of that size in the one-scan kernel costs its launch 0.45 us
+// they are for (a batch sharing the chip: make_plan); code of that size in the one-scan kernel costs its launch 0.45 us
 // by its mere presence (measured with the first form of the queue, profiles/r5_e_ab.md)
 // P2P (multi-GPU, option "shard_p2p"): the join over the ranks happens INSIDE the prologue, over the peer-mapped mailboxes
 // (p2p_exchange above) — the launch sequence of a sharded registration is then the single-GPU one.

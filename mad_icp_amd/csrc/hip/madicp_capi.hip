@@ -26,7 +26,6 @@
 #include <memory>
 #include <string>
 #include <thread>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -124,21 +123,6 @@ struct DevMoving {
   unsigned long long copy_seq = 0;  // `ready` is the copy_seq-th event recorded on the copy stream for a moving set
 };
 
-struct GraphKey {  // everything a captured launch sequence bakes in
-  int grid, batch, iters, qpt, comm, lds, K, rpt, trace, slot, persist;  // persist: 0 per-round launches, 1 icp_persist, 2 xcd_fold
-  bool operator<(const GraphKey& o) const {
-    return std::tie(grid, batch, iters, qpt, comm, lds, K, rpt, trace, slot, persist) <
-           std::tie(o.grid, o.batch, o.iters, o.qpt, o.comm, o.lds, o.K, o.rpt, o.trace, o.slot, o.persist);
-  }
-};
-struct Geometry {
-  int grid;             // workgroups per scan (multiple of 8)
-  int ranges_per_tree;  // units per tree
-  int qpt;              // leaves a lane walks at once: 1, 2 or 4
-  int lds_bytes;        // dynamic LDS of the launch: kTopLdsBytes when units are big enough to stage a tree's top, else 0
-  int queue;            // 1: units are long enough for queued walks (the QUEUE instantiation of icp_round is launched)
-};
-
 // one streamed registration in flight (madicp_stream_submit .. madicp_stream_collect)
 struct StreamSlot {
   int moving_id = -1;       // a DevMoving owned by this slot
@@ -199,7 +183,6 @@ struct madicp_ctx {
   unsigned int* d_tickets = nullptr;  // [MADICP_MAX_BATCH]: arrival counters of icp_round's TAIL variant (zero between launches)
   hipStream_t stream2 = nullptr;      // second half of a sharded batch (option "shard_split"); created on first use
   hipStream_t pub = nullptr;          // streamed registrations: icp_publish carries results to the host beside the next registration
-  int publish_side = 1;               // option "publish_side"
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   unsigned long long* d_xch = nullptr;  // icp_persist's exchange granules (kernels.hip.h), sized for every admissible geometry
   uint32_t epoch = 0;          // one per enqueued registration: Job::epoch
@@ -217,45 +200,8 @@ struct madicp_ctx {
   StreamSlot slots[kStreamSlots];
   int next_ticket = 0;
 
-  // options
-  int blocks_per_cu = 1;  // icp_round workgroups (768 threads) per CU
-  int deal_trees = 2;     // a Job lists the caller's trees dealt over the eight XCD pieces, rows of eight in alternating direction (fill_job)
-  int units_per_wg = 1;   // when a scan has more trees than workgroups: cut every tree's leaves into enough ranges for at least
-                          // this many (tree, range) units per workgroup (see pick_geometry)
-  int use_graph = 1;
-  int comm_graph = 0;     // capture the RCCL calls too (off: rounds are launched eagerly with a communicator)
-  int qpt_override = 0;
-  int cache_corr = 1;  // reuse correspondences across GN rounds when provably unchanged
-  int deep_min_leaves = 512;  // option "deep_min_leaves": with 24 keyframes or more and two scans in flight (48 or more and one), a launch with
-                         // more trees than workgroups per XCD piece is DEEP (one range x all the piece's trees per workgroup) when a range
-                         // holds at least this many leaves (pick_geometry)
-  int interleave = 2;    // option "interleave_ranges": a range is every RPT-th group of 64 leaves instead of a contiguous stretch of the
-                         // scan (kernels.hip.h, "Ranges"): 0 never, 1 DEEP launches (a batch shares the chip), 2 every launch
-  int cache_gate = 1;   // option "cache_gate": a pair that keeps its leaf and was rejected with more slack than it has moved since is
-                        // not evaluated again (kernels.hip.h, "Gate reuse")
-  int queue_walks = 8192; // option "leaf_major": a DEEP launch (a batch shares the chip) runs a round leaf-major — moving leaf once per
-                        // pass for all the workgroup's trees, walkers queued and walked densely — when the workgroup walked fewer
-                        // than this many nodes per pass in the previous round (0: never; icp_leaf_major.inc.h)
-  int nn_lds_top = 0;  // option "nn_lds_top": nn_search batches of >= 16 k queries walk the tree's top levels from LDS
-                       // (nn_descend_top).  Off: measured SLOWER for one 120 k-query launch (8.7 vs 6.6 us against a
-                       // 20 k-leaf tree, 10.7 vs 9.2 us against a 120 k-leaf tree) — staging 48 KiB per workgroup costs
-                       // more than the ~11 LDS levels save in a kernel this short
-  int eager_when_busy = 1; // a registration queued behind another is launched kernel by kernel, not as a graph (run_rounds)
-  int seq_completion = 1;  // streamed registrations publish completion through HostResult::seq instead of an event
-  int host_feed_wait = 1;  // ... and the host, not the stream, waits for their feed while another one is in flight
-  int match_all = 0;       // option "match_all_rounds": the matched flags a registration returns are the OR over all its rounds
-  int persistent = 0;      // all rounds of a registration as ONE launch (icp_persist) where the geometry admits it
-  int xcd_fold = 0;        // per-round launches whose group leaders fold their XCD's rows at the end of the launch (experiment)
-  int debug_collective_us = 0;  // development: a delay kernel of this length behind every collective (tools/shard_probe.py)
-  int shard_tail = 0;      // sharded rounds leave the rank's adders themselves (icp_round's TAIL variant) instead of an icp_reduce
-                           // launch.  Off: built, bit-identical, measured SLOWER (profiles/r4_c_shard_probe.md: the 256 tickets
-                           // on one address and the cross-XCD read of the rows cost ~8 us at the end of every round; the
-                           // separate icp_reduce launch costs 4.5 us and no gap)
-  int build_after_registration = 0;  // option (experiment, default off): a look-ahead construction's kernels wait for the registration in
-                                     // flight (frontend_capi.inc.h; measured: does not remove the look-ahead cliff, profiles/r5_lookahead_matrix.md)
+  Options opt;  // every tunable (launch_plan.h); written by madicp_ctx_set_option alone
   hipEvent_t ev_build_gate = nullptr;
-  int shard_p2p = 0;       // sharded rounds join over peer-mapped mailboxes inside the round kernel (madicp_p2p_attach) instead
-                           // of icp_reduce + a collective between two rounds
   unsigned long long* p2p_box = nullptr;                  // this rank's mailbox (kP2pBoxWords; fine-grained device memory)
   unsigned long long* p2p_peer[madicp::kMaxRanks] = {};   // every rank's mailbox as mapped here ([rank] = p2p_box)
   bool p2p_opened[madicp::kMaxRanks] = {};                // ... opened through hipIpcOpenMemHandle (to be closed)
@@ -265,15 +211,13 @@ struct madicp_ctx {
   bool p2p_broken = false;   // a registration of this mailbox session lost a peer: the ranks' counters may disagree from here on
   void* d_f32[2] = {nullptr, nullptr};  // device landing blocks of float uploads, one per pinned staging block (h_tree)
   size_t d_f32_cap[2] = {0, 0};
-  int upload_f32 = 1;        // option "upload_f32": a cloud of float-exact coordinates crosses PCIe as floats (frontend_capi.inc.h)
-  int p2p_allow_coarse = 0;  // option "p2p_allow_coarse": accept a coarse-grained mailbox (ranks that share ONE device only)
   unsigned int p2p_epoch = 0;                             // sharded registrations so far (the same count on every rank)
-  int shard_split = 1;     // a sharded batch of >= 4 scans runs as two halves on two streams: one half's all-reduce under the
-                           // other half's round (profiles/r4_c_shard_probe.md: -14 % per registration at 8 scans with a 15 us
-                           // collective; a loss without one, and with halves of one scan)
-  int stage_min_leaves = 1024;  // LDS staging threshold (leaves per unit); 0 = always, huge = never (measured break-even ~1000)
 
-  std::map<GraphKey, hipGraphExec_t> graphs;
+  std::map<GraphKey, hipGraphExec_t> graphs;  // captured launch sequences, by everything they bake in
+  void drop_graphs() {
+    for (auto& g : graphs) hipGraphExecDestroy(g.second);
+    graphs.clear();
+  }
 
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // measurement entry points
 
@@ -284,12 +228,8 @@ struct madicp_ctx {
   char* h_comm = nullptr;       // pinned staging of the host transport (grow-only)
   size_t h_comm_cap = 0;
   int n_ranks = 1, rank = 0;
-  int comm_timeout_ms = 60000;  // bounded host wait behind a registration's collectives
   bool sharded() const { return comm != nullptr || host_ar != nullptr; }
-
-  // how the host waits for a sequence number the device publishes (stream_collect, tree_build)
-  int wait_mode = 0;        // 0 spin, 1 sched_yield, 2 sleep ~50 us
-  int wait_timeout_ms = 0;  // 0: unbounded
+  PlanEnv env() const { return PlanEnv{n_cus, comm != nullptr, host_ar != nullptr, p2p_attached, n_ranks}; }  // what make_plan sees
 
   // device front-end (frontend_capi.inc.h): resident clouds + builder scratch, created on first use
   struct Front;
@@ -384,16 +324,15 @@ int ensure_partials(madicp_ctx* ctx, size_t doubles) {
   ctx->partials_cap = doubles;
   ctx->partials_key = -1;
   // cached graphs hold the old pointer
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-  ctx->graphs.clear();
+  ctx->drop_graphs();
   return MADICP_OK;
 }
 
 // one poll of a host wait loop, by option "wait_mode"
 inline void wait_pause(const madicp_ctx* ctx) {
-  if (ctx->wait_mode == 1)
+  if (ctx->opt.wait_mode == 1)
     sched_yield();
-  else if (ctx->wait_mode == 2)
+  else if (ctx->opt.wait_mode == 2)
     std::this_thread::sleep_for(std::chrono::microseconds(50));
   else
     __builtin_ia32_pause();
@@ -402,8 +341,7 @@ inline void wait_pause(const madicp_ctx* ctx) {
 // A collective that will not complete: the communicator is aborted (which releases the kernels parked on the stream), the
 // graphs that captured its calls are dropped, the context falls back to one rank.  Always MADICP_ERR_COMM.
 int comm_abort(madicp_ctx* ctx, const std::string& why) {
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-  ctx->graphs.clear();
+  ctx->drop_graphs();
   if (ctx->comm) ncclCommAbort(ctx->comm);
   ctx->comm = nullptr;
   ctx->n_ranks = 1;
@@ -428,9 +366,9 @@ int bounded_sync(madicp_ctx* ctx, hipStream_t s) {
       ncclResult_t ar = ncclSuccess;
       const bool bad = ncclCommGetAsyncError(ctx->comm, &ar) == ncclSuccess && ar != ncclSuccess && ar != ncclInProgress;
       const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-      if (bad || ms > ctx->comm_timeout_ms)
+      if (bad || ms > ctx->opt.comm_timeout_ms)
         return comm_abort(ctx, bad ? std::string("RCCL asynchronous error: ") + ncclGetErrorString(ar)
-                                   : "a collective did not complete within " + std::to_string(ctx->comm_timeout_ms) +
+                                   : "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) +
                                          " ms (a rank did not join?)");
     }
     if (spins < 256)
@@ -448,8 +386,8 @@ int all_reduce(madicp_ctx* ctx, void* d_buf, size_t count, int kind, hipStream_t
       NCCL_TRY(ncclAllReduce(d_buf, d_buf, count, ncclDouble, ncclSum, ctx->comm, s));
     else
       NCCL_TRY(ncclAllReduce(d_buf, d_buf, count, ncclUint8, ncclMax, ctx->comm, s));
-    if (ctx->debug_collective_us > 0)  // (development: a one-rank all-reduce launches nothing — stand in for its latency)
-      hipLaunchKernelGGL(debug_delay, dim3(1), dim3(64), 0, s, (unsigned long long)ctx->debug_collective_us * 100ull);
+    if (ctx->opt.debug_collective_us > 0)  // (development: a one-rank all-reduce launches nothing — stand in for its latency)
+      hipLaunchKernelGGL(debug_delay, dim3(1), dim3(64), 0, s, (unsigned long long)ctx->opt.debug_collective_us * 100ull);
     return MADICP_OK;
   }
   const size_t bytes = count * (kind == MADICP_REDUCE_SUM_F64 ? sizeof(double) : 1);
@@ -470,63 +408,13 @@ int all_reduce(madicp_ctx* ctx, void* d_buf, size_t count, int kind, hipStream_t
   return MADICP_OK;
 }
 
-// launch geometry: 8 XCDs x slots workgroups per scan, about blocks_per_cu * n_cus in total over the batch, and
-// one (tree, range) unit per workgroup so that every workgroup gets the same number of leaves
-Geometry pick_geometry(const madicp_ctx* ctx, int max_L, int K, int batch) {
-  Geometry g;
-  // One 768-thread workgroup per CU (3 waves per SIMD is what the kernel's registers allow), one (tree, range) unit
-  // per workgroup; a batch shares the CUs between its scans.  One leaf per lane and pass by default (two leaves per
-  // lane share their loads but were not measured faster).
-  g.qpt = ctx->qpt_override == 2 ? 2 : 1;
-  long long grid = std::max<long long>(8, (long long)ctx->blocks_per_cu * ctx->n_cus / std::max(1, batch));
-  const long long max_useful = (long long)std::max(1, K) * ((max_L + 63) / 64);  // never below one wave of leaves per unit
-  grid = std::max<long long>(8, std::min(grid, max_useful) / 8 * 8);
-  g.grid = static_cast<int>(grid);
-  g.ranges_per_tree = static_cast<int>(std::max<long long>(1, grid / std::max(1, K)));
-  if (ctx->units_per_wg > 1 && K > 0) {
-    // More trees than workgroups (a batch shares the chip): with one range per tree a workgroup owns whole trees, and trees
-    // differ in cost (how many of the scan's leaves still have to walk them, how many match) — the launch waits for the
-    // workgroup with the expensive ones.  Finer ranges give every workgroup of an XCD piece a slice of ALL the piece's trees.
-    const long long want = ((long long)ctx->units_per_wg * grid + K - 1) / K;
-    const long long cap = std::max<long long>(1, max_L / 256);  // (a range of fewer than 256 leaves is not worth a descriptor)
-    g.ranges_per_tree = static_cast<int>(std::max<long long>(g.ranges_per_tree, std::min(want, cap)));
-  }
-  // DEEP launches: more trees than workgroups per XCD piece (a batch shares the chip).  Every workgroup then gets ONE range
-  // of the scan and ALL the trees of its piece — ranges_per_tree = workgroups per piece, so that its units u_first, u_first +
-  // nslots, ... are the same range of consecutive trees — which is what the leaf-major rounds need (icp_leaf_major.inc.h)
-  const int nslots = g.grid / 8;
-  // (how many leaves a range must hold for that: two passes of a workgroup — below, the leaf-major queue has nothing to compact —
-  // unless the piece holds three trees or more: then one unit per workgroup means the launch waits for the workgroups that drew
-  // the newest keyframes, and one range of ALL the piece's trees per workgroup pays from 512 leaves on; measured,
-  // profiles/r6_deep_threshold.md: 24-64 keyframes x 1-2 scans in flight + 3 .. + 40 %, 16 keyframes - 9 %)
-  // (one scan in flight against 24-47 keyframes stays as it was: - 2 .. - 4 % that way at 32 keyframes, + 3 % at 24)
-  const bool small_ranges_pay = K >= 24 && (batch >= 2 || K >= 48);
-  const int deep_min = small_ranges_pay ? ctx->deep_min_leaves : std::max(ctx->deep_min_leaves, madicp::kQueueMinPasses * madicp::kBlock);
-  if (K >= 8 && ctx->queue_walks > 0 && g.qpt == 1 && g.ranges_per_tree < nslots &&
-      max_L / nslots >= deep_min && (K + 7) / 8 + 1 <= madicp::kDeepTrees)
-    g.ranges_per_tree = nslots;
-  const int per_range = (max_L + g.ranges_per_tree - 1) / g.ranges_per_tree;
-  g.lds_bytes = (K > 0 && per_range >= ctx->stage_min_leaves) ? kTopLdsBytes : 0;
-  g.queue = (K >= 8 && ctx->queue_walks > 0 && g.qpt == 1 && g.ranges_per_tree == nslots &&
-             per_range >= deep_min) ? 1 : 0;
-  return g;
+// the share of a Job that its registration's plan decides (launch_plan.h: made once, read by everything below)
+void plan_job(const madicp_ctx* ctx, const Plan& pl, Job& j) {
+  j.ranges_per_tree = pl.rpt;
+  if (pl.interleave) j.flags |= kFlagInterleave;
+  j.stage_min_leaves = ctx->opt.stage_min_leaves;
+  j.lds_top = pl.lds ? 1 : 0;
 }
-
-struct Launch {  // one registration's launch shape
-  int grid, batch, iters, qpt, lds, K, rpt, trace, queue;
-};
-
-constexpr size_t kXchRowsMax = 1024 + 8 * MADICP_MAX_BATCH;  // level-1 rows + level-2 rows of the largest admissible launch
-
-// May this registration run as ONE launch?  icp_persist needs every workgroup resident at once (one 768-thread workgroup
-// per CU is all a CU holds), no collective between rounds, and tags of 8 bits of round.
-bool use_persist(const madicp_ctx* ctx, const Launch& l) {
-  return ctx->persistent && !ctx->sharded() && !l.trace && l.iters >= 2 && l.iters <= 250 && ctx->blocks_per_cu == 1 &&
-         (long long)l.grid * l.batch <= ctx->n_cus && (l.grid >> 3) <= kJoinGroups && l.K >= 1 &&
-         madicp::xch_granules(l.batch, l.grid) <= kXchRowsMax * 2 * madicp::kRowGranules;
-}
-
-bool use_fold(const madicp_ctx* ctx, const Launch& l);
 
 // Where a launch sequence runs and which scratch it owns.  A registration is one part on the compute stream with the
 // context's buffers; a sharded batch split in two halves (option "shard_split") is two parts with disjoint regions of the
@@ -552,26 +440,6 @@ Part whole_part(madicp_ctx* ctx, Job* d_jobs) {
   return p;
 }
 
-// sharded rounds that leave the rank's adders themselves: the TAIL variant of icp_round publishes rows as exchange granules
-bool use_tail(const madicp_ctx* ctx, const Launch& l) {
-  return ctx->sharded() && ctx->shard_tail && !l.trace && l.qpt == 1 && l.iters <= 250 &&
-         madicp::xch_level1(l.batch, l.grid) <= kXchRowsMax * 2 * madicp::kRowGranules;
-}
-
-// sharded rounds that join over the peer-mapped mailboxes inside the round kernel (option "shard_p2p", madicp_p2p_attach)
-bool use_p2p(const madicp_ctx* ctx, const Launch& l) {
-  return ctx->sharded() && ctx->shard_p2p && ctx->p2p_attached && !l.trace && l.qpt == 1 && l.iters <= 250;
-}
-// ... and whose matched flags travel over the mailboxes too (icp_final): the whole registration is then free of collectives —
-// the single-GPU launch sequence, capturable, results out through the side stream.  Every scan's leaves must fit a flag row
-// (every rank holds the same moving sets, so every rank decides the same way).
-bool p2p_flags_fit(const madicp_ctx* ctx, const int* moving_ids, int n) {
-  for (int s = 0; s < n; ++s) {
-    auto it = ctx->movings.find(moving_ids[s]);
-    if (it == ctx->movings.end() || it->second.L > madicp::kP2pFlagLeaves) return false;
-  }
-  return true;
-}
 madicp::PeerBox peer_box(const madicp_ctx* ctx, int scan0, bool on, bool flags_in_box = false) {
   madicp::PeerBox pb{};
   if (!on) return pb;  // (n_ranks = 0: not a mailbox launch)
@@ -580,16 +448,16 @@ madicp::PeerBox peer_box(const madicp_ctx* ctx, int scan0, bool on, bool flags_i
   pb.rank = ctx->rank;
   pb.flags_in_box = flags_in_box ? 1 : 0;
   pb.scan0 = scan0;
-  pb.spin_ticks = (unsigned long long)std::max(1, ctx->comm_timeout_ms) * 100000ull;  // 100 MHz ticks
+  pb.spin_ticks = (unsigned long long)std::max(1, ctx->opt.comm_timeout_ms) * 100000ull;  // 100 MHz ticks
   return pb;
 }
 
 // The registration counter of the mailbox session: every rank submits the same sequence of sharded registrations, so every
 // rank's counter names the same registration — it tags the rows and picks their slot.  Taken once per registration (all scans of
 // a batch), after every check that can refuse the submission and right before the Jobs are uploaded.
-int next_p2p_epoch(madicp_ctx* ctx, const Launch& l, unsigned* out) {
+int next_p2p_epoch(madicp_ctx* ctx, const Plan& pl, unsigned* out) {
   *out = 0;
-  if (!use_p2p(ctx, l)) return MADICP_OK;
+  if (pl.route != Route::P2p) return MADICP_OK;
   if (ctx->p2p_broken)
     return fail(MADICP_ERR_COMM, "this mailbox session lost a peer in an earlier registration: the ranks' registration counters may "
                                  "disagree — madicp_p2p_export + madicp_p2p_attach again on every rank (or switch shard_p2p off)");
@@ -597,61 +465,46 @@ int next_p2p_epoch(madicp_ctx* ctx, const Launch& l, unsigned* out) {
   return MADICP_OK;
 }
 
-void launch_round(madicp_ctx* ctx, const Launch& l, const Part& p, int round, const double* totals) {
-  dim3 g(l.grid, l.batch), b(kBlock);
-  const madicp::PeerBox none{};
-  if (use_p2p(ctx, l)) {
-    const madicp::PeerBox pb = peer_box(ctx, p.scan0, true);
-    if (l.queue)
-      hipLaunchKernelGGL((icp_round<1, false, false, false, true, true>), g, b, l.lds, p.s, (const Job*)p.jobs, p.jobs, p.partials,
-                         (const double*)nullptr, round, l.iters, l.K, l.rpt, p.xch, (double*)nullptr, (unsigned int*)nullptr, pb);
-    else
-      hipLaunchKernelGGL((icp_round<1, false, false, false, false, true>), g, b, l.lds, p.s, (const Job*)p.jobs, p.jobs, p.partials,
-                         (const double*)nullptr, round, l.iters, l.K, l.rpt, p.xch, (double*)nullptr, (unsigned int*)nullptr, pb);
-    return;
-  }
-  if (use_tail(ctx, l)) {
-    hipLaunchKernelGGL((icp_round<1, false, false, true>), g, b, l.lds, p.s, (const Job*)p.jobs, p.jobs, p.partials, totals, round,
-                       l.iters, l.K, l.rpt, p.xch, p.totals[round & 1], p.tickets, none);
-    return;
-  }
+void launch_round(madicp_ctx* ctx, const Plan& l, const Part& p, int round, const double* totals) {
   void (*kern)(const Job*, Job*, double*, const double*, int, int, int, int, unsigned long long*, double*, unsigned int*,
-               const madicp::PeerBox) =
-      l.trace ? (l.qpt == 2 ? icp_round<2, true> : icp_round<1, true>) : (l.qpt == 2 ? icp_round<2, false> : icp_round<1, false>);
-  if (use_fold(ctx, l)) kern = icp_round<1, false, true>;
-  else if (l.queue && !l.trace && l.qpt == 1) kern = icp_round<1, false, false, false, true>;  // units of many passes: queued walks
-  hipLaunchKernelGGL(kern, g, b, l.lds, p.s, (const Job*)p.jobs, p.jobs, p.partials, totals, round, l.iters, l.K, l.rpt, p.xch,
-                     (double*)nullptr, (unsigned int*)nullptr, none);
-}
-
-// (experiment, option "xcd_fold") per-round launches with the XCD-hierarchical join: same admission rules as icp_persist
-// except residency — the leaders only wait for workgroups of their own launch, which all run to completion
-bool use_fold(const madicp_ctx* ctx, const Launch& l) {
-  return ctx->xcd_fold && !ctx->persistent && !ctx->sharded() && !l.trace && l.qpt == 1 && l.iters >= 2 && l.iters <= 250 &&
-         (l.grid >> 3) <= kJoinGroups && l.K >= 1 &&
-         madicp::xch_granules(l.batch, l.grid) <= kXchRowsMax * 2 * madicp::kRowGranules;
+               const madicp::PeerBox) = nullptr;
+  switch (l.route) {
+    case Route::P2p: kern = l.queue ? icp_round<1, false, false, false, true, true> : icp_round<1, false, false, false, false, true>; break;
+    case Route::Tail: kern = icp_round<1, false, false, true>; break;
+    case Route::Fold: kern = icp_round<1, false, true>; break;
+    case Route::Rounds:
+    case Route::Persist:  // (a persistent registration's rounds are one icp_persist launch: only the measurement build asks here)
+      if (l.trace) kern = l.qpt == 2 ? icp_round<2, true> : icp_round<1, true>;
+      else if (l.qpt == 2) kern = icp_round<2, false>;
+      else kern = l.queue ? icp_round<1, false, false, false, true> : icp_round<1, false>;  // units of many passes: queued walks
+      break;
+  }
+  // only the TAIL variant leaves totals and counts tickets; only the mailbox variant gets a PeerBox (and no totals: it joins itself)
+  const bool p2p = l.route == Route::P2p, tail = l.route == Route::Tail;
+  hipLaunchKernelGGL(kern, dim3(l.grid, l.batch), dim3(kBlock), l.lds, p.s, (const Job*)p.jobs, p.jobs, p.partials,
+                     p2p ? (const double*)nullptr : totals, round, l.iters, l.K, l.rpt, p.xch, tail ? p.totals[round & 1] : (double*)nullptr,
+                     tail ? p.tickets : (unsigned int*)nullptr, peer_box(ctx, p.scan0, p2p));
 }
 
 // one round of a part, and what a sharded round needs behind it: this rank's share of the adders (a rank that owns no tree
 // contributes zeros) -> one all-reduce of [H(21) b(6) n v w] per scan over xGMI: the serial sum of mad_icp.cpp:106-109
-int enqueue_round(madicp_ctx* ctx, const Launch& l, const Part& p, int it) {
-  if (use_p2p(ctx, l)) {  // the join over the ranks is inside the round kernel's prologue: the single-GPU launch sequence
+int enqueue_round(madicp_ctx* ctx, const Plan& l, const Part& p, int it) {
+  if (l.route == Route::P2p) {  // the join over the ranks is inside the round kernel's prologue: the single-GPU launch sequence
     launch_round(ctx, l, p, it, nullptr);
     return MADICP_OK;
   }
   launch_round(ctx, l, p, it, (ctx->sharded() && it > 0) ? p.totals[(it - 1) & 1] : nullptr);
   if (ctx->sharded()) {
-    if (!use_tail(ctx, l))
+    if (l.route != Route::Tail)
       hipLaunchKernelGGL(icp_reduce, dim3(l.batch), dim3(kBlock), 0, p.s, p.partials, l.grid, l.batch, it, p.totals[it & 1]);
     RC_TRY(all_reduce(ctx, p.totals[it & 1], (size_t)l.batch * kAcc, MADICP_REDUCE_SUM_F64, p.s));
   }
   return MADICP_OK;
 }
 // what closes a part: the matched flags OR-ed over the ranks, then icp_final
-int enqueue_close(madicp_ctx* ctx, const Launch& l, const Part& p, const int* moving_ids) {
-  const bool p2p = use_p2p(ctx, l);
-  const bool box_flags = p2p && p2p_flags_fit(ctx, moving_ids, l.batch);  // (icp_final ORs them over the mailboxes itself)
-  if (ctx->sharded() && !box_flags) {
+int enqueue_close(madicp_ctx* ctx, const Plan& l, const Part& p, const int* moving_ids) {
+  const bool p2p = l.route == Route::P2p;
+  if (ctx->sharded() && !l.flags_in_box) {  // (in the box: icp_final ORs them over the mailboxes itself)
     // a leaf is an inlier if ANY keyframe on ANY rank matched it (mad_icp.cpp:85, pipeline.cpp:197-204): the scans' flag
     // arrays as ONE grouped RCCL operation (one launch for the batch, not one per scan)
     if (ctx->comm && l.batch > 1) NCCL_TRY(ncclGroupStart());
@@ -666,16 +519,16 @@ int enqueue_close(madicp_ctx* ctx, const Launch& l, const Part& p, const int* mo
   // (icp_reduce / icp_final join with kBlock threads, like icp_round: same summation order with and without ranks)
   hipLaunchKernelGGL(icp_final, dim3(l.batch), dim3(kBlock), 0, p.s, p.jobs, p.partials,
                      (ctx->sharded() && !p2p) ? (const double*)p.totals[(l.iters - 1) & 1] : (const double*)nullptr, l.grid, l.batch,
-                     use_fold(ctx, l) ? (const unsigned long long*)p.xch : (const unsigned long long*)nullptr,
-                     peer_box(ctx, p.scan0, p2p, box_flags));
+                     l.route == Route::Fold ? (const unsigned long long*)p.xch : (const unsigned long long*)nullptr,
+                     peer_box(ctx, p.scan0, p2p, l.flags_in_box));
   HIP_TRY(hipGetLastError());
   return MADICP_OK;
 }
 
 // the launch sequence of one (batched) registration; valid both eagerly and under stream capture
-int enqueue_rounds(madicp_ctx* ctx, const Launch& l, Job* d_jobs, const std::vector<int>& moving_ids) {
+int enqueue_rounds(madicp_ctx* ctx, const Plan& l, Job* d_jobs, const std::vector<int>& moving_ids) {
   const int grid = l.grid, batch = l.batch, iters = l.iters;
-  if (use_persist(ctx, l)) {
+  if (l.route == Route::Persist) {
     dim3 g(grid, batch), b(kBlock);
     void (*kern)(const Job*, Job*, unsigned long long*, int, int, int) = l.qpt == 2 ? icp_persist<2> : icp_persist<1>;
     hipLaunchKernelGGL(kern, g, b, l.lds, ctx->stream, (const Job*)d_jobs, d_jobs, ctx->d_xch, iters, l.K, l.rpt);
@@ -694,7 +547,7 @@ int enqueue_rounds(madicp_ctx* ctx, const Launch& l, Job* d_jobs, const std::vec
 // under the other half's round kernel instead of standing between two rounds of the same scans.  The collectives are
 // enqueued in ONE order on every rank — A(0), B(0), A(1), B(1), ... — so RCCL's per-communicator ordering never
 // deadlocks; each half has its own jobs, exchange rows, totals and tickets.  `l` / `p`: the two halves.
-int enqueue_rounds_split(madicp_ctx* ctx, const Launch l[2], const Part p[2], const int* moving_ids) {
+int enqueue_rounds_split(madicp_ctx* ctx, const Plan l[2], const Part p[2], const int* moving_ids) {
   HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));  // (jobs, moving sets, trees: everything the halves read is behind this)
   HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
   int rc = MADICP_OK;
@@ -709,25 +562,13 @@ int enqueue_rounds_split(madicp_ctx* ctx, const Launch l[2], const Part p[2], co
 }
 
 // slot: which device Job array the sequence works on (-1: ctx->d_jobs; >= 0: that stream slot's) — part of the graph key
-// queued_behind: the stream is known to be busy with an earlier registration.  A graph launch costs the QUEUE ~8 us more
-// than the same kernels launched one by one (markers around the graph: 234 vs 229 us per streamed registration) but costs
-// the HOST less, so a registration that would start at once goes as a graph (its first kernel starts sooner: 300 vs 307 us
-// submit-to-result) and one that has to wait for its predecessor anyway goes kernel by kernel.
-int run_rounds(madicp_ctx* ctx, const Launch& l, Job* d_jobs, int slot, const std::vector<int>& moving_ids, bool queued_behind) {
-  // with a communicator the RCCL calls are captured only on request (option "comm_graph"): it could not be
-  // exercised on more than one rank where this was developed
-  // (a host-staged transport makes a host round trip per round: never capturable)
-  // over the peer mailboxes with the flags in them (p2p_free) nothing of the registration is a collective or a host step: it
-  // is captured like a single-GPU one (the tags come from Job::p2p_epoch, not from a kernel argument)
-  const bool p2p = use_p2p(ctx, l);
-  const bool p2p_free = p2p && p2p_flags_fit(ctx, moving_ids.data(), l.batch);
-  const bool graph_ok = ctx->use_graph && (p2p_free || (!ctx->host_ar && (!ctx->comm || ctx->comm_graph) && !p2p)) &&
-                        !(queued_behind && ctx->eager_when_busy && (!ctx->comm || p2p_free));
-  if (!graph_ok) return enqueue_rounds(ctx, l, d_jobs, moving_ids);
+// queued_behind, allow_graph: see graph_ok (launch_plan.h)
+int run_rounds(madicp_ctx* ctx, const Plan& l, Job* d_jobs, int slot, const std::vector<int>& moving_ids, bool queued_behind,
+               bool allow_graph) {
+  if (!graph_ok(l, ctx->opt, ctx->env(), queued_behind, allow_graph)) return enqueue_rounds(ctx, l, d_jobs, moving_ids);
   // (with a communicator the matched-flag all-reduce bakes the moving buffer's address: key on the slot only — the
   // batch path never takes the graph route with a communicator unless every scan's buffer is stable, see below)
-  const GraphKey key{l.grid, l.batch, l.iters, l.qpt, (ctx->comm ? 1 : 0) + (p2p_free ? 2 : 0), l.lds, l.K, l.rpt, l.trace, slot,
-                     (use_persist(ctx, l) ? 1 : (use_fold(ctx, l) ? 2 : 0)) + 4 * l.queue};
+  const GraphKey key{l, slot, ctx->comm != nullptr};
   auto it = ctx->graphs.find(key);
   if (it == ctx->graphs.end()) {
     auto instantiate = [&](Job* jobs, const GraphKey& k) -> int {
@@ -746,7 +587,7 @@ int run_rounds(madicp_ctx* ctx, const Launch& l, Job* d_jobs, int slot, const st
       ctx->graphs.emplace(k, exec);
       return MADICP_OK;
     };
-    if (slot >= 0 && (!ctx->comm || p2p_free)) {
+    if (slot >= 0 && (!ctx->comm || l.flags_in_box)) {
       // a streamed registration: instantiate this shape for EVERY slot now (a few ms each, once), so that the first
       // lap around the ring costs the same as every later one
       for (int s = 0; s < madicp_ctx::kStreamSlots; ++s) {
@@ -791,10 +632,7 @@ int reserve_moving(madicp_ctx* ctx, DevMoving& m, int L, hipStream_t user) {
   m.xyzn = nullptr; m.matched = nullptr; m.cache_leaf = nullptr; m.cache_margin = nullptr;
   m.cache_cap = 0;
   m.cap_L = 0;
-  if (ctx->sharded()) {  // a captured sequence with collectives bakes the matched-flag buffer's address
-    for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-    ctx->graphs.clear();
-  }
+  if (ctx->sharded()) ctx->drop_graphs();  // a captured sequence with collectives bakes the matched-flag buffer's address
   const int cap = (L + L / 8 + 255) / 256 * 256;  // head-room: consecutive scans differ by a few per cent
   void* p = nullptr;
   RC_TRY(pool_alloc(ctx, sizeof(double) * 4 * (size_t)cap, user, &p));
@@ -890,8 +728,14 @@ struct RegArgs {
   int flags;
   uint32_t* d_corr;     // single-scan debug trace (device) or null
   double* d_x_iters;    // single-scan (device) or null
-  int time_launches = 0;    // > 0: measurement mode, see madicp_icp_time_linearize
-  double* out_avg_us = nullptr;
+  bool allow_graph = true;    // false: launched eagerly whatever option "use_graph" says (pointers in the Job that differ per call)
+  bool measure_only = false;  // staged for the measurement build, which launches it itself: no cache, no split, no mailbox epoch
+};
+// what staging a registration leaves for launching it
+struct Staged {
+  Plan halves[2];  // [0]: the registration, or the first half of a split sharded batch
+  bool split = false;
+  size_t part_doubles[2] = {0, 0};
 };
 
 // A start pose that is not a rigid motion breaks the displacement bound of the correspondence reuse (it assumes
@@ -921,9 +765,9 @@ int fill_job(madicp_ctx* ctx, Job& j, DevMoving& mv, const int* tree_ids, int K,
   j.epoch = ++ctx->epoch;  // (24 bits of it reach the granule tags: a tag recurs after 16 M registrations, far beyond
                            // the life of any granule of a geometry in use)
   j.error = 0;
-  j.flags = flags | ((ctx->cache_corr && is_rigid(X0)) ? 0 : kFlagNoReuse) | (ctx->match_all ? kFlagMatchAll : 0) |
-            (ctx->cache_gate ? 0 : kFlagNoGateReuse);
-  j.queue_nodes = ctx->queue_walks;
+  j.flags = flags | ((ctx->opt.cache_corr && is_rigid(X0)) ? 0 : kFlagNoReuse) | (ctx->opt.match_all ? kFlagMatchAll : 0) |
+            (ctx->opt.cache_gate ? 0 : kFlagNoGateReuse);
+  j.queue_nodes = ctx->opt.queue_walks;
   std::memcpy(j.X, X0, 12 * sizeof(double));
   std::memcpy(j.Xring[0], X0, 12 * sizeof(double));
   std::memcpy(j.Xring[1], X0, 12 * sizeof(double));
@@ -940,10 +784,10 @@ int fill_job(madicp_ctx* ctx, Job& j, DevMoving& mv, const int* tree_ids, int K,
   // quarter every four keyframes at BASELINE configs[4], and round-robin hands piece 7 a tree seven places newer than piece 0's
   // in EVERY row)
   int p = 0;
-  const int cols = ctx->deal_trees ? 8 : 1;
+  const int cols = ctx->opt.deal_trees ? 8 : 1;
   for (int c = 0; c < cols; ++c)
     for (int row = 0; row * cols < K; ++row) {
-      const int k = row * cols + ((ctx->deal_trees == 2 && (row & 1)) ? cols - 1 - c : c);
+      const int k = row * cols + ((ctx->opt.deal_trees == 2 && (row & 1)) ? cols - 1 - c : c);
       if (k >= K) continue;
       auto tit = ctx->trees.find(tree_ids[k]);
       if (tit == ctx->trees.end()) return fail(MADICP_ERR_INVALID, "unknown tree id");
@@ -972,7 +816,7 @@ size_t partial_doubles_of(int grid, int n_scans) {
   return align_up(((size_t)2 * n_scans * prows * kAcc + (size_t)2 * n_scans * grid + kAcc) * sizeof(double)) / sizeof(double);
 }
 // (`parts` launch shapes side by side: the halves of a split sharded batch each own a region; out_doubles[h] = its size)
-int prepare_partials(madicp_ctx* ctx, const Launch* shapes, int parts, size_t* out_doubles) {
+int prepare_partials(madicp_ctx* ctx, const Plan* shapes, int parts, size_t* out_doubles) {
   size_t total = 0;
   long long key = parts;
   for (int h = 0; h < parts; ++h) {
@@ -1004,7 +848,8 @@ void mark_moving_used(madicp_ctx* ctx, const std::vector<int>& ids) {
   }
 }
 
-int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
+// staging: checks, Jobs, plan, partials, the one upload
+int stage_registration(madicp_ctx* ctx, const RegArgs& a, Staged* st) {
   RC_TRY(check_reg_args(ctx, a.moving_ids, a.X0, a.params, a.K, a.n_iters));
   if (a.K > 0 && !a.tree_ids) return fail(MADICP_ERR_INVALID, "null argument");
   if (a.n_scans < 1 || a.n_scans > MADICP_MAX_BATCH) return fail(MADICP_ERR_CAPACITY, "n_scans out of range");
@@ -1017,7 +862,8 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
 
   int max_L = 0;
   ctx->last_moving.assign(a.moving_ids, a.moving_ids + a.n_scans);
-  const bool use_cache = a.n_iters > 1 && !a.time_launches;
+  const bool use_cache = a.n_iters > 1 && !a.measure_only;
+  bool flags_fit = true;  // every scan's leaves fit a mailbox flag row (Plan::flags_in_box)
   {
     // the batch's sets that were made ready on the copy stream: that stream runs in order, so ONE wait — for the set whose
     // event was recorded last — covers them all (a wait per set was a barrier packet each on the compute stream)
@@ -1027,6 +873,7 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
       if (mit == ctx->movings.end()) return fail(MADICP_ERR_INVALID, "unknown moving id");
       DevMoving& mv = mit->second;
       if (mv.on_copy && (!latest || mv.copy_seq > latest->copy_seq)) latest = &mv;
+      flags_fit = flags_fit && mv.L <= madicp::kP2pFlagLeaves;
     }
     if (latest) {
       HIP_TRY(hipStreamWaitEvent(ctx->stream, latest->ready, 0));
@@ -1034,9 +881,7 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
     }
   }
   for (int s = 0; s < a.n_scans; ++s) {
-    auto mit = ctx->movings.find(a.moving_ids[s]);
-    if (mit == ctx->movings.end()) return fail(MADICP_ERR_INVALID, "unknown moving id");
-    DevMoving& mv = mit->second;
+    DevMoving& mv = ctx->movings.at(a.moving_ids[s]);
     if (use_cache) RC_TRY(reserve_cache(ctx, mv, std::max(1, a.K)));
     Job& j = h_jobs[s];
     RC_TRY(fill_job(ctx, j, mv, a.tree_ids, a.K, a.X0 + 12 * s, a.params, a.n_iters, a.flags, use_cache));
@@ -1044,34 +889,23 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
     j.x_iters = (s == 0) ? a.d_x_iters : nullptr;
     max_L = std::max(max_L, mv.L);
     // flags are cleared on the device before the last round; with a single round that is "now"
-    if (a.n_iters == 1 || ctx->match_all) HIP_TRY(hipMemsetAsync(mv.matched, 0, (size_t)mv.L, ctx->stream));
+    if (a.n_iters == 1 || ctx->opt.match_all) HIP_TRY(hipMemsetAsync(mv.matched, 0, (size_t)mv.L, ctx->stream));
   }
   // a sharded batch of two or more scans goes as two halves on two streams (enqueue_rounds_split): each half is a launch
   // shape of its own — its scans share the chip among themselves, not with the other half's
   // (option value 2: split from two scans on — tests, probes; never over the peer mailboxes: there is no collective to hide)
-  const bool split = ctx->sharded() && a.n_scans >= (ctx->shard_split >= 2 ? 2 : 4) && ctx->shard_split && !a.time_launches &&
-                     !a.d_corr && !a.d_x_iters && !(ctx->shard_p2p && ctx->p2p_attached);
-  const int n_first = split ? a.n_scans / 2 : a.n_scans;
-  Launch halves[2];
-  Geometry geo = pick_geometry(ctx, max_L, a.K, n_first);
-  for (int h = 0; h < (split ? 2 : 1); ++h) {
+  st->split = ctx->sharded() && a.n_scans >= (ctx->opt.shard_split >= 2 ? 2 : 4) && ctx->opt.shard_split && !a.measure_only &&
+              !a.d_corr && !a.d_x_iters && !(ctx->opt.shard_p2p && ctx->p2p_attached);
+  const int n_first = st->split ? a.n_scans / 2 : a.n_scans;
+  for (int h = 0; h < (st->split ? 2 : 1); ++h) {
     const int first = h ? n_first : 0, count = h ? a.n_scans - n_first : n_first;
-    if (h) geo = pick_geometry(ctx, max_L, a.K, count);
-    halves[h] = Launch{geo.grid, count, a.n_iters, geo.qpt, geo.lds_bytes, a.K, geo.ranges_per_tree, a.d_corr ? 1 : 0, geo.queue};
-    for (int s = first; s < first + count; ++s) {
-      h_jobs[s].ranges_per_tree = geo.ranges_per_tree;
-      if (ctx->interleave == 2 || (ctx->interleave == 1 && geo.queue)) h_jobs[s].flags |= kFlagInterleave;
-      h_jobs[s].stage_min_leaves = ctx->stage_min_leaves;
-      h_jobs[s].lds_top = geo.lds_bytes ? 1 : 0;
-    }
+    st->halves[h] = make_plan(ctx->opt, ctx->env(), max_L, a.K, count, a.n_iters, a.d_corr != nullptr, flags_fit);
+    for (int s = first; s < first + count; ++s) plan_job(ctx, st->halves[h], h_jobs[s]);
   }
-  const Launch launch = halves[0];
-  const int grid = launch.grid;
-  size_t part_doubles[2] = {0, 0};
-  RC_TRY(prepare_partials(ctx, halves, split ? 2 : 1, part_doubles));
-  if (!a.time_launches) {
+  RC_TRY(prepare_partials(ctx, st->halves, st->split ? 2 : 1, st->part_doubles));
+  if (!a.measure_only) {
     unsigned reg_epoch = 0;
-    RC_TRY(next_p2p_epoch(ctx, launch, &reg_epoch));
+    RC_TRY(next_p2p_epoch(ctx, st->halves[0], &reg_epoch));
     for (int s = 0; s < a.n_scans; ++s) h_jobs[s].p2p_epoch = reg_epoch;
   }
   const size_t job_bytes = offsetof(Job, trees) + sizeof(TreeDesc) * (size_t)std::max(1, a.K);
@@ -1080,35 +914,12 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
   HIP_TRY(hipMemcpyAsync(ctx->d_jobs, h_jobs, sizeof(Job) * (size_t)(a.n_scans - 1) + job_bytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipEventRecord(ctx->stage_ev[slot], ctx->stream));
   ctx->last_batch = a.n_scans;
-  if (a.time_launches > 0) {
-    // n back-to-back launches of the dominant kernel inside ONE captured graph, bracketed by two events: the
-    // per-launch time is defined exactly like a profiler trace of the registration graph defines it
-    if (!ctx->ev_t0) {
-      HIP_TRY(hipEventCreate(&ctx->ev_t0));
-      HIP_TRY(hipEventCreate(&ctx->ev_t1));
-    }
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < a.time_launches; ++i) launch_round(ctx, launch, whole_part(ctx, ctx->d_jobs), 0, nullptr);
-    HIP_TRY(hipStreamEndCapture(ctx->stream, &graph));
-    HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    HIP_TRY(hipGraphLaunch(exec, ctx->stream));  // warm-up replay
-    HIP_TRY(hipEventRecord(ctx->ev_t0, ctx->stream));
-    HIP_TRY(hipGraphLaunch(exec, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_t1, ctx->stream));
-    // fold the last launch's partials (round parity 0) into job->visits / H / b: icp_final with n_iters = 1 semantics
-    hipLaunchKernelGGL(icp_final, dim3(a.n_scans), dim3(kBlock), 0, ctx->stream, ctx->d_jobs, ctx->d_partials,
-                       (const double*)nullptr, grid, a.n_scans, (const unsigned long long*)nullptr, madicp::PeerBox{});
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
-    hipGraphExecDestroy(exec);
-    hipGraphDestroy(graph);
-    if (a.out_avg_us) *a.out_avg_us = 1e3 * ms / a.time_launches;
-    return MADICP_OK;
-  }
-  if (split) {
+  return MADICP_OK;
+}
+
+int launch_registration(madicp_ctx* ctx, const Staged& st, bool allow_graph) {
+  const Plan* halves = st.halves;
+  if (st.split) {
     if (!ctx->stream2) {
       HIP_TRY(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
       HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
@@ -1116,16 +927,17 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
     }
     Part parts[2] = {whole_part(ctx, ctx->d_jobs), whole_part(ctx, ctx->d_jobs)};
     Part& q = parts[1];
+    const int n_first = halves[0].batch;
     q.s = ctx->stream2;
     q.jobs = ctx->d_jobs + n_first;
-    q.partials = ctx->d_partials + part_doubles[0];
+    q.partials = ctx->d_partials + st.part_doubles[0];
     q.xch = ctx->d_xch + madicp::xch_granules(halves[0].batch, halves[0].grid);
     q.totals[0] += (size_t)n_first * kAcc;
     q.totals[1] += (size_t)n_first * kAcc;
     q.tickets += n_first;
     // the exchange rows are only read by the TAIL variant of the round kernel (option "shard_tail"): only then do the two
     // halves need disjoint regions of them that both fit
-    const bool rows_used = use_tail(ctx, halves[0]) || use_tail(ctx, halves[1]);
+    const bool rows_used = halves[0].route == Route::Tail || halves[1].route == Route::Tail;
     if (!rows_used) {
       q.xch = ctx->d_xch;
     } else if (madicp::xch_granules(halves[0].batch, halves[0].grid) + madicp::xch_granules(halves[1].batch, halves[1].grid) >
@@ -1138,13 +950,17 @@ int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
   }
   // with a communicator a captured sequence would bake the matched-flag buffers of THESE scans: launch eagerly
   // (over the mailboxes with the flags in them there is no collective: captured like a single-GPU batch)
-  const int saved = ctx->use_graph;
-  if (ctx->sharded() && !(use_p2p(ctx, launch) && p2p_flags_fit(ctx, ctx->last_moving.data(), a.n_scans))) ctx->use_graph = 0;
-  const bool queued_behind = ctx->use_graph && ctx->eager_when_busy && hipStreamQuery(ctx->stream) == hipErrorNotReady;
-  const int rc = run_rounds(ctx, launch, ctx->d_jobs, -1, ctx->last_moving, queued_behind);
-  ctx->use_graph = saved;
+  allow_graph = allow_graph && (!ctx->sharded() || halves[0].flags_in_box);
+  const bool queued_behind = allow_graph && ctx->opt.use_graph && ctx->opt.eager_when_busy && hipStreamQuery(ctx->stream) == hipErrorNotReady;
+  const int rc = run_rounds(ctx, halves[0], ctx->d_jobs, -1, ctx->last_moving, queued_behind, allow_graph);
   if (rc == MADICP_OK) mark_moving_used(ctx, ctx->last_moving);
   return rc;
+}
+
+int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
+  Staged st;
+  RC_TRY(stage_registration(ctx, a, &st));
+  return launch_registration(ctx, st, a.allow_graph);
 }
 
 }  // namespace
@@ -1317,85 +1133,11 @@ int madicp_ctx_synchronize(madicp_ctx* ctx) {
 
 int madicp_ctx_set_option(madicp_ctx* ctx, const char* key, int64_t value) {
   if (!ctx || !key) return fail(MADICP_ERR_INVALID, "null argument");
-  const std::string k(key);
-  if (k == "grid_blocks_per_cu") {
-    if (value < 1 || value > 4) return fail(MADICP_ERR_INVALID, "grid_blocks_per_cu must be in 1..4");
-    ctx->blocks_per_cu = (int)value;
-  } else if (k == "publish_side") {
-    ctx->publish_side = value ? 1 : 0;
-  } else if (k == "deal_trees") {
-    if (value < 0 || value > 2) return fail(MADICP_ERR_INVALID, "deal_trees is 0 (as listed), 1 (round-robin over the XCD pieces) or 2 (alternating rows)");
-    ctx->deal_trees = (int)value;
-  } else if (k == "units_per_workgroup") {
-    if (value < 1 || value > 64) return fail(MADICP_ERR_INVALID, "units_per_workgroup must be in 1..64");
-    ctx->units_per_wg = (int)value;
-  } else if (k == "use_graph") {
-    ctx->use_graph = value ? 1 : 0;
-  } else if (k == "comm_graph") {
-    ctx->comm_graph = value ? 1 : 0;
-  } else if (k == "cache_correspondences") {
-    ctx->cache_corr = value ? 1 : 0;
-  } else if (k == "cache_gate") {
-    ctx->cache_gate = value ? 1 : 0;
-  } else if (k == "deep_min_leaves") {
-    if (value < 64 || value > (1 << 24)) return fail(MADICP_ERR_INVALID, "deep_min_leaves must be in 64 .. 2^24");
-    ctx->deep_min_leaves = (int)value;
-  } else if (k == "interleave_ranges") {
-    if (value < 0 || value > 2) return fail(MADICP_ERR_INVALID, "interleave_ranges is 0 (never), 1 (batches that share the chip) or 2 (always)");
-    ctx->interleave = (int)value;
-  } else if (k == "leaf_major") {
-    if (value < 0 || value > (1 << 20)) return fail(MADICP_ERR_INVALID, "leaf_major must be 0 (never) or a node count per pass");
-    ctx->queue_walks = (int)value;
-  } else if (k == "lds_stage_min_leaves") {
-    if (value < 0) return fail(MADICP_ERR_INVALID, "lds_stage_min_leaves must be >= 0");
-    ctx->stage_min_leaves = (int)std::min<int64_t>(value, 1 << 30);
-  } else if (k == "eager_when_busy") {
-    ctx->eager_when_busy = value ? 1 : 0;
-  } else if (k == "seq_completion") {
-    ctx->seq_completion = value ? 1 : 0;
-  } else if (k == "host_feed_wait") {
-    ctx->host_feed_wait = value ? 1 : 0;
-  } else if (k == "xcd_fold") {
-    ctx->xcd_fold = value ? 1 : 0;
-  } else if (k == "debug_collective_us") {
-    ctx->debug_collective_us = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1000));
-  } else if (k == "shard_tail") {
-    ctx->shard_tail = value ? 1 : 0;
-  } else if (k == "build_after_registration") {
-    ctx->build_after_registration = value ? 1 : 0;
-  } else if (k == "shard_p2p") {
-    ctx->shard_p2p = value ? 1 : 0;
-  } else if (k == "shard_split") {
-    ctx->shard_split = value < 0 ? 0 : (value > 2 ? 2 : (int)value);
-  } else if (k == "match_all_rounds") {
-    ctx->match_all = value ? 1 : 0;
-  } else if (k == "persistent") {
-    ctx->persistent = value ? 1 : 0;
-  } else if (k == "wait_mode") {
-    if (value < 0 || value > 2) return fail(MADICP_ERR_INVALID, "wait_mode must be 0 (spin), 1 (yield) or 2 (sleep)");
-    ctx->wait_mode = (int)value;
-  } else if (k == "wait_timeout_ms") {
-    if (value < 0) return fail(MADICP_ERR_INVALID, "wait_timeout_ms must be >= 0");
-    ctx->wait_timeout_ms = (int)std::min<int64_t>(value, 1 << 30);
-  } else if (k == "comm_timeout_ms") {
-    if (value < 1) return fail(MADICP_ERR_INVALID, "comm_timeout_ms must be >= 1");
-    ctx->comm_timeout_ms = (int)std::min<int64_t>(value, 1 << 30);
-    if (ctx->p2p_attached) {  // (captured mailbox launches carry the bound of their polls as a kernel argument)
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-      ctx->graphs.clear();
-    }
-  } else if (k == "p2p_allow_coarse") {
-    ctx->p2p_allow_coarse = value ? 1 : 0;
-  } else if (k == "upload_f32") {
-    ctx->upload_f32 = value ? 1 : 0;
-  } else if (k == "nn_lds_top") {
-    ctx->nn_lds_top = value ? 1 : 0;
-  } else if (k == "queries_per_lane") {
-    if (value != 0 && value != 1 && value != 2) return fail(MADICP_ERR_INVALID, "queries_per_lane must be 0 (default), 1 or 2");
-    ctx->qpt_override = (int)value;
-  } else {
-    return fail(MADICP_ERR_INVALID, "unknown option: " + k);
+  std::string err;
+  if (!option_set(ctx->opt, key, value, &err)) return fail(MADICP_ERR_INVALID, err);
+  if (std::string(key) == "comm_timeout_ms" && ctx->p2p_attached) {  // (captured mailbox launches carry the bound of their polls as a kernel argument)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->drop_graphs();
   }
   return MADICP_OK;
 }
@@ -1404,40 +1146,10 @@ int madicp_ctx_get_option(madicp_ctx* ctx, const char* key, int64_t* out_value) 
   if (!ctx || !key || !out_value) return fail(MADICP_ERR_INVALID, "null argument");
   const std::string k(key);
   int64_t v = 0;
-  if (k == "grid_blocks_per_cu") v = ctx->blocks_per_cu;
-  else if (k == "publish_side") v = ctx->publish_side;
-  else if (k == "deal_trees") v = ctx->deal_trees;
-  else if (k == "units_per_workgroup") v = ctx->units_per_wg;
-  else if (k == "use_graph") v = ctx->use_graph;
-  else if (k == "comm_graph") v = ctx->comm_graph;
-  else if (k == "cache_correspondences") v = ctx->cache_corr;
-  else if (k == "cache_gate") v = ctx->cache_gate;
-  else if (k == "interleave_ranges") v = ctx->interleave;
-  else if (k == "deep_min_leaves") v = ctx->deep_min_leaves;
-  else if (k == "leaf_major") v = ctx->queue_walks;
-  else if (k == "lds_stage_min_leaves") v = ctx->stage_min_leaves;
-  else if (k == "eager_when_busy") v = ctx->eager_when_busy;
-  else if (k == "seq_completion") v = ctx->seq_completion;
-  else if (k == "host_feed_wait") v = ctx->host_feed_wait;
-  else if (k == "xcd_fold") v = ctx->xcd_fold;
-  else if (k == "debug_collective_us") v = ctx->debug_collective_us;
-  else if (k == "shard_tail") v = ctx->shard_tail;
-  else if (k == "build_after_registration") v = ctx->build_after_registration;
-  else if (k == "shard_p2p") v = ctx->shard_p2p;
-  else if (k == "shard_split") v = ctx->shard_split;
-  else if (k == "match_all_rounds") v = ctx->match_all;
-  else if (k == "persistent") v = ctx->persistent;
-  else if (k == "wait_mode") v = ctx->wait_mode;
-  else if (k == "wait_timeout_ms") v = ctx->wait_timeout_ms;
-  else if (k == "comm_timeout_ms") v = ctx->comm_timeout_ms;
-  else if (k == "p2p_allow_coarse") v = ctx->p2p_allow_coarse;
-  else if (k == "upload_f32") v = ctx->upload_f32;
-  else if (k == "p2p_fine_grained") v = (ctx->p2p_box && ctx->p2p_fine) ? 1 : 0;  // (read-only: what madicp_p2p_export obtained)
-  else if (k == "nn_lds_top") v = ctx->nn_lds_top;
-  else if (k == "queries_per_lane") v = ctx->qpt_override;
+  if (k == "p2p_fine_grained") v = (ctx->p2p_box && ctx->p2p_fine) ? 1 : 0;  // (read-only: what madicp_p2p_export obtained)
   else if (k == "comm_ranks") v = ctx->sharded() ? ctx->n_ranks : 0;  // (read-only: ranks of the installed communicator, 0: none)
   else if (k == "comm_rank") v = ctx->sharded() ? ctx->rank : -1;     // (read-only: this context's rank in it, -1: none)
-  else return fail(MADICP_ERR_INVALID, "unknown option: " + k);
+  else if (!option_get(ctx->opt, k, &v)) return fail(MADICP_ERR_INVALID, "unknown option: " + k);
   *out_value = v;
   return MADICP_OK;
 }
@@ -1685,7 +1397,7 @@ int madicp_nn_search_device_enqueue(madicp_ctx* ctx, int tree_id, const double* 
   if (!d_queries) return fail(MADICP_ERR_INVALID, "queries is null");
   HIP_TRY(hipSetDevice(ctx->device));
   RC_TRY(wait_tree(ctx, it->second));
-  if (n >= 16384 && it->second.desc.n_top > 0 && ctx->nn_lds_top) {
+  if (n >= 16384 && it->second.desc.n_top > 0 && ctx->opt.nn_lds_top) {
     // searchCloud-sized batch: one 1024-thread workgroup per CU stages the tree's top levels in LDS and walks them there
     const long long blocks = std::min<long long>((n + 1023) / 1024, (long long)ctx->n_cus);
     hipLaunchKernelGGL(nn_descend_top, dim3((unsigned)blocks), dim3(1024), kTopLdsBytes, ctx->stream, it->second.desc, d_queries,
@@ -1856,22 +1568,13 @@ int stream_submit_impl(madicp_ctx* ctx, const double* leaf_means, int32_t L, int
   }
   Job& j = *sl.h_job;
   RC_TRY(fill_job(ctx, j, mv, tree_ids, K, X0, params, n_iters, 0, use_cache));
-  const Geometry geo = pick_geometry(ctx, L, K, 1);
-  j.ranges_per_tree = geo.ranges_per_tree;
-  if (ctx->interleave == 2 || (ctx->interleave == 1 && geo.queue)) j.flags |= kFlagInterleave;
-  j.stage_min_leaves = ctx->stage_min_leaves;
-  j.lds_top = geo.lds_bytes ? 1 : 0;
+  const Plan launch = make_plan(ctx->opt, ctx->env(), L, K, 1, n_iters, false, L <= madicp::kP2pFlagLeaves);
+  plan_job(ctx, launch, j);
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&j.host_out), sl.h_out, 0));
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&j.host_matched), sl.h_matched, 0));
-  // results out: through the device-resident outbox and icp_publish on the side stream (kernels.hip.h, Outbox), unless the
-  // completion is an event on the compute stream or the loop is sharded (its matched flags are reduced behind icp_final)
-  // — or the rounds need the whole chip to themselves: icp_persist / the xcd_fold variant wait INSIDE a launch for workgroups
-  // that must all be resident, at 3 x 168 registers per SIMD lane nothing fits beside them, and an icp_publish workgroup that got
-  // its CU first (the compute stream is still waiting for the feed) would keep one of them out until their bounded waits expire
-  const Launch launch{geo.grid, 1, n_iters, geo.qpt, geo.lds_bytes, K, geo.ranges_per_tree, 0, geo.queue};
-  const bool p2p_free = use_p2p(ctx, launch) && L <= madicp::kP2pFlagLeaves;  // (sharded, yet no collective and no host step)
-  const bool side = ctx->publish_side && ctx->seq_completion && (!ctx->sharded() || p2p_free) && !use_persist(ctx, launch) &&
-                    !use_fold(ctx, launch);
+  // results out: through the device-resident outbox and icp_publish on the side stream (kernels.hip.h, Outbox) where the plan
+  // admits it (side_publish, launch_plan.h)
+  const bool side = side_publish(launch, ctx->opt, ctx->env());
   j.outbox = side ? sl.d_outbox : nullptr;
   RC_TRY(next_p2p_epoch(ctx, launch, &j.p2p_epoch));
   const size_t job_bytes = offsetof(Job, trees) + sizeof(TreeDesc) * (size_t)std::max(1, K);
@@ -1885,28 +1588,28 @@ int stream_submit_impl(madicp_ctx* ctx, const double* leaf_means, int32_t L, int
   // no barrier packet between two registrations; with nothing in flight the wait is the stream's (lowest latency).
   bool busy = false;
   for (const StreamSlot& other : ctx->slots) busy = busy || other.pending;
-  if (busy && ctx->host_feed_wait)
+  if (busy && ctx->opt.host_feed_wait)
     HIP_TRY(hipEventSynchronize(sl.ev_up));
   else
     HIP_TRY(hipStreamWaitEvent(ctx->stream, sl.ev_up, 0));
-  if (n_iters == 1 || ctx->match_all) HIP_TRY(hipMemsetAsync(mv.matched, 0, (size_t)L, ctx->stream));
+  if (n_iters == 1 || ctx->opt.match_all) HIP_TRY(hipMemsetAsync(mv.matched, 0, (size_t)L, ctx->stream));
   {
     size_t doubles = 0;
     RC_TRY(prepare_partials(ctx, &launch, 1, &doubles));
   }
   const std::vector<int> ids{sl.moving_id};
-  RC_TRY(run_rounds(ctx, launch, sl.d_job, ticket % madicp_ctx::kStreamSlots, ids, busy));
+  RC_TRY(run_rounds(ctx, launch, sl.d_job, ticket % madicp_ctx::kStreamSlots, ids, busy, true));
   if (side) {
     // (its wait is bounded by the longest the CALLER is prepared to wait, never less than 10 s: a compute stream legitimately
     // stalled for longer than a fixed bound would otherwise lose a registration that later completes)
-    const unsigned long long spin_ms = (unsigned long long)std::max(10000, std::max(ctx->wait_timeout_ms, ctx->comm_timeout_ms));
+    const unsigned long long spin_ms = (unsigned long long)std::max(10000, std::max(ctx->opt.wait_timeout_ms, ctx->opt.comm_timeout_ms));
     hipLaunchKernelGGL(icp_publish, dim3(1), dim3(256), 0, ctx->pub, (const Outbox*)sl.d_outbox, (const uint8_t*)mv.matched, L, ticket + 1,
                        j.host_out, j.host_matched, spin_ms * 100000ull);
     HIP_TRY(hipGetLastError());
   }
   sl.side = side;
-  if (!ctx->seq_completion) HIP_TRY(hipEventRecord(sl.ev_done, ctx->stream));
-  sl.by_seq = ctx->seq_completion != 0;
+  if (!ctx->opt.seq_completion) HIP_TRY(hipEventRecord(sl.ev_done, ctx->stream));
+  sl.by_seq = ctx->opt.seq_completion != 0;
   sl.pending = true;
   sl.ticket = ticket;
   sl.L = L;
@@ -1938,8 +1641,8 @@ int madicp_stream_collect(madicp_ctx* ctx, int ticket, double out_X[12], double 
     // (terminal errors give the slot back: a later submission must not find it "pending" for ever)
     const int32_t want = ticket + 1;
     const int32_t* seq = &sl.h_out->seq;
-    const unsigned check_mask = ctx->wait_mode == 0 ? 0x3ffu : 0xfu;  // stream health: every few tens of microseconds
-    const bool bounded = ctx->wait_timeout_ms > 0 || ctx->comm;
+    const unsigned check_mask = ctx->opt.wait_mode == 0 ? 0x3ffu : 0xfu;  // stream health: every few tens of microseconds
+    const bool bounded = ctx->opt.wait_timeout_ms > 0 || ctx->comm;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spins = 1; __atomic_load_n(seq, __ATOMIC_ACQUIRE) != want; ++spins) {
       if ((spins & check_mask) == 0) {
@@ -1955,15 +1658,15 @@ int madicp_stream_collect(madicp_ctx* ctx, int ticket, double out_X[12], double 
         }
         if (bounded) {
           const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-          if (ctx->comm && ms > ctx->comm_timeout_ms) {
+          if (ctx->comm && ms > ctx->opt.comm_timeout_ms) {
             // over the limit: unless the results arrived this very moment the communicator is aborted and the ticket is
             // gone — never MADICP_OK without the results copied out, and no second wait of comm_timeout_ms
             if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) break;
             sl.pending = false;
-            return comm_abort(ctx, "a collective did not complete within " + std::to_string(ctx->comm_timeout_ms) +
+            return comm_abort(ctx, "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) +
                                        " ms (a rank did not join?)");
           }
-          if (ctx->wait_timeout_ms > 0 && ms > ctx->wait_timeout_ms)
+          if (ctx->opt.wait_timeout_ms > 0 && ms > ctx->opt.wait_timeout_ms)
             return fail(MADICP_ERR_TIMEOUT, "registration still in flight after wait_timeout_ms; collect the ticket again");
         }
       }
@@ -2085,9 +1788,9 @@ int madicp_icp_publish_collect(madicp_ctx* ctx, int ticket, int n_scans, double*
         }
         if (q != hipErrorNotReady) return fail(MADICP_ERR_DEVICE, std::string("batch failed: ") + hipGetErrorString(q));
         const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (ctx->comm && ms > ctx->comm_timeout_ms)
-          return comm_abort(ctx, "a collective did not complete within " + std::to_string(ctx->comm_timeout_ms) + " ms (a rank did not join?)");
-        if (ctx->wait_timeout_ms > 0 && ms > ctx->wait_timeout_ms)
+        if (ctx->comm && ms > ctx->opt.comm_timeout_ms)
+          return comm_abort(ctx, "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) + " ms (a rank did not join?)");
+        if (ctx->opt.wait_timeout_ms > 0 && ms > ctx->opt.wait_timeout_ms)
           return fail(MADICP_ERR_TIMEOUT, "batch still in flight after wait_timeout_ms; collect the ticket again");
       }
       wait_pause(ctx);
@@ -2151,11 +1854,9 @@ int madicp_icp_linearize(madicp_ctx* ctx, int moving_id, const int* tree_ids, in
   HIP_TRY(hipSetDevice(ctx->device));
   void* d_corr = nullptr;
   if (out_corr && K > 0) RC_TRY(pool_alloc(ctx, sizeof(uint32_t) * (size_t)K * L, ctx->stream, &d_corr));
-  RegArgs a{1, &moving_id, tree_ids, K, X, params, 1, kFlagNoUpdate, static_cast<uint32_t*>(d_corr), nullptr};
-  const int saved_graph = ctx->use_graph;
-  ctx->use_graph = 0;  // pointers in the job differ per call; nothing to gain from a graph for one round
+  // (eagerly: pointers in the job differ per call; nothing to gain from a graph for one round)
+  RegArgs a{1, &moving_id, tree_ids, K, X, params, 1, kFlagNoUpdate, static_cast<uint32_t*>(d_corr), nullptr, /*allow_graph=*/false};
   int rc = enqueue_registration(ctx, a);
-  ctx->use_graph = saved_graph;
   if (rc == MADICP_OK) rc = madicp_icp_fetch(ctx, 1, nullptr, out_H, out_b, nullptr, out_visits);
   if (rc == MADICP_OK && out_matched) rc = madicp_icp_fetch_matched(ctx, 0, out_matched, L);
   if (rc == MADICP_OK && d_corr) {
@@ -2176,10 +1877,35 @@ int madicp_icp_time_linearize(madicp_ctx* ctx, int n_scans, const int* moving_id
                               uint64_t* out_visits_per_launch) {
   if (n_launches < 1) return fail(MADICP_ERR_INVALID, "n_launches must be >= 1");
   // a one-round registration without pose update, its round-0 kernel launched n_launches times
-  RegArgs a{n_scans, moving_ids, tree_ids, K, X0, params, 1, kFlagNoUpdate, nullptr, nullptr, n_launches, out_avg_us};
-  int rc = enqueue_registration(ctx, a);
-  if (rc == MADICP_OK && out_visits_per_launch) rc = madicp_icp_fetch(ctx, n_scans, nullptr, nullptr, nullptr, nullptr, out_visits_per_launch);
-  return rc;
+  RegArgs a{n_scans, moving_ids, tree_ids, K, X0, params, 1, kFlagNoUpdate, nullptr, nullptr, true, /*measure_only=*/true};
+  Staged st;
+  RC_TRY(stage_registration(ctx, a, &st));
+  // n back-to-back launches of the dominant kernel inside ONE captured graph, bracketed by two events: the
+  // per-launch time is defined exactly like a profiler trace of the registration graph defines it
+  if (!ctx->ev_t0) {
+    HIP_TRY(hipEventCreate(&ctx->ev_t0));
+    HIP_TRY(hipEventCreate(&ctx->ev_t1));
+  }
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+  for (int i = 0; i < n_launches; ++i) launch_round(ctx, st.halves[0], whole_part(ctx, ctx->d_jobs), 0, nullptr);
+  HIP_TRY(hipStreamEndCapture(ctx->stream, &graph));
+  HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+  HIP_TRY(hipGraphLaunch(exec, ctx->stream));  // warm-up replay
+  HIP_TRY(hipEventRecord(ctx->ev_t0, ctx->stream));
+  HIP_TRY(hipGraphLaunch(exec, ctx->stream));
+  HIP_TRY(hipEventRecord(ctx->ev_t1, ctx->stream));
+  // fold the last launch's partials (round parity 0) into job->visits / H / b: icp_final with n_iters = 1 semantics
+  hipLaunchKernelGGL(icp_final, dim3(n_scans), dim3(kBlock), 0, ctx->stream, ctx->d_jobs, ctx->d_partials,
+                     (const double*)nullptr, st.halves[0].grid, n_scans, (const unsigned long long*)nullptr, madicp::PeerBox{});
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
+  hipGraphExecDestroy(exec);
+  hipGraphDestroy(graph);
+  if (out_avg_us) *out_avg_us = 1e3 * ms / n_launches;
+  return out_visits_per_launch ? madicp_icp_fetch(ctx, n_scans, nullptr, nullptr, nullptr, nullptr, out_visits_per_launch) : MADICP_OK;
 }
 
 int madicp_icp_time_registration(madicp_ctx* ctx, int n_scans, const int* moving_ids, const int* tree_ids, int K,
@@ -2194,12 +1920,12 @@ int madicp_icp_time_registration(madicp_ctx* ctx, int n_scans, const int* moving
     HIP_TRY(hipEventCreate(&ctx->ev_t1));
   }
   RegArgs a{n_scans, moving_ids, tree_ids, K, X0, params, n_iters, 0, nullptr, nullptr};
-  int rc = enqueue_registration(ctx, a);  // warm-up; also instantiates the graph
-  if (rc != MADICP_OK) return rc;
-  HIP_TRY(hipEventRecord(ctx->ev_t0, ctx->stream));
-  for (int r = 0; r < reps; ++r) {
-    rc = enqueue_registration(ctx, a);
-    if (rc != MADICP_OK) return rc;
+  Staged st;  // (not sharded: never split, halves[0] is the whole batch)
+  int rc = MADICP_OK;
+  for (int r = -1; r < reps; ++r) {  // r = -1: warm-up; also instantiates the graph
+    RC_TRY(stage_registration(ctx, a, &st));
+    RC_TRY(launch_registration(ctx, st, a.allow_graph));
+    if (r < 0) HIP_TRY(hipEventRecord(ctx->ev_t0, ctx->stream));
   }
   HIP_TRY(hipEventRecord(ctx->ev_t1, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2214,13 +1940,12 @@ int madicp_icp_time_registration(madicp_ctx* ctx, int n_scans, const int* moving
     for (int s = 0; s < n_scans; ++s) out_walked_per_launch[s] = ctx->h_fetch[s].walked / (uint64_t)n_iters;
   // icp_final alone, `reps` of them back to back inside ONE graph (a graph per launch would add the idle queue between two
   // graph launches, ~10 us, to a 5 us kernel): what is left of a registration is its n_iters icp_round launches
-  const Geometry geo = pick_geometry(ctx, [&] { int m = 0; for (int s = 0; s < n_scans; ++s) m = std::max(m, ctx->movings.at(moving_ids[s]).L); return m; }(), K, n_scans);
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
   for (int r = 0; r < reps; ++r)
     hipLaunchKernelGGL(icp_final, dim3(n_scans), dim3(kBlock), 0, ctx->stream, ctx->d_jobs, ctx->d_partials,
-                       (const double*)nullptr, geo.grid, n_scans, (const unsigned long long*)nullptr, madicp::PeerBox{});
+                       (const double*)nullptr, st.halves[0].grid, n_scans, (const unsigned long long*)nullptr, madicp::PeerBox{});
   HIP_TRY(hipStreamEndCapture(ctx->stream, &graph));
   HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
   {
@@ -2407,8 +2132,7 @@ int madicp_comm_init(madicp_ctx* ctx, const uint8_t unique_id[128], int n_ranks,
   ctx->n_ranks = n_ranks;
   ctx->rank = rank;
   // graphs captured without the collectives are no longer the right sequence
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-  ctx->graphs.clear();
+  ctx->drop_graphs();
   return MADICP_OK;
 }
 
@@ -2422,8 +2146,7 @@ int madicp_comm_init_host(madicp_ctx* ctx, int n_ranks, int rank, madicp_host_al
   ctx->host_ar_user = user;
   ctx->n_ranks = n_ranks;
   ctx->rank = rank;
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);  // captured without the join over ranks
-  ctx->graphs.clear();
+  ctx->drop_graphs();  // captured without the join over ranks
   return MADICP_OK;
 }
 
@@ -2444,7 +2167,7 @@ int madicp_p2p_export(madicp_ctx* ctx, uint8_t out_handle[64]) {
     // cross-device visibility while a kernel runs — over xGMI the polls could spin until comm_timeout_ms — so it is only taken
     // on request (option "p2p_allow_coarse": ranks that share ONE device, where the same L2 / memory serves writer and reader).
     for (int attempt = 0; attempt < 2 && !ctx->p2p_box; ++attempt) {
-      if (attempt == 1 && !ctx->p2p_allow_coarse)
+      if (attempt == 1 && !ctx->opt.p2p_allow_coarse)
         return fail(MADICP_ERR_DEVICE, "mailbox: no exportable fine-grained device memory on this runtime (option p2p_allow_coarse = 1 "
                                        "accepts coarse-grained memory, for ranks that share one device only)");
       void* p = nullptr;
@@ -2474,8 +2197,7 @@ int madicp_p2p_detach(madicp_ctx* ctx) {
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->stream) HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (ctx->pub) HIP_TRY(hipStreamSynchronize(ctx->pub));
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);  // (captured launches carry the peers' mappings)
-  ctx->graphs.clear();
+  ctx->drop_graphs();  // (captured launches carry the peers' mappings)
   for (int q = 0; q < madicp::kMaxRanks; ++q) {
     if (ctx->p2p_opened[q] && ctx->p2p_peer[q]) hipIpcCloseMemHandle(ctx->p2p_peer[q]);
     ctx->p2p_opened[q] = false;
@@ -2497,8 +2219,7 @@ int madicp_p2p_attach(madicp_ctx* ctx, const uint8_t* handles, int n_ranks, int 
                                     "session, whose tags the new session's registration counter would meet again");
   if (ctx->p2p_attached) RC_TRY(madicp_p2p_detach(ctx));
   HIP_TRY(hipSetDevice(ctx->device));
-  for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);  // (captured without the join over the ranks)
-  ctx->graphs.clear();
+  ctx->drop_graphs();  // (captured without the join over the ranks)
   for (int q = 0; q < n_ranks; ++q) {
     if (q == rank) {
       ctx->p2p_peer[q] = ctx->p2p_box;
@@ -2535,8 +2256,7 @@ int madicp_comm_destroy(madicp_ctx* ctx) {
   }
   if (ctx->comm) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (auto& g : ctx->graphs) hipGraphExecDestroy(g.second);
-    ctx->graphs.clear();
+    ctx->drop_graphs();
     NCCL_TRY(ncclCommDestroy(ctx->comm));
     ctx->comm = nullptr;
     ctx->n_ranks = 1;

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 
 DEFAULT_ROUTE = {"use_graph": 1, "eager_when_busy": 1, "seq_completion": 1, "host_feed_wait": 1, "wait_mode": 0, "nn_lds_top": 0,
-                 "persistent": 0, "xcd_fold": 0}  # madicp_capi.hip
+                 "persistent": 0, "xcd_fold": 0}  # struct Options, launch_plan.h
 
 
 def descend(nodes, q):

@@ -283,7 +283,7 @@ def test_ranges_dealt_in_groups_of_64_leaves_same_decisions(ctx, K, n_queries):
 
 def test_deep_launch_with_ranges_of_less_than_a_pass(ctx):
     """From 24 keyframes on a launch is DEEP — one range of the scan and all the trees of its XCD piece per workgroup — as soon as a
-    range holds 512 leaves (option deep_min_leaves; pick_geometry), i.e. less than one pass of a workgroup: three scans in flight
+    range holds 512 leaves (option deep_min_leaves; make_plan), i.e. less than one pass of a workgroup: three scans in flight
     here, ten workgroups per XCD piece, ranges of ~640 leaves.  Same decisions as the unit-per-workgroup launch of the same
     registration (deep_min_leaves out of reach), poses and H to summation-order rounding, and the oracle's poses."""
     pb, hts, ots, tids, qh, qo, mids = _setup_registration(ctx, 24, n_queries=3)
