@@ -265,7 +265,8 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
  * order, like the reference's.  Points whose azimuths tie exactly may come out in a different order than std::sort
  * leaves them (it is not stable), and the device atan2 may differ from libm's in the last bit: the result is the
  * reference's up to the order of such ties.  out_chunks (n, optional): the time chunk of every point in walk order
- * (largest azimuth first) — synchronises when given. */
+ * (largest azimuth first) — synchronises when given.  A cloud that carries stamps (madicp_cloud_ingest_records) LOSES them
+ * here: the points are sorted, the stamps would no longer line up. */
 int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks);
 /* Motion compensation from PER-POINT TIMESTAMPS, for callers whose driver delivers them (a PointCloud2 `t` / `timestamp` /
  * `time` field): additive, the reference has no such path — its azimuth guess above fits a single 360-degree head that starts
@@ -281,6 +282,52 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
  * input order — synchronises when given.  Bit-equal to madicp_host_deskew_stamped (madicp_host.h) for the same velocity. */
 int madicp_cloud_deskew_stamped(madicp_ctx* ctx, int cloud_id, const double* stamps01, int64_t n, const double velocity[6],
                                 double sensor_hz, int32_t* out_chunks);
+/* RAW POINT RECORDS WITH A TIME FIELD — what a LiDAR driver actually delivers: a PointCloud2-style byte buffer of records
+ * `point_step` bytes apart, little-endian float32 x / y / z at byte offsets, and a `t` / `time` / `timestamp` field of uint32,
+ * float32 or float64.  Additive.  madicp_cloud_ingest_records takes such a buffer to a resident, range-filtered cloud that
+ * CARRIES ITS OWN normalised stamps (a device buffer owned by the cloud, pooled like the points, released with it), and
+ * madicp_cloud_deskew_own_stamps motion-compensates by them: the stamps never cross PCIe as doubles.  Everything in fp64
+ * without contraction:
+ *   survivors     madicp_cloud_ingest_f32's rule on the three floats read from off_x / off_y / off_z: float norm
+ *                 sqrtf(x*x + (y*y + z*z)) compared in double, ON a bound stays, NaN coordinates dropped, the same KITTI
+ *                 rotation, input order kept — the same points, bit for bit, as madicp_cloud_ingest_f32 gives for the (n,3)
+ *                 float32 view of the same coordinates.
+ *   time          t64 = (double)field, exact for all three types.
+ *   range         t_range == NULL: t0 / t1 = min / max of t64 over ALL records with a FINITE time, dropped ones included (the
+ *                 reference's apps/utils/point_cloud2.py:90-93 takes the whole message; ignoring non-finite values is an
+ *                 addition — one NaN would poison its np.min), each canonicalised as t + 0.0 (a -0.0 extreme becomes +0.0);
+ *                 +inf / -inf when no record has a finite time.  Else {t_begin, t_end}, both finite with t_end > t_begin.
+ *   stamp         s = (t64 - t0) / (t1 - t0); every stamp NaN unless t1 - t0 > 0 (all times equal, no finite time): the
+ *                 chunk rule below sends NaN to chunk 1023, the scan's end.  +-inf and values outside [0, 1] are left as
+ *                 IEEE produces them; the chunk rule clamps them.
+ * out_n: the survivors; out_t_range (optional): the t0, t1 used — it travels with the one device-to-host copy of the survivor
+ * count (one synchronisation, like madicp_cloud_ingest_f32).  With t_type == MADICP_T_NONE the cloud has no stamps, off_t is
+ * ignored and out_t_range is +inf, -inf.  MADICP_ERR_INVALID — before anything is launched or allocated, no cloud created —
+ * for a null argument, n_records outside 1 .. 2^30, point_step outside 12 .. 256, a field that does not lie inside
+ * [0, point_step), an unknown t_type, a t_range that is not finite and increasing; MADICP_ERR_INVALID as well when no record
+ * survives; MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Bit-equal to madicp_host_ingest_records
+ * (madicp_host.h). */
+#define MADICP_T_NONE 0 /* time field types: sensor_msgs/PointField's own codes */
+#define MADICP_T_U32 6
+#define MADICP_T_F32 7
+#define MADICP_T_F64 8
+typedef struct madicp_record_layout {
+  int32_t point_step;          /* bytes from one record to the next, 12 .. 256, ANY value (13, 22, 26 ... are legal) */
+  int32_t off_x, off_y, off_z; /* byte offsets of the little-endian float32 coordinates, any alignment */
+  int32_t off_t;               /* byte offset of the time field (ignored when t_type == MADICP_T_NONE) */
+  int32_t t_type;
+} madicp_record_layout;
+int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_records, const madicp_record_layout* layout,
+                                double min_range, double max_range, int kitti_correction,
+                                const double* t_range /* NULL: min / max over the records; else {t_begin, t_end} */,
+                                int* out_cloud_id, int64_t* out_n, double out_t_range[2] /* optional */);
+/* the stamps a cloud carries (n = the cloud's size), in the cloud's order; MADICP_ERR_INVALID when it has none: only clouds of
+ * madicp_cloud_ingest_records with a time field do, and madicp_cloud_deskew — which SORTS the points — drops them */
+int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int64_t n);
+/* madicp_cloud_deskew_stamped with the stamps read from the cloud's own device buffer: the same kernel, the same pose table, the
+ * same refusals and out_chunks; MADICP_ERR_INVALID for a cloud without stamps.  The cloud keeps its stamps (input order is
+ * kept). */
+int madicp_cloud_deskew_own_stamps(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes
  * a resident tree exactly like one given to madicp_tree_upload (same node format, madicp_tree_download returns it).
  * Same decisions as the reference node by node, the reference's member order (the permutation utils.h:37-52 leaves), and
@@ -301,8 +348,8 @@ int madicp_tree_build(madicp_ctx* ctx, int cloud_id, double b_max, double b_min,
  * enqueues the whole level loop on a stream of its own — the library's BUILD stream, so that neither the registration on
  * the compute stream nor its feed on the copy stream queues behind it — and returns without waiting; _end waits for the
  * leaf count, sizes and emits the tree and returns its id.  One look-ahead per context: a second _begin, or
- * madicp_tree_build / madicp_cloud_ingest_f32 / madicp_cloud_deskew / madicp_cloud_deskew_stamped / madicp_tree_build_stats
- * before the _end, return
+ * madicp_tree_build / madicp_cloud_ingest_f32 / madicp_cloud_ingest_records / madicp_cloud_deskew /
+ * madicp_cloud_deskew_stamped / madicp_cloud_deskew_own_stamps / madicp_tree_build_stats before the _end, return
  * MADICP_ERR_CAPACITY (they share the builder's scratch).  Registrations, uploads, transforms, searches and releases are
  * free to run in between.  The tree is the one madicp_cloud_upload + madicp_tree_build give for the same scan, bit for bit. */
 int madicp_tree_build_begin(madicp_ctx* ctx, const double* xyz, int64_t n, double b_max, double b_min);

@@ -70,6 +70,17 @@ int madicp_host_debug_deskew(double* points, int64_t n, const double T_prev[12],
 int madicp_host_deskew_stamped(double* points, const double* stamps01, int64_t n, const double T_prev[12], const double T_now[12],
                                double sensor_hz, double* out_velocity6, int32_t* out_chunks);
 
+/* The host twin of madicp_cloud_ingest_records (madicp_hip.h: the same rules, the same per-record source
+ * csrc/common/ingest_point.h, bit-equal): a driver's byte records -> the range-filtered points in input order and their stamps
+ * normalised over the scan; what a Pipeline with the host front-end runs for computeRecordsStamped.  Every field is read through
+ * memcpy; nothing past data[n_records * point_step) is touched.  out_xyz: room for (n_records, 3) doubles; out_stamps01: room
+ * for n_records doubles (optional; not written without a time field); the first *out_n rows / values are written.
+ * out_t_range (optional): the t0, t1 used.  Returns 0 — also when no record survives (*out_n = 0) — and -1 for the arguments
+ * madicp_cloud_ingest_records refuses with MADICP_ERR_INVALID, nothing written. */
+int madicp_host_ingest_records(const void* data, int64_t n_records, const madicp_record_layout* layout, double min_range,
+                               double max_range, int kitti_correction, const double* t_range, double* out_xyz, double* out_stamps01,
+                               int64_t* out_n, double out_t_range[2]);
+
 /* ---- the keyframe map sharded over the ranks of a node (Pipeline::setShard, csrc/host/pipeline.h) ---- */
 /* The rank that owns the keyframe of ORDINAL k — promotion order: the first scan is 0, every promotion adds 1; not the frame
  * id, which has gaps — among `world` ranks: rows of `world`, alternate rows reversed (csrc/common/keyframe_owner.h; the same

@@ -29,6 +29,12 @@ class IcpParams(C.Structure):
     _fields_ = [("min_ball", C.c_double), ("rho_ker", C.c_double), ("b_ratio", C.c_double)]
 
 
+class RecordLayoutC(C.Structure):
+    """madicp_record_layout (include/madicp_hip.h)"""
+    _fields_ = [("point_step", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("off_z", C.c_int32), ("off_t", C.c_int32),
+                ("t_type", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _u8p = C.POINTER(C.c_uint8)
@@ -140,6 +146,10 @@ def hip_lib():
         L.madicp_cloud_download.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64]
         L.madicp_cloud_ingest_f32.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int, C.c_double, C.c_double,
                                               C.c_int, _ip, _i64p]
+        L.madicp_cloud_ingest_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RecordLayoutC), C.c_double, C.c_double,
+                                                  C.c_int, _dp, _ip, _i64p, _dp]
+        L.madicp_cloud_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64]
+        L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
         L.madicp_tree_build.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, _ip, _i32p]
@@ -186,6 +196,8 @@ def host_lib():
         L.madicp_host_debug_deskew.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_double, C.c_int, _dp]
         L.madicp_host_deskew_stamped.argtypes = [_dp, _dp, C.c_int64, _dp, _dp, C.c_double, _dp, _i32p]
         L.madicp_host_debug_tree_points.restype = C.c_int64
+        L.madicp_host_ingest_records.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RecordLayoutC), C.c_double, C.c_double, C.c_int, _dp,
+                                                 _dp, _dp, _i64p, _dp]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
         L.madicp_host_debug_partition.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_int]
@@ -379,6 +391,38 @@ def host_deskew_stamped(points, stamps, T_prev, T_now, sensor_hz):
     return pts, vel, chunks
 
 
+def _records_args(records, layout, time_field, t_range):
+    """(array kept alive, n_records, RecordLayoutC, t_range pointer or None) of a records call: a 1-D structured array (layout
+    read off its dtype by mad_icp_amd.records unless given) or an (n, point_step) uint8 array with an explicit layout.  The
+    layout is NOT validated here when given explicitly: the native refusals are what the callers of this plumbing test."""
+    from mad_icp_amd import records as _records
+
+    r = np.ascontiguousarray(records)
+    if layout is None:
+        layout = _records.layout_of(r.dtype, time_field)
+    lay = RecordLayoutC(*(int(v) for v in layout))
+    n = r.shape[0]
+    if r.nbytes != n * lay.point_step and 12 <= lay.point_step <= 256:
+        raise ValueError("records hold %d bytes, the layout says %d x %d" % (r.nbytes, n, lay.point_step))
+    tr = None if t_range is None else np.ascontiguousarray(t_range, dtype=np.float64).reshape(2)
+    return r, n, lay, tr
+
+
+def host_ingest_records(records, min_range, max_range, kitti_correction, layout=None, time_field=None, t_range=None):
+    """madicp_host_ingest_records: the host twin of Context.cloud_ingest_records.  Returns (points (kept, 3) float64, stamps (kept,)
+    float64 or None without a time field, (t0, t1))."""
+    r, n, lay, tr = _records_args(records, layout, time_field, t_range)
+    xyz, st = np.empty((max(n, 1), 3)), np.empty(max(n, 1))
+    kept, rng = C.c_int64(0), np.empty(2)
+    rc = host_lib().madicp_host_ingest_records(r.ctypes.data_as(C.c_void_p), n, C.byref(lay), float(min_range), float(max_range),
+                                               int(bool(kitti_correction)), tr.ctypes.data_as(_dp) if tr is not None else None,
+                                               xyz.ctypes.data_as(_dp), st.ctypes.data_as(_dp), C.byref(kept), rng.ctypes.data_as(_dp))
+    if rc != 0:
+        raise MadIcpError("madicp_host_ingest_records: bad arguments")
+    k = kept.value
+    return xyz[:k].copy(), (st[:k].copy() if lay.t_type != 0 else None), (float(rng[0]), float(rng[1]))
+
+
 class Context:
     """One device + one stream (include/madicp_hip.h)."""
 
@@ -506,6 +550,32 @@ class Context:
                                                  float(min_range), float(max_range), int(bool(kitti_correction)),
                                                  C.byref(cid), C.byref(kept)))
         return cid.value, kept.value
+
+    def cloud_ingest_records(self, records, min_range, max_range, kitti_correction, layout=None, time_field=None, t_range=None):
+        """A driver's byte records (see _records_args) -> a resident, filtered cloud that carries its own normalised stamps.
+        Returns (cloud id, points kept, (t0, t1))."""
+        r, n, lay, tr = _records_args(records, layout, time_field, t_range)
+        cid, kept, rng = C.c_int(0), C.c_int64(0), np.empty(2)
+        _check(hip_lib().madicp_cloud_ingest_records(self._h, r.ctypes.data_as(C.c_void_p), n, C.byref(lay), float(min_range),
+                                                     float(max_range), int(bool(kitti_correction)),
+                                                     tr.ctypes.data_as(_dp) if tr is not None else None, C.byref(cid), C.byref(kept),
+                                                     rng.ctypes.data_as(_dp)))
+        return cid.value, kept.value, (float(rng[0]), float(rng[1]))
+
+    def cloud_stamps(self, cid):
+        """The stamps a cloud of cloud_ingest_records carries, (n,) float64 in the cloud's order; MadIcpError when it has none."""
+        n = self.cloud_size(cid)
+        out = np.empty(n)
+        _check(hip_lib().madicp_cloud_stamps(self._h, cid, out.ctypes.data_as(_dp), n))
+        return out
+
+    def cloud_deskew_own_stamps(self, cid, velocity, sensor_hz, want_chunks=False):
+        """cloud_deskew_stamped from the stamps the cloud carries itself.  Returns the chunks (n,) int32 when asked for."""
+        v = _f64(velocity, (6,))
+        chunks = np.empty(self.cloud_size(cid), np.int32) if want_chunks else None
+        _check(hip_lib().madicp_cloud_deskew_own_stamps(self._h, cid, v.ctypes.data_as(_dp), float(sensor_hz),
+                                                        chunks.ctypes.data_as(_i32p) if want_chunks else None))
+        return chunks
 
     def cloud_deskew(self, cid, velocity, sensor_hz, want_chunks=False):
         v = _f64(velocity, (6,))

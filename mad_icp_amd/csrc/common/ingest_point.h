@@ -1,0 +1,105 @@
+// What happens to ONE sensor record on its way into a cloud — ONE source for the device ingest kernels (csrc/hip/frontend.hip.h:
+// ingest_mark / ingest_scatter on float32 rows, records_mark / records_scatter on byte records) and for the host twin
+// (csrc/host/ingest_records.cpp), so the three cannot drift apart: the range filter of apps/cpp_runners/bin_runner.cpp:149-151,
+// the "kitti magic correction" of :153-158, and the normalisation of a record's time field.  Every translation unit that
+// includes this is compiled WITHOUT floating-point contraction (-ffp-contract=off; the device header adds the pragma).
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+#include "eig3.h"  // MADICP_HD, sum3c, sum3s
+
+namespace madicp_host {
+
+// the record is DROPPED: |p| < min_range or |p| > max_range or a NaN coordinate; |p| evaluated in float like
+// Eigen::Vector3f::norm() (squares summed as x^2 + (y^2 + z^2): the unrolled scalar reduction of a 3-vector, no packet for three
+// floats), compared in double.  ON a bound stays.
+MADICP_HD inline bool ingest_drops(float x, float y, float z, double min_range, double max_range) {
+  const float nrm = sqrtf(x * x + (y * y + z * z));
+  return (double)nrm < min_range || (double)nrm > max_range || x != x || y != y || z != z;
+}
+
+// float coordinates -> the cloud's doubles; kitti: rotate the point by VERTICAL_ANGLE_OFFSET about the normalised p x (0,0,1).
+// sin / cos of the constant angle come from the caller (host libm).  The rotation is Eigen's AngleAxisd::toRotationMatrix()
+// followed by a 3x3 * vector product.
+MADICP_HD inline void ingest_point(float xf, float yf, float zf, int kitti, double sin_a, double cos_a, double* o) {
+  const double x = (double)xf, y = (double)yf, z = (double)zf;
+  double o0 = x, o1 = y, o2 = z;
+  if (kitti) {
+    // rotation_vector = p.cross((0,0,1)) = (y*1 - z*0, z*0 - x*1, x*0 - y*0)
+    const double r0 = y * 1.0 - z * 0.0, r1 = z * 0.0 - x * 1.0, r2 = x * 0.0 - y * 0.0;
+    double a0 = r0, a1 = r1, a2 = r2;
+    const double sq = sum3c(r0 * r0, r1 * r1, r2 * r2);  // squaredNorm of a contiguous Vector3d
+    if (sq > 0.0) {  // Eigen's normalized(): left alone when the squared norm is not positive
+      const double nn = sqrt(sq);
+      a0 = r0 / nn; a1 = r1 / nn; a2 = r2 / nn;
+    }
+    const double s0 = sin_a * a0, s1 = sin_a * a1, s2 = sin_a * a2;
+    const double c1_0 = (1.0 - cos_a) * a0, c1_1 = (1.0 - cos_a) * a1, c1_2 = (1.0 - cos_a) * a2;
+    double R[9];
+    double tmp = c1_0 * a1;
+    R[1] = tmp - s2; R[3] = tmp + s2;
+    tmp = c1_0 * a2;
+    R[2] = tmp + s1; R[6] = tmp - s1;
+    tmp = c1_1 * a2;
+    R[5] = tmp - s0; R[7] = tmp + s0;
+    R[0] = c1_0 * a0 + cos_a; R[4] = c1_1 * a1 + cos_a; R[8] = c1_2 * a2 + cos_a;
+    o0 = sum3s(R[0] * x, R[1] * y, R[2] * z);
+    o1 = sum3s(R[3] * x, R[4] * y, R[5] * z);
+    o2 = sum3s(R[6] * x, R[7] * y, R[8] * z);
+  }
+  o[0] = o0; o[1] = o1; o[2] = o2;
+}
+// VERTICAL_ANGLE_OFFSET = (0.205 * M_PI) / 180.0 (bin_runner.cpp:55)
+inline double ingest_kitti_angle() { return (0.205 * M_PI) / 180.0; }
+
+// ---- byte records (include/madicp_hip.h: madicp_record_layout) ------------------------------------------------------------------
+// The fields of a record sit at ANY alignment (a packed 22-byte XYZIRT record, a float64 time at offset 18): they are read
+// byte-wise through memcpy, never through a cast of the address.  Little-endian, like the machine.
+constexpr int kTimeNone = 0, kTimeU32 = 6, kTimeF32 = 7, kTimeF64 = 8;  // sensor_msgs/PointField's codes (MADICP_T_*)
+constexpr int kRecordStepMin = 12, kRecordStepMax = 256;
+
+struct RecordLayout {  // madicp_record_layout, validated (record_layout_ok)
+  int32_t step, off_x, off_y, off_z, off_t, t_type;
+};
+
+inline bool record_layout_ok(const RecordLayout& L) {
+  if (L.step < kRecordStepMin || L.step > kRecordStepMax) return false;
+  const int32_t offs[3] = {L.off_x, L.off_y, L.off_z};
+  for (int32_t o : offs)
+    if (o < 0 || o > L.step - 4) return false;
+  if (L.t_type == kTimeNone) return true;
+  if (L.t_type != kTimeU32 && L.t_type != kTimeF32 && L.t_type != kTimeF64) return false;
+  const int32_t width = L.t_type == kTimeF64 ? 8 : 4;
+  return L.off_t >= 0 && L.off_t <= L.step - width;
+}
+
+MADICP_HD inline float record_f32(const unsigned char* p) {
+  float v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
+}
+// the time of a record as a double: exact for all three field types
+MADICP_HD inline double record_time(const unsigned char* p, int t_type) {
+  if (t_type == kTimeF64) {
+    double v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+  }
+  if (t_type == kTimeF32) return (double)record_f32(p);
+  uint32_t u;
+  __builtin_memcpy(&u, p, 4);
+  return (double)u;
+}
+MADICP_HD inline bool time_is_finite(double t) { return t - t == 0.0; }  // (inf - inf and NaN - NaN are NaN)
+
+// the stamp of a record, normalised over [t0, t1]: NaN unless the span is positive (all times equal, or no finite time at all);
+// +-inf and values outside [0, 1] are left as IEEE produces them — stamp_chunk() clamps them
+MADICP_HD inline double record_stamp(double t64, double t0, double t1) {
+  const double span = t1 - t0;
+  if (!(span > 0.0)) return std::numeric_limits<double>::quiet_NaN();
+  return (t64 - t0) / span;
+}
+
+}  // namespace madicp_host

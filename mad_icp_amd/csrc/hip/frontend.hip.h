@@ -4,6 +4,8 @@
 //            angle correction — apps/cpp_runners/bin_runner.cpp:126-166 of the reference
 //   deskew : Pipeline::deskew, mad_icp/src/odometry/pipeline.cpp:79-123 — azimuth sort + per-chunk constant-velocity
 //            compensation
+//   ingest of raw byte records (additive): a driver's PointCloud2-style buffer — any record step, fields at any alignment, a
+//            uint32 / float32 / float64 time field — to a filtered cloud that carries its own normalised stamps
 //   deskew from per-point timestamps (additive, the reference has none): the same time model with the chunk read off the
 //            acquisition time the sensor driver delivers for every point — one streaming kernel, input order kept
 // All of it is HBM-bound streaming work (24-32 bytes per point per pass); the kernels are coalesced grid-stride
@@ -13,6 +15,7 @@
 #include <stdint.h>
 
 #include "tree_build.hip.h"
+#include "../common/ingest_point.h"
 
 #pragma clang fp contract(off)
 
@@ -33,16 +36,14 @@ __global__ __launch_bounds__(256) void cloud_widen_f32(const float* __restrict__
 
 // ---- ingest ----------------------------------------------------------------------------------------------------
 // keep[i] = the record survives bin_runner.cpp:149-151: NOT (|p| < min_range or |p| > max_range or a NaN coordinate),
-// |p| evaluated in float like Eigen::Vector3f::norm() (squares summed as x^2 + (y^2 + z^2): the unrolled scalar
-// reduction of a 3-vector, no packet for three floats), compared in double.
+// |p| evaluated in float like Eigen::Vector3f::norm(), compared in double: madicp_host::ingest_drops
+// (csrc/common/ingest_point.h, shared with the byte-record kernels below and the host twin).
 __global__ void ingest_mark(const float* __restrict__ rec, long n, int stride, double min_range, double max_range,
                             uint32_t* __restrict__ keep) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i <= n; i += (long)gridDim.x * blockDim.x) {
     uint32_t k = 0;
     if (i < n) {
-      const float x = rec[i * stride], y = rec[i * stride + 1], z = rec[i * stride + 2];
-      const float nrm = sqrtf(x * x + (y * y + z * z));
-      const bool drop = (double)nrm < min_range || (double)nrm > max_range || isnan(x) || isnan(y) || isnan(z);
+      const bool drop = madicp_host::ingest_drops(rec[i * stride], rec[i * stride + 1], rec[i * stride + 2], min_range, max_range);
       k = drop ? 0u : 1u;
     }
     keep[i] = k;  // (entry n: the scan needs a terminator)
@@ -50,38 +51,166 @@ __global__ void ingest_mark(const float* __restrict__ rec, long n, int stride, d
 }
 // compaction in input order + conversion + the "kitti magic correction" (bin_runner.cpp:153-158): rotate the point by
 // VERTICAL_ANGLE_OFFSET about the normalised p x (0,0,1).  sin / cos of the constant angle come from the host (libm).
-// The rotation is Eigen's AngleAxisd::toRotationMatrix() followed by a 3x3 * vector product.
+// The arithmetic is madicp_host::ingest_point (csrc/common/ingest_point.h).
 __global__ void ingest_scatter(const float* __restrict__ rec, long n, int stride, const uint32_t* __restrict__ keep,
                                const uint32_t* __restrict__ pos, int kitti, double sin_a, double cos_a, double* __restrict__ out) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     if (!keep[i]) continue;
-    const double x = (double)rec[i * stride], y = (double)rec[i * stride + 1], z = (double)rec[i * stride + 2];
-    double o0 = x, o1 = y, o2 = z;
-    if (kitti) {
-      // rotation_vector = p.cross((0,0,1)) = (y*1 - z*0, z*0 - x*1, x*0 - y*0)
-      const double r0 = y * 1.0 - z * 0.0, r1 = z * 0.0 - x * 1.0, r2 = x * 0.0 - y * 0.0;
-      double a0 = r0, a1 = r1, a2 = r2;
-      const double sq = madicp_host::sum3c(r0 * r0, r1 * r1, r2 * r2);  // squaredNorm of a contiguous Vector3d
-      if (sq > 0.0) {  // Eigen's normalized(): left alone when the squared norm is not positive
-        const double nn = sqrt(sq);
-        a0 = r0 / nn; a1 = r1 / nn; a2 = r2 / nn;
-      }
-      const double s0 = sin_a * a0, s1 = sin_a * a1, s2 = sin_a * a2;
-      const double c1_0 = (1.0 - cos_a) * a0, c1_1 = (1.0 - cos_a) * a1, c1_2 = (1.0 - cos_a) * a2;
-      double R[9];
-      double tmp = c1_0 * a1;
-      R[1] = tmp - s2; R[3] = tmp + s2;
-      tmp = c1_0 * a2;
-      R[2] = tmp + s1; R[6] = tmp - s1;
-      tmp = c1_1 * a2;
-      R[5] = tmp - s0; R[7] = tmp + s0;
-      R[0] = c1_0 * a0 + cos_a; R[4] = c1_1 * a1 + cos_a; R[8] = c1_2 * a2 + cos_a;
-      o0 = madicp_host::sum3s(R[0] * x, R[1] * y, R[2] * z);
-      o1 = madicp_host::sum3s(R[3] * x, R[4] * y, R[5] * z);
-      o2 = madicp_host::sum3s(R[6] * x, R[7] * y, R[8] * z);
-    }
+    double o[3];
+    madicp_host::ingest_point(rec[i * stride], rec[i * stride + 1], rec[i * stride + 2], kitti, sin_a, cos_a, o);
     const long d = pos[i];
-    out[3 * d] = o0; out[3 * d + 1] = o1; out[3 * d + 2] = o2;
+    out[3 * d] = o[0]; out[3 * d + 1] = o[1]; out[3 * d + 2] = o[2];
+  }
+}
+
+// ---- ingest of raw byte records with a time field -----------------------------------------------------------------------------
+// What a LiDAR driver delivers (a PointCloud2-style buffer): records `step` bytes apart — ANY step from 12 to 256, so with 13 or
+// 22 every record sits at another alignment — float32 x / y / z at byte offsets, and a uint32 / float32 / float64 time field (a
+// float64 at offset 18 is never 8-aligned).  No lane may therefore load a field from global memory with a typed load.  Instead
+// a workgroup takes a TILE of consecutive records, copies the tile's bytes into LDS with coalesced aligned 16-byte loads (the
+// tail with dword loads), and each lane assembles its record's fields from LDS bytes (madicp_host::record_f32 / record_time:
+// memcpy, never a cast of the address).
+// Tile size: records_per_tile(step) records — 256 up to a step of 64 bytes, 128 up to 128, 64 up to 256 — so that a tile is at
+// most 16 KiB of LDS whatever the step: at the cap (256 records x 256 bytes = 64 KiB) two workgroups would fill a CU's 160 KiB
+// and leave three quarters of its wave slots empty, with 16 KiB the LDS never limits the eight 256-thread workgroups a CU can
+// hold.  Every tile size times any step is a multiple of 64 bytes: a tile starts 16-byte aligned.  (Chosen from the resource
+// numbers alone; this path has not been timed.)
+// The last tile's loads round its length up to a dword: up to 3 bytes past the records, which the caller's buffers cover
+// (madicp_cloud_ingest_records).  Loop bounds come from the record count, never from the tile size.
+constexpr int kRecTileDwords = 4096;  // 16 KiB
+constexpr int kRecMaxBlocks = 4096;   // workgroups of records_mark (one pair of partial extremes each)
+__host__ __device__ inline int records_per_tile(int step) { return step <= 64 ? 256 : (step <= 128 ? 128 : 64); }
+
+struct RecordsResult {  // what the host reads back after the mark pass, in one copy
+  double t0, t1;        // the range the stamps are normalised over
+  int32_t kept, pad;
+};
+
+// `src`: 16-byte aligned start of a tile in global memory, `n_bytes` <= 4 * kRecTileDwords
+__device__ inline void records_stage(const unsigned char* __restrict__ src, int n_bytes, uint32_t* __restrict__ s_tile) {
+  const int n_dw = (n_bytes + 3) >> 2, n_q = n_dw >> 2;
+  const uint4* src_q = reinterpret_cast<const uint4*>(src);
+  uint4* dst_q = reinterpret_cast<uint4*>(s_tile);
+  for (int k = threadIdx.x; k < n_q; k += blockDim.x) dst_q[k] = src_q[k];
+  const uint32_t* src_d = reinterpret_cast<const uint32_t*>(src);
+  for (int k = 4 * n_q + threadIdx.x; k < n_dw; k += blockDim.x) s_tile[k] = src_d[k];
+}
+
+// mark pass: keep[i] (entry n: the scan's terminator) and, per workgroup, the min / max of the FINITE times of ALL its records,
+// dropped ones included (the reference's point_cloud2.py:90-93 takes the whole message): part[2 b], part[2 b + 1]; +inf / -inf
+// where a workgroup saw none.  Plain comparisons and a fixed reduction shape, no floating-point atomics: min / max do not depend
+// on the order once the sign of a zero extreme is canonicalised (records_range).
+__global__ __launch_bounds__(256) void records_mark(const unsigned char* __restrict__ rec, long n, madicp_host::RecordLayout L, int per_tile,
+                                                    double min_range, double max_range, uint32_t* __restrict__ keep,
+                                                    double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
+  __shared__ double s_mn[4], s_mx[4];
+  const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
+  const long n_tiles = (n + per_tile - 1) / per_tile;
+  double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
+  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long first = tile * per_tile;
+    const int cnt = (int)min((long)per_tile, n - first);
+    records_stage(rec + first * L.step, cnt * L.step, s_tile);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const unsigned char* p = s_bytes + threadIdx.x * L.step;
+      const bool drop = madicp_host::ingest_drops(madicp_host::record_f32(p + L.off_x), madicp_host::record_f32(p + L.off_y),
+                                                  madicp_host::record_f32(p + L.off_z), min_range, max_range);
+      keep[first + threadIdx.x] = drop ? 0u : 1u;
+      if (L.t_type != madicp_host::kTimeNone) {
+        const double t = madicp_host::record_time(p + L.off_t, L.t_type);
+        if (madicp_host::time_is_finite(t)) {
+          if (t < mn) mn = t;
+          if (t > mx) mx = t;
+        }
+      }
+    }
+    __syncthreads();  // (the next trip overwrites the tile)
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) keep[n] = 0;
+  for (int m = 32; m > 0; m >>= 1) {
+    const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
+    if (a < mn) mn = a;
+    if (b > mx) mx = b;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_mn[threadIdx.x >> 6] = mn;
+    s_mx[threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      if (s_mn[w] < mn) mn = s_mn[w];
+      if (s_mx[w] > mx) mx = s_mx[w];
+    }
+    part[2 * blockIdx.x] = mn;
+    part[2 * blockIdx.x + 1] = mx;
+  }
+}
+
+// one workgroup: the join of the workgroups' extremes, canonicalised as t + 0.0 (a -0.0 extreme becomes +0.0: which of two equal
+// zeros a reduction keeps depends on its shape) — or the caller's explicit range — and the survivor count the scan left, into the
+// one block the host copies back
+__global__ __launch_bounds__(256) void records_range(const double* __restrict__ part, int n_part, int has_time, int explicit_range,
+                                                     double e0, double e1, const int32_t* __restrict__ total,
+                                                     RecordsResult* __restrict__ res) {
+  __shared__ double s_mn[4], s_mx[4];
+  double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
+  if (has_time && !explicit_range)
+    for (int k = threadIdx.x; k < n_part; k += blockDim.x) {
+      const double a = part[2 * k], b = part[2 * k + 1];
+      if (a < mn) mn = a;
+      if (b > mx) mx = b;
+    }
+  for (int m = 32; m > 0; m >>= 1) {
+    const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
+    if (a < mn) mn = a;
+    if (b > mx) mx = b;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_mn[threadIdx.x >> 6] = mn;
+    s_mx[threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      if (s_mn[w] < mn) mn = s_mn[w];
+      if (s_mx[w] > mx) mx = s_mx[w];
+    }
+    res->t0 = explicit_range ? e0 : mn + 0.0;
+    res->t1 = explicit_range ? e1 : mx + 0.0;
+    res->kept = *total;
+    res->pad = 0;
+  }
+}
+
+// scatter pass: the same staging; the survivors' points (madicp_host::ingest_point, the arithmetic of ingest_scatter) and their
+// normalised stamps (madicp_host::record_stamp over the range records_range left in device memory) to the survivor's position,
+// input order kept.  stamps == nullptr: a layout without a time field.
+__global__ __launch_bounds__(256) void records_scatter(const unsigned char* __restrict__ rec, long n, madicp_host::RecordLayout L, int per_tile,
+                                                       const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos, int kitti,
+                                                       double sin_a, double cos_a, const RecordsResult* __restrict__ res,
+                                                       double* __restrict__ out, double* __restrict__ stamps) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
+  const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
+  const long n_tiles = (n + per_tile - 1) / per_tile;
+  const double t0 = res->t0, t1 = res->t1;
+  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long first = tile * per_tile;
+    const int cnt = (int)min((long)per_tile, n - first);
+    records_stage(rec + first * L.step, cnt * L.step, s_tile);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt && keep[first + threadIdx.x]) {
+      const unsigned char* p = s_bytes + threadIdx.x * L.step;
+      double o[3];
+      madicp_host::ingest_point(madicp_host::record_f32(p + L.off_x), madicp_host::record_f32(p + L.off_y),
+                                madicp_host::record_f32(p + L.off_z), kitti, sin_a, cos_a, o);
+      const long d = pos[first + threadIdx.x];
+      out[3 * d] = o[0]; out[3 * d + 1] = o[1]; out[3 * d + 2] = o[2];
+      if (stamps) stamps[d] = madicp_host::record_stamp(madicp_host::record_time(p + L.off_t, L.t_type), t0, t1);
+    }
+    __syncthreads();
   }
 }
 

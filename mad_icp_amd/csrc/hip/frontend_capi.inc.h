@@ -12,6 +12,7 @@ namespace {
 
 struct DevCloud {
   double* xyz = nullptr;  // (n,3)
+  double* stamps = nullptr;  // (n) normalised acquisition times, the cloud's order: clouds of madicp_cloud_ingest_records only (pooled)
   int64_t n = 0;
   hipEvent_t ready = nullptr;  // recorded on the copy stream behind whatever produced xyz
 };
@@ -38,6 +39,10 @@ struct FrontScratch {
   bool state_stale = false;      // h_state is older than the device State
   double* h_table = nullptr;     // pinned, same layout as `table`
   hipEvent_t h_table_read = nullptr;
+  // ingest of byte records: the workgroups' partial time extremes, the result block and its pinned copy
+  double* rec_part = nullptr;    // (2 * fe::kRecMaxBlocks)
+  fe::RecordsResult* rec_res = nullptr;
+  fe::RecordsResult* h_rec_res = nullptr;
   // a construction between its two halves (tree_build_begin_on / tree_build_end_on)
   struct InFlight {
     bool active = false;
@@ -99,6 +104,7 @@ int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
     std::memset(fs.h_line, 0, sizeof(tb::HostLine));
     HIP_TRY(hipHostMalloc(&fs.h_table, sizeof(double) * kDeskewTableMax * 13, hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&fs.h_table_read, hipEventDisableTiming));
+    HIP_TRY(hipHostMalloc(&fs.h_rec_res, sizeof(fe::RecordsResult), hipHostMallocDefault));
   }
   if (n <= fs.n_cap) return MADICP_OK;
   if (fs.block) {
@@ -146,6 +152,8 @@ int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
   const size_t o_g = take(sizeof(int32_t) * (size_t)nc);
   const size_t o_tmin = take(sizeof(int32_t) * ((size_t)nc / tb::kScanTile + 8));
   const size_t o_table = take(sizeof(double) * kDeskewTableMax * 13);
+  const size_t o_recpart = take(sizeof(double) * 2 * fe::kRecMaxBlocks);
+  const size_t o_recres = take(sizeof(fe::RecordsResult));
   const size_t sort_bytes = sort_temp_bytes(nc);
   const size_t o_sort = take(sort_bytes);
   HIP_TRY(hipMalloc(&fs.block, off));
@@ -185,6 +193,8 @@ int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
   fs.g = reinterpret_cast<int32_t*>(b + o_g);
   fs.tile_min = reinterpret_cast<int32_t*>(b + o_tmin);
   fs.table = reinterpret_cast<double*>(b + o_table);
+  fs.rec_part = reinterpret_cast<double*>(b + o_recpart);
+  fs.rec_res = reinterpret_cast<fe::RecordsResult*>(b + o_recres);
   fs.sort_tmp = b + o_sort;
   fs.sort_tmp_bytes = sort_bytes;
   return MADICP_OK;
@@ -203,6 +213,7 @@ void front_destroy(madicp_ctx* ctx) {  // called by madicp_ctx_destroy (streams 
   if (fs.h_state) hipHostFree(fs.h_state);
   if (fs.h_line) hipHostFree(fs.h_line);
   if (fs.h_table) hipHostFree(fs.h_table);
+  if (fs.h_rec_res) hipHostFree(fs.h_rec_res);
   if (fs.h_table_read) hipEventDestroy(fs.h_table_read);
   delete ctx->front;
   ctx->front = nullptr;
@@ -228,6 +239,7 @@ int drop_cloud(madicp_ctx* ctx, DevCloud& c, int rc) {
   EventRef after;
   if (fence_event(ctx, &after) != MADICP_OK) after = nullptr;
   pool_free(ctx, c.xyz, after);
+  pool_free(ctx, c.stamps, after);
   if (c.ready) hipEventDestroy(c.ready);
   c = DevCloud{};
   return rc;
@@ -402,6 +414,7 @@ int madicp_cloud_release(madicp_ctx* ctx, int cloud_id) {
   EventRef after;
   RC_TRY(fence_event(ctx, &after));
   pool_free(ctx, c->xyz, after);
+  pool_free(ctx, c->stamps, after);
   if (c->ready) hipEventDestroy(c->ready);
   ctx->front->clouds.erase(cloud_id);
   return MADICP_OK;
@@ -476,6 +489,84 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
   front_of(ctx).clouds[id] = c;
   *out_cloud_id = id;
   *out_n = kept;
+  return MADICP_OK;
+}
+
+// A driver's byte records -> a filtered cloud with its own normalised stamps (include/madicp_hip.h; kernels: fe::records_mark,
+// fe::records_range, fe::records_scatter).  Like madicp_cloud_ingest_f32 the raw bytes go through the pinned staging into
+// buf[0] of the scratch; BOTH are sized for the length rounded up to a dword, because the last tile's loads are.
+int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_records, const madicp_record_layout* layout,
+                                double min_range, double max_range, int kitti_correction, const double* t_range, int* out_cloud_id,
+                                int64_t* out_n, double out_t_range[2]) {
+  if (!ctx || !data || !layout || !out_cloud_id || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  if (n_records < 1 || n_records > 0x3fffffff) return fail(MADICP_ERR_INVALID, "1 .. 2^30 records");
+  const madicp_host::RecordLayout L{layout->point_step, layout->off_x, layout->off_y, layout->off_z, layout->off_t, layout->t_type};
+  if (!madicp_host::record_layout_ok(L))
+    return fail(MADICP_ERR_INVALID, "record layout: point_step 12 .. 256, every field inside the record, t_type one of MADICP_T_*");
+  const bool has_time = L.t_type != madicp_host::kTimeNone;
+  if (t_range && !(std::isfinite(t_range[0]) && std::isfinite(t_range[1]) && t_range[1] > t_range[0]))
+    return fail(MADICP_ERR_INVALID, "t_range: both values finite, t_end > t_begin");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  const size_t bytes = (size_t)L.step * (size_t)n_records;
+  const size_t padded = (bytes + 3) & ~(size_t)3;  // what the last tile's dword loads reach
+  const int64_t n_layout = std::max<int64_t>(n_records, (int64_t)((padded + 23) / 24));  // (a point of the scratch is 24 bytes)
+  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
+  RC_TRY(ensure_scratch(ctx, n_layout, &fs));
+  const int hb = ctx->h_tree_next;
+  ctx->h_tree_next ^= 1;
+  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
+  if (ctx->h_tree_cap[hb] < padded) {
+    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
+    ctx->h_tree[hb] = nullptr;
+    ctx->h_tree_cap[hb] = 0;
+    const size_t cap = padded + padded / 4;
+    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
+    ctx->h_tree_cap[hb] = cap;
+  }
+  std::memcpy(ctx->h_tree[hb], data, bytes);
+  std::memset(ctx->h_tree[hb] + bytes, 0, padded - bytes);
+  unsigned char* d_rec = reinterpret_cast<unsigned char*>(fs->P.buf[0]);
+  HIP_TRY(hipMemcpyAsync(d_rec, ctx->h_tree[hb], padded, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], ctx->copy));
+  uint32_t* keep = fs->P.leaf_start;
+  const int per_tile = fe::records_per_tile(L.step);
+  const int64_t n_tiles = (n_records + per_tile - 1) / per_tile;
+  const int blocks = static_cast<int>(std::min<int64_t>(n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
+  hipLaunchKernelGGL(fe::records_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned char*)d_rec, (long)n_records, L, per_tile,
+                     min_range, max_range, keep, fs->rec_part);
+  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_records, &fs->P.st->n_leaves));
+  hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, has_time ? 1 : 0,
+                     (has_time && t_range) ? 1 : 0, t_range ? t_range[0] : 0.0, t_range ? t_range[1] : 0.0,
+                     (const int32_t*)&fs->P.st->n_leaves, fs->rec_res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(fs->h_rec_res, fs->rec_res, sizeof(fe::RecordsResult), hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the size of the result decides the allocation; the range comes with it
+  const int64_t kept = fs->h_rec_res->kept;
+  if (kept < 1) return fail(MADICP_ERR_INVALID, "no point survives the range filter");
+  DevCloud c;
+  RC_TRY(new_cloud(ctx, kept, &c));
+  if (has_time) {
+    void* p = nullptr;
+    const int rc = pool_alloc(ctx, sizeof(double) * (size_t)kept, ctx->copy, &p);
+    if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
+    c.stamps = static_cast<double*>(p);
+  }
+  const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
+  hipLaunchKernelGGL(fe::records_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned char*)d_rec, (long)n_records, L, per_tile,
+                     (const uint32_t*)keep, (const uint32_t*)fs->S, kitti_correction ? 1 : 0, std::sin(angle), std::cos(angle),
+                     (const fe::RecordsResult*)fs->rec_res, c.xyz, c.stamps);
+  CLOUD_TRY(hipGetLastError());
+  CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
+  const int id = ctx->next_id++;
+  front_of(ctx).clouds[id] = c;
+  *out_cloud_id = id;
+  *out_n = kept;
+  if (out_t_range) {
+    out_t_range[0] = fs->h_rec_res->t0;
+    out_t_range[1] = fs->h_rec_res->t1;
+  }
   return MADICP_OK;
 }
 
@@ -589,6 +680,8 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   }
   pool_free(ctx, c->xyz, after);
   c->xyz = static_cast<double*>(fresh);
+  pool_free(ctx, c->stamps, after);  // (the points are now in azimuth order: stamps in input order no longer line up)
+  c->stamps = nullptr;
   HIP_TRY(hipEventRecord(c->ready, ctx->copy));
   if (out_chunks) {  // debugging / parity aid: the time chunk of every point, in walk order (largest azimuth first)
     HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
@@ -596,6 +689,51 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   }
   return MADICP_OK;
 }
+
+}  // extern "C"
+
+namespace {
+// the second half of both stamped deskews: `d_stamps` (n, device memory, ordered on the copy stream) -> the cloud compensated
+// in place of its points
+int deskew_stamped_on(madicp_ctx* ctx, DevCloud* c, FrontScratch* fs, const double* d_stamps, const double velocity[6], double sensor_hz,
+                      int32_t* out_chunks) {
+  const int64_t n = c->n;
+  // the chunk poses, where the azimuth path keeps them (behind the thresholds, which this path does not read)
+  HIP_TRY(hipEventSynchronize(fs->h_table_read));
+  double* h_poses = fs->h_table + kDeskewTableMax;
+  double* d_poses = fs->table + kDeskewTableMax;
+  (void)deskew_table(velocity, sensor_hz, fe::kStampChunks, nullptr, h_poses);
+  HIP_TRY(hipMemcpyAsync(d_poses, h_poses, sizeof(double) * 12 * fe::kStampChunks, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
+  // the compensated cloud replaces the input: written to a fresh buffer, the old one goes back to the pool
+  void* fresh = nullptr;
+  RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)n, ctx->copy, &fresh));
+  int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;
+  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+  hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, d_stamps, (long)n,
+                     (const double*)d_poses, static_cast<double*>(fresh), d_chunks);
+  EventRef after;
+  {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
+    const hipError_t le = hipGetLastError();
+    const int frc = le == hipSuccess ? fence_event(ctx, &after) : MADICP_OK;
+    if (le != hipSuccess || frc != MADICP_OK) {
+      hipStreamSynchronize(ctx->copy);
+      pool_free(ctx, fresh, nullptr);
+      return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string("deskew_stamped: ") + hipGetErrorString(le)) : frc;
+    }
+  }
+  pool_free(ctx, c->xyz, after);
+  c->xyz = static_cast<double*>(fresh);
+  HIP_TRY(hipEventRecord(c->ready, ctx->copy));
+  if (out_chunks) {  // the time chunk of every point, in input order
+    HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
+    HIP_TRY(hipStreamSynchronize(ctx->copy));
+  }
+  return MADICP_OK;
+}
+}  // namespace
+
+extern "C" {
 
 // Motion compensation from the acquisition time of every point (fe::deskew_stamped): the same time model and pose table as
 // above, the chunk taken from the point's own stamp.  One kernel; the cloud keeps its input order.
@@ -627,37 +765,32 @@ int madicp_cloud_deskew_stamped(madicp_ctx* ctx, int cloud_id, const double* sta
   double* d_stamps = fs->key[0];
   HIP_TRY(hipMemcpyAsync(d_stamps, ctx->h_tree[hb], bytes, hipMemcpyHostToDevice, ctx->copy));
   HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], ctx->copy));
-  // the chunk poses, where the azimuth path keeps them (behind the thresholds, which this path does not read)
-  HIP_TRY(hipEventSynchronize(fs->h_table_read));
-  double* h_poses = fs->h_table + kDeskewTableMax;
-  double* d_poses = fs->table + kDeskewTableMax;
-  (void)deskew_table(velocity, sensor_hz, fe::kStampChunks, nullptr, h_poses);
-  HIP_TRY(hipMemcpyAsync(d_poses, h_poses, sizeof(double) * 12 * fe::kStampChunks, hipMemcpyHostToDevice, ctx->copy));
-  HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
-  // the compensated cloud replaces the input: written to a fresh buffer, the old one goes back to the pool
-  void* fresh = nullptr;
-  RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)n, ctx->copy, &fresh));
-  int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;
-  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
-  hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (const double*)d_stamps, (long)n,
-                     (const double*)d_poses, static_cast<double*>(fresh), d_chunks);
-  EventRef after;
-  {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
-    const hipError_t le = hipGetLastError();
-    const int frc = le == hipSuccess ? fence_event(ctx, &after) : MADICP_OK;
-    if (le != hipSuccess || frc != MADICP_OK) {
-      hipStreamSynchronize(ctx->copy);
-      pool_free(ctx, fresh, nullptr);
-      return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string("deskew_stamped: ") + hipGetErrorString(le)) : frc;
-    }
-  }
-  pool_free(ctx, c->xyz, after);
-  c->xyz = static_cast<double*>(fresh);
-  HIP_TRY(hipEventRecord(c->ready, ctx->copy));
-  if (out_chunks) {  // the time chunk of every point, in input order
-    HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
-    HIP_TRY(hipStreamSynchronize(ctx->copy));
-  }
+  return deskew_stamped_on(ctx, c, fs, d_stamps, velocity, sensor_hz, out_chunks);
+}
+
+// ... and from the stamps the cloud carries itself (madicp_cloud_ingest_records): nothing crosses PCIe but the pose table
+int madicp_cloud_deskew_own_stamps(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks) {
+  if (!ctx || !velocity) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (!c->stamps) return fail(MADICP_ERR_INVALID, "the cloud carries no stamps (madicp_cloud_ingest_records with a time field makes one that does)");
+  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, c->n, &fs));
+  return deskew_stamped_on(ctx, c, fs, c->stamps, velocity, sensor_hz, out_chunks);
+}
+
+int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int64_t n) {
+  if (!ctx || !out_stamps01) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (!c->stamps) return fail(MADICP_ERR_INVALID, "the cloud carries no stamps");
+  if (n != c->n) return fail(MADICP_ERR_INVALID, "n mismatch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out_stamps01, c->stamps, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
   return MADICP_OK;
 }
 

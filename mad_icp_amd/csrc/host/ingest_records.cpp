@@ -1,0 +1,14 @@
+// madicp_host_ingest_records (include/madicp_host.h): the C entry point of the host records ingest (ingest_records.h).  Compiled
+// without floating-point contraction, like csrc/host/deskew.cpp.
+#include "ingest_records.h"
+
+#include "madicp_host.h"
+
+extern "C" int madicp_host_ingest_records(const void* data, int64_t n_records, const madicp_record_layout* layout, double min_range,
+                                          double max_range, int kitti_correction, const double* t_range, double* out_xyz,
+                                          double* out_stamps01, int64_t* out_n, double out_t_range[2]) {
+  if (!layout) return -1;
+  const madicp_host::RecordLayout L{layout->point_step, layout->off_x, layout->off_y, layout->off_z, layout->off_t, layout->t_type};
+  return madicp_host::ingest_records(data, n_records, L, min_range, max_range, kitti_correction != 0, t_range, out_xyz, out_stamps01,
+                                     out_n, out_t_range);
+}

@@ -1,0 +1,64 @@
+// The host twin of madicp_cloud_ingest_records (include/madicp_hip.h; kernels in csrc/hip/frontend.hip.h): a driver's byte
+// records — any record step, float32 x / y / z and a uint32 / float32 / float64 time field at any alignment — to the
+// range-filtered points in input order and their stamps normalised over the scan.  The per-record arithmetic is
+// csrc/common/ingest_point.h, the one source the device kernels use as well, and this file is compiled without floating-point
+// contraction like csrc/host/deskew.cpp: bit-equal to the device by construction.  Every field is read through memcpy; nothing
+// past data[n * step) is touched.  What a Pipeline with the host front-end runs for computeRecordsStamped.
+// Defined inline here, so that every program that compiles pipeline.cpp has it whatever else it links; ingest_records.cpp holds
+// the exported C entry point (madicp_host_ingest_records, include/madicp_host.h).
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "../common/ingest_point.h"
+
+namespace madicp_host {
+
+// out_xyz: room for (n, 3) doubles, out_stamps01: room for n doubles (may be null; not written without a time field) — the first
+// *out_n rows / values are written.  t_range: null = min / max of the finite times of ALL records, each canonicalised as t + 0.0;
+// else {t_begin, t_end}.  out_t_range (optional): the range used (+inf, -inf without a time field or a finite time).
+// Returns 0; -1 on bad arguments (a null pointer, n outside 1 .. 2^30, a layout record_layout_ok refuses, a t_range that is not
+// finite and increasing), nothing written.  No survivor is NOT an error here: *out_n = 0.
+inline int ingest_records(const void* data, int64_t n, const RecordLayout& L, double min_range, double max_range, bool kitti_correction,
+                          const double* t_range, double* out_xyz, double* out_stamps01, int64_t* out_n, double* out_t_range) {
+  if (!data || !out_xyz || !out_n) return -1;
+  if (n < 1 || n > 0x3fffffff) return -1;
+  if (!record_layout_ok(L)) return -1;
+  if (t_range && !(std::isfinite(t_range[0]) && std::isfinite(t_range[1]) && t_range[1] > t_range[0])) return -1;
+  const unsigned char* rec = static_cast<const unsigned char*>(data);
+  const bool has_time = L.t_type != kTimeNone;
+  // the range: the whole message, dropped records included (apps/utils/point_cloud2.py:90-93), finite times only
+  double t0 = HUGE_VAL, t1 = -HUGE_VAL;
+  if (has_time && t_range) {
+    t0 = t_range[0];
+    t1 = t_range[1];
+  } else if (has_time) {
+    for (int64_t i = 0; i < n; ++i) {
+      const double t = record_time(rec + i * L.step + L.off_t, L.t_type);
+      if (!time_is_finite(t)) continue;
+      if (t < t0) t0 = t;
+      if (t > t1) t1 = t;
+    }
+    t0 = t0 + 0.0;  // (a -0.0 extreme becomes +0.0: which of two equal zeros a reduction keeps depends on its shape)
+    t1 = t1 + 0.0;
+  }
+  const double angle = ingest_kitti_angle();
+  const double sin_a = std::sin(angle), cos_a = std::cos(angle);
+  int64_t kept = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const unsigned char* p = rec + i * L.step;
+    const float x = record_f32(p + L.off_x), y = record_f32(p + L.off_y), z = record_f32(p + L.off_z);
+    if (ingest_drops(x, y, z, min_range, max_range)) continue;
+    ingest_point(x, y, z, kitti_correction ? 1 : 0, sin_a, cos_a, out_xyz + 3 * kept);
+    if (has_time && out_stamps01) out_stamps01[kept] = record_stamp(record_time(p + L.off_t, L.t_type), t0, t1);
+    ++kept;
+  }
+  *out_n = kept;
+  if (out_t_range) {
+    out_t_range[0] = t0;
+    out_t_range[1] = t1;
+  }
+  return 0;
+}
+
+}  // namespace madicp_host

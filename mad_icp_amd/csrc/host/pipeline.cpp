@@ -232,7 +232,7 @@ void Pipeline::prefetch(ContainerType next_cloud) {
 
 // the device front-end for one frame: the cloud is resident; deskew when the reference would (pipeline.cpp:138-139),
 // build, hand the cloud's buffer back
-std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* stamps, size_t n_stamps) {
+std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* stamps, size_t n_stamps, bool own_stamps) {
   DeviceLock lock(Device::mutex());
   madicp_ctx* ctx = Device::ctx();
   MADtree::cancelDeviceBuild(0);  // deskew and build need the builder's scratch: a look-ahead of another Pipeline gives way
@@ -241,7 +241,9 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
     if (is_initialized_ && deskew_ && trajectory_.size() > 1) {
       double vel[6];
       naiveVelocity(trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], vel);
-      if (stamps)
+      if (own_stamps)
+        check(madicp_cloud_deskew_own_stamps(ctx, cloud_id, vel, sensor_hz_, nullptr), "madicp_cloud_deskew_own_stamps");
+      else if (stamps)
         check(madicp_cloud_deskew_stamped(ctx, cloud_id, stamps, static_cast<int64_t>(n_stamps), vel, sensor_hz_, nullptr),
               "madicp_cloud_deskew_stamped");
       else
@@ -273,6 +275,55 @@ void Pipeline::computeRecords(const double& curr_stamp, const float* records, si
           "madicp_cloud_ingest_f32");
   }
   computeWithTree(curr_stamp, buildOnDevice(cloud_id), nullptr, t_pre);
+}
+
+// A frame from a driver's byte records (pipeline.h).  The time field matters only where stamps can: deskew = true and a layout
+// that has one — everywhere else the layout is taken without it, so nothing is normalised, stored or read.
+void Pipeline::computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout,
+                                     double min_range, double max_range, bool kitti_correction, const double* t_range) {
+  if (!data || n_records == 0) throw std::invalid_argument("Pipeline::computeRecordsStamped: no records");
+  RecordLayout L = layout;
+  if (!record_layout_ok(L)) throw std::invalid_argument("Pipeline::computeRecordsStamped: bad record layout");
+  if (n_records > 0x3fffffff) throw std::invalid_argument("Pipeline::computeRecordsStamped: 1 .. 2^30 records");
+  if (t_range && !(std::isfinite(t_range[0]) && std::isfinite(t_range[1]) && t_range[1] > t_range[0]))
+    throw std::invalid_argument("Pipeline::computeRecordsStamped: t_range needs two finite values, t_end > t_begin");
+  if (!deskew_) {
+    L.t_type = kTimeNone;
+    t_range = nullptr;
+  }
+  const bool stamped = L.t_type != kTimeNone;
+  const madicp_record_layout cl{L.step, L.off_x, L.off_y, L.off_z, L.off_t, L.t_type};
+  if (device_frontend_) {
+    is_map_updated_ = false;
+    const double t_pre = now_ms();
+    waitPrefetched();
+    dropDeviceLookAhead();          // (ingest shares the builder's scratch ...
+    MADtree::cancelDeviceBuild(0);  //  ... with every Pipeline of the process)
+    int cloud_id = -1;
+    {
+      DeviceLock lock(Device::mutex());
+      int64_t kept = 0;
+      check(madicp_cloud_ingest_records(Device::ctx(), data, static_cast<int64_t>(n_records), &cl, min_range, max_range,
+                                        kitti_correction ? 1 : 0, t_range, &cloud_id, &kept, nullptr),
+            "madicp_cloud_ingest_records");
+    }
+    computeWithTree(curr_stamp, buildOnDevice(cloud_id, nullptr, 0, stamped), nullptr, t_pre);
+    return;
+  }
+  ContainerType cloud(n_records);
+  std::vector<double> stamps(stamped ? n_records : 0);
+  int64_t kept = 0;
+  if (ingest_records(data, static_cast<int64_t>(n_records), L, min_range, max_range, kitti_correction, t_range, cloud[0].data(),
+                     stamped ? stamps.data() : nullptr, &kept, nullptr) != 0)
+    throw std::invalid_argument("Pipeline::computeRecordsStamped: bad arguments (record count or t_range)");
+  if (kept < 1) throw std::invalid_argument("Pipeline::computeRecordsStamped: no point survives the range filter");
+  cloud.resize(static_cast<size_t>(kept));
+  if (stamped) {
+    stamps.resize(static_cast<size_t>(kept));
+    computeStamped(curr_stamp, std::move(cloud), stamps);
+  } else {
+    compute(curr_stamp, std::move(cloud));
+  }
 }
 
 // pipeline.cpp:125-265, the device front-end's half: the scan is only READ (key of a look-ahead, or the upload), so a view does

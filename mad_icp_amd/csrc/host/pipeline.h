@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "deskew.h"
+#include "ingest_records.h"
 #include "keyframe_ledger.h"
 #include "linalg.h"
 #include "mad_icp.h"
@@ -117,6 +118,18 @@ class Pipeline {
   void computeRecords(const double& curr_stamp, const float* records, size_t n_records, int stride_floats, double min_range,
                       double max_range, bool kitti_correction);
 
+  // additive: one frame straight from a driver's BYTE records with a time field (a PointCloud2-style buffer: `layout.step` bytes
+  // apart, float32 x / y / z and a uint32 / float32 / float64 time at byte offsets, any alignment — madicp_record_layout).
+  // Device front-end: madicp_cloud_ingest_records — range filter, compaction and the stamps normalised over the scan, on the
+  // device — then, where the reference deskews, madicp_cloud_deskew_own_stamps from the stamps the cloud carries, build and
+  // registration: the time column never exists on the host.  Host front-end: the host twin (ingest_records.h), then
+  // deskew_cloud_stamped and the host builder — the same bits.  t_range: null = the min / max time over the message, else
+  // {t_begin, t_end}.  With layout.t_type == kTimeNone the frame is computeRecords' on the same coordinates, azimuth deskew
+  // included; with deskew = false the time field is ignored entirely.  No look-ahead for records.  std::invalid_argument for
+  // no records or a layout / t_range the ingest refuses.
+  void computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout, double min_range,
+                             double max_range, bool kitti_correction, const double* t_range);
+
   // additive: the keyframe map sharded over the ranks of a node.  Every rank runs ONE Pipeline and is
   // fed the same scans in the same order; setShard(rank, world) makes this one keep the tree of a keyframe only when
   // keyframe_owner(ordinal, world) == rank (csrc/common/keyframe_owner.h; ordinal: promotion order, the first scan is 0) and
@@ -160,7 +173,8 @@ class Pipeline {
   void deskew(ContainerType& curr_cloud, const Pose& T_prev, const Pose& T_now, const DeskewOrder* prep = nullptr);
   void naiveVelocity(const Pose& T_prev, const Pose& T_now, double* vel6) const;  // pipeline.cpp:82-86
   // deskew (if due; from `stamps`, one per point, when given) + build + release of the cloud
-  std::unique_ptr<MADtree> buildOnDevice(int cloud_id, const double* stamps = nullptr, size_t n_stamps = 0);
+  // (`own_stamps`: from the stamps the cloud carries itself — madicp_cloud_ingest_records)
+  std::unique_ptr<MADtree> buildOnDevice(int cloud_id, const double* stamps = nullptr, size_t n_stamps = 0, bool own_stamps = false);
   void computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree> current_tree, ContainerType* curr_cloud, double t_pre);
 
   MADicp icp_;

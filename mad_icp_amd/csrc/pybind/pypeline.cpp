@@ -2,6 +2,8 @@
 #include "common.h"
 #include "pipeline.h"
 
+#include <stdexcept>
+
 PYBIND11_MODULE(pypeline, m) {
   m.doc() = "mad_icp_amd: MAD-ICP odometry pipeline with the registration on MI355X, drop-in for mad_icp.src.pybind.pypeline";
   // the reference registers the same container in pyvector and pypeline; module_local lets both be imported
@@ -72,6 +74,36 @@ PYBIND11_MODULE(pypeline, m) {
                                max_range, kitti);
          },
          py::arg("stamp"), py::arg("records"), py::arg("min_range"), py::arg("max_range"), py::arg("kitti_correction") = false)
+    // additive: a frame straight from a driver's byte records WITH a time field (Pipeline::computeRecordsStamped): a C-contiguous
+    // 1-D numpy structured array — what a PointCloud2 reader returns — whose layout mad_icp_amd.records reads off the dtype
+    // (x, y, z float32; the time field by name, default the first of t / timestamp / time present; time_field=False: none), or
+    // an (n, point_step) uint8 array with an explicit layout = (point_step, off_x, off_y, off_z, off_t, t_type).  The array
+    // is read in place.  time_range: None = the min / max time over the message, else (t_begin, t_end).  ValueError for what the
+    // helper or the ingest refuses.
+    .def("computeRecordsStamped",
+         [](Pipeline& self, double stamp, py::array rec, double min_range, double max_range, bool kitti, py::object time_field,
+            py::object time_range, py::object layout) {
+           const py::tuple r = py::module_::import("mad_icp_amd.records").attr("resolve")(rec, time_field, layout);
+           const size_t n = r[0].cast<size_t>();
+           const py::tuple l = r[1];
+           const madicp_host::RecordLayout L{l[0].cast<int32_t>(), l[1].cast<int32_t>(), l[2].cast<int32_t>(),
+                                             l[3].cast<int32_t>(), l[4].cast<int32_t>(), l[5].cast<int32_t>()};
+           double range[2];
+           const bool have_range = !time_range.is_none();
+           if (have_range) {
+             const py::sequence tr = time_range.cast<py::sequence>();
+             if (py::len(tr) != 2) throw py::value_error("time_range must be (t_begin, t_end)");
+             range[0] = tr[0].cast<double>();
+             range[1] = tr[1].cast<double>();
+           }
+           try {
+             self.computeRecordsStamped(stamp, rec.data(), n, L, min_range, max_range, kitti, have_range ? range : nullptr);
+           } catch (const std::invalid_argument& e) {
+             throw py::value_error(e.what());
+           }
+         },
+         py::arg("stamp"), py::arg("records"), py::arg("min_range"), py::arg("max_range"), py::arg("kitti_correction") = false,
+         py::arg("time_field") = py::none(), py::arg("time_range") = py::none(), py::arg("layout") = py::none())
     // additive: the keyframe map sharded over the ranks of a node (csrc/host/pipeline.h; mad_icp_amd.sharded.shard_pipeline
     // installs the communicator and calls this)
     .def("setShard", &Pipeline::setShard, py::arg("rank"), py::arg("world"))
