@@ -31,7 +31,7 @@ struct FrontScratch {
   int32_t* g = nullptr;
   int32_t* tile_min = nullptr;
   double* table = nullptr;       // thresholds | poses
-  void* sort_tmp = nullptr;
+  char* sort_tmp = nullptr;
   size_t sort_tmp_bytes = 0;
   tb::State* h_state = nullptr;  // pinned: copy of the device State (diagnostics, big clouds)
   tb::HostLine* h_line = nullptr; // pinned: what a build publishes to the host (tb_finish_b)
@@ -95,6 +95,57 @@ int busy_with_lookahead(madicp_ctx* ctx) {
   return MADICP_OK;
 }
 
+// The scratch's sub-buffers for `nc` points, walked once: over a null base for the block's size, over the block for the pointers.
+// (The order and the sizes fix the byte count and every sub-buffer's place in the block.)
+size_t carve_scratch(FrontScratch& fs, char* base, int64_t nc) {
+  const size_t n = (size_t)nc;
+  const size_t slots = n / tb::kChunk + tb::kMaxBig + 8;
+  size_t off = 0;
+  auto carve = [&](auto*& p, size_t count) {
+    using T = std::remove_reference_t<decltype(*p)>;
+    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off = align_up(off + sizeof(T) * count);
+  };
+  tb::Params& P = fs.P;
+  carve(P.st, 1);
+  carve(P.buf[0], 3 * n);
+  carve(P.buf[1], 3 * n);
+  carve(P.nodes, 2 * n);
+  P.node_cap = static_cast<int32_t>(std::min<int64_t>(2 * nc, 0x7ffffff0));
+  carve(P.q[0], n / tb::kSmallMax + 64);  // wave-regime nodes hold > kSmallMax points
+  carve(P.q[1], n / tb::kSmallMax + 64);
+  carve(P.team[0], n / tb::kTeamMin + 64);
+  carve(P.team[1], n / tb::kTeamMin + 64);
+  carve(P.big[0], tb::kMaxBig);
+  carve(P.big[1], tb::kMaxBig);
+  carve(P.small[0], n);
+  carve(P.small[1], n);
+  carve(P.leaf_start, n + 8);
+  carve(fs.S, n + 8);
+  carve(fs.tile_sums, n / tb::kScanTile + 8);
+  P.S = fs.S;
+  P.tile_sums = fs.tile_sums;
+  carve(P.partLR, 18 * slots * (tb::kChipLevels + 1));
+  P.part_stride = (long)(18 * slots);
+  carve(P.part2, 8 * slots);
+  carve(P.tab, n + 8);
+  carve(P.top_ids, kTopMax);
+  carve(P.top_link, kTopMax);
+  carve(P.top_front, 2 + 2 * 1024);
+  carve(fs.key[0], n);
+  carve(fs.key[1], n);
+  carve(fs.idx[0], n);
+  carve(fs.idx[1], n);
+  carve(fs.g, n);
+  carve(fs.tile_min, n / tb::kScanTile + 8);
+  carve(fs.table, kDeskewTableMax * 13);
+  carve(fs.rec_part, 2 * fe::kRecMaxBlocks);
+  carve(fs.rec_res, 1);
+  fs.sort_tmp_bytes = sort_temp_bytes(nc);
+  carve(fs.sort_tmp, fs.sort_tmp_bytes);
+  return off;
+}
+
 int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
   FrontScratch& fs = front_of(ctx).scratch;
   *out = &fs;
@@ -117,86 +168,12 @@ int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
     fs.n_cap = 0;
   }
   const int64_t nc = n + n / 8 + 1024;  // head-room: consecutive scans differ by a few per cent
-  const size_t slots = (size_t)nc / tb::kChunk + tb::kMaxBig + 8;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes);
-    return o;
-  };
-  const size_t o_state = take(sizeof(tb::State));
-  const size_t o_buf0 = take(sizeof(double) * 3 * (size_t)nc);
-  const size_t o_buf1 = take(sizeof(double) * 3 * (size_t)nc);
-  const size_t o_nodes = take(sizeof(tb::BNode) * 2 * (size_t)nc);
-  const size_t o_q0 = take(sizeof(int4) * ((size_t)nc / tb::kSmallMax + 64));  // wave-regime nodes hold > kSmallMax points
-  const size_t o_q1 = take(sizeof(int4) * ((size_t)nc / tb::kSmallMax + 64));
-  const size_t o_team0 = take(sizeof(int4) * ((size_t)nc / tb::kTeamMin + 64));
-  const size_t o_team1 = take(sizeof(int4) * ((size_t)nc / tb::kTeamMin + 64));
-  const size_t o_big0 = take(sizeof(int32_t) * tb::kMaxBig);
-  const size_t o_big1 = take(sizeof(int32_t) * tb::kMaxBig);
-  const size_t o_small0 = take(sizeof(int4) * (size_t)nc);
-  const size_t o_small1 = take(sizeof(int4) * (size_t)nc);
-  const size_t o_leaf = take(sizeof(uint32_t) * ((size_t)nc + 8));
-  const size_t o_S = take(sizeof(uint32_t) * ((size_t)nc + 8));
-  const size_t o_tiles = take(sizeof(uint32_t) * ((size_t)nc / tb::kScanTile + 8));
-  const size_t o_p1 = take(sizeof(double) * 18 * slots * (tb::kChipLevels + 1));
-  const size_t o_p2 = take(sizeof(double) * 8 * slots);
-  const size_t o_tab = take(sizeof(int32_t) * ((size_t)nc + 8));
-  const size_t o_topids = take(sizeof(int32_t) * kTopMax);
-  const size_t o_toplink = take(sizeof(uint32_t) * kTopMax);
-  const size_t o_topfront = take(sizeof(int32_t) * (2 + 2 * 1024));
-  const size_t o_key0 = take(sizeof(double) * (size_t)nc);
-  const size_t o_key1 = take(sizeof(double) * (size_t)nc);
-  const size_t o_idx0 = take(sizeof(uint32_t) * (size_t)nc);
-  const size_t o_idx1 = take(sizeof(uint32_t) * (size_t)nc);
-  const size_t o_g = take(sizeof(int32_t) * (size_t)nc);
-  const size_t o_tmin = take(sizeof(int32_t) * ((size_t)nc / tb::kScanTile + 8));
-  const size_t o_table = take(sizeof(double) * kDeskewTableMax * 13);
-  const size_t o_recpart = take(sizeof(double) * 2 * fe::kRecMaxBlocks);
-  const size_t o_recres = take(sizeof(fe::RecordsResult));
-  const size_t sort_bytes = sort_temp_bytes(nc);
-  const size_t o_sort = take(sort_bytes);
-  HIP_TRY(hipMalloc(&fs.block, off));
-  fs.cap = off;
-  fs.n_cap = nc;
-  char* b = fs.block;
   fs.P = tb::Params{};
-  fs.P.st = reinterpret_cast<tb::State*>(b + o_state);
-  fs.P.buf[0] = reinterpret_cast<double*>(b + o_buf0);
-  fs.P.buf[1] = reinterpret_cast<double*>(b + o_buf1);
-  fs.P.nodes = reinterpret_cast<tb::BNode*>(b + o_nodes);
-  fs.P.node_cap = static_cast<int32_t>(std::min<int64_t>(2 * nc, 0x7ffffff0));
-  fs.P.q[0] = reinterpret_cast<int4*>(b + o_q0);
-  fs.P.q[1] = reinterpret_cast<int4*>(b + o_q1);
-  fs.P.team[0] = reinterpret_cast<int4*>(b + o_team0);
-  fs.P.team[1] = reinterpret_cast<int4*>(b + o_team1);
-  fs.P.big[0] = reinterpret_cast<int32_t*>(b + o_big0);
-  fs.P.big[1] = reinterpret_cast<int32_t*>(b + o_big1);
-  fs.P.small[0] = reinterpret_cast<int4*>(b + o_small0);
-  fs.P.small[1] = reinterpret_cast<int4*>(b + o_small1);
-  fs.P.leaf_start = reinterpret_cast<uint32_t*>(b + o_leaf);
-  fs.P.partLR = reinterpret_cast<double*>(b + o_p1);
-  fs.P.part_stride = (long)(18 * slots);
-  fs.P.part2 = reinterpret_cast<double*>(b + o_p2);
-  fs.P.tab = reinterpret_cast<int32_t*>(b + o_tab);
-  fs.P.top_ids = reinterpret_cast<int32_t*>(b + o_topids);
-  fs.P.top_link = reinterpret_cast<uint32_t*>(b + o_toplink);
-  fs.P.top_front = reinterpret_cast<int32_t*>(b + o_topfront);
-  fs.S = reinterpret_cast<uint32_t*>(b + o_S);
-  fs.tile_sums = reinterpret_cast<uint32_t*>(b + o_tiles);
-  fs.P.S = fs.S;
-  fs.P.tile_sums = fs.tile_sums;
-  fs.key[0] = reinterpret_cast<double*>(b + o_key0);
-  fs.key[1] = reinterpret_cast<double*>(b + o_key1);
-  fs.idx[0] = reinterpret_cast<uint32_t*>(b + o_idx0);
-  fs.idx[1] = reinterpret_cast<uint32_t*>(b + o_idx1);
-  fs.g = reinterpret_cast<int32_t*>(b + o_g);
-  fs.tile_min = reinterpret_cast<int32_t*>(b + o_tmin);
-  fs.table = reinterpret_cast<double*>(b + o_table);
-  fs.rec_part = reinterpret_cast<double*>(b + o_recpart);
-  fs.rec_res = reinterpret_cast<fe::RecordsResult*>(b + o_recres);
-  fs.sort_tmp = b + o_sort;
-  fs.sort_tmp_bytes = sort_bytes;
+  const size_t bytes = carve_scratch(fs, nullptr, nc);
+  HIP_TRY(hipMalloc(&fs.block, bytes));
+  fs.cap = bytes;
+  fs.n_cap = nc;
+  carve_scratch(fs, fs.block, nc);
   return MADICP_OK;
 }
 
@@ -328,18 +305,10 @@ bool block_to_f32_exact(const double* src, float* dst, size_t count) {
 int stage_and_send_cloud(madicp_ctx* ctx, const double* xyz, int64_t n, double* d_xyz, hipStream_t s) {
   const size_t n3 = 3 * (size_t)n;
   const size_t bytes = sizeof(double) * n3;
-  const int hb = ctx->h_tree_next;
-  ctx->h_tree_next ^= 1;
-  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
-  if (ctx->h_tree_cap[hb] < bytes) {
-    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
-    ctx->h_tree[hb] = nullptr;
-    ctx->h_tree_cap[hb] = 0;
-    const size_t cap = bytes + bytes / 4;
-    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
-    ctx->h_tree_cap[hb] = cap;
-  }
-  char* stage = ctx->h_tree[hb];
+  StagingSlots& st = ctx->staging;
+  int hb = 0;
+  char* stage = nullptr;
+  RC_TRY(st.acquire(bytes, &hb, &stage));
   size_t done3 = 0;  // values already on their way as floats
   void* d_f32 = nullptr;
   if (ctx->opt.upload_f32 && n3 >= 4096) {
@@ -349,15 +318,15 @@ int stage_and_send_cloud(madicp_ctx* ctx, const double* xyz, int64_t n, double* 
       const size_t len = std::min(piece3, n3 - off);
       if (!block_to_f32_exact(xyz + off, hf + off, len)) break;
       if (!d_f32) {  // (one device block per staging block: the event that frees the staging block is behind the widening too)
-        if (ctx->d_f32_cap[hb] < sizeof(float) * n3) {
-          if (ctx->d_f32[hb]) HIP_TRY(hipFree(ctx->d_f32[hb]));
-          ctx->d_f32[hb] = nullptr;
-          ctx->d_f32_cap[hb] = 0;
+        if (st.d_f32_cap[hb] < sizeof(float) * n3) {
+          if (st.d_f32[hb]) HIP_TRY(hipFree(st.d_f32[hb]));
+          st.d_f32[hb] = nullptr;
+          st.d_f32_cap[hb] = 0;
           const size_t cap = sizeof(float) * (n3 + n3 / 4);
-          HIP_TRY(hipMalloc(&ctx->d_f32[hb], cap));
-          ctx->d_f32_cap[hb] = cap;
+          HIP_TRY(hipMalloc(&st.d_f32[hb], cap));
+          st.d_f32_cap[hb] = cap;
         }
-        d_f32 = ctx->d_f32[hb];
+        d_f32 = st.d_f32[hb];
       }
       HIP_TRY(hipMemcpyAsync(static_cast<float*>(d_f32) + off, hf + off, sizeof(float) * len, hipMemcpyHostToDevice, s));
       done3 = off + len;
@@ -367,7 +336,7 @@ int stage_and_send_cloud(madicp_ctx* ctx, const double* xyz, int64_t n, double* 
       HIP_TRY(hipGetLastError());
     }
     if (done3 == n3) {
-      HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], s));
+      HIP_TRY(st.sent(hb, s));
       return MADICP_OK;
     }
   }
@@ -380,7 +349,35 @@ int stage_and_send_cloud(madicp_ctx* ctx, const double* xyz, int64_t n, double* 
       HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(d_xyz) + off, stage + off, len, hipMemcpyHostToDevice, s));
     }
   }
-  HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], s));
+  HIP_TRY(st.sent(hb, s));
+  return MADICP_OK;
+}
+
+// the epilogue of everything that makes a cloud: it gets its id
+int register_cloud(madicp_ctx* ctx, const DevCloud& c, int* out_id) {
+  const int id = ctx->next_id++;
+  front_of(ctx).clouds[id] = c;
+  *out_id = id;
+  return MADICP_OK;
+}
+
+// the prologue of both ingests: the raw records — `bytes` of them, sent as `padded` >= bytes with the rest zero — go through
+// the pinned staging into buf[0] of a scratch sized for them (a point of the scratch is 24 bytes, a KITTI record 16: wider
+// records ask for a scratch laid out for proportionally more points)
+int stage_records(madicp_ctx* ctx, const void* data, int64_t n_records, size_t bytes, size_t padded, FrontScratch** fs, void** d_rec) {
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t n_layout = std::max<int64_t>(n_records, (int64_t)((padded + 23) / 24));
+  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
+  RC_TRY(ensure_scratch(ctx, n_layout, fs));
+  int hb = 0;
+  char* stage = nullptr;
+  RC_TRY(ctx->staging.acquire(padded, &hb, &stage));
+  std::memcpy(stage, data, bytes);
+  std::memset(stage + bytes, 0, padded - bytes);
+  *d_rec = (*fs)->P.buf[0];
+  HIP_TRY(hipMemcpyAsync(*d_rec, stage, padded, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(ctx->staging.sent(hb, ctx->copy));
   return MADICP_OK;
 }
 
@@ -400,10 +397,7 @@ int madicp_cloud_upload(madicp_ctx* ctx, const double* xyz, int64_t n, int* out_
     if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
   }
   CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
-  const int id = ctx->next_id++;
-  front_of(ctx).clouds[id] = c;
-  *out_cloud_id = id;
-  return MADICP_OK;
+  return register_cloud(ctx, c, out_cloud_id);
 }
 
 int madicp_cloud_release(madicp_ctx* ctx, int cloud_id) {
@@ -444,33 +438,14 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
   if (!ctx || !records || !out_cloud_id || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
   if (n_records < 1 || n_records > 0x3fffffff) return fail(MADICP_ERR_INVALID, "1 .. 2^30 records");
   if (stride_floats < 3) return fail(MADICP_ERR_INVALID, "a record holds at least x, y, z");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
-  // the raw records go through the pinned staging into buf[0] of the scratch (a KITTI record is 16 bytes, a point of the
-  // scratch 24: wider records ask for a scratch laid out for proportionally more points)
+  void* d_raw = nullptr;
   const size_t bytes = sizeof(float) * (size_t)stride_floats * (size_t)n_records;
-  const int64_t n_layout = std::max<int64_t>(n_records, (int64_t)((bytes + 23) / 24));
-  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
-  RC_TRY(ensure_scratch(ctx, n_layout, &fs));
-  const int hb = ctx->h_tree_next;
-  ctx->h_tree_next ^= 1;
-  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
-  if (ctx->h_tree_cap[hb] < bytes) {
-    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
-    ctx->h_tree[hb] = nullptr;
-    ctx->h_tree_cap[hb] = 0;
-    const size_t cap = bytes + bytes / 4;
-    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
-    ctx->h_tree_cap[hb] = cap;
-  }
-  std::memcpy(ctx->h_tree[hb], records, bytes);
-  float* d_rec = reinterpret_cast<float*>(fs->P.buf[0]);
-  HIP_TRY(hipMemcpyAsync(d_rec, ctx->h_tree[hb], bytes, hipMemcpyHostToDevice, ctx->copy));
-  HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], ctx->copy));
+  RC_TRY(stage_records(ctx, records, n_records, bytes, bytes, &fs, &d_raw));
+  const float* d_rec = static_cast<const float*>(d_raw);
   uint32_t* keep = fs->P.leaf_start;
   const int blocks = static_cast<int>(std::min<int64_t>((n_records + 255) / 256, (int64_t)ctx->n_cus * 8));
-  hipLaunchKernelGGL(fe::ingest_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const float*)d_rec, (long)n_records, stride_floats,
+  hipLaunchKernelGGL(fe::ingest_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, stride_floats,
                      min_range, max_range, keep);
   RC_TRY(scan_marks(ctx->copy, *fs, keep, n_records, &fs->P.st->n_leaves));
   HIP_TRY(hipMemcpyAsync(&fs->h_state->n_leaves, &fs->P.st->n_leaves, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
@@ -479,17 +454,13 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
   if (kept < 1) return fail(MADICP_ERR_INVALID, "no point survives the range filter");
   DevCloud c;
   RC_TRY(new_cloud(ctx, kept, &c));
-  // VERTICAL_ANGLE_OFFSET = (0.205 * M_PI) / 180.0 (bin_runner.cpp:55); libm sin / cos like Eigen::AngleAxisd
-  const double angle = (0.205 * M_PI) / 180.0;
-  hipLaunchKernelGGL(fe::ingest_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const float*)d_rec, (long)n_records, stride_floats,
+  const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
+  hipLaunchKernelGGL(fe::ingest_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, stride_floats,
                      (const uint32_t*)keep, (const uint32_t*)fs->S, kitti_correction ? 1 : 0, std::sin(angle), std::cos(angle), c.xyz);
   CLOUD_TRY(hipGetLastError());
   CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
-  const int id = ctx->next_id++;
-  front_of(ctx).clouds[id] = c;
-  *out_cloud_id = id;
   *out_n = kept;
-  return MADICP_OK;
+  return register_cloud(ctx, c, out_cloud_id);
 }
 
 // A driver's byte records -> a filtered cloud with its own normalised stamps (include/madicp_hip.h; kernels: fe::records_mark,
@@ -506,35 +477,17 @@ int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_rec
   const bool has_time = L.t_type != madicp_host::kTimeNone;
   if (t_range && !(std::isfinite(t_range[0]) && std::isfinite(t_range[1]) && t_range[1] > t_range[0]))
     return fail(MADICP_ERR_INVALID, "t_range: both values finite, t_end > t_begin");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
+  void* d_raw = nullptr;
   const size_t bytes = (size_t)L.step * (size_t)n_records;
   const size_t padded = (bytes + 3) & ~(size_t)3;  // what the last tile's dword loads reach
-  const int64_t n_layout = std::max<int64_t>(n_records, (int64_t)((padded + 23) / 24));  // (a point of the scratch is 24 bytes)
-  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
-  RC_TRY(ensure_scratch(ctx, n_layout, &fs));
-  const int hb = ctx->h_tree_next;
-  ctx->h_tree_next ^= 1;
-  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
-  if (ctx->h_tree_cap[hb] < padded) {
-    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
-    ctx->h_tree[hb] = nullptr;
-    ctx->h_tree_cap[hb] = 0;
-    const size_t cap = padded + padded / 4;
-    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
-    ctx->h_tree_cap[hb] = cap;
-  }
-  std::memcpy(ctx->h_tree[hb], data, bytes);
-  std::memset(ctx->h_tree[hb] + bytes, 0, padded - bytes);
-  unsigned char* d_rec = reinterpret_cast<unsigned char*>(fs->P.buf[0]);
-  HIP_TRY(hipMemcpyAsync(d_rec, ctx->h_tree[hb], padded, hipMemcpyHostToDevice, ctx->copy));
-  HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], ctx->copy));
+  RC_TRY(stage_records(ctx, data, n_records, bytes, padded, &fs, &d_raw));
+  const unsigned char* d_rec = static_cast<const unsigned char*>(d_raw);
   uint32_t* keep = fs->P.leaf_start;
   const int per_tile = fe::records_per_tile(L.step);
   const int64_t n_tiles = (n_records + per_tile - 1) / per_tile;
   const int blocks = static_cast<int>(std::min<int64_t>(n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
-  hipLaunchKernelGGL(fe::records_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned char*)d_rec, (long)n_records, L, per_tile,
+  hipLaunchKernelGGL(fe::records_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, L, per_tile,
                      min_range, max_range, keep, fs->rec_part);
   RC_TRY(scan_marks(ctx->copy, *fs, keep, n_records, &fs->P.st->n_leaves));
   hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, has_time ? 1 : 0,
@@ -554,20 +507,17 @@ int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_rec
     c.stamps = static_cast<double*>(p);
   }
   const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
-  hipLaunchKernelGGL(fe::records_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned char*)d_rec, (long)n_records, L, per_tile,
+  hipLaunchKernelGGL(fe::records_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, L, per_tile,
                      (const uint32_t*)keep, (const uint32_t*)fs->S, kitti_correction ? 1 : 0, std::sin(angle), std::cos(angle),
                      (const fe::RecordsResult*)fs->rec_res, c.xyz, c.stamps);
   CLOUD_TRY(hipGetLastError());
   CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
-  const int id = ctx->next_id++;
-  front_of(ctx).clouds[id] = c;
-  *out_cloud_id = id;
   *out_n = kept;
   if (out_t_range) {
     out_t_range[0] = fs->h_rec_res->t0;
     out_t_range[1] = fs->h_rec_res->t1;
   }
-  return MADICP_OK;
+  return register_cloud(ctx, c, out_cloud_id);
 }
 
 }  // extern "C"
@@ -631,6 +581,59 @@ int deskew_table(const double velocity[6], double sensor_hz, int count, double* 
   }
   return n_thr;
 }
+
+// an entry point's prologue once its cloud is found: the scratch, free of a look-ahead and sized for the cloud
+int deskew_prologue(madicp_ctx* ctx, const DevCloud* c, double sensor_hz, FrontScratch** fs) {
+  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  return ensure_scratch(ctx, c->n, fs);
+}
+
+// deskew_table through its pinned copy to the scratch's `table` ([kDeskewTableMax thresholds | poses], both deskews keep the
+// poses in the same place): `count` poses, with the thresholds in front of them or without
+int send_deskew_table(madicp_ctx* ctx, FrontScratch* fs, const double velocity[6], double sensor_hz, int count, bool thresholds, int* n_thr) {
+  HIP_TRY(hipEventSynchronize(fs->h_table_read));
+  *n_thr = deskew_table(velocity, sensor_hz, count, thresholds ? fs->h_table : nullptr, fs->h_table + kDeskewTableMax);
+  const size_t skip = thresholds ? 0 : kDeskewTableMax;
+  HIP_TRY(hipMemcpyAsync(fs->table + skip, fs->h_table + skip, sizeof(double) * (kDeskewTableMax - skip + 12 * (size_t)count),
+                         hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
+  return MADICP_OK;
+}
+
+// The compensated cloud replaces the input: `launch(fresh)` enqueues the kernel that writes the points into a fresh buffer, the
+// old one goes back to the pool behind it — with the cloud's stamps (`drop_stamps`) where the new order no longer lines up
+// with them.  `out_chunks` (debugging / parity aid): the time chunk of every point, which the kernel left in `d_chunks`.
+template <class Launch>
+int replace_points(madicp_ctx* ctx, DevCloud* c, const char* what, bool drop_stamps, int32_t* out_chunks, const int32_t* d_chunks,
+                   Launch launch) {
+  void* fresh = nullptr;
+  RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)c->n, ctx->copy, &fresh));
+  launch(static_cast<double*>(fresh));
+  EventRef after;
+  {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
+    const hipError_t le = hipGetLastError();
+    const int frc = le == hipSuccess ? fence_event(ctx, &after) : MADICP_OK;
+    if (le != hipSuccess || frc != MADICP_OK) {
+      hipStreamSynchronize(ctx->copy);
+      pool_free(ctx, fresh, nullptr);
+      return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(le)) : frc;
+    }
+  }
+  pool_free(ctx, c->xyz, after);
+  c->xyz = static_cast<double*>(fresh);
+  if (drop_stamps) {
+    pool_free(ctx, c->stamps, after);
+    c->stamps = nullptr;
+  }
+  HIP_TRY(hipEventRecord(c->ready, ctx->copy));
+  if (out_chunks) {
+    HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)c->n, hipMemcpyDeviceToHost, ctx->copy));
+    HIP_TRY(hipStreamSynchronize(ctx->copy));
+  }
+  return MADICP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -639,17 +642,12 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   if (!ctx || !velocity) return fail(MADICP_ERR_INVALID, "null argument");
   DevCloud* c = find_cloud(ctx, cloud_id);
   if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
-  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
-  RC_TRY(ensure_scratch(ctx, c->n, &fs));
+  RC_TRY(deskew_prologue(ctx, c, sensor_hz, &fs));
   const int64_t n = c->n;
-  HIP_TRY(hipEventSynchronize(fs->h_table_read));
-  const int n_thr = deskew_table(velocity, sensor_hz, kDeskewTableMax, fs->h_table, fs->h_table + kDeskewTableMax);
+  int n_thr = 0;
+  RC_TRY(send_deskew_table(ctx, fs, velocity, sensor_hz, kDeskewTableMax, true, &n_thr));
   const int n_poses = std::min(n_thr + 1, kDeskewTableMax);
-  HIP_TRY(hipMemcpyAsync(fs->table, fs->h_table, sizeof(double) * kDeskewTableMax * 13, hipMemcpyHostToDevice, ctx->copy));
-  HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
   const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
   hipLaunchKernelGGL(fe::deskew_keys, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, fs->key[0], fs->idx[0]);
   HIP_TRY(hipGetLastError());
@@ -661,33 +659,14 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   const int tiles = static_cast<int>((n + tb::kScanTile - 1) / tb::kScanTile);
   hipLaunchKernelGGL(fe::pmin_tiles, dim3(tiles), dim3(256), 0, ctx->copy, (const int32_t*)fs->g, (long)n, fs->tile_min);
   hipLaunchKernelGGL(fe::pmin_top, dim3(1), dim3(256), 0, ctx->copy, fs->tile_min, tiles);
-  // the compensated cloud replaces the input: written to a fresh buffer, the old one goes back to the pool
-  void* fresh = nullptr;
-  RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)n, ctx->copy, &fresh));
+  // (the points end up in azimuth order — the chunks, when asked for, in walk order, largest azimuth first — and stamps in
+  // input order would no longer line up)
   int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;
-  hipLaunchKernelGGL(fe::deskew_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const double*)c->xyz, (const uint32_t*)fs->idx[1], (long)n,
-                     (const int32_t*)fs->g, (const int32_t*)fs->tile_min, (const double*)(fs->table + kDeskewTableMax), n_poses,
-                     static_cast<double*>(fresh), d_chunks);
-  EventRef after;
-  {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
-    const hipError_t le = hipGetLastError();
-    const int frc = le == hipSuccess ? fence_event(ctx, &after) : MADICP_OK;
-    if (le != hipSuccess || frc != MADICP_OK) {
-      hipStreamSynchronize(ctx->copy);
-      pool_free(ctx, fresh, nullptr);
-      return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string("deskew: ") + hipGetErrorString(le)) : frc;
-    }
-  }
-  pool_free(ctx, c->xyz, after);
-  c->xyz = static_cast<double*>(fresh);
-  pool_free(ctx, c->stamps, after);  // (the points are now in azimuth order: stamps in input order no longer line up)
-  c->stamps = nullptr;
-  HIP_TRY(hipEventRecord(c->ready, ctx->copy));
-  if (out_chunks) {  // debugging / parity aid: the time chunk of every point, in walk order (largest azimuth first)
-    HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
-    HIP_TRY(hipStreamSynchronize(ctx->copy));
-  }
-  return MADICP_OK;
+  return replace_points(ctx, c, "deskew", true, out_chunks, d_chunks, [&](double* fresh) {
+    hipLaunchKernelGGL(fe::deskew_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const double*)c->xyz, (const uint32_t*)fs->idx[1], (long)n,
+                       (const int32_t*)fs->g, (const int32_t*)fs->tile_min, (const double*)(fs->table + kDeskewTableMax), n_poses, fresh,
+                       d_chunks);
+  });
 }
 
 }  // extern "C"
@@ -698,38 +677,15 @@ namespace {
 int deskew_stamped_on(madicp_ctx* ctx, DevCloud* c, FrontScratch* fs, const double* d_stamps, const double velocity[6], double sensor_hz,
                       int32_t* out_chunks) {
   const int64_t n = c->n;
-  // the chunk poses, where the azimuth path keeps them (behind the thresholds, which this path does not read)
-  HIP_TRY(hipEventSynchronize(fs->h_table_read));
-  double* h_poses = fs->h_table + kDeskewTableMax;
-  double* d_poses = fs->table + kDeskewTableMax;
-  (void)deskew_table(velocity, sensor_hz, fe::kStampChunks, nullptr, h_poses);
-  HIP_TRY(hipMemcpyAsync(d_poses, h_poses, sizeof(double) * 12 * fe::kStampChunks, hipMemcpyHostToDevice, ctx->copy));
-  HIP_TRY(hipEventRecord(fs->h_table_read, ctx->copy));
-  // the compensated cloud replaces the input: written to a fresh buffer, the old one goes back to the pool
-  void* fresh = nullptr;
-  RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)n, ctx->copy, &fresh));
-  int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;
+  int n_thr = 0;  // (this path reads no thresholds)
+  RC_TRY(send_deskew_table(ctx, fs, velocity, sensor_hz, fe::kStampChunks, false, &n_thr));
+  const double* d_poses = fs->table + kDeskewTableMax;
+  int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;  // (input order)
   const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
-  hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, d_stamps, (long)n,
-                     (const double*)d_poses, static_cast<double*>(fresh), d_chunks);
-  EventRef after;
-  {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
-    const hipError_t le = hipGetLastError();
-    const int frc = le == hipSuccess ? fence_event(ctx, &after) : MADICP_OK;
-    if (le != hipSuccess || frc != MADICP_OK) {
-      hipStreamSynchronize(ctx->copy);
-      pool_free(ctx, fresh, nullptr);
-      return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string("deskew_stamped: ") + hipGetErrorString(le)) : frc;
-    }
-  }
-  pool_free(ctx, c->xyz, after);
-  c->xyz = static_cast<double*>(fresh);
-  HIP_TRY(hipEventRecord(c->ready, ctx->copy));
-  if (out_chunks) {  // the time chunk of every point, in input order
-    HIP_TRY(hipMemcpyAsync(out_chunks, d_chunks, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
-    HIP_TRY(hipStreamSynchronize(ctx->copy));
-  }
-  return MADICP_OK;
+  return replace_points(ctx, c, "deskew_stamped", false, out_chunks, d_chunks, [&](double* fresh) {
+    hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, d_stamps, (long)n, d_poses, fresh,
+                       d_chunks);
+  });
 }
 }  // namespace
 
@@ -743,28 +699,17 @@ int madicp_cloud_deskew_stamped(madicp_ctx* ctx, int cloud_id, const double* sta
   DevCloud* c = find_cloud(ctx, cloud_id);
   if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
   if (n != c->n) return fail(MADICP_ERR_INVALID, "n mismatch: one stamp per point of the cloud");
-  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
-  RC_TRY(ensure_scratch(ctx, n, &fs));
-  // the stamps: pinned staging shared with the cloud and tree uploads (two buffers, alternating) -> key[0] of the scratch
+  RC_TRY(deskew_prologue(ctx, c, sensor_hz, &fs));
+  // the stamps: pinned staging shared with the cloud and tree uploads -> key[0] of the scratch
   const size_t bytes = sizeof(double) * (size_t)n;
-  const int hb = ctx->h_tree_next;
-  ctx->h_tree_next ^= 1;
-  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
-  if (ctx->h_tree_cap[hb] < bytes) {
-    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
-    ctx->h_tree[hb] = nullptr;
-    ctx->h_tree_cap[hb] = 0;
-    const size_t cap = bytes + bytes / 4;
-    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
-    ctx->h_tree_cap[hb] = cap;
-  }
-  std::memcpy(ctx->h_tree[hb], stamps01, bytes);
+  int hb = 0;
+  char* stage = nullptr;
+  RC_TRY(ctx->staging.acquire(bytes, &hb, &stage));
+  std::memcpy(stage, stamps01, bytes);
   double* d_stamps = fs->key[0];
-  HIP_TRY(hipMemcpyAsync(d_stamps, ctx->h_tree[hb], bytes, hipMemcpyHostToDevice, ctx->copy));
-  HIP_TRY(hipEventRecord(ctx->h_tree_ev[hb], ctx->copy));
+  HIP_TRY(hipMemcpyAsync(d_stamps, stage, bytes, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(ctx->staging.sent(hb, ctx->copy));
   return deskew_stamped_on(ctx, c, fs, d_stamps, velocity, sensor_hz, out_chunks);
 }
 
@@ -774,11 +719,8 @@ int madicp_cloud_deskew_own_stamps(madicp_ctx* ctx, int cloud_id, const double v
   DevCloud* c = find_cloud(ctx, cloud_id);
   if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
   if (!c->stamps) return fail(MADICP_ERR_INVALID, "the cloud carries no stamps (madicp_cloud_ingest_records with a time field makes one that does)");
-  if (!(sensor_hz > 0.0)) return fail(MADICP_ERR_INVALID, "sensor_hz must be positive");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
-  RC_TRY(ensure_scratch(ctx, c->n, &fs));
+  RC_TRY(deskew_prologue(ctx, c, sensor_hz, &fs));
   return deskew_stamped_on(ctx, c, fs, c->stamps, velocity, sensor_hz, out_chunks);
 }
 
@@ -892,30 +834,6 @@ int tb_summary_wait(madicp_ctx* ctx, FrontScratch& fs, int next_step) {
   return MADICP_OK;
 }
 
-// a built tree's block: [nodes | top exit | top dfs | top link | screening records | leaf records | top records], laid out
-// for CAPACITIES (the exact counts when the host knows them, the previous scan's with head-room when it does not yet)
-size_t layout_built_tree(DevTree& t, char* blk, size_t node_cap, size_t leaf_cap, size_t top_cap) {
-  const size_t off_nodes = 0;
-  const size_t off_exit = align_up(off_nodes + sizeof(madicp_node) * node_cap);
-  const size_t off_dfs = align_up(off_exit + sizeof(int4) * top_cap);
-  const size_t off_link = align_up(off_dfs + sizeof(int) * top_cap);
-  const size_t off_cnodes = align_up(off_link + sizeof(unsigned int) * top_cap);
-  const size_t off_leaves = align_up(off_cnodes + sizeof(CNode) * node_cap);
-  const size_t off_top = align_up(off_leaves + sizeof(LeafRec) * leaf_cap);
-  const size_t total = align_up(off_top + sizeof(CNode) * std::max<size_t>(top_cap, 1));
-  if (blk) {
-    t.block = blk;
-    t.nodes = reinterpret_cast<madicp_node*>(blk + off_nodes);
-    t.top_exit = top_cap ? reinterpret_cast<int4*>(blk + off_exit) : nullptr;
-    t.top_dfs = top_cap ? reinterpret_cast<int*>(blk + off_dfs) : nullptr;
-    t.top_link = top_cap ? reinterpret_cast<unsigned int*>(blk + off_link) : nullptr;
-    t.cnodes = reinterpret_cast<CNode*>(blk + off_cnodes);
-    t.leaves = reinterpret_cast<LeafRec*>(blk + off_leaves);
-    t.top = top_cap ? reinterpret_cast<CNode*>(blk + off_top) : nullptr;
-  }
-  return total;
-}
-
 // first half of a construction: everything up to the summary of step 20 is enqueued on `s`; nothing is waited for
 int tree_build_begin_on(madicp_ctx* ctx, FrontScratch& fs, const double* d_xyz, int64_t n, double b_max, double b_min, hipStream_t s) {
   FrontScratch::InFlight& f = fs.fly;
@@ -963,8 +881,8 @@ int tree_build_begin_on(madicp_ctx* ctx, FrontScratch& fs, const double* d_xyz, 
     const size_t node_cap = 2 * (size_t)leaf_cap - 1, top_cap = (size_t)kTopMax - 1;
     DevTree t;
     void* blk = nullptr;
-    RC_TRY(pool_alloc(ctx, layout_built_tree(t, nullptr, node_cap, (size_t)leaf_cap, top_cap), s, &blk));
-    layout_built_tree(t, static_cast<char*>(blk), node_cap, (size_t)leaf_cap, top_cap);
+    RC_TRY(pool_alloc(ctx, layout_tree_block(t, nullptr, node_cap, (size_t)leaf_cap, top_cap).total, s, &blk));
+    layout_tree_block(t, static_cast<char*>(blk), node_cap, (size_t)leaf_cap, top_cap);
     hipLaunchKernelGGL(tb::tb_emit, dim3(((int)node_cap + 255) / 256 + ((int)top_cap + 255) / 256), dim3(256), 0, s, f.P, (int)node_cap, t.nodes,
                        t.cnodes, t.leaves, (int)top_cap, t.top_dfs, t.top_link, t.top_exit, t.top, 0.0, 0.0, 0.0, leaf_cap);
     const hipError_t e = hipGetLastError();
@@ -1049,8 +967,8 @@ int tree_build_end_on(madicp_ctx* ctx, FrontScratch& fs, int* out_tree_id, int32
     set_desc(t, st.origin);
   } else {
     void* blk = nullptr;
-    RC_TRY(pool_alloc(ctx, layout_built_tree(t, nullptr, (size_t)n_nodes, (size_t)n_leaves, nt), s, &blk));
-    layout_built_tree(t, static_cast<char*>(blk), (size_t)n_nodes, (size_t)n_leaves, nt);
+    RC_TRY(pool_alloc(ctx, layout_tree_block(t, nullptr, (size_t)n_nodes, (size_t)n_leaves, nt).total, s, &blk));
+    layout_tree_block(t, static_cast<char*>(blk), (size_t)n_nodes, (size_t)n_leaves, nt);
     set_desc(t, st.origin);
     // ONE launch: the DFS-preorder node array, the screening / dense leaf records and the staged top (tree_build.hip.h)
     hipLaunchKernelGGL(tb::tb_emit, dim3((n_nodes + 255) / 256 + (t.n_top + 255) / 256), dim3(256), 0, s, P, n_nodes, t.nodes, t.cnodes, t.leaves,

@@ -26,6 +26,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -141,6 +142,40 @@ struct StreamSlot {
   int L = 0;
 };
 
+// Pinned staging of whatever the host sends for the builder and the registrations to read — trees, clouds, raw records,
+// stamps: two grow-only blocks, alternating, so that the next user stages while the previous copy is in flight.  This is
+// the one place where a host write can race a DMA still reading the same pinned block, hence one owner: acquire() waits
+// for the slot's event before anybody writes, sent() records it behind the copy that reads.  Events and memory are
+// created / freed by madicp_ctx_create / _destroy.
+struct StagingSlots {
+  char* h_tree[2] = {nullptr, nullptr};
+  size_t h_tree_cap[2] = {0, 0};
+  hipEvent_t h_tree_ev[2] = {nullptr, nullptr};
+  int h_tree_next = 0;
+  void* d_f32[2] = {nullptr, nullptr};  // device landing blocks of float uploads, one per pinned block (freed by its event too)
+  size_t d_f32_cap[2] = {0, 0};
+
+  // the next slot, its previous copy finished, at least `bytes` large (a failed grow leaves it empty)
+  int acquire(size_t bytes, int* slot, char** ptr) {
+    const int hb = h_tree_next;
+    h_tree_next ^= 1;
+    HIP_TRY(hipEventSynchronize(h_tree_ev[hb]));
+    if (h_tree_cap[hb] < bytes) {
+      if (h_tree[hb]) HIP_TRY(hipHostFree(h_tree[hb]));
+      h_tree[hb] = nullptr;
+      h_tree_cap[hb] = 0;
+      const size_t cap = bytes + bytes / 4;
+      HIP_TRY(hipHostMalloc(&h_tree[hb], cap, hipHostMallocDefault));
+      h_tree_cap[hb] = cap;
+    }
+    *slot = hb;
+    *ptr = h_tree[hb];
+    return MADICP_OK;
+  }
+  // the copy out of `slot` (and whatever else must finish before the slot is written again) is enqueued on `s`
+  hipError_t sent(int slot, hipStream_t s) { return hipEventRecord(h_tree_ev[slot], s); }
+};
+
 }  // namespace
 
 struct madicp_ctx {
@@ -189,11 +224,7 @@ struct madicp_ctx {
   int last_batch = 0;
   std::vector<int> last_moving;
 
-  // pinned staging for tree uploads (two buffers, alternating)
-  char* h_tree[2] = {nullptr, nullptr};
-  size_t h_tree_cap[2] = {0, 0};
-  hipEvent_t h_tree_ev[2] = {nullptr, nullptr};
-  int h_tree_next = 0;
+  StagingSlots staging;  // pinned staging of tree, cloud, record and stamp uploads
 
   // streamed registrations
   static constexpr int kStreamSlots = 4;
@@ -209,8 +240,6 @@ struct madicp_ctx {
   bool p2p_fresh = false;    // the own mailbox has been zeroed and exported since the last attach (madicp_p2p_export)
   bool p2p_fine = false;     // ... and it is fine-grained device memory (peers' stores are visible to a running kernel)
   bool p2p_broken = false;   // a registration of this mailbox session lost a peer: the ranks' counters may disagree from here on
-  void* d_f32[2] = {nullptr, nullptr};  // device landing blocks of float uploads, one per pinned staging block (h_tree)
-  size_t d_f32_cap[2] = {0, 0};
   unsigned int p2p_epoch = 0;                             // sharded registrations so far (the same count on every rank)
 
   std::map<GraphKey, hipGraphExec_t> graphs;  // captured launch sequences, by everything they bake in
@@ -1029,7 +1058,7 @@ int madicp_ctx_create(int device_id, void* stream, madicp_ctx** out) {
     e = hipHostMalloc(&ctx->h_stage[i], sizeof(Job) * MADICP_MAX_BATCH, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming);
   }
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ctx->h_tree_ev[i], hipEventDisableTiming);
+  for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ctx->staging.h_tree_ev[i], hipEventDisableTiming);
   if (e == hipSuccess) e = hipHostMalloc(&ctx->h_fetch, sizeof(Job) * MADICP_MAX_BATCH, hipHostMallocDefault);
   if (e == hipSuccess) e = hipMalloc(&ctx->d_totals, sizeof(double) * kAcc * MADICP_MAX_BATCH * 2);
   if (e == hipSuccess) e = hipMalloc(&ctx->d_tickets, sizeof(unsigned int) * MADICP_MAX_BATCH);
@@ -1086,8 +1115,8 @@ int madicp_ctx_destroy(madicp_ctx* ctx) {
     if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]);
   }
   for (int i = 0; i < 2; ++i) {
-    if (ctx->h_tree[i]) hipHostFree(ctx->h_tree[i]);
-    if (ctx->h_tree_ev[i]) hipEventDestroy(ctx->h_tree_ev[i]);
+    if (ctx->staging.h_tree[i]) hipHostFree(ctx->staging.h_tree[i]);
+    if (ctx->staging.h_tree_ev[i]) hipEventDestroy(ctx->staging.h_tree_ev[i]);
   }
   for (int i = 0; i < madicp_ctx::kStreamSlots; ++i) {
     StreamSlot& sl = ctx->slots[i];
@@ -1100,7 +1129,7 @@ int madicp_ctx_destroy(madicp_ctx* ctx) {
     if (sl.ev_done) hipEventDestroy(sl.ev_done);
   }
   if (ctx->h_fetch) hipHostFree(ctx->h_fetch);
-  for (void* p : ctx->d_f32)
+  for (void* p : ctx->staging.d_f32)
     if (p) hipFree(p);
   for (auto* hp : ctx->h_pub)
     if (hp) hipHostFree(hp);
@@ -1217,6 +1246,35 @@ void layout_top(const madicp_node* nodes, std::vector<int>& dfs, std::vector<uns
   }
 }
 
+// A tree's block: [nodes | top exit | top dfs | top link] — what an upload sends, one contiguous copy — and behind it what the
+// device derives from that: [screening records | leaf records | top records].  Laid out for CAPACITIES (the exact counts when
+// the host knows them, the previous scan's with head-room when it does not yet) over `blk`, device or pinned; null: the sizes
+// only.  Without a top the top pointers are null and the tail is sized for one record.
+struct TreeBlockSize {
+  size_t total, uploaded;
+};
+TreeBlockSize layout_tree_block(DevTree& t, char* blk, size_t node_cap, size_t leaf_cap, size_t top_cap) {
+  const size_t off_nodes = 0;
+  const size_t off_exit = align_up(off_nodes + sizeof(madicp_node) * node_cap);
+  const size_t off_dfs = align_up(off_exit + sizeof(int4) * top_cap);
+  const size_t off_link = align_up(off_dfs + sizeof(int) * top_cap);
+  const size_t off_cnodes = align_up(off_link + sizeof(unsigned int) * top_cap);
+  const size_t off_leaves = align_up(off_cnodes + sizeof(CNode) * node_cap);
+  const size_t off_top = align_up(off_leaves + sizeof(LeafRec) * leaf_cap);
+  const size_t total = align_up(off_top + sizeof(CNode) * std::max<size_t>(top_cap, 1));
+  if (blk) {
+    t.block = blk;
+    t.nodes = reinterpret_cast<madicp_node*>(blk + off_nodes);
+    t.top_exit = top_cap ? reinterpret_cast<int4*>(blk + off_exit) : nullptr;
+    t.top_dfs = top_cap ? reinterpret_cast<int*>(blk + off_dfs) : nullptr;
+    t.top_link = top_cap ? reinterpret_cast<unsigned int*>(blk + off_link) : nullptr;
+    t.cnodes = reinterpret_cast<CNode*>(blk + off_cnodes);
+    t.leaves = reinterpret_cast<LeafRec*>(blk + off_leaves);
+    t.top = top_cap ? reinterpret_cast<CNode*>(blk + off_top) : nullptr;
+  }
+  return TreeBlockSize{total, off_cnodes};
+}
+
 void set_desc(DevTree& t, const double origin[3]) {
   t.desc.nodes = t.nodes;
   t.desc.cnodes = t.cnodes;
@@ -1280,49 +1338,27 @@ int tree_upload_impl(madicp_ctx* ctx, const madicp_node* nodes, int32_t n_nodes,
   std::vector<int4> top_exit;
   layout_top(nodes, top_dfs, top_link, top_exit);
   t.n_top = static_cast<int32_t>(top_dfs.size());
-  // one device block: what is uploaded first (contiguous, one copy), what the device derives from it behind
+  // one device block (layout_tree_block); its uploaded prefix is staged in the same layout: pinned, two blocks, so that the
+  // next upload can be staged while this one is in flight
   const size_t nt = (size_t)t.n_top;
-  const size_t off_nodes = 0;
-  const size_t off_exit = align_up(off_nodes + sizeof(madicp_node) * (size_t)n_nodes);
-  const size_t off_dfs = align_up(off_exit + sizeof(int4) * nt);
-  const size_t off_link = align_up(off_dfs + sizeof(int) * nt);
-  const size_t up_bytes = align_up(off_link + sizeof(unsigned int) * nt);
-  const size_t off_cnodes = up_bytes;
-  const size_t off_leaves = align_up(off_cnodes + sizeof(CNode) * (size_t)n_nodes);
-  const size_t off_top = align_up(off_leaves + sizeof(LeafRec) * (size_t)n_leaves);
-  const size_t total = align_up(off_top + sizeof(CNode) * std::max<size_t>(nt, 1));
-  // pinned staging (grow-only, two buffers so that the next upload can be staged while this one is in flight)
-  const int hb = ctx->h_tree_next;
-  ctx->h_tree_next ^= 1;
-  HIP_TRY(hipEventSynchronize(ctx->h_tree_ev[hb]));
-  if (ctx->h_tree_cap[hb] < up_bytes) {
-    if (ctx->h_tree[hb]) HIP_TRY(hipHostFree(ctx->h_tree[hb]));
-    ctx->h_tree[hb] = nullptr;
-    ctx->h_tree_cap[hb] = 0;
-    const size_t cap = up_bytes + up_bytes / 4;
-    HIP_TRY(hipHostMalloc(&ctx->h_tree[hb], cap, hipHostMallocDefault));
-    ctx->h_tree_cap[hb] = cap;
-  }
-  char* hs = ctx->h_tree[hb];
-  std::memcpy(hs + off_nodes, nodes, sizeof(madicp_node) * (size_t)n_nodes);
+  const TreeBlockSize size = layout_tree_block(t, nullptr, (size_t)n_nodes, (size_t)n_leaves, nt);
+  int hb = 0;
+  char* hs = nullptr;
+  RC_TRY(ctx->staging.acquire(size.uploaded, &hb, &hs));
+  DevTree staged;
+  layout_tree_block(staged, hs, (size_t)n_nodes, (size_t)n_leaves, nt);
+  std::memcpy(staged.nodes, nodes, sizeof(madicp_node) * (size_t)n_nodes);
   if (nt) {
-    std::memcpy(hs + off_exit, top_exit.data(), sizeof(int4) * nt);
-    std::memcpy(hs + off_dfs, top_dfs.data(), sizeof(int) * nt);
-    std::memcpy(hs + off_link, top_link.data(), sizeof(unsigned int) * nt);
+    std::memcpy(staged.top_exit, top_exit.data(), sizeof(int4) * nt);
+    std::memcpy(staged.top_dfs, top_dfs.data(), sizeof(int) * nt);
+    std::memcpy(staged.top_link, top_link.data(), sizeof(unsigned int) * nt);
   }
   void* blk = nullptr;
-  RC_TRY(pool_alloc(ctx, total, ctx->copy, &blk));
-  t.block = static_cast<char*>(blk);
-  t.nodes = reinterpret_cast<madicp_node*>(t.block + off_nodes);
-  t.top_exit = nt ? reinterpret_cast<int4*>(t.block + off_exit) : nullptr;
-  t.top_dfs = nt ? reinterpret_cast<int*>(t.block + off_dfs) : nullptr;
-  t.top_link = nt ? reinterpret_cast<unsigned int*>(t.block + off_link) : nullptr;
-  t.cnodes = reinterpret_cast<CNode*>(t.block + off_cnodes);
-  t.leaves = reinterpret_cast<LeafRec*>(t.block + off_leaves);
-  t.top = nt ? reinterpret_cast<CNode*>(t.block + off_top) : nullptr;
+  RC_TRY(pool_alloc(ctx, size.total, ctx->copy, &blk));
+  layout_tree_block(t, static_cast<char*>(blk), (size_t)n_nodes, (size_t)n_leaves, nt);
   set_desc(t, nodes[0].mean);
-  hipError_t e = hipMemcpyAsync(t.block, hs, up_bytes, hipMemcpyHostToDevice, ctx->copy);
-  if (e == hipSuccess) e = hipEventRecord(ctx->h_tree_ev[hb], ctx->copy);
+  hipError_t e = hipMemcpyAsync(t.block, hs, size.uploaded, hipMemcpyHostToDevice, ctx->copy);
+  if (e == hipSuccess) e = ctx->staging.sent(hb, ctx->copy);
   int rc = MADICP_OK;
   if (e == hipSuccess) rc = compact_tree(t, ctx->copy);
   if (e == hipSuccess && rc == MADICP_OK) e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);

@@ -69,9 +69,24 @@ Pipeline::Pipeline(double sensor_hz, bool deskew, double b_max, double rho_ker, 
 
 void Pipeline::waitPrefetched() {
   for (Prefetched& p : prefetched_)
-    if (p.tree.valid()) p.tree.wait();
+    if (p.result.valid()) p.result.wait();
   for (DeskewAhead& a : deskew_ahead_)
-    if (a.order.valid()) a.order.wait();
+    if (a.result.valid()) a.result.wait();
+}
+
+template <class T>
+bool Pipeline::takeLookAhead(std::deque<LookAhead<T>>& ahead, const Vector3d* cloud, size_t n, LookAhead<T>* hit) {
+  for (size_t q = 0; q < ahead.size(); ++q) {
+    if (!ahead[q].key.matches(cloud, n)) continue;
+    for (size_t d = 0; d < q; ++d) {
+      if (ahead.front().result.valid()) ahead.front().result.wait();
+      ahead.pop_front();
+    }
+    *hit = std::move(ahead.front());
+    ahead.pop_front();
+    return true;
+  }
+  return false;
 }
 
 // A look-ahead result belongs to the scan it was computed from: size, end points and a digest of a strided sample of the
@@ -207,24 +222,24 @@ void Pipeline::prefetch(ContainerType next_cloud) {
   // azimuth of every point and their order do not (deskew.h): that half is started now
   if (deskew_ && is_initialized_) {
     while (deskew_ahead_.size() >= kMaxLookAhead) {
-      if (deskew_ahead_.front().order.valid()) deskew_ahead_.front().order.wait();
+      if (deskew_ahead_.front().result.valid()) deskew_ahead_.front().result.wait();
       deskew_ahead_.pop_front();
     }
     DeskewAhead a;
     a.key = DevKey::of(next_cloud);
-    a.order = std::async(std::launch::async, [cloud = std::move(next_cloud)]() { return deskew_order(cloud); });
+    a.result = std::async(std::launch::async, [cloud = std::move(next_cloud)]() { return deskew_order(cloud); });
     deskew_ahead_.push_back(std::move(a));
     return;
   }
   while (prefetched_.size() >= kMaxLookAhead) {  // the oldest one makes room (its build is waited for)
-    if (prefetched_.front().tree.valid()) prefetched_.front().tree.wait();
+    if (prefetched_.front().result.valid()) prefetched_.front().result.wait();
     prefetched_.pop_front();
   }
   Prefetched p;
   p.key = DevKey::of(next_cloud);
   const double b_max = b_max_, b_min = b_min_;
   const int levels = max_parallel_levels_;
-  p.tree = std::async(std::launch::async, [cloud = std::move(next_cloud), b_max, b_min, levels]() mutable {
+  p.result = std::async(std::launch::async, [cloud = std::move(next_cloud), b_max, b_min, levels]() mutable {
     return build_tree(cloud.front().data(), static_cast<int64_t>(cloud.size()), b_max, b_min, levels);
   });
   prefetched_.push_back(std::move(p));
@@ -258,14 +273,27 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
   return tree;
 }
 
+std::unique_ptr<MADtree> Pipeline::uploadAndBuild(const Vector3d* cloud, size_t n, const double* stamps) {
+  int cloud_id = -1;
+  {
+    DeviceLock lock(Device::mutex());
+    check(madicp_cloud_upload(Device::ctx(), cloud[0].data(), static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
+  }
+  return buildOnDevice(cloud_id, stamps, stamps ? n : 0);
+}
+
+void Pipeline::ingestPrologue() {
+  waitPrefetched();
+  dropDeviceLookAhead();          // (ingest shares the builder's scratch ...
+  MADtree::cancelDeviceBuild(0);  //  ... with every Pipeline of the process)
+}
+
 void Pipeline::computeRecords(const double& curr_stamp, const float* records, size_t n_records, int stride_floats,
                               double min_range, double max_range, bool kitti_correction) {
   is_map_updated_ = false;
   if (!records || n_records == 0) throw std::invalid_argument("Pipeline::computeRecords: no records");
   const double t_pre = now_ms();
-  waitPrefetched();
-  dropDeviceLookAhead();          // (ingest shares the builder's scratch ...
-  MADtree::cancelDeviceBuild(0);  //  ... with every Pipeline of the process)
+  ingestPrologue();
   int cloud_id = -1;
   {
     DeviceLock lock(Device::mutex());
@@ -296,9 +324,7 @@ void Pipeline::computeRecordsStamped(const double& curr_stamp, const void* data,
   if (device_frontend_) {
     is_map_updated_ = false;
     const double t_pre = now_ms();
-    waitPrefetched();
-    dropDeviceLookAhead();          // (ingest shares the builder's scratch ...
-    MADtree::cancelDeviceBuild(0);  //  ... with every Pipeline of the process)
+    ingestPrologue();
     int cloud_id = -1;
     {
       DeviceLock lock(Device::mutex());
@@ -350,12 +376,7 @@ void Pipeline::computeView(const double& curr_stamp, const Vector3d* curr_cloud,
     // first scan came without a prefetch stays one ahead from there on): it is collected and kept — the synchronous build
     // below needs the builder's scratch, so it has to be finished either way — not thrown away.
     collectDeviceLookAhead();
-    int cloud_id = -1;
-    {
-      DeviceLock lock(Device::mutex());
-      check(madicp_cloud_upload(Device::ctx(), curr_cloud[0].data(), static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
-    }
-    current_tree = buildOnDevice(cloud_id);
+    current_tree = uploadAndBuild(curr_cloud, n);
   }
   computeWithTree(curr_stamp, std::move(current_tree), nullptr, t_pre);
 }
@@ -374,22 +395,11 @@ void Pipeline::computeStampedView(const double& curr_stamp, const Vector3d* curr
   std::unique_ptr<MADtree> current_tree;
   if (device_frontend_) {
     collectDeviceLookAhead();  // (the synchronous build needs the builder's scratch: as in computeView)
-    int cloud_id = -1;
-    {
-      DeviceLock lock(Device::mutex());
-      check(madicp_cloud_upload(Device::ctx(), curr_cloud[0].data(), static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
-    }
-    current_tree = buildOnDevice(cloud_id, stamps, n);
+    current_tree = uploadAndBuild(curr_cloud, n, stamps);
   } else {
     // the azimuth order prefetch() computed ahead for this scan (and older ones: scans that never came) is not needed
-    for (size_t q = 0; q < deskew_ahead_.size(); ++q) {
-      if (!deskew_ahead_[q].key.matches(curr_cloud, n)) continue;
-      for (size_t d = 0; d <= q; ++d) {
-        if (deskew_ahead_.front().order.valid()) deskew_ahead_.front().order.wait();
-        deskew_ahead_.pop_front();
-      }
-      break;
-    }
+    DeskewAhead unused;
+    if (takeLookAhead(deskew_ahead_, curr_cloud, n, &unused) && unused.result.valid()) unused.result.wait();
     ContainerType cloud(curr_cloud, curr_cloud + n);  // (the host builder takes the points over)
     deskew_cloud_stamped(cloud, stamps, trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], sensor_hz_, nullptr);
     current_tree = std::make_unique<MADtree>(std::move(cloud), b_max_, b_min_, max_parallel_levels_);
@@ -420,19 +430,10 @@ void Pipeline::compute(const double& curr_stamp, ContainerType curr_cloud) {
   const double t_pre = now_ms();
   if (!prefetched_.empty() && !(deskew_ && is_initialized_ && trajectory_.size() > 1)) {
     // the look-ahead built for exactly this scan, if there is one; older look-aheads are for scans that never came
-    for (size_t q = 0; q < prefetched_.size(); ++q) {
-      const Prefetched& p = prefetched_[q];
-      if (p.key.matches(curr_cloud)) {
-        for (size_t d = 0; d < q; ++d) {
-          if (prefetched_.front().tree.valid()) prefetched_.front().tree.wait();
-          prefetched_.pop_front();
-        }
-        LinearTree built = prefetched_.front().tree.get();  // (waits for the builder thread)
-        prefetched_.pop_front();
-        current_tree = std::make_unique<MADtree>(std::move(built));
-        ++look_ahead_hits_;
-        break;
-      }
+    Prefetched p;
+    if (takeLookAhead(prefetched_, curr_cloud.data(), curr_cloud.size(), &p)) {
+      current_tree = std::make_unique<MADtree>(p.result.get());  // (waits for the builder thread)
+      ++look_ahead_hits_;
     }
   }
   computeWithTree(curr_stamp, std::move(current_tree), &curr_cloud, t_pre);
@@ -467,16 +468,10 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
     if (deskew_ && trajectory_.size() > 1) {
       // the azimuth order computed ahead for exactly this scan, if there is one (older ones: scans that never came)
       DeskewOrder ahead;
-      bool have = false;
-      for (size_t q = 0; q < deskew_ahead_.size() && !have; ++q) {
-        if (!deskew_ahead_[q].key.matches(*cloud)) continue;
-        for (size_t d = 0; d < q; ++d) {
-          if (deskew_ahead_.front().order.valid()) deskew_ahead_.front().order.wait();
-          deskew_ahead_.pop_front();
-        }
-        ahead = deskew_ahead_.front().order.get();
-        deskew_ahead_.pop_front();
-        have = true;
+      DeskewAhead a;
+      const bool have = takeLookAhead(deskew_ahead_, cloud->data(), cloud->size(), &a);
+      if (have) {
+        ahead = a.result.get();
         ++look_ahead_hits_;
       }
       deskew(*cloud, trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], have ? &ahead : nullptr);

@@ -175,6 +175,8 @@ class Pipeline {
   // deskew (if due; from `stamps`, one per point, when given) + build + release of the cloud
   // (`own_stamps`: from the stamps the cloud carries itself — madicp_cloud_ingest_records)
   std::unique_ptr<MADtree> buildOnDevice(int cloud_id, const double* stamps = nullptr, size_t n_stamps = 0, bool own_stamps = false);
+  std::unique_ptr<MADtree> uploadAndBuild(const Vector3d* cloud, size_t n, const double* stamps = nullptr);  // madicp_cloud_upload + buildOnDevice
+  void ingestPrologue();  // the builder's scratch is this frame's: no look-ahead of this Pipeline or another one holds it
   void computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree> current_tree, ContainerType* curr_cloud, double t_pre);
 
   MADicp icp_;
@@ -203,10 +205,16 @@ class Pipeline {
   };
   // look-ahead builds: up to three scans ahead of the one being consumed (kMaxLookAhead), each matched to its scan by its
   // key (a prefetch(i + 1) issued BEFORE compute(i) must not cost scan i its tree)
-  struct Prefetched {
+  template <class T>
+  struct LookAhead {
     DevKey key;
-    std::future<LinearTree> tree;
+    std::future<T> result;
   };
+  using Prefetched = LookAhead<LinearTree>;
+  // the look-ahead made for exactly this scan, if `ahead` holds one: handed out in *hit and taken off the queue, with the
+  // older ones in front of it (scans that never came; each is waited for)
+  template <class T>
+  static bool takeLookAhead(std::deque<LookAhead<T>>& ahead, const Vector3d* cloud, size_t n, LookAhead<T>* hit);
   static constexpr size_t kMaxLookAhead = 4;  // scan i being consumed, up to three more building
   std::deque<Prefetched> prefetched_;
   void waitPrefetched();  // every look-ahead build has finished (their trees stay available)
@@ -215,10 +223,7 @@ class Pipeline {
   // compute(i) the tree of scan i is collected at prefetch(i + 1) and scan i + 1 is built while scan i registers
   // deskewed datasets: the tree needs the two previous poses, but the azimuth order of the scan does not — that half of
   // Pipeline::deskew (atan2 per point, the sort: most of a deskewed frame on the host) is what prefetch() computes ahead
-  struct DeskewAhead {
-    DevKey key;
-    std::future<DeskewOrder> order;
-  };
+  using DeskewAhead = LookAhead<DeskewOrder>;
   std::deque<DeskewAhead> deskew_ahead_;
   unsigned dev_pending_ = 0;  // ticket (MADtree::beginDeviceBuild), 0: none
   ContainerType dev_next_cloud_;  // the scan prefetch() was given, staged and begun by compute() WHILE its registration is in
