@@ -218,7 +218,8 @@ int madicp_icp_fetch_matched(madicp_ctx* ctx, int scan, uint8_t* out_matched, in
  * number.  madicp_icp_publish_collect(ticket) waits for that number (bounded like madicp_stream_collect: "wait_mode",
  * "wait_timeout_ms", "comm_timeout_ms") and copies the results out — whenever the caller likes, typically after it has uploaded
  * (madicp_moving_update_async) and enqueued the NEXT batch.  A ring of four result blocks: a ticket must be collected before
- * the fourth batch after it is published. */
+ * the fourth batch after it is published.  Only MADICP_ERR_TIMEOUT keeps the ticket (the batch is still in flight: collect it
+ * again); every other error of madicp_icp_publish_collect is terminal and releases the ticket and its block, like a success. */
 int madicp_icp_publish_enqueue(madicp_ctx* ctx, int n_scans, int* out_ticket);
 int madicp_icp_publish_collect(madicp_ctx* ctx, int ticket, int n_scans, double* out_X, double* out_H, double* out_b,
                                int32_t* out_n_matched, uint64_t* out_visits);

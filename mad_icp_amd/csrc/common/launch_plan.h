@@ -86,9 +86,9 @@ struct Options {
                            // collective; a loss without one, and with halves of one scan)
   int stage_min_leaves = 1024;  // LDS staging threshold (leaves per unit); 0 = always, huge = never (measured break-even ~1000)
   int comm_timeout_ms = 60000;  // bounded host wait behind a registration's collectives
-  // how the host waits for a sequence number the device publishes (stream_collect, tree_build)
+  // how the host waits for a sequence number the device publishes (seq_wait.h: stream_collect, icp_publish_collect, tree_build)
   int wait_mode = 0;        // 0 spin, 1 sched_yield, 2 sleep ~50 us
-  int wait_timeout_ms = 0;  // 0: unbounded
+  int wait_timeout_ms = 0;  // 0: unbounded; the two collects only — a tree build has no ticket to collect again and waits unbounded
 };
 
 // One row per settable key.  Bool: any non-zero value is 1.  Range: a value outside lo..hi is refused with `err`.

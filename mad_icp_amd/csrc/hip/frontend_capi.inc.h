@@ -805,19 +805,11 @@ int tb_summary_wait(madicp_ctx* ctx, FrontScratch& fs, int next_step) {
   FrontScratch::InFlight& f = fs.fly;
   tb::HostLine& hl = *fs.h_line;
   if (f.n_tiles <= tb::kScanDirectMax) {
-    const int seq = f.seq;
-    const unsigned check_mask = ctx->opt.wait_mode == 0 ? 0x3ffu : 0xfu;  // (option "wait_mode": spin / yield / sleep)
-    for (unsigned spins = 1; __atomic_load_n(&hl.seq, __ATOMIC_ACQUIRE) != seq; ++spins) {
-      if ((spins & check_mask) == 0) {  // every few tens of microseconds: is the stream still alive?
-        const hipError_t q = hipStreamQuery(f.s);
-        if (q == hipSuccess) {
-          if (__atomic_load_n(&hl.seq, __ATOMIC_ACQUIRE) == seq) break;
-          return fail(MADICP_ERR_DEVICE, "tree build: finished without publishing its summary");
-        }
-        if (q != hipErrorNotReady) return fail(MADICP_ERR_DEVICE, std::string("tree build: ") + hipGetErrorString(q));
-      }
-      wait_pause(ctx);
-    }
+    // (unbounded: a build has no ticket to collect again, and no collective behind it; option "wait_mode" alone applies)
+    const SeqWait w = wait_for_seq(ctx, &hl.seq, f.seq, WaitLimits{ctx->opt.wait_mode, 0, 0}, 0, f.s);
+    if (w.outcome == WaitOutcome::FinishedSilent) return fail(MADICP_ERR_DEVICE, "tree build: finished without publishing its summary");
+    if (w.outcome == WaitOutcome::StreamError)
+      return fail(MADICP_ERR_DEVICE, std::string("tree build: ") + hipGetErrorString((hipError_t)w.stream_error));
     return MADICP_OK;
   }
   // huge clouds: three-kernel scan, summary, the State copied back

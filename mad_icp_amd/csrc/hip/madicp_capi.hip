@@ -10,6 +10,7 @@
 #include "madicp_hip_measure.h"
 #include "kernels.hip.h"
 #include "frontend.hip.h"  // + tree_build.hip.h: device front-end
+#include "../common/seq_wait.h"
 
 #include <hip/hip_ext.h>
 #include <rccl/rccl.h>
@@ -378,6 +379,39 @@ int comm_abort(madicp_ctx* ctx, const std::string& why) {
   return fail(MADICP_ERR_COMM, why + "; communicator aborted");
 }
 
+std::string comm_timeout_text(const madicp_ctx* ctx) {
+  return "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) + " ms (a rank did not join?)";
+}
+
+long long now_ms() {
+  return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+// the bounds of a wait for a sequence number the device publishes (seq_wait.h)
+WaitLimits wait_limits(const madicp_ctx* ctx) {
+  return WaitLimits{ctx->opt.wait_mode, ctx->opt.wait_timeout_ms, ctx->comm ? ctx->opt.comm_timeout_ms : 0};
+}
+// ... and the wait: `s` is the stream the number comes from, `t0` the now_ms() the bounds count from
+inline SeqWait wait_for_seq(const madicp_ctx* ctx, const int32_t* seq, int32_t want, const WaitLimits& lim, long long t0, hipStream_t s) {
+  return seq_wait(
+      seq, want, lim, t0,
+      [s] {
+        const hipError_t q = hipStreamQuery(s);
+        return q == hipSuccess ? kStreamDone : q == hipErrorNotReady ? kStreamRunning : (int)q;
+      },
+      now_ms, [ctx] { wait_pause(ctx); });
+}
+// What a collect by ticket returns for a wait that did not end in Published; `what`: "registration" / "batch".  WaitTimeout
+// alone leaves the ticket collectable — the caller gives the slot back on every other outcome.
+int wait_failure(madicp_ctx* ctx, const SeqWait& w, const std::string& what) {
+  switch (w.outcome) {
+    case WaitOutcome::WaitTimeout: return fail(MADICP_ERR_TIMEOUT, what + " still in flight after wait_timeout_ms; collect the ticket again");
+    case WaitOutcome::FinishedSilent: return fail(MADICP_ERR_DEVICE, what + " finished without publishing its results");
+    case WaitOutcome::StreamError: return fail(MADICP_ERR_DEVICE, what + " failed: " + hipGetErrorString((hipError_t)w.stream_error));
+    // over the limit and no results: the communicator is aborted and the ticket is gone — no second wait of comm_timeout_ms
+    default: return comm_abort(ctx, comm_timeout_text(ctx));
+  }
+}
+
 // Host wait for everything enqueued on `s`.  Without a communicator this is hipStreamSynchronize.  With one, a peer
 // that never joins a collective would park this rank's stream for ever: poll instead, ask RCCL for asynchronous errors,
 // and after "comm_timeout_ms" abort the communicator — the hang becomes MADICP_ERR_COMM.
@@ -396,9 +430,7 @@ int bounded_sync(madicp_ctx* ctx, hipStream_t s) {
       const bool bad = ncclCommGetAsyncError(ctx->comm, &ar) == ncclSuccess && ar != ncclSuccess && ar != ncclInProgress;
       const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
       if (bad || ms > ctx->opt.comm_timeout_ms)
-        return comm_abort(ctx, bad ? std::string("RCCL asynchronous error: ") + ncclGetErrorString(ar)
-                                   : "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) +
-                                         " ms (a rank did not join?)");
+        return comm_abort(ctx, bad ? std::string("RCCL asynchronous error: ") + ncclGetErrorString(ar) : comm_timeout_text(ctx));
     }
     if (spins < 256)
       __builtin_ia32_pause();
@@ -590,6 +622,34 @@ int enqueue_rounds_split(madicp_ctx* ctx, const Plan l[2], const Part p[2], cons
   return rc;
 }
 
+// What `enqueue` puts on the compute stream, captured and instantiated.  The capture is ended whatever `enqueue` returns, and the
+// graph does not outlive the call.
+template <class Enqueue>
+int capture_graph(madicp_ctx* ctx, Enqueue&& enqueue, hipGraphExec_t* out_exec) {
+  hipGraph_t graph = nullptr;
+  HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue();
+  hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
+  if (rc != MADICP_OK || e != hipSuccess) {
+    if (graph) hipGraphDestroy(graph);
+    return rc != MADICP_OK ? rc : fail(MADICP_ERR_DEVICE, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+  }
+  e = hipGraphInstantiate(out_exec, graph, nullptr, nullptr, 0);
+  hipGraphDestroy(graph);
+  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+  return MADICP_OK;
+}
+
+#ifdef MADICP_MEASURE
+// the two timing events of the measurement entry points, created on first use
+int timing_events(madicp_ctx* ctx) {
+  if (ctx->ev_t0) return MADICP_OK;
+  HIP_TRY(hipEventCreate(&ctx->ev_t0));
+  HIP_TRY(hipEventCreate(&ctx->ev_t1));
+  return MADICP_OK;
+}
+#endif
+
 // slot: which device Job array the sequence works on (-1: ctx->d_jobs; >= 0: that stream slot's) — part of the graph key
 // queued_behind, allow_graph: see graph_ok (launch_plan.h)
 int run_rounds(madicp_ctx* ctx, const Plan& l, Job* d_jobs, int slot, const std::vector<int>& moving_ids, bool queued_behind,
@@ -601,18 +661,8 @@ int run_rounds(madicp_ctx* ctx, const Plan& l, Job* d_jobs, int slot, const std:
   auto it = ctx->graphs.find(key);
   if (it == ctx->graphs.end()) {
     auto instantiate = [&](Job* jobs, const GraphKey& k) -> int {
-      hipGraph_t graph = nullptr;
-      HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      const int rc = enqueue_rounds(ctx, l, jobs, moving_ids);
-      hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
-      if (rc != MADICP_OK || e != hipSuccess) {
-        if (graph) hipGraphDestroy(graph);
-        return rc != MADICP_OK ? rc : fail(MADICP_ERR_DEVICE, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-      }
       hipGraphExec_t exec = nullptr;
-      e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-      if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+      RC_TRY(capture_graph(ctx, [&] { return enqueue_rounds(ctx, l, jobs, moving_ids); }, &exec));
       ctx->graphs.emplace(k, exec);
       return MADICP_OK;
     };
@@ -986,10 +1036,51 @@ int launch_registration(madicp_ctx* ctx, const Staged& st, bool allow_graph) {
   return rc;
 }
 
+// The tail of madicp_icp_register / madicp_icp_linearize: the optional device buffer of a registration that ended with `rc` is
+// downloaded, the stream drained, the buffer given back to the pool.  `what`: the prefix of a failed download's message.
+int download_and_free(madicp_ctx* ctx, int rc, void* d_buf, void* out, size_t bytes, const char* what) {
+  if (!d_buf) return rc;
+  if (rc == MADICP_OK) {
+    hipError_t e = hipMemcpyAsync(out, d_buf, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = fail(MADICP_ERR_DEVICE, std::string(what) + hipGetErrorString(e));
+  }
+  hipStreamSynchronize(ctx->stream);
+  pool_free(ctx, d_buf, nullptr);
+  return rc;
+}
+
 int enqueue_registration(madicp_ctx* ctx, const RegArgs& a) {
   Staged st;
   RC_TRY(stage_registration(ctx, a, &st));
   return launch_registration(ctx, st, a.allow_graph);
+}
+
+// What a non-zero Job::error — fetched with the Job, or carried out in HostResult::error — says, and who raises it:
+//   1  icp_round's TAIL variant, icp_persist: an in-launch wait for another workgroup's row ran out
+//   2  icp_final behind icp_persist: a round never published its folded row
+//   3  icp_round's FOLD variant: a fold leader gave up, its row never came
+//      (HostResult::error of a result that came through the outbox: icp_publish never saw icp_final's tags)
+//   4  icp_round / icp_final over the peer mailboxes: a peer's adders or flags never arrived (p2p_mark_lost)
+// `via_outbox`: the result was carried out by icp_publish (StreamSlot::side).
+int device_error(madicp_ctx* ctx, int code, bool via_outbox) {
+  if (code == 4) {
+    ctx->p2p_broken = true;
+    return fail(MADICP_ERR_COMM, "sharded registration: a peer's adders never arrived in this rank's mailbox (comm_timeout_ms)");
+  }
+  if (code == 3 && via_outbox) return fail(MADICP_ERR_DEVICE, "registration never left its results in the outbox (icp_publish timed out)");
+  return fail(MADICP_ERR_DEVICE, "registration aborted on the device: an in-launch wait of the persistent round kernel ran out (code " +
+                                     std::to_string(code) + ")");
+}
+
+// a registration's results, from the Job it left on the device or the HostResult a kernel published, into scan `s` of the caller's arrays
+template <class Result>
+void copy_result(const Result& r, int s, double* out_X, double* out_H, double* out_b, int32_t* out_n_matched, uint64_t* out_visits) {
+  if (out_X) std::memcpy(out_X + 12 * s, r.X, 12 * sizeof(double));
+  if (out_H) std::memcpy(out_H + 36 * s, r.H, 36 * sizeof(double));
+  if (out_b) std::memcpy(out_b + 6 * s, r.b, 6 * sizeof(double));
+  if (out_n_matched) out_n_matched[s] = r.n_matched;
+  if (out_visits) out_visits[s] = r.visits;
 }
 
 }  // namespace
@@ -1675,38 +1766,12 @@ int madicp_stream_collect(madicp_ctx* ctx, int ticket, double out_X[12], double 
   if (sl.by_seq) {
     // icp_final releases HostResult::seq after everything else it writes to the pinned block (kernels.hip.h)
     // (terminal errors give the slot back: a later submission must not find it "pending" for ever)
-    const int32_t want = ticket + 1;
-    const int32_t* seq = &sl.h_out->seq;
-    const unsigned check_mask = ctx->opt.wait_mode == 0 ? 0x3ffu : 0xfu;  // stream health: every few tens of microseconds
-    const bool bounded = ctx->opt.wait_timeout_ms > 0 || ctx->comm;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1; __atomic_load_n(seq, __ATOMIC_ACQUIRE) != want; ++spins) {
-      if ((spins & check_mask) == 0) {
-        const hipError_t q = hipStreamQuery(sl.side ? ctx->pub : ctx->stream);  // (the stream the sequence number comes from)
-        if (q == hipSuccess) {
-          if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) break;
-          sl.pending = false;
-          return fail(MADICP_ERR_DEVICE, "registration finished without publishing its results");
-        }
-        if (q != hipErrorNotReady) {
-          sl.pending = false;
-          return fail(MADICP_ERR_DEVICE, std::string("registration failed: ") + hipGetErrorString(q));
-        }
-        if (bounded) {
-          const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-          if (ctx->comm && ms > ctx->opt.comm_timeout_ms) {
-            // over the limit: unless the results arrived this very moment the communicator is aborted and the ticket is
-            // gone — never MADICP_OK without the results copied out, and no second wait of comm_timeout_ms
-            if (__atomic_load_n(seq, __ATOMIC_ACQUIRE) == want) break;
-            sl.pending = false;
-            return comm_abort(ctx, "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) +
-                                       " ms (a rank did not join?)");
-          }
-          if (ctx->opt.wait_timeout_ms > 0 && ms > ctx->opt.wait_timeout_ms)
-            return fail(MADICP_ERR_TIMEOUT, "registration still in flight after wait_timeout_ms; collect the ticket again");
-        }
-      }
-      wait_pause(ctx);
+    const WaitLimits lim = wait_limits(ctx);
+    const SeqWait w = wait_for_seq(ctx, &sl.h_out->seq, ticket + 1, lim, lim.bounded() ? now_ms() : 0,
+                                   sl.side ? ctx->pub : ctx->stream);  // (the stream the sequence number comes from)
+    if (w.outcome != WaitOutcome::Published) {
+      if (w.outcome != WaitOutcome::WaitTimeout) sl.pending = false;
+      return wait_failure(ctx, w, "registration");
     }
   } else {
     const hipError_t e = hipEventSynchronize(sl.ev_done);
@@ -1715,23 +1780,11 @@ int madicp_stream_collect(madicp_ctx* ctx, int ticket, double out_X[12], double 
       return fail(MADICP_ERR_DEVICE, std::string("registration failed: ") + hipGetErrorString(e));
     }
   }
-  const HostResult& r = *sl.h_out;
-  if (r.error) {
-    sl.pending = false;
-    if (r.error == 4) {
-      ctx->p2p_broken = true;
-      return fail(MADICP_ERR_COMM, "sharded registration: a peer's adders never arrived in this rank's mailbox (comm_timeout_ms)");
-    }
-    return fail(MADICP_ERR_DEVICE, r.error == 3 ? std::string("registration never left its results in the outbox (icp_publish timed out)")
-                                                : "registration aborted on the device: an in-launch wait of the persistent round kernel ran out (code " + std::to_string(r.error) + ")");
-  }
-  if (out_X) std::memcpy(out_X, r.X, sizeof(r.X));
-  if (out_H) std::memcpy(out_H, r.H, sizeof(r.H));
-  if (out_b) std::memcpy(out_b, r.b, sizeof(r.b));
-  if (out_matched) std::memcpy(out_matched, sl.h_matched, (size_t)sl.L);
-  if (out_n_matched) *out_n_matched = r.n_matched;
-  if (out_visits) *out_visits = r.visits;
   sl.pending = false;
+  const HostResult& r = *sl.h_out;
+  if (r.error) return device_error(ctx, r.error, sl.side);
+  copy_result(r, 0, out_X, out_H, out_b, out_n_matched, out_visits);
+  if (out_matched) std::memcpy(out_matched, sl.h_matched, (size_t)sl.L);
   return MADICP_OK;
 }
 
@@ -1752,16 +1805,8 @@ int madicp_icp_fetch(madicp_ctx* ctx, int n_scans, double* out_X, double* out_H,
   RC_TRY(bounded_sync(ctx, ctx->stream));
   for (int s = 0; s < n_scans; ++s) {
     const Job& j = ctx->h_fetch[s];
-    if (j.error == 4) {
-      ctx->p2p_broken = true;
-      return fail(MADICP_ERR_COMM, "sharded registration: a peer's adders never arrived in this rank's mailbox (comm_timeout_ms)");
-    }
-    if (j.error) return fail(MADICP_ERR_DEVICE, "registration aborted on the device: an in-launch wait of the persistent round kernel ran out (code " + std::to_string(j.error) + ")");
-    if (out_X) std::memcpy(out_X + 12 * s, j.X, 12 * sizeof(double));
-    if (out_H) std::memcpy(out_H + 36 * s, j.H, 36 * sizeof(double));
-    if (out_b) std::memcpy(out_b + 6 * s, j.b, 6 * sizeof(double));
-    if (out_n_matched) out_n_matched[s] = j.n_matched;
-    if (out_visits) out_visits[s] = j.visits;
+    if (j.error) return device_error(ctx, j.error, false);
+    copy_result(j, s, out_X, out_H, out_b, out_n_matched, out_visits);
   }
   return MADICP_OK;
 }
@@ -1813,38 +1858,19 @@ int madicp_icp_publish_collect(madicp_ctx* ctx, int ticket, int n_scans, double*
   if (ctx->pub_ticket[slot] != ticket || n_scans < 1 || n_scans > ctx->pub_n[slot])
     return fail(MADICP_ERR_INVALID, "unknown, overwritten or already collected ticket (a ring of four batches)");
   const madicp::HostResult* h = ctx->h_pub[slot];
-  const auto t0 = std::chrono::steady_clock::now();
+  // (terminal errors give the block back, like madicp_stream_collect: only a wait that ran out keeps the ticket)
+  const WaitLimits lim = wait_limits(ctx);
+  const long long t0 = lim.bounded() ? now_ms() : 0;  // one start for the whole batch
   for (int s_ = 0; s_ < n_scans; ++s_) {
-    for (unsigned spins = 1; __atomic_load_n(&h[s_].seq, __ATOMIC_ACQUIRE) != ticket + 1; ++spins) {
-      if ((spins & 0x3ffu) == 0) {
-        const hipError_t q = hipStreamQuery(ctx->stream);
-        if (q == hipSuccess) {
-          if (__atomic_load_n(&h[s_].seq, __ATOMIC_ACQUIRE) == ticket + 1) break;
-          return fail(MADICP_ERR_DEVICE, "batch finished without publishing its results");
-        }
-        if (q != hipErrorNotReady) return fail(MADICP_ERR_DEVICE, std::string("batch failed: ") + hipGetErrorString(q));
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (ctx->comm && ms > ctx->opt.comm_timeout_ms)
-          return comm_abort(ctx, "a collective did not complete within " + std::to_string(ctx->opt.comm_timeout_ms) + " ms (a rank did not join?)");
-        if (ctx->opt.wait_timeout_ms > 0 && ms > ctx->opt.wait_timeout_ms)
-          return fail(MADICP_ERR_TIMEOUT, "batch still in flight after wait_timeout_ms; collect the ticket again");
-      }
-      wait_pause(ctx);
-    }
+    const SeqWait w = wait_for_seq(ctx, &h[s_].seq, ticket + 1, lim, t0, ctx->stream);
+    if (w.outcome == WaitOutcome::Published) continue;
+    if (w.outcome != WaitOutcome::WaitTimeout) ctx->pub_ticket[slot] = -1;
+    return wait_failure(ctx, w, "batch");
   }
   ctx->pub_ticket[slot] = -1;
   for (int s_ = 0; s_ < n_scans; ++s_) {
-    const madicp::HostResult& r = h[s_];
-    if (r.error == 4) {
-      ctx->p2p_broken = true;
-      return fail(MADICP_ERR_COMM, "sharded registration: a peer's adders never arrived in this rank's mailbox (comm_timeout_ms)");
-    }
-    if (r.error) return fail(MADICP_ERR_DEVICE, "registration aborted on the device (code " + std::to_string(r.error) + ")");
-    if (out_X) std::memcpy(out_X + 12 * s_, r.X, sizeof(r.X));
-    if (out_H) std::memcpy(out_H + 36 * s_, r.H, sizeof(r.H));
-    if (out_b) std::memcpy(out_b + 6 * s_, r.b, sizeof(r.b));
-    if (out_n_matched) out_n_matched[s_] = r.n_matched;
-    if (out_visits) out_visits[s_] = r.visits;
+    if (h[s_].error) return device_error(ctx, h[s_].error, false);
+    copy_result(h[s_], s_, out_X, out_H, out_b, out_n_matched, out_visits);
   }
   return MADICP_OK;
 }
@@ -1868,16 +1894,7 @@ int madicp_icp_register(madicp_ctx* ctx, int moving_id, const int* tree_ids, int
   int rc = enqueue_registration(ctx, a);
   if (rc == MADICP_OK) rc = madicp_icp_fetch(ctx, 1, X, out_H, out_b, nullptr, out_visits);
   if (rc == MADICP_OK && out_matched) rc = madicp_icp_fetch_matched(ctx, 0, out_matched, ctx->movings.at(moving_id).L);
-  if (rc == MADICP_OK && d_xi) {
-    hipError_t e = hipMemcpyAsync(out_X_iters, d_xi, sizeof(double) * 12 * (size_t)n_iters, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = fail(MADICP_ERR_DEVICE, std::string("x_iters copy: ") + hipGetErrorString(e));
-  }
-  if (d_xi) {
-    hipStreamSynchronize(ctx->stream);
-    pool_free(ctx, d_xi, nullptr);
-  }
-  return rc;
+  return download_and_free(ctx, rc, d_xi, out_X_iters, sizeof(double) * 12 * (size_t)n_iters, "x_iters copy: ");
 }
 
 int madicp_icp_linearize(madicp_ctx* ctx, int moving_id, const int* tree_ids, int K, const double X[12],
@@ -1895,16 +1912,7 @@ int madicp_icp_linearize(madicp_ctx* ctx, int moving_id, const int* tree_ids, in
   int rc = enqueue_registration(ctx, a);
   if (rc == MADICP_OK) rc = madicp_icp_fetch(ctx, 1, nullptr, out_H, out_b, nullptr, out_visits);
   if (rc == MADICP_OK && out_matched) rc = madicp_icp_fetch_matched(ctx, 0, out_matched, L);
-  if (rc == MADICP_OK && d_corr) {
-    hipError_t e = hipMemcpyAsync(out_corr, d_corr, sizeof(uint32_t) * (size_t)K * L, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = fail(MADICP_ERR_DEVICE, std::string("corr copy: ") + hipGetErrorString(e));
-  }
-  if (d_corr) {
-    hipStreamSynchronize(ctx->stream);
-    pool_free(ctx, d_corr, nullptr);
-  }
-  return rc;
+  return download_and_free(ctx, rc, d_corr, out_corr, sizeof(uint32_t) * (size_t)K * L, "corr copy: ");
 }
 
 #ifdef MADICP_MEASURE  // ---- measurement / test aids (include/madicp_hip_measure.h): only in the measurement build (mad_icp_amd/_measure)
@@ -1918,16 +1926,12 @@ int madicp_icp_time_linearize(madicp_ctx* ctx, int n_scans, const int* moving_id
   RC_TRY(stage_registration(ctx, a, &st));
   // n back-to-back launches of the dominant kernel inside ONE captured graph, bracketed by two events: the
   // per-launch time is defined exactly like a profiler trace of the registration graph defines it
-  if (!ctx->ev_t0) {
-    HIP_TRY(hipEventCreate(&ctx->ev_t0));
-    HIP_TRY(hipEventCreate(&ctx->ev_t1));
-  }
-  hipGraph_t graph = nullptr;
+  RC_TRY(timing_events(ctx));
   hipGraphExec_t exec = nullptr;
-  HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  for (int i = 0; i < n_launches; ++i) launch_round(ctx, st.halves[0], whole_part(ctx, ctx->d_jobs), 0, nullptr);
-  HIP_TRY(hipStreamEndCapture(ctx->stream, &graph));
-  HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+  RC_TRY(capture_graph(ctx, [&] {
+    for (int i = 0; i < n_launches; ++i) launch_round(ctx, st.halves[0], whole_part(ctx, ctx->d_jobs), 0, nullptr);
+    return MADICP_OK;
+  }, &exec));
   HIP_TRY(hipGraphLaunch(exec, ctx->stream));  // warm-up replay
   HIP_TRY(hipEventRecord(ctx->ev_t0, ctx->stream));
   HIP_TRY(hipGraphLaunch(exec, ctx->stream));
@@ -1939,7 +1943,6 @@ int madicp_icp_time_linearize(madicp_ctx* ctx, int n_scans, const int* moving_id
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_t0, ctx->ev_t1));
   hipGraphExecDestroy(exec);
-  hipGraphDestroy(graph);
   if (out_avg_us) *out_avg_us = 1e3 * ms / n_launches;
   return out_visits_per_launch ? madicp_icp_fetch(ctx, n_scans, nullptr, nullptr, nullptr, nullptr, out_visits_per_launch) : MADICP_OK;
 }
@@ -1951,10 +1954,7 @@ int madicp_icp_time_registration(madicp_ctx* ctx, int n_scans, const int* moving
   if (!ctx || reps < 1 || n_iters < 1) return fail(MADICP_ERR_INVALID, "bad argument");
   if (ctx->sharded()) return fail(MADICP_ERR_INVALID, "not available with a communicator");
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->ev_t0) {
-    HIP_TRY(hipEventCreate(&ctx->ev_t0));
-    HIP_TRY(hipEventCreate(&ctx->ev_t1));
-  }
+  RC_TRY(timing_events(ctx));
   RegArgs a{n_scans, moving_ids, tree_ids, K, X0, params, n_iters, 0, nullptr, nullptr};
   Staged st;  // (not sharded: never split, halves[0] is the whole batch)
   int rc = MADICP_OK;
@@ -1976,14 +1976,13 @@ int madicp_icp_time_registration(madicp_ctx* ctx, int n_scans, const int* moving
     for (int s = 0; s < n_scans; ++s) out_walked_per_launch[s] = ctx->h_fetch[s].walked / (uint64_t)n_iters;
   // icp_final alone, `reps` of them back to back inside ONE graph (a graph per launch would add the idle queue between two
   // graph launches, ~10 us, to a 5 us kernel): what is left of a registration is its n_iters icp_round launches
-  hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  for (int r = 0; r < reps; ++r)
-    hipLaunchKernelGGL(icp_final, dim3(n_scans), dim3(kBlock), 0, ctx->stream, ctx->d_jobs, ctx->d_partials,
-                       (const double*)nullptr, st.halves[0].grid, n_scans, (const unsigned long long*)nullptr, madicp::PeerBox{});
-  HIP_TRY(hipStreamEndCapture(ctx->stream, &graph));
-  HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+  RC_TRY(capture_graph(ctx, [&] {
+    for (int r = 0; r < reps; ++r)
+      hipLaunchKernelGGL(icp_final, dim3(n_scans), dim3(kBlock), 0, ctx->stream, ctx->d_jobs, ctx->d_partials,
+                         (const double*)nullptr, st.halves[0].grid, n_scans, (const unsigned long long*)nullptr, madicp::PeerBox{});
+    return MADICP_OK;
+  }, &exec));
   {
     hipGraphLaunch(exec, ctx->stream);
     hipEventRecord(ctx->ev_t0, ctx->stream);
@@ -2000,7 +1999,6 @@ int madicp_icp_time_registration(madicp_ctx* ctx, int n_scans, const int* moving
     }
   }
   hipGraphExecDestroy(exec);
-  hipGraphDestroy(graph);
   return rc;
 }
 
@@ -2011,10 +2009,7 @@ int madicp_nn_time_descend(madicp_ctx* ctx, int tree_id, const double* queries, 
   auto it = ctx->trees.find(tree_id);
   if (it == ctx->trees.end()) return fail(MADICP_ERR_INVALID, "unknown tree id");
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->ev_t0) {
-    HIP_TRY(hipEventCreate(&ctx->ev_t0));
-    HIP_TRY(hipEventCreate(&ctx->ev_t1));
-  }
+  RC_TRY(timing_events(ctx));
   const size_t nq = (size_t)n;
   const size_t off_leaf = align_up(sizeof(double) * 3 * nq);
   const size_t off_dist = align_up(off_leaf + sizeof(uint32_t) * nq);
@@ -2065,10 +2060,7 @@ int madicp_debug_stream_copy(madicp_ctx* ctx, int64_t bytes, int reps, double* o
   if (!ctx || !out_gbs) return fail(MADICP_ERR_INVALID, "null argument");
   if (bytes < 4096 || reps < 1) return fail(MADICP_ERR_INVALID, "bytes >= 4096 and reps >= 1");
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->ev_t0) {
-    HIP_TRY(hipEventCreate(&ctx->ev_t0));
-    HIP_TRY(hipEventCreate(&ctx->ev_t1));
-  }
+  RC_TRY(timing_events(ctx));
   const size_t n16 = (size_t)bytes / 16;
   void *a = nullptr, *b = nullptr;
   HIP_TRY(hipMalloc(&a, n16 * 16));
@@ -2117,10 +2109,7 @@ int madicp_debug_gather16(madicp_ctx* ctx, int64_t region_bytes, int64_t n_gathe
   if (!ctx || !out_avg_us) return fail(MADICP_ERR_INVALID, "null argument");
   if (region_bytes < 4096 || n_gathers < 1 || reps < 1) return fail(MADICP_ERR_INVALID, "region_bytes >= 4096, n_gathers >= 1, reps >= 1");
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->ev_t0) {
-    HIP_TRY(hipEventCreate(&ctx->ev_t0));
-    HIP_TRY(hipEventCreate(&ctx->ev_t1));
-  }
+  RC_TRY(timing_events(ctx));
   const size_t n16 = (size_t)region_bytes / 16;
   void* a = nullptr;
   unsigned int* sink = nullptr;

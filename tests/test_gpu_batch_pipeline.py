@@ -84,3 +84,38 @@ def test_pipelined_batches_are_the_synchronous_batches(ctx):
         ctx.tree_release(t)
     for m in sets[0] + sets[1]:
         ctx.moving_release(m)
+
+
+def test_publish_collect_wait_modes_are_the_fetched_batch(ctx):
+    """Option "wait_mode" on the publish path: a batch collected by ticket while the host spins, yields or sleeps (bounded by
+    "wait_timeout_ms") is the batch madicp_icp_fetch returns, bit for bit, and its ticket is collected once."""
+    B = 2
+    pb = street_problem(2, n_queries=2)
+    tids = []
+    for s, T in zip(pb["keyframe_scans"], pb["keyframe_poses"]):
+        ht = capi.HostTree(s, B_MAX, B_MIN, 2)
+        ht.transform(T[:3, :3], T[:3, 3])
+        tids.append(ctx.upload(ht))
+    mids = [ctx.moving_upload(capi.HostTree(s, B_MAX, B_MIN, 2).leaf_means()) for s in pb["query_scans"][:B]]
+    guesses = np.stack([capi.pose12(T) for T in pb["query_guess"][:B]])
+    saved = {k: ctx.get_option(k) for k in ("wait_mode", "wait_timeout_ms")}
+    try:
+        ctx.icp_register_batch_enqueue(mids, tids, guesses, PARAMS, N_ITERS)
+        ref = ctx.icp_fetch(B)
+        for mode in (0, 1, 2):
+            ctx.set_option("wait_mode", mode)
+            ctx.set_option("wait_timeout_ms", 5000)
+            ctx.icp_register_batch_enqueue(mids, tids, guesses, PARAMS, N_ITERS)
+            tk = ctx.icp_publish_enqueue(B)
+            got = ctx.icp_publish_collect(tk, B)
+            for k in ("X", "H", "b", "n_matched", "visits"):
+                assert np.array_equal(got[k], ref[k]), (mode, k)
+            with pytest.raises(capi.MadIcpError):
+                ctx.icp_publish_collect(tk, B)
+    finally:
+        for k, v in saved.items():
+            ctx.set_option(k, v)
+        for t in tids:
+            ctx.tree_release(t)
+        for m in mids:
+            ctx.moving_release(m)
