@@ -329,6 +329,48 @@ int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int
  * same refusals and out_chunks; MADICP_ERR_INVALID for a cloud without stamps.  The cloud keeps its stamps (input order is
  * kept). */
 int madicp_cloud_deskew_own_stamps(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks);
+/* SEVERAL SENSORS' RECORDS INTO ONE CLOUD — a multi-head rig (two Ousters on one vehicle, each with its lidar_to_base) delivers
+ * S buffers per frame: each in its own sensor frame, often with its own point_step and time type, each time field counting
+ * from its own message header.  Additive.  madicp_cloud_ingest_sources takes the S buffers to ONE resident cloud in the base
+ * frame with ONE set of normalised stamps, in one chain of launches and one host synchronisation whatever S is (all sources
+ * cross PCIe in one copy).  The survivors of source 0 come first in input order, then source 1's, and so on; the cloud carries
+ * stamps exactly when the sources have a time field, and madicp_cloud_stamps / madicp_cloud_deskew_own_stamps work on it
+ * unchanged.  Per record, madicp_cloud_ingest_records' rules with two additions, everything in fp64 without contraction:
+ *   survivors     the range filter on the raw floats IN THE SENSOR'S OWN FRAME, with that source's own min_range / max_range:
+ *                 that is where self-hits and the maximum range are defined.
+ *   common clock  tc = t64 * t_scale + t_offset (two roundings, no fma); a source with t_scale == 1.0 and t_offset == 0.0
+ *                 exactly takes t64 as it is.  Finiteness is judged on tc.  t_range == NULL: t0 / t1 = min / max of tc over ALL
+ *                 records of ALL sources with a finite tc, dropped ones included, each canonicalised as t + 0.0; else the
+ *                 caller's {t_begin, t_end} ON THE COMMON CLOCK.  stamp = (tc - t0) / (t1 - t0), NaN unless t1 - t0 > 0.
+ *                 PRECISION: pass t_offset relative to the frame's start, not an absolute epoch — an offset of 1.7e9 s leaves
+ *                 tc a resolution of 2.4e-7 s and eats the nanoseconds of a uint32 field.
+ *   sensor->base  after the optional KITTI rotation (which belongs to the sensor frame): base[i] = t[i] + (R[3i] * o0 +
+ *                 (R[3i+1] * o1 + R[3i+2] * o2)) — the evaluation order of pose * point in madicp_cloud_deskew_stamped; a
+ *                 source whose R is exactly the identity and whose t is exactly zero skips it.  R is used AS GIVEN: that it is
+ *                 orthonormal is the caller's business (a scaled or sheared R scales or shears the points).
+ * One source with the identity, t_scale 1 and t_offset 0 is madicp_cloud_ingest_records on the same buffer, bit for bit.
+ * out_n: all survivors; out_n_per_source (n_sources values, optional): those of every source (they ride in the same one
+ * device-to-host copy); out_t_range (optional): the t0, t1 used, +inf, -inf without a time field or a finite time.
+ * MADICP_ERR_INVALID — before anything is staged, launched or allocated, no cloud created — for a null argument (a source's
+ * data included), n_sources outside 1 .. MADICP_MAX_SOURCES, an n_records < 1 or a total above 2^30, a layout
+ * madicp_cloud_ingest_records refuses, a non-finite entry of R or t, a t_scale that is not finite and > 0, a non-finite t_offset,
+ * sources with AND without a time field (all or none), a t_range that is not finite and increasing; MADICP_ERR_INVALID as well
+ * when no record of any source survives; MADICP_ERR_CAPACITY while a look-ahead build is in flight.  The caller's buffers are
+ * read up to data[n_records * point_step) and no further.  Bit-equal to madicp_host_ingest_sources (madicp_host.h). */
+#define MADICP_MAX_SOURCES 8
+typedef struct madicp_record_source {
+  const void* data;
+  int64_t n_records;             /* >= 1 */
+  madicp_record_layout layout;
+  double R[9], t[3];             /* sensor -> base, R row-major */
+  double min_range, max_range;   /* in the sensor's frame */
+  double t_scale, t_offset;      /* field units -> the common clock */
+  int32_t kitti_correction, reserved;
+} madicp_record_source;
+int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources,
+                                const double* t_range /* NULL: min / max over all records; else {t_begin, t_end} */,
+                                int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source /* n_sources, optional */,
+                                double out_t_range[2] /* optional */);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes
  * a resident tree exactly like one given to madicp_tree_upload (same node format, madicp_tree_download returns it).
  * Same decisions as the reference node by node, the reference's member order (the permutation utils.h:37-52 leaves), and
@@ -349,7 +391,7 @@ int madicp_tree_build(madicp_ctx* ctx, int cloud_id, double b_max, double b_min,
  * enqueues the whole level loop on a stream of its own — the library's BUILD stream, so that neither the registration on
  * the compute stream nor its feed on the copy stream queues behind it — and returns without waiting; _end waits for the
  * leaf count, sizes and emits the tree and returns its id.  One look-ahead per context: a second _begin, or
- * madicp_tree_build / madicp_cloud_ingest_f32 / madicp_cloud_ingest_records / madicp_cloud_deskew /
+ * madicp_tree_build / madicp_cloud_ingest_f32 / madicp_cloud_ingest_records / madicp_cloud_ingest_sources / madicp_cloud_deskew /
  * madicp_cloud_deskew_stamped / madicp_cloud_deskew_own_stamps / madicp_tree_build_stats before the _end, return
  * MADICP_ERR_CAPACITY (they share the builder's scratch).  Registrations, uploads, transforms, searches and releases are
  * free to run in between.  The tree is the one madicp_cloud_upload + madicp_tree_build give for the same scan, bit for bit. */

@@ -80,6 +80,15 @@ int madicp_host_deskew_stamped(double* points, const double* stamps01, int64_t n
 int madicp_host_ingest_records(const void* data, int64_t n_records, const madicp_record_layout* layout, double min_range,
                                double max_range, int kitti_correction, const double* t_range, double* out_xyz, double* out_stamps01,
                                int64_t* out_n, double out_t_range[2]);
+/* The host twin of madicp_cloud_ingest_sources (madicp_hip.h: the same rules from the same per-record source, bit-equal):
+ * several sensors' byte records -> one base-frame cloud, source 0's survivors first, with one set of stamps on the common
+ * clock; what a Pipeline with the host front-end runs for computeSourcesStamped.  out_xyz: room for (total records, 3) doubles;
+ * out_stamps01: room for that many doubles (optional; not written without a time field); out_n_per_source (n_sources values),
+ * out_t_range: optional.  Nothing past data[n_records * point_step) of any source is touched.  Returns 0 — also when no record
+ * survives (*out_n = 0) — and -1 for the arguments madicp_cloud_ingest_sources refuses with MADICP_ERR_INVALID, nothing
+ * written. */
+int madicp_host_ingest_sources(const madicp_record_source* sources, int n_sources, const double* t_range, double* out_xyz,
+                               double* out_stamps01, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]);
 
 /* ---- the keyframe map sharded over the ranks of a node (Pipeline::setShard, csrc/host/pipeline.h) ---- */
 /* The rank that owns the keyframe of ORDINAL k — promotion order: the first scan is 0, every promotion adds 1; not the frame

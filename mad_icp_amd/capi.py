@@ -35,6 +35,13 @@ class RecordLayoutC(C.Structure):
                 ("t_type", C.c_int32)]
 
 
+class RecordSourceC(C.Structure):
+    """madicp_record_source (include/madicp_hip.h)"""
+    _fields_ = [("data", C.c_void_p), ("n_records", C.c_int64), ("layout", RecordLayoutC), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("min_range", C.c_double), ("max_range", C.c_double), ("t_scale", C.c_double), ("t_offset", C.c_double),
+                ("kitti_correction", C.c_int32), ("reserved", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _u8p = C.POINTER(C.c_uint8)
@@ -148,6 +155,7 @@ def hip_lib():
                                               C.c_int, _ip, _i64p]
         L.madicp_cloud_ingest_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RecordLayoutC), C.c_double, C.c_double,
                                                   C.c_int, _dp, _ip, _i64p, _dp]
+        L.madicp_cloud_ingest_sources.argtypes = [C.c_void_p, C.POINTER(RecordSourceC), C.c_int, _dp, _ip, _i64p, _i64p, _dp]
         L.madicp_cloud_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
@@ -198,6 +206,7 @@ def host_lib():
         L.madicp_host_debug_tree_points.restype = C.c_int64
         L.madicp_host_ingest_records.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RecordLayoutC), C.c_double, C.c_double, C.c_int, _dp,
                                                  _dp, _dp, _i64p, _dp]
+        L.madicp_host_ingest_sources.argtypes = [C.POINTER(RecordSourceC), C.c_int, _dp, _dp, _dp, _i64p, _i64p, _dp]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
         L.madicp_host_debug_partition.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_int]
@@ -423,6 +432,44 @@ def host_ingest_records(records, min_range, max_range, kitti_correction, layout=
     return xyz[:k].copy(), (st[:k].copy() if lay.t_type != 0 else None), (float(rng[0]), float(rng[1]))
 
 
+def _sources_args(sources, t_range):
+    """(arrays kept alive, RecordSourceC array, total records, has a time field, t_range pointer or None) of a sources call.
+    `sources`: mad_icp_amd.records.Source objects; a Source's layout is read off its dtype unless given, and like _records_args
+    NOTHING is validated here — the native refusals are what the callers of this plumbing test."""
+    from mad_icp_amd import records as _records
+
+    alive, arr = [], (RecordSourceC * max(len(sources), 1))()
+    for k, src in enumerate(sources):
+        r = np.ascontiguousarray(src.records)
+        layout = src.layout if src.layout is not None else _records.layout_of(r.dtype, src.time_field)
+        T = np.eye(4) if src.sensor_to_base is None else np.asarray(src.sensor_to_base, dtype=np.float64)
+        c = arr[k]
+        c.data, c.n_records, c.layout = r.ctypes.data, r.shape[0], RecordLayoutC(*(int(v) for v in layout))
+        c.R[:], c.t[:] = [float(v) for v in T[:3, :3].reshape(-1)], [float(v) for v in T[:3, 3]]
+        c.min_range, c.max_range, c.t_scale, c.t_offset = float(src.min_range), float(src.max_range), float(src.time_scale), float(src.time_offset)
+        c.kitti_correction, c.reserved = int(bool(src.kitti_correction)), 0
+        alive.append(r)
+    total = sum(int(a.shape[0]) for a in alive)
+    timed = bool(sources) and arr[0].layout.t_type != 0
+    tr = None if t_range is None else np.ascontiguousarray(t_range, dtype=np.float64).reshape(2)
+    return alive, arr, total, timed, tr
+
+
+def host_ingest_sources(sources, t_range=None):
+    """madicp_host_ingest_sources: the host twin of Context.cloud_ingest_sources.  Returns (points (kept, 3) float64, stamps (kept,)
+    float64 or None without a time field, (t0, t1), survivors per source)."""
+    alive, arr, total, timed, tr = _sources_args(sources, t_range)
+    xyz, st = np.empty((max(total, 1), 3)), np.empty(max(total, 1))
+    kept, rng, per = C.c_int64(0), np.empty(2), np.zeros(max(len(sources), 1), np.int64)
+    rc = host_lib().madicp_host_ingest_sources(arr, len(sources), tr.ctypes.data_as(_dp) if tr is not None else None,
+                                               xyz.ctypes.data_as(_dp), st.ctypes.data_as(_dp), C.byref(kept), per.ctypes.data_as(_i64p),
+                                               rng.ctypes.data_as(_dp))
+    if rc != 0:
+        raise MadIcpError("madicp_host_ingest_sources: bad arguments")
+    k = kept.value
+    return xyz[:k].copy(), (st[:k].copy() if timed else None), (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]]
+
+
 class Context:
     """One device + one stream (include/madicp_hip.h)."""
 
@@ -561,6 +608,15 @@ class Context:
                                                      tr.ctypes.data_as(_dp) if tr is not None else None, C.byref(cid), C.byref(kept),
                                                      rng.ctypes.data_as(_dp)))
         return cid.value, kept.value, (float(rng[0]), float(rng[1]))
+
+    def cloud_ingest_sources(self, sources, t_range=None):
+        """Several sensors' byte records (mad_icp_amd.records.Source objects, see _sources_args) -> ONE resident base-frame cloud
+        with one set of stamps on the common clock.  Returns (cloud id, points kept, (t0, t1), survivors per source)."""
+        alive, arr, _, _, tr = _sources_args(sources, t_range)
+        cid, kept, rng, per = C.c_int(0), C.c_int64(0), np.empty(2), np.zeros(max(len(sources), 1), np.int64)
+        _check(hip_lib().madicp_cloud_ingest_sources(self._h, arr, len(sources), tr.ctypes.data_as(_dp) if tr is not None else None,
+                                                     C.byref(cid), C.byref(kept), per.ctypes.data_as(_i64p), rng.ctypes.data_as(_dp)))
+        return cid.value, kept.value, (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]]
 
     def cloud_stamps(self, cid):
         """The stamps a cloud of cloud_ingest_records carries, (n,) float64 in the cloud's order; MadIcpError when it has none."""

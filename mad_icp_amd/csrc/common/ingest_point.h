@@ -102,4 +102,88 @@ MADICP_HD inline double record_stamp(double t64, double t0, double t1) {
   return (t64 - t0) / span;
 }
 
+// ---- several sources into one cloud (include/madicp_hip.h: madicp_record_source) ------------------------------------------------
+// the time of a record on the clock all sources share: tc = t64 * t_scale + t_offset, two roundings (no fma: these translation
+// units are compiled without contraction).  `as_is`: the host found t_scale == 1.0 and t_offset == 0.0 exactly — the time is
+// taken unchanged (x * 1.0 + 0.0 would turn a -0.0 into +0.0), which makes one such source the single-source ingest bit for bit.
+MADICP_HD inline double source_clock(double t64, int as_is, double t_scale, double t_offset) {
+  if (as_is) return t64;
+  const double scaled = t64 * t_scale;
+  return scaled + t_offset;
+}
+inline bool source_clock_as_is(double t_scale, double t_offset) { return t_scale == 1.0 && t_offset == 0.0; }
+
+// sensor frame -> base frame, AFTER ingest_point (the KITTI rotation belongs to the sensor frame): R row-major, the evaluation
+// order of pose * point in the stamped deskew (fe::deskew_stamped / deskew_cloud_stamped), both of its branches.  In place.
+MADICP_HD inline void sensor_to_base(const double* R, const double* t, double* o) {
+  const double x = o[0], y = o[1], z = o[2];
+#ifdef MADICP_XFORM_HOMOGENEOUS
+  o[0] = ((R[0] * x + R[1] * y) + R[2] * z) + t[0];
+  o[1] = ((R[3] * x + R[4] * y) + R[5] * z) + t[1];
+  o[2] = ((R[6] * x + R[7] * y) + R[8] * z) + t[2];
+#else
+  o[0] = t[0] + sum3s(R[0] * x, R[1] * y, R[2] * z);
+  o[1] = t[1] + sum3s(R[3] * x, R[4] * y, R[5] * z);
+  o[2] = t[2] + sum3s(R[6] * x, R[7] * y, R[8] * z);
+#endif
+}
+// a source whose extrinsic is exactly the identity skips sensor_to_base (0.0 + (x + (0.0 + 0.0)) would lose the sign of a zero)
+inline bool source_extrinsic_is_identity(const double* R, const double* t) {
+  for (int i = 0; i < 9; ++i)
+    if (R[i] != ((i % 4 == 0) ? 1.0 : 0.0)) return false;
+  return t[0] == 0.0 && t[1] == 0.0 && t[2] == 0.0;
+}
+
+constexpr int kMaxSources = 8;  // MADICP_MAX_SOURCES
+struct RecordSource {           // madicp_record_source with its layout as a RecordLayout
+  const void* data;
+  int64_t n;
+  RecordLayout L;
+  double R[9], t[3];
+  double min_range, max_range;
+  double t_scale, t_offset;
+  int32_t kitti;
+};
+// (from the C ABI's madicp_record_source: a template, so that this header needs none of the C headers)
+template <class CSource>
+inline RecordSource record_source_of(const CSource& c) {
+  RecordSource S;
+  S.data = c.data;
+  S.n = c.n_records;
+  S.L = RecordLayout{c.layout.point_step, c.layout.off_x, c.layout.off_y, c.layout.off_z, c.layout.off_t, c.layout.t_type};
+  for (int i = 0; i < 9; ++i) S.R[i] = c.R[i];
+  for (int i = 0; i < 3; ++i) S.t[i] = c.t[i];
+  S.min_range = c.min_range;
+  S.max_range = c.max_range;
+  S.t_scale = c.t_scale;
+  S.t_offset = c.t_offset;
+  S.kitti = c.kitti_correction;
+  return S;
+}
+
+// what every layer refuses before it touches a record (null = nothing to refuse): the device entry, the host twin and Pipeline
+// ask this one function
+inline const char* record_sources_refusal(const RecordSource* src, int n_sources, const double* t_range) {
+  if (!src) return "null argument";
+  if (n_sources < 1 || n_sources > kMaxSources) return "1 .. 8 sources";
+  int64_t total = 0;
+  for (int s = 0; s < n_sources; ++s) {
+    const RecordSource& S = src[s];
+    if (!S.data) return "null argument";
+    if (S.n < 1 || S.n > 0x40000000) return "every source holds at least one record, all of them together at most 2^30";
+    total += S.n;
+    if (!record_layout_ok(S.L)) return "record layout: point_step 12 .. 256, every field inside the record, t_type one of MADICP_T_*";
+    for (double v : S.R)
+      if (!time_is_finite(v)) return "R and t: finite entries";
+    for (double v : S.t)
+      if (!time_is_finite(v)) return "R and t: finite entries";
+    if (!time_is_finite(S.t_scale) || !(S.t_scale > 0.0) || !time_is_finite(S.t_offset)) return "t_scale finite and > 0, t_offset finite";
+    if ((S.L.t_type != kTimeNone) != (src[0].L.t_type != kTimeNone)) return "a time field in every source or in none";
+  }
+  if (total > 0x40000000) return "every source holds at least one record, all of them together at most 2^30";
+  if (t_range && !(time_is_finite(t_range[0]) && time_is_finite(t_range[1]) && t_range[1] > t_range[0]))
+    return "t_range: both values finite, t_end > t_begin";
+  return nullptr;
+}
+
 }  // namespace madicp_host

@@ -6,6 +6,8 @@
 //            compensation
 //   ingest of raw byte records (additive): a driver's PointCloud2-style buffer — any record step, fields at any alignment, a
 //            uint32 / float32 / float64 time field — to a filtered cloud that carries its own normalised stamps
+//   ingest of several sources' byte records (additive): the buffers of a multi-head rig, each in its own frame and on its own
+//            clock, to ONE base-frame cloud with one set of stamps — the same chain of launches whatever their number
 //   deskew from per-point timestamps (additive, the reference has none): the same time model with the chunk read off the
 //            acquisition time the sensor driver delivers for every point — one streaming kernel, input order kept
 // All of it is HBM-bound streaming work (24-32 bytes per point per pass); the kernels are coalesced grid-stride
@@ -209,6 +211,145 @@ __global__ __launch_bounds__(256) void records_scatter(const unsigned char* __re
       const long d = pos[first + threadIdx.x];
       out[3 * d] = o[0]; out[3 * d + 1] = o[1]; out[3 * d + 2] = o[2];
       if (stamps) stamps[d] = madicp_host::record_stamp(madicp_host::record_time(p + L.off_t, L.t_type), t0, t1);
+    }
+    __syncthreads();
+  }
+}
+
+// ---- ingest of SEVERAL sources' byte records into one cloud ---------------------------------------------------------------------
+// A multi-head rig delivers S buffers per frame, each in its own sensor frame, often with its own record step and time type, each
+// time field counting from its own message header (madicp_cloud_ingest_sources).  All of them are staged into ONE device buffer,
+// every source at a 64-byte aligned offset, and the two kernels below walk ONE grid-stride loop over the GLOBAL tile index: the
+// tiles of source 0, then those of source 1 ... — a source's tiles hold records_per_tile(its step) records, so the 16 KiB tile and
+// everything said about it above holds unchanged.  keep[] / pos[] are indexed by GLOBAL record (source 0's records, then source
+// 1's ...): the one scan of records_mark's caller gives the concatenated order, keep[total] is its terminator.
+// The table of the sources travels BY VALUE as a kernel argument (1.6 KB of the 4 KB a launch may carry): it is wave-uniform, the
+// workgroup finds the source of its tile with at most kMaxSources - 1 scalar comparisons and reads the entry through scalar loads.
+// Per record, madicp_host's rules (csrc/common/ingest_point.h): the range filter on the raw floats in the SENSOR's frame with the
+// source's own bounds; the time on the common clock (source_clock) — its finiteness, the extremes and the stamp are all judged
+// there; the point through ingest_point (the KITTI rotation belongs to the sensor frame) and then sensor_to_base.
+constexpr int kSrcKitti = 1, kSrcIdentity = 2, kSrcClockAsIs = 4;  // SourceEntry::flags (decided once, on the host)
+struct SourceEntry {
+  long byte_off;    // of the source's first record in the staged buffer, a multiple of 64
+  long first_tile;  // global index of its first tile
+  long first_rec;   // global index of its first record: the base into keep[] / pos[]
+  long n;           // records
+  madicp_host::RecordLayout L;
+  int32_t per_tile, flags;
+  double min_range, max_range;
+  double t_scale, t_offset;
+  double R[9], t[3];
+};
+struct SourceTable {
+  int32_t n_sources, has_time;
+  long n_tiles, n_total;
+  SourceEntry src[madicp_host::kMaxSources];
+};
+static_assert(sizeof(SourceTable) <= 2048, "the table is a kernel argument");
+
+// the source a global tile belongs to (first_tile ascends with the source)
+__device__ inline int source_of_tile(const SourceTable& T, long tile) {
+  int s = 0;
+  for (int k = 1; k < T.n_sources; ++k)
+    if (tile >= T.src[k].first_tile) s = k;
+  return s;
+}
+
+// mark pass: records_mark over the global tile index; the partial extremes are those of the times on the COMMON clock
+__global__ __launch_bounds__(256) void sources_mark(const unsigned char* __restrict__ rec, SourceTable T, uint32_t* __restrict__ keep,
+                                                    double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
+  __shared__ double s_mn[4], s_mx[4];
+  const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
+  double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
+  for (long tile = blockIdx.x; tile < T.n_tiles; tile += gridDim.x) {
+    const SourceEntry& E = T.src[source_of_tile(T, tile)];
+    const madicp_host::RecordLayout L = E.L;
+    const long first = (tile - E.first_tile) * E.per_tile;  // within the source
+    const int cnt = (int)min((long)E.per_tile, E.n - first);
+    records_stage(rec + E.byte_off + first * L.step, cnt * L.step, s_tile);
+    __syncthreads();
+    if ((int)threadIdx.x < cnt) {
+      const unsigned char* p = s_bytes + threadIdx.x * L.step;
+      const bool drop = madicp_host::ingest_drops(madicp_host::record_f32(p + L.off_x), madicp_host::record_f32(p + L.off_y),
+                                                  madicp_host::record_f32(p + L.off_z), E.min_range, E.max_range);
+      keep[E.first_rec + first + threadIdx.x] = drop ? 0u : 1u;
+      if (T.has_time) {
+        const double tc = madicp_host::source_clock(madicp_host::record_time(p + L.off_t, L.t_type), E.flags & kSrcClockAsIs, E.t_scale,
+                                                    E.t_offset);
+        if (madicp_host::time_is_finite(tc)) {
+          if (tc < mn) mn = tc;
+          if (tc > mx) mx = tc;
+        }
+      }
+    }
+    __syncthreads();  // (the next trip overwrites the tile)
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) keep[T.n_total] = 0;
+  for (int m = 32; m > 0; m >>= 1) {
+    const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
+    if (a < mn) mn = a;
+    if (b > mx) mx = b;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_mn[threadIdx.x >> 6] = mn;
+    s_mx[threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      if (s_mn[w] < mn) mn = s_mn[w];
+      if (s_mx[w] > mx) mx = s_mx[w];
+    }
+    part[2 * blockIdx.x] = mn;
+    part[2 * blockIdx.x + 1] = mx;
+  }
+}
+
+// what the host reads back in its one copy: records_range's block, and — only for a caller that asks — the survivors per source
+struct SourcesResult {
+  RecordsResult r;
+  int32_t kept_of[madicp_host::kMaxSources];
+};
+// one wavefront, launched only for a caller that asks for the counts: survivors of source s = pos[first record of the next
+// source] - pos[its own first record] (pos[total] is the scan's last entry: the survivor count)
+__global__ __launch_bounds__(64) void sources_counts(SourceTable T, const uint32_t* __restrict__ pos, SourcesResult* __restrict__ res) {
+  const int s = threadIdx.x;
+  if (s >= T.n_sources) return;
+  const long end = s + 1 < T.n_sources ? T.src[s + 1].first_rec : T.n_total;
+  res->kept_of[s] = (int32_t)(pos[end] - pos[T.src[s].first_rec]);
+}
+
+// scatter pass: records_scatter over the global tile index, the survivor's point taken to the base frame and its stamp normalised
+// on the common clock.  stamps == nullptr: sources without a time field.
+__global__ __launch_bounds__(256) void sources_scatter(const unsigned char* __restrict__ rec, SourceTable T, const uint32_t* __restrict__ keep,
+                                                       const uint32_t* __restrict__ pos, double sin_a, double cos_a,
+                                                       const RecordsResult* __restrict__ res, double* __restrict__ out,
+                                                       double* __restrict__ stamps) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
+  const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
+  const double t0 = res->t0, t1 = res->t1;
+  for (long tile = blockIdx.x; tile < T.n_tiles; tile += gridDim.x) {
+    const SourceEntry& E = T.src[source_of_tile(T, tile)];
+    const madicp_host::RecordLayout L = E.L;
+    const long first = (tile - E.first_tile) * E.per_tile;
+    const int cnt = (int)min((long)E.per_tile, E.n - first);
+    records_stage(rec + E.byte_off + first * L.step, cnt * L.step, s_tile);
+    __syncthreads();
+    const long g = E.first_rec + first + threadIdx.x;
+    if ((int)threadIdx.x < cnt && keep[g]) {
+      const unsigned char* p = s_bytes + threadIdx.x * L.step;
+      double o[3];
+      madicp_host::ingest_point(madicp_host::record_f32(p + L.off_x), madicp_host::record_f32(p + L.off_y),
+                                madicp_host::record_f32(p + L.off_z), E.flags & kSrcKitti, sin_a, cos_a, o);
+      if (!(E.flags & kSrcIdentity)) madicp_host::sensor_to_base(E.R, E.t, o);
+      const long d = pos[g];
+      out[3 * d] = o[0]; out[3 * d + 1] = o[1]; out[3 * d + 2] = o[2];
+      if (stamps) {
+        const double tc = madicp_host::source_clock(madicp_host::record_time(p + L.off_t, L.t_type), E.flags & kSrcClockAsIs, E.t_scale,
+                                                    E.t_offset);
+        stamps[d] = madicp_host::record_stamp(tc, t0, t1);
+      }
     }
     __syncthreads();
   }

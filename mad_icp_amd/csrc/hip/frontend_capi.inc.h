@@ -43,6 +43,9 @@ struct FrontScratch {
   double* rec_part = nullptr;    // (2 * fe::kRecMaxBlocks)
   fe::RecordsResult* rec_res = nullptr;
   fe::RecordsResult* h_rec_res = nullptr;
+  // ... of several sources' records: the same block with the survivors per source behind it, and its pinned copy
+  fe::SourcesResult* src_res = nullptr;
+  fe::SourcesResult* h_src_res = nullptr;
   // a construction between its two halves (tree_build_begin_on / tree_build_end_on)
   struct InFlight {
     bool active = false;
@@ -141,6 +144,7 @@ size_t carve_scratch(FrontScratch& fs, char* base, int64_t nc) {
   carve(fs.table, kDeskewTableMax * 13);
   carve(fs.rec_part, 2 * fe::kRecMaxBlocks);
   carve(fs.rec_res, 1);
+  carve(fs.src_res, 1);
   fs.sort_tmp_bytes = sort_temp_bytes(nc);
   carve(fs.sort_tmp, fs.sort_tmp_bytes);
   return off;
@@ -156,6 +160,7 @@ int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
     HIP_TRY(hipHostMalloc(&fs.h_table, sizeof(double) * kDeskewTableMax * 13, hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&fs.h_table_read, hipEventDisableTiming));
     HIP_TRY(hipHostMalloc(&fs.h_rec_res, sizeof(fe::RecordsResult), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&fs.h_src_res, sizeof(fe::SourcesResult), hipHostMallocDefault));
   }
   if (n <= fs.n_cap) return MADICP_OK;
   if (fs.block) {
@@ -191,6 +196,7 @@ void front_destroy(madicp_ctx* ctx) {  // called by madicp_ctx_destroy (streams 
   if (fs.h_line) hipHostFree(fs.h_line);
   if (fs.h_table) hipHostFree(fs.h_table);
   if (fs.h_rec_res) hipHostFree(fs.h_rec_res);
+  if (fs.h_src_res) hipHostFree(fs.h_src_res);
   if (fs.h_table_read) hipEventDestroy(fs.h_table_read);
   delete ctx->front;
   ctx->front = nullptr;
@@ -516,6 +522,107 @@ int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_rec
   if (out_t_range) {
     out_t_range[0] = fs->h_rec_res->t0;
     out_t_range[1] = fs->h_rec_res->t1;
+  }
+  return register_cloud(ctx, c, out_cloud_id);
+}
+
+// Several sources' byte records -> ONE filtered base-frame cloud with one set of stamps on a common clock (include/madicp_hip.h;
+// kernels: fe::sources_mark, fe::records_range, fe::sources_scatter).  All sources go through ONE acquisition of the pinned
+// staging and ONE host-to-device copy into buf[0] of the scratch, each at a 64-byte aligned offset (a tile then starts 16-byte
+// aligned whatever the steps in front of it), the gaps zeroed: the last tile of a source loads up to 3 bytes past its records.
+// The chain — mark, scan, range, one copy of the result block, one synchronisation, scatter — is the single-source ingest's,
+// whatever the number of sources.
+int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources, const double* t_range,
+                                int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]) {
+  if (!ctx || !sources || !out_cloud_id || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  if (n_sources < 1 || n_sources > MADICP_MAX_SOURCES) return fail(MADICP_ERR_INVALID, "1 .. 8 sources");
+  madicp_host::RecordSource src[MADICP_MAX_SOURCES];
+  for (int s = 0; s < n_sources; ++s) src[s] = madicp_host::record_source_of(sources[s]);
+  if (const char* why = madicp_host::record_sources_refusal(src, n_sources, t_range)) return fail(MADICP_ERR_INVALID, why);
+  // the table of the sources: where each one's bytes, tiles and records begin
+  fe::SourceTable T{};
+  T.n_sources = n_sources;
+  T.has_time = src[0].L.t_type != madicp_host::kTimeNone ? 1 : 0;
+  size_t staged = 0;  // bytes of the one copy
+  for (int s = 0; s < n_sources; ++s) {
+    fe::SourceEntry& E = T.src[s];
+    const size_t bytes = (size_t)src[s].L.step * (size_t)src[s].n;
+    E.byte_off = (long)((staged + 63) & ~(size_t)63);
+    E.first_tile = T.n_tiles;
+    E.first_rec = T.n_total;
+    E.n = (long)src[s].n;
+    E.L = src[s].L;
+    E.per_tile = fe::records_per_tile(E.L.step);
+    E.flags = (src[s].kitti ? fe::kSrcKitti : 0) | (madicp_host::source_extrinsic_is_identity(src[s].R, src[s].t) ? fe::kSrcIdentity : 0) |
+              (madicp_host::source_clock_as_is(src[s].t_scale, src[s].t_offset) ? fe::kSrcClockAsIs : 0);
+    E.min_range = src[s].min_range;
+    E.max_range = src[s].max_range;
+    E.t_scale = src[s].t_scale;
+    E.t_offset = src[s].t_offset;
+    std::memcpy(E.R, src[s].R, sizeof(E.R));
+    std::memcpy(E.t, src[s].t, sizeof(E.t));
+    T.n_tiles += (E.n + E.per_tile - 1) / E.per_tile;
+    T.n_total += E.n;
+    staged = (size_t)E.byte_off + ((bytes + 3) & ~(size_t)3);  // what the source's last tile's dword loads reach
+  }
+  const int64_t n_total = T.n_total;
+  // (a point of the scratch is 24 bytes: wider records ask for a scratch laid out for proportionally more points)
+  const int64_t n_layout = std::max<int64_t>(n_total, (int64_t)((staged + 23) / 24));
+  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, n_layout, &fs));
+  {
+    int hb = 0;
+    char* stage = nullptr;
+    RC_TRY(ctx->staging.acquire(staged, &hb, &stage));
+    size_t at = 0;
+    for (int s = 0; s < n_sources; ++s) {
+      const size_t bytes = (size_t)src[s].L.step * (size_t)src[s].n;
+      std::memset(stage + at, 0, (size_t)T.src[s].byte_off - at);
+      std::memcpy(stage + T.src[s].byte_off, src[s].data, bytes);
+      at = (size_t)T.src[s].byte_off + bytes;
+    }
+    std::memset(stage + at, 0, staged - at);
+    HIP_TRY(hipMemcpyAsync(fs->P.buf[0], stage, staged, hipMemcpyHostToDevice, ctx->copy));
+    HIP_TRY(ctx->staging.sent(hb, ctx->copy));
+  }
+  const unsigned char* d_rec = reinterpret_cast<const unsigned char*>(fs->P.buf[0]);
+  uint32_t* keep = fs->P.leaf_start;
+  const int blocks = static_cast<int>(std::min<int64_t>(T.n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
+  hipLaunchKernelGGL(fe::sources_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, keep, fs->rec_part);
+  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_total, &fs->P.st->n_leaves));
+  hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, T.has_time,
+                     (T.has_time && t_range) ? 1 : 0, t_range ? t_range[0] : 0.0, t_range ? t_range[1] : 0.0,
+                     (const int32_t*)&fs->P.st->n_leaves, &fs->src_res->r);
+  if (out_n_per_source)  // (the survivors per source ride in the same copy)
+    hipLaunchKernelGGL(fe::sources_counts, dim3(1), dim3(64), 0, ctx->copy, T, (const uint32_t*)fs->S, fs->src_res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(fs->h_src_res, fs->src_res, out_n_per_source ? sizeof(fe::SourcesResult) : sizeof(fe::RecordsResult),
+                         hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the size of the result decides the allocation; the range comes with it
+  const int64_t kept = fs->h_src_res->r.kept;
+  if (kept < 1) return fail(MADICP_ERR_INVALID, "no point of any source survives the range filter");
+  DevCloud c;
+  RC_TRY(new_cloud(ctx, kept, &c));
+  if (T.has_time) {
+    void* p = nullptr;
+    const int rc = pool_alloc(ctx, sizeof(double) * (size_t)kept, ctx->copy, &p);
+    if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
+    c.stamps = static_cast<double*>(p);
+  }
+  const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
+  hipLaunchKernelGGL(fe::sources_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, (const uint32_t*)keep, (const uint32_t*)fs->S,
+                     std::sin(angle), std::cos(angle), (const fe::RecordsResult*)&fs->src_res->r, c.xyz, c.stamps);
+  CLOUD_TRY(hipGetLastError());
+  CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
+  *out_n = kept;
+  if (out_n_per_source)
+    for (int s = 0; s < n_sources; ++s) out_n_per_source[s] = fs->h_src_res->kept_of[s];
+  if (out_t_range) {
+    out_t_range[0] = fs->h_src_res->r.t0;
+    out_t_range[1] = fs->h_src_res->r.t1;
   }
   return register_cloud(ctx, c, out_cloud_id);
 }

@@ -5,7 +5,7 @@
 // contraction like csrc/host/deskew.cpp: bit-equal to the device by construction.  Every field is read through memcpy; nothing
 // past data[n * step) is touched.  What a Pipeline with the host front-end runs for computeRecordsStamped.
 // Defined inline here, so that every program that compiles pipeline.cpp has it whatever else it links; ingest_records.cpp holds
-// the exported C entry point (madicp_host_ingest_records, include/madicp_host.h).
+// the exported C entry points (madicp_host_ingest_records, madicp_host_ingest_sources: include/madicp_host.h).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -52,6 +52,68 @@ inline int ingest_records(const void* data, int64_t n, const RecordLayout& L, do
     ingest_point(x, y, z, kitti_correction ? 1 : 0, sin_a, cos_a, out_xyz + 3 * kept);
     if (has_time && out_stamps01) out_stamps01[kept] = record_stamp(record_time(p + L.off_t, L.t_type), t0, t1);
     ++kept;
+  }
+  *out_n = kept;
+  if (out_t_range) {
+    out_t_range[0] = t0;
+    out_t_range[1] = t1;
+  }
+  return 0;
+}
+
+// The host twin of madicp_cloud_ingest_sources: several sources' records -> one base-frame cloud, source 0's survivors first in
+// input order, then source 1's ..., with one set of stamps normalised on the common clock (ingest_point.h: source_clock,
+// sensor_to_base; the range filter in each sensor's own frame with its own bounds).  out_xyz: room for (total records, 3)
+// doubles, out_stamps01: room for that many (may be null; not written without a time field); out_n_per_source (n_sources
+// values) and out_t_range: optional.  Returns 0; -1 for what record_sources_refusal refuses or a null out_xyz / out_n, nothing
+// written.  No survivor is NOT an error here: *out_n = 0.  Nothing past data[n * step) of any source is touched.
+inline int ingest_sources(const RecordSource* src, int n_sources, const double* t_range, double* out_xyz, double* out_stamps01,
+                          int64_t* out_n, int64_t* out_n_per_source, double* out_t_range) {
+  if (!out_xyz || !out_n) return -1;
+  if (record_sources_refusal(src, n_sources, t_range)) return -1;
+  const bool has_time = src[0].L.t_type != kTimeNone;
+  bool as_is[kMaxSources];
+  for (int s = 0; s < n_sources; ++s) as_is[s] = source_clock_as_is(src[s].t_scale, src[s].t_offset);
+  // the range: every record of every source, dropped ones included, finite times on the common clock only
+  double t0 = HUGE_VAL, t1 = -HUGE_VAL;
+  if (has_time && t_range) {
+    t0 = t_range[0];
+    t1 = t_range[1];
+  } else if (has_time) {
+    for (int s = 0; s < n_sources; ++s) {
+      const RecordSource& S = src[s];
+      const unsigned char* rec = static_cast<const unsigned char*>(S.data);
+      for (int64_t i = 0; i < S.n; ++i) {
+        const double tc = source_clock(record_time(rec + i * S.L.step + S.L.off_t, S.L.t_type), as_is[s] ? 1 : 0, S.t_scale, S.t_offset);
+        if (!time_is_finite(tc)) continue;
+        if (tc < t0) t0 = tc;
+        if (tc > t1) t1 = tc;
+      }
+    }
+    t0 = t0 + 0.0;  // (a -0.0 extreme becomes +0.0)
+    t1 = t1 + 0.0;
+  }
+  const double angle = ingest_kitti_angle();
+  const double sin_a = std::sin(angle), cos_a = std::cos(angle);
+  int64_t kept = 0;
+  for (int s = 0; s < n_sources; ++s) {
+    const RecordSource& S = src[s];
+    const RecordLayout& L = S.L;
+    const unsigned char* rec = static_cast<const unsigned char*>(S.data);
+    const bool identity = source_extrinsic_is_identity(S.R, S.t);
+    const int64_t before = kept;
+    for (int64_t i = 0; i < S.n; ++i) {
+      const unsigned char* p = rec + i * L.step;
+      const float x = record_f32(p + L.off_x), y = record_f32(p + L.off_y), z = record_f32(p + L.off_z);
+      if (ingest_drops(x, y, z, S.min_range, S.max_range)) continue;
+      double* o = out_xyz + 3 * kept;
+      ingest_point(x, y, z, S.kitti ? 1 : 0, sin_a, cos_a, o);
+      if (!identity) sensor_to_base(S.R, S.t, o);
+      if (has_time && out_stamps01)
+        out_stamps01[kept] = record_stamp(source_clock(record_time(p + L.off_t, L.t_type), as_is[s] ? 1 : 0, S.t_scale, S.t_offset), t0, t1);
+      ++kept;
+    }
+    if (out_n_per_source) out_n_per_source[s] = kept - before;
   }
   *out_n = kept;
   if (out_t_range) {

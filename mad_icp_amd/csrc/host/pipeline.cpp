@@ -352,6 +352,64 @@ void Pipeline::computeRecordsStamped(const double& curr_stamp, const void* data,
   }
 }
 
+// A frame from several sensors' byte records (pipeline.h): computeRecordsStamped with the multi-source ingest in front.
+void Pipeline::computeSourcesStamped(const double& curr_stamp, const RecordSource* sources, int n_sources, const double* t_range) {
+  if (const char* why = record_sources_refusal(sources, n_sources, t_range))
+    throw std::invalid_argument(std::string("Pipeline::computeSourcesStamped: ") + why);
+  RecordSource src[kMaxSources];
+  int64_t total = 0;
+  for (int s = 0; s < n_sources; ++s) {
+    src[s] = sources[s];
+    if (!deskew_) src[s].L.t_type = kTimeNone;
+    total += src[s].n;
+  }
+  if (!deskew_) t_range = nullptr;
+  const bool stamped = src[0].L.t_type != kTimeNone;
+  if (device_frontend_) {
+    madicp_record_source cs[MADICP_MAX_SOURCES];
+    for (int s = 0; s < n_sources; ++s) {
+      const RecordSource& S = src[s];
+      madicp_record_source& c = cs[s];
+      c.data = S.data;
+      c.n_records = S.n;
+      c.layout = madicp_record_layout{S.L.step, S.L.off_x, S.L.off_y, S.L.off_z, S.L.off_t, S.L.t_type};
+      std::copy(S.R, S.R + 9, c.R);
+      std::copy(S.t, S.t + 3, c.t);
+      c.min_range = S.min_range;
+      c.max_range = S.max_range;
+      c.t_scale = S.t_scale;
+      c.t_offset = S.t_offset;
+      c.kitti_correction = S.kitti ? 1 : 0;
+      c.reserved = 0;
+    }
+    is_map_updated_ = false;
+    const double t_pre = now_ms();
+    ingestPrologue();
+    int cloud_id = -1;
+    {
+      DeviceLock lock(Device::mutex());
+      int64_t kept = 0;
+      check(madicp_cloud_ingest_sources(Device::ctx(), cs, n_sources, t_range, &cloud_id, &kept, nullptr, nullptr),
+            "madicp_cloud_ingest_sources");
+    }
+    computeWithTree(curr_stamp, buildOnDevice(cloud_id, nullptr, 0, stamped), nullptr, t_pre);
+    return;
+  }
+  ContainerType cloud(static_cast<size_t>(total));
+  std::vector<double> stamps(stamped ? static_cast<size_t>(total) : 0);
+  int64_t kept = 0;
+  if (ingest_sources(src, n_sources, t_range, cloud[0].data(), stamped ? stamps.data() : nullptr, &kept, nullptr, nullptr) != 0)
+    throw std::invalid_argument("Pipeline::computeSourcesStamped: bad arguments");
+  if (kept < 1) throw std::invalid_argument("Pipeline::computeSourcesStamped: no point survives the range filter");
+  cloud.resize(static_cast<size_t>(kept));
+  if (stamped) {
+    stamps.resize(static_cast<size_t>(kept));
+    computeStamped(curr_stamp, std::move(cloud), stamps);
+  } else {
+    compute(curr_stamp, std::move(cloud));
+  }
+}
+
 // pipeline.cpp:125-265, the device front-end's half: the scan is only READ (key of a look-ahead, or the upload), so a view does
 void Pipeline::computeView(const double& curr_stamp, const Vector3d* curr_cloud, size_t n) {
   if (!curr_cloud || n == 0) throw std::invalid_argument("Pipeline::compute: empty cloud");

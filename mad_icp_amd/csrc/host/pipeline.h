@@ -130,6 +130,15 @@ class Pipeline {
   void computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout, double min_range,
                              double max_range, bool kitti_correction, const double* t_range);
 
+  // additive: one frame from SEVERAL sensors' byte records (a multi-head rig: every source in its own sensor frame, with its own
+  // layout, range bounds, sensor -> base extrinsic and time scale / offset onto one common clock — RecordSource, ingest_point.h).
+  // Device front-end: madicp_cloud_ingest_sources — one staged copy, one chain of launches, one synchronisation whatever n is —
+  // then deskew by the merged cloud's own stamps, build and registration, as computeRecordsStamped.  Host front-end: the host
+  // twin (ingest_records.h: ingest_sources), then computeStamped / compute — the same bits.  t_range: null = the min / max time
+  // over all sources on the common clock, else {t_begin, t_end} there.  With deskew = false the time fields and t_range are
+  // ignored.  std::invalid_argument for what the ingest refuses (record_sources_refusal) and when no record survives.
+  void computeSourcesStamped(const double& curr_stamp, const RecordSource* sources, int n_sources, const double* t_range);
+
   // additive: the keyframe map sharded over the ranks of a node.  Every rank runs ONE Pipeline and is
   // fed the same scans in the same order; setShard(rank, world) makes this one keep the tree of a keyframe only when
   // keyframe_owner(ordinal, world) == rank (csrc/common/keyframe_owner.h; ordinal: promotion order, the first scan is 0) and

@@ -3,6 +3,7 @@
 #include "pipeline.h"
 
 #include <stdexcept>
+#include <vector>
 
 PYBIND11_MODULE(pypeline, m) {
   m.doc() = "mad_icp_amd: MAD-ICP odometry pipeline with the registration on MI355X, drop-in for mad_icp.src.pybind.pypeline";
@@ -104,6 +105,49 @@ PYBIND11_MODULE(pypeline, m) {
          },
          py::arg("stamp"), py::arg("records"), py::arg("min_range"), py::arg("max_range"), py::arg("kitti_correction") = false,
          py::arg("time_field") = py::none(), py::arg("time_range") = py::none(), py::arg("layout") = py::none())
+    // additive: a frame from SEVERAL sensors' byte records (Pipeline::computeSourcesStamped): a sequence of
+    // mad_icp_amd.records.Source — the buffer as computeRecordsStamped takes it, the range bounds in the sensor's frame, the 4x4
+    // sensor_to_base and the time field's scale / offset onto the common clock.  The arrays are read in place.  time_range:
+    // None = the min / max over all sources on the common clock, else (t_begin, t_end) there.  ValueError for what the helper or
+    // the ingest refuses.
+    .def("computeSourcesStamped",
+         [](Pipeline& self, double stamp, py::object sources, py::object time_range) {
+           const py::list rs = py::module_::import("mad_icp_amd.records").attr("resolve_sources")(sources);
+           std::vector<madicp_host::RecordSource> src(py::len(rs));
+           std::vector<py::array> keep;  // (the buffers stay alive across the call)
+           for (size_t k = 0; k < src.size(); ++k) {
+             const py::tuple r = rs[k];
+             keep.push_back(r[0].cast<py::array>());
+             madicp_host::RecordSource& S = src[k];
+             S.data = keep.back().data();
+             S.n = r[1].cast<int64_t>();
+             const py::tuple l = r[2];
+             S.L = madicp_host::RecordLayout{l[0].cast<int32_t>(), l[1].cast<int32_t>(), l[2].cast<int32_t>(),
+                                             l[3].cast<int32_t>(), l[4].cast<int32_t>(), l[5].cast<int32_t>()};
+             const py::tuple R = r[3], t = r[4];
+             for (int i = 0; i < 9; ++i) S.R[i] = R[i].cast<double>();
+             for (int i = 0; i < 3; ++i) S.t[i] = t[i].cast<double>();
+             S.min_range = r[5].cast<double>();
+             S.max_range = r[6].cast<double>();
+             S.t_scale = r[7].cast<double>();
+             S.t_offset = r[8].cast<double>();
+             S.kitti = r[9].cast<bool>() ? 1 : 0;
+           }
+           double range[2];
+           const bool have_range = !time_range.is_none();
+           if (have_range) {
+             const py::sequence tr = time_range.cast<py::sequence>();
+             if (py::len(tr) != 2) throw py::value_error("time_range must be (t_begin, t_end)");
+             range[0] = tr[0].cast<double>();
+             range[1] = tr[1].cast<double>();
+           }
+           try {
+             self.computeSourcesStamped(stamp, src.data(), static_cast<int>(src.size()), have_range ? range : nullptr);
+           } catch (const std::invalid_argument& e) {
+             throw py::value_error(e.what());
+           }
+         },
+         py::arg("stamp"), py::arg("sources"), py::arg("time_range") = py::none())
     // additive: the keyframe map sharded over the ranks of a node (csrc/host/pipeline.h; mad_icp_amd.sharded.shard_pipeline
     // installs the communicator and calls this)
     .def("setShard", &Pipeline::setShard, py::arg("rank"), py::arg("world"))

@@ -8,6 +8,12 @@ that array's dtype into the six integers of madicp_record_layout (include/madicp
     layout_of(dtype, time_field=None) -> RecordLayout(point_step, off_x, off_y, off_z, off_t, t_type)
     resolve(records, time_field=None, layout=None) -> (n_records, RecordLayout)     what Pipeline.computeRecordsStamped calls
 
+and, for a rig of several sensors (Pipeline.computeSourcesStamped, madicp_cloud_ingest_sources):
+
+    Source(records, min_range, max_range, sensor_to_base=None, time_scale=1.0, time_offset=0.0, kitti_correction=False,
+           time_field=None, layout=None)                                           one sensor's buffer and how to read it
+    resolve_sources(sources) -> [ResolvedSource(...)]                              what Pipeline.computeSourcesStamped calls
+
 `time_field=None` takes the first of `t`, `timestamp`, `time` that the dtype has (point_cloud2.py:72), and no time field at
 all (t_type = T_NONE) when it has none; `time_field=False` ignores a time field that is there.
 """
@@ -101,3 +107,73 @@ def resolve(records, time_field=None, layout=None):
     if lay.point_step != records.shape[1]:
         raise ValueError("layout.point_step differs from the rows' length")
     return int(records.shape[0]), lay
+
+
+MAX_SOURCES = 8  # MADICP_MAX_SOURCES
+MAX_RECORDS = 2 ** 30
+
+
+class Source:
+    """One sensor's records in a frame of several (madicp_record_source): the buffer as resolve() takes it, the range bounds IN
+    THE SENSOR'S FRAME, `sensor_to_base` (4x4, None = identity: the upper 3x4 is used as given, orthonormality is the caller's
+    business) and the time field's way onto the clock all sources share: common = field * time_scale + time_offset (uint32
+    nanoseconds: time_scale=1e-9, time_offset = the message's header stamp RELATIVE TO THE FRAME'S START — an absolute epoch
+    as offset eats the nanoseconds)."""
+
+    __slots__ = ("records", "min_range", "max_range", "sensor_to_base", "time_scale", "time_offset", "kitti_correction",
+                 "time_field", "layout")
+
+    def __init__(self, records, min_range, max_range, sensor_to_base=None, time_scale=1.0, time_offset=0.0, kitti_correction=False,
+                 time_field=None, layout=None):
+        self.records = records
+        self.min_range = min_range
+        self.max_range = max_range
+        self.sensor_to_base = sensor_to_base
+        self.time_scale = time_scale
+        self.time_offset = time_offset
+        self.kitti_correction = kitti_correction
+        self.time_field = time_field
+        self.layout = layout
+
+
+ResolvedSource = collections.namedtuple(
+    "ResolvedSource", "records n_records layout R t min_range max_range time_scale time_offset kitti_correction")
+
+
+def resolve_sources(sources):
+    """[ResolvedSource] of what Pipeline.computeSourcesStamped was given — resolve() per source, R (9 floats, row-major) and t (3)
+    of sensor_to_base.  ValueError where the native layers would refuse: no source or more than MAX_SOURCES, a source that is not
+    a Source, what resolve() refuses, an empty source or more than 2^30 records in all, a sensor_to_base that is not 4x4 or not
+    finite in its upper 3x4, a time_scale that is not finite and > 0, a non-finite time_offset, sources with and without a time
+    field."""
+    sources = list(sources)
+    if not 1 <= len(sources) <= MAX_SOURCES:
+        raise ValueError("1 .. %d sources, got %d" % (MAX_SOURCES, len(sources)))
+    out = []
+    for k, src in enumerate(sources):
+        if not isinstance(src, Source):
+            raise ValueError("source %d is not a mad_icp_amd.records.Source" % k)
+        n, lay = resolve(src.records, src.time_field, src.layout)
+        if n < 1:
+            raise ValueError("source %d holds no records" % k)
+        if src.sensor_to_base is None:
+            T = np.eye(4)
+        else:
+            T = np.asarray(src.sensor_to_base, dtype=np.float64)
+            if T.shape != (4, 4):
+                raise ValueError("source %d: sensor_to_base must be 4x4" % k)
+            if not np.isfinite(T[:3]).all():
+                raise ValueError("source %d: sensor_to_base has a non-finite entry" % k)
+        scale, offset = float(src.time_scale), float(src.time_offset)
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError("source %d: time_scale must be finite and > 0" % k)
+        if not np.isfinite(offset):
+            raise ValueError("source %d: time_offset must be finite" % k)
+        out.append(ResolvedSource(src.records, n, lay, tuple(float(v) for v in T[:3, :3].reshape(-1)),
+                                  tuple(float(v) for v in T[:3, 3]), float(src.min_range), float(src.max_range), scale, offset,
+                                  bool(src.kitti_correction)))
+    if sum(r.n_records for r in out) > MAX_RECORDS:
+        raise ValueError("more than 2^30 records in all")
+    if len({r.layout.t_type != T_NONE for r in out}) != 1:
+        raise ValueError("a time field in every source or in none")
+    return out
