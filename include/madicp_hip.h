@@ -371,6 +371,26 @@ int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sou
                                 const double* t_range /* NULL: min / max over all records; else {t_begin, t_end} */,
                                 int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source /* n_sources, optional */,
                                 double out_t_range[2] /* optional */);
+/* A RESIDENT CLOUD OUT — what a mapping, loop-closure or visualisation consumer wants of a registered scan: the points in
+ * another frame (the map's), as float32, thinned to one point per voxel.  Additive.  The rule, everything in fp64 without
+ * contraction (one source for the device and the host twin: mad_icp_amd/csrc/common/export_point.h):
+ *   position      q[i] = t[i] + (R[3i] * p0 + (R[3i+1] * p1 + R[3i+2] * p2)), R row-major — the evaluation order of pose * point in
+ *                 madicp_cloud_deskew_stamped and of sensor->base above.  R is used AS GIVEN.
+ *   output        (float)q[i], round to nearest even; overflow to +-inf as IEEE gives it.
+ *   voxel == 0    every point goes out, in cloud order; nothing is dropped, NaN rows included: *out_n = the cloud's size.
+ *   voxel > 0     cell per axis f = floor(q[i] / voxel), a true division.  A point is a CANDIDATE only if all three cells satisfy
+ *                 -1048576.0 <= f < 1048576.0 — NaN and +-inf fail and the point is dropped.  Key = (kx + 2^20) | (ky + 2^20) << 21
+ *                 | (kz + 2^20) << 42.  Of the candidates that share a key the one with the LOWEST INDEX in cloud order is kept;
+ *                 kept points go out in ascending index order.  No candidate at all is MADICP_OK with *out_n = 0.
+ * The result is a function of the input alone: no scheduling order shows in it, two calls give the same bytes.  The cloud — and
+ * the stamps it may carry — is only read.  Runs on the copy stream in idle parts of the builder's scratch; at most two host
+ * synchronisations (the row count, then the rows; voxel == 0: one).  MADICP_ERR_INVALID — before anything is launched or
+ * allocated, nothing written — for a null argument, an unknown cloud, a non-finite entry of R or t, a voxel that is negative or
+ * not finite.  MADICP_ERR_CAPACITY while a look-ahead build is in flight (nothing written), and when capacity_rows is smaller
+ * than the rows needed: *out_n is that number and out_xyz is not written — call again with room for *out_n rows (the cloud's
+ * size always suffices).  Bit-equal to madicp_host_cloud_export_f32 (madicp_host.h). */
+int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
+                            int64_t capacity_rows, int64_t* out_n);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes
  * a resident tree exactly like one given to madicp_tree_upload (same node format, madicp_tree_download returns it).
  * Same decisions as the reference node by node, the reference's member order (the permutation utils.h:37-52 leaves), and

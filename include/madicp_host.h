@@ -89,6 +89,15 @@ int madicp_host_ingest_records(const void* data, int64_t n_records, const madicp
  * written. */
 int madicp_host_ingest_sources(const madicp_record_source* sources, int n_sources, const double* t_range, double* out_xyz,
                                double* out_stamps01, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]);
+/* The host twin of madicp_cloud_export_f32 (madicp_hip.h: the same rule from the same per-point source
+ * csrc/common/export_point.h, bit-equal): xyz (n, 3) float64, n >= 0, taken through (R row-major, t) and written as float32
+ * rows, every point in cloud order (voxel == 0) or the lowest-index point of every voxel in ascending index order (voxel > 0);
+ * what a Pipeline with the host front-end runs for registeredScan().  xyz is only read.  Returns MADICP_OK with the row count in
+ * *out_n (0 is legal: no candidate) and rows [0, *out_n) of out_xyz written; MADICP_ERR_CAPACITY when capacity_rows is smaller
+ * than the rows needed — *out_n is that number, out_xyz is not written; MADICP_ERR_INVALID, nothing written at all, for a null
+ * argument, n < 0 or > 2^30, a non-finite entry of R or t, a voxel that is negative or not finite. */
+int madicp_host_cloud_export_f32(const double* xyz, int64_t n, const double R[9], const double t[3], double voxel, float* out_xyz,
+                                 int64_t capacity_rows, int64_t* out_n);
 
 /* ---- the keyframe map sharded over the ranks of a node (Pipeline::setShard, csrc/host/pipeline.h) ---- */
 /* The rank that owns the keyframe of ORDINAL k — promotion order: the first scan is 0, every promotion adds 1; not the frame

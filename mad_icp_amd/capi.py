@@ -157,6 +157,7 @@ def hip_lib():
                                                   C.c_int, _dp, _ip, _i64p, _dp]
         L.madicp_cloud_ingest_sources.argtypes = [C.c_void_p, C.POINTER(RecordSourceC), C.c_int, _dp, _ip, _i64p, _i64p, _dp]
         L.madicp_cloud_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64]
+        L.madicp_cloud_export_f32.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
@@ -207,6 +208,7 @@ def host_lib():
         L.madicp_host_ingest_records.argtypes = [C.c_void_p, C.c_int64, C.POINTER(RecordLayoutC), C.c_double, C.c_double, C.c_int, _dp,
                                                  _dp, _dp, _i64p, _dp]
         L.madicp_host_ingest_sources.argtypes = [C.POINTER(RecordSourceC), C.c_int, _dp, _dp, _dp, _i64p, _i64p, _dp]
+        L.madicp_host_cloud_export_f32.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
         L.madicp_host_debug_partition.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_int]
@@ -470,6 +472,20 @@ def host_ingest_sources(sources, t_range=None):
     return xyz[:k].copy(), (st[:k].copy() if timed else None), (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]]
 
 
+def host_cloud_export_f32(xyz, R, t, voxel):
+    """madicp_host_cloud_export_f32: the host twin of Context.cloud_export_f32.  xyz (n, 3) float64 through (R (3, 3), t (3,)) as
+    float32 rows: every point (voxel = 0) or the lowest-index point of every voxel.  Returns (M, 3) float32."""
+    a = _f64(xyz).reshape(-1, 3)
+    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+    n = a.shape[0]
+    out, m = np.empty((max(n, 1), 3), np.float32), C.c_int64(0)
+    rc = host_lib().madicp_host_cloud_export_f32(a.ctypes.data_as(_dp), n, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), float(voxel),
+                                                 out.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(m))
+    if rc != 0:
+        raise MadIcpError("madicp_host_cloud_export_f32: error %d (bad arguments)" % rc)
+    return out[:m.value].copy()
+
+
 class Context:
     """One device + one stream (include/madicp_hip.h)."""
 
@@ -624,6 +640,16 @@ class Context:
         out = np.empty(n)
         _check(hip_lib().madicp_cloud_stamps(self._h, cid, out.ctypes.data_as(_dp), n))
         return out
+
+    def cloud_export_f32(self, cid, R, t, voxel):
+        """A resident cloud out (madicp_cloud_export_f32): through (R (3, 3), t (3,)) as float32 rows, every point in cloud order
+        (voxel = 0) or the lowest-index point of every voxel in ascending index order.  Returns (M, 3) float32."""
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        n = self.cloud_size(cid)
+        out, m = np.empty((max(n, 1), 3), np.float32), C.c_int64(0)
+        _check(hip_lib().madicp_cloud_export_f32(self._h, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), float(voxel),
+                                                 out.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(m)))
+        return out[:m.value].copy()
 
     def cloud_deskew_own_stamps(self, cid, velocity, sensor_hz, want_chunks=False):
         """cloud_deskew_stamped from the stamps the cloud carries itself.  Returns the chunks (n,) int32 when asked for."""

@@ -1,0 +1,56 @@
+// What happens to ONE point of a registered scan on its way OUT — ONE source for the device export kernels (csrc/hip/frontend.hip.h:
+// export_claim / export_mark / export_scatter) and for the host twin (csrc/host/cloud_export.cpp), so the two cannot drift apart:
+// the position in the target frame, the float that goes out, and the voxel a position falls in.  Every translation unit that
+// includes this is compiled WITHOUT floating-point contraction (-ffp-contract=off; the device header adds the pragma).
+//
+// The rule (include/madicp_hip.h: madicp_cloud_export_f32), everything in fp64:
+//   position  q[i] = t[i] + (R[3i] p0 + (R[3i+1] p1 + R[3i+2] p2))   — the order of pose * point in the stamped deskew and the
+//             sources ingest (sensor_to_base's default branch)
+//   output    (float)q[i], round to nearest even; overflow to +-inf as IEEE gives it
+//   voxel > 0 cell f = floor(q[i] / voxel) per axis, a true division; the point is a CANDIDATE only if all three satisfy
+//             -2^20 <= f < 2^20 (NaN and +-inf fail every comparison: dropped); key = (kx + 2^20) | (ky + 2^20) << 21 |
+//             (kz + 2^20) << 42; of the candidates that share a key the one with the LOWEST index is kept, kept points go out in
+//             ascending index order
+//   voxel == 0 every point goes out, in cloud order, NaN rows included
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "eig3.h"  // MADICP_HD, sum3s
+
+namespace madicp_host {
+
+constexpr double kExportCellMin = -1048576.0, kExportCellEnd = 1048576.0;  // -2^20 <= cell < 2^20
+constexpr uint64_t kExportNoKey = ~uint64_t(0);  // "not a candidate"; bit 63 of a real key is never set (3 x 21 bits)
+
+MADICP_HD inline void export_position(const double* p, const double* R, const double* t, double* q) {
+  q[0] = t[0] + sum3s(R[0] * p[0], R[1] * p[1], R[2] * p[2]);
+  q[1] = t[1] + sum3s(R[3] * p[0], R[4] * p[1], R[5] * p[2]);
+  q[2] = t[2] + sum3s(R[6] * p[0], R[7] * p[1], R[8] * p[2]);
+}
+
+MADICP_HD inline float export_value(double q) { return static_cast<float>(q); }
+
+// the key of the voxel a position falls in, kExportNoKey when the point is no candidate; voxel > 0
+MADICP_HD inline uint64_t export_key(const double* q, double voxel) {
+  uint64_t key = 0;
+  for (int i = 0; i < 3; ++i) {
+    const double f = floor(q[i] / voxel);
+    if (!(f >= kExportCellMin && f < kExportCellEnd)) return kExportNoKey;
+    key |= static_cast<uint64_t>(static_cast<int64_t>(f) + 1048576) << (21 * i);
+  }
+  return key;
+}
+
+// what both entry points refuse before they look at a point (null = nothing to refuse)
+inline const char* export_refusal(const double* R, const double* t, double voxel) {
+  if (!R || !t) return "null argument";
+  for (int i = 0; i < 9; ++i)
+    if (!(R[i] - R[i] == 0.0)) return "R and t: finite entries";
+  for (int i = 0; i < 3; ++i)
+    if (!(t[i] - t[i] == 0.0)) return "R and t: finite entries";
+  if (!(voxel - voxel == 0.0) || voxel < 0.0) return "voxel: finite and >= 0 (0 = every point)";
+  return nullptr;
+}
+
+}  // namespace madicp_host

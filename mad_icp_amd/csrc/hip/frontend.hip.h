@@ -10,6 +10,8 @@
 //            clock, to ONE base-frame cloud with one set of stamps — the same chain of launches whatever their number
 //   deskew from per-point timestamps (additive, the reference has none): the same time model with the chunk read off the
 //            acquisition time the sensor driver delivers for every point — one streaming kernel, input order kept
+//   export (additive, the way OUT): a resident cloud taken through a pose, written as float32 and thinned to the lowest-index point
+//            of every voxel — a hash table of voxel keys claimed with integer atomics, then the tile scan and one scatter
 // All of it is HBM-bound streaming work (24-32 bytes per point per pass); the kernels are coalesced grid-stride
 // passes, the sort is rocPRIM's radix sort, scans are the three-kernel tile scans of tree_build.hip.h.
 #pragma once
@@ -18,6 +20,7 @@
 
 #include "tree_build.hip.h"
 #include "../common/ingest_point.h"
+#include "../common/export_point.h"
 
 #pragma clang fp contract(off)
 
@@ -505,6 +508,80 @@ __global__ __launch_bounds__(256) void deskew_stamped(const double* __restrict__
     out[3 * i + 2] = P[11] + madicp_host::sum3s(P[6] * x, P[7] * y, P[8] * z);
 #endif
     if (chunk_of) chunk_of[i] = k;
+  }
+}
+
+// ---- export: a resident cloud out, in another frame, as float32, one point per voxel ------------------------------------------
+// The rule is madicp_host's (csrc/common/export_point.h: export_position, export_value, export_key — shared with the host twin).
+// "The lowest index of every voxel" must not depend on which lane arrives first, so it is decided by two integer atomics whose
+// results commute, and read only behind a kernel boundary:
+//   export_claim   one lane per point: position, key; the key's slot in an open-addressing table (`slots` >= 2 n entries of
+//                  64-bit keys, empty = all ones, linear probing from a hash of the key) is found or claimed with a 64-bit
+//                  compare-and-swap — whoever wins, the slot ends up holding that key, and a slot never changes once it is set —
+//                  then atomicMin(owner[slot], index).  At most n distinct keys in >= 2 n slots: a probe always ends.
+//   export_mark    mark[i] = the point is a candidate and owner[slot_of[i]] == i (every claim has finished: kernel boundary)
+//   tile scan      tb_scan_tiles / tb_scan_top / tb_scan_apply: S[i] = marks before i, the total
+//   export_scatter the kept points' positions, recomputed, as three floats at row S[i]; marks == nullptr (voxel == 0): every point
+//                  at row i
+// Contention: a plain (relaxed, device-scope) load in front of each atomic skips it where it can no longer change anything — a
+// slot that already holds the key, an owner that is already <= the index (owners only fall, so a stale value only costs the
+// atomic it would have saved).  All points in ONE voxel is the worst case: one compare-and-swap wins, the lanes of the first
+// wavefronts serialise on one owner word, everybody later reads a smaller owner and passes.  Correct; not tuned for.
+constexpr uint32_t kExportNoSlot = 0xffffffffu;  // slot_of[] of a point that is no candidate; also the initial owner
+struct ExportPose {  // by value, wave-uniform: scalar loads
+  double R[9], t[3];
+};
+__device__ inline uint32_t export_slot0(uint64_t key, uint32_t slots) {
+  uint64_t h = key;  // (the 64-bit finaliser of MurmurHash3: neighbouring cells differ in a few low bits of each 21-bit field)
+  h ^= h >> 33; h *= 0xff51afd7ed558ccdull;
+  h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull;
+  h ^= h >> 33;
+  return __umulhi((uint32_t)(h >> 32), slots);  // [0, slots) without a division
+}
+__global__ __launch_bounds__(256) void export_claim(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
+                                                    unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
+                                                    uint32_t* __restrict__ slot_of) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    double q[3];
+    madicp_host::export_position(p, X.R, X.t, q);
+    const unsigned long long key = madicp_host::export_key(q, voxel);
+    uint32_t s = kExportNoSlot;
+    if (key != madicp_host::kExportNoKey) {
+      s = export_slot0(key, slots);
+      for (;;) {
+        unsigned long long seen = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (seen == madicp_host::kExportNoKey) seen = atomicCAS(&keys[s], (unsigned long long)madicp_host::kExportNoKey, key);
+        if (seen == madicp_host::kExportNoKey || seen == key) break;  // claimed now, or this key's already
+        s = (s + 1 == slots) ? 0u : s + 1;
+      }
+      if (__hip_atomic_load(&owner[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)i) atomicMin(&owner[s], (uint32_t)i);
+    }
+    slot_of[i] = s;
+  }
+}
+__global__ __launch_bounds__(256) void export_mark(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ owner, long n,
+                                                   uint32_t* __restrict__ mark) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i <= n; i += (long)gridDim.x * blockDim.x) {
+    uint32_t m = 0;
+    if (i < n) {
+      const uint32_t s = slot_of[i];
+      m = (s != kExportNoSlot && owner[s] == (uint32_t)i) ? 1u : 0u;
+    }
+    mark[i] = m;  // (entry n: the scan needs a terminator)
+  }
+}
+__global__ __launch_bounds__(256) void export_scatter(const double* __restrict__ xyz, long n, ExportPose X, const uint32_t* __restrict__ mark,
+                                                      const uint32_t* __restrict__ pos, float* __restrict__ out) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    if (mark && !mark[i]) continue;
+    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    double q[3];
+    madicp_host::export_position(p, X.R, X.t, q);
+    const long d = mark ? (long)pos[i] : i;
+    out[3 * d] = madicp_host::export_value(q[0]);
+    out[3 * d + 1] = madicp_host::export_value(q[1]);
+    out[3 * d + 2] = madicp_host::export_value(q[2]);
   }
 }
 

@@ -843,6 +843,68 @@ int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int
   return MADICP_OK;
 }
 
+// A resident cloud OUT: through (R, t), as float32 rows, thinned to the lowest-index point of every voxel (include/madicp_hip.h;
+// kernels: fe::export_claim, fe::export_mark, the tile scan, fe::export_scatter).  The cloud is only read.  Everything lives in
+// idle parts of the builder's scratch, which this call owns like every other madicp_cloud_* call — the block does not grow:
+//   buf[0]  (24 bytes per point)  the table: 2 n 64-bit keys, behind them 2 n 32-bit owners — exactly 24 n bytes, set to all
+//                                 ones by ONE memset (the empty key and the "no owner yet" index are both all ones)
+//   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->kept  the scan's total
+//   buf[1]  the float rows (12 of its 24 bytes per point)
+// The scatter is enqueued BEHIND the scan, before the host knows the count: it writes scratch only, so a refusal for capacity
+// still leaves out_xyz alone, and the rows are ready when the count arrives.  Two synchronisations: the count, then the rows
+// (voxel == 0: the count is the cloud's size — one).
+int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
+                            int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !R || !t || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (const char* why = madicp_host::export_refusal(R, t, voxel)) return fail(MADICP_ERR_INVALID, why);
+  RC_TRY(busy_with_lookahead(ctx));
+  const int64_t n = c->n;
+  if (voxel == 0.0 && capacity_rows < n) {
+    *out_n = n;
+    return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the cloud has points");
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, n, &fs));
+  fe::ExportPose X;
+  std::memcpy(X.R, R, sizeof(X.R));
+  std::memcpy(X.t, t, sizeof(X.t));
+  float* d_rows = reinterpret_cast<float*>(fs->P.buf[1]);
+  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+  int64_t rows = n;
+  if (voxel == 0.0) {
+    hipLaunchKernelGGL(fe::export_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_rows);
+    HIP_TRY(hipGetLastError());
+  } else {
+    const uint32_t slots = static_cast<uint32_t>(2 * n);  // (n <= 2^30)
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(fs->P.buf[0]);
+    uint32_t* owner = reinterpret_cast<uint32_t*>(keys + slots);
+    uint32_t* slot_of = fs->idx[0];
+    uint32_t* mark = fs->P.leaf_start;
+    HIP_TRY(hipMemsetAsync(keys, 0xff, (sizeof(unsigned long long) + sizeof(uint32_t)) * (size_t)slots, ctx->copy));
+    hipLaunchKernelGGL(fe::export_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, keys, owner, slots,
+                       slot_of);
+    hipLaunchKernelGGL(fe::export_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)owner, (long)n, mark);
+    RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->kept));
+    HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->kept, &fs->rec_res->kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
+    hipLaunchKernelGGL(fe::export_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, (const uint32_t*)mark,
+                       (const uint32_t*)fs->S, d_rows);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count decides whether the caller's buffer is large enough
+    rows = fs->h_rec_res->kept;
+    *out_n = rows;
+    if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the export needs (*out_n)");
+    if (rows == 0) return MADICP_OK;  // (no candidate: every point outside the 2^21 cells per axis, or not finite)
+  }
+  HIP_TRY(hipMemcpyAsync(out_xyz, d_rows, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  *out_n = rows;
+  return MADICP_OK;
+}
+
 }  // extern "C"
 
 // ---- MAD-tree construction on the device ------------------------------------------------------------------------------

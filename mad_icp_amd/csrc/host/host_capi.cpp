@@ -1,4 +1,6 @@
 // libmadicp_host.so — C ABI over the host tree builder (include/madicp_host.h).
+// (madicp_host_ingest_records / _sources live in ingest_records.cpp and madicp_host_cloud_export_f32 in cloud_export.cpp: each
+// links on its own into the stand-alone checks under tests/cpp.)
 #include <cstring>
 #include <vector>
 

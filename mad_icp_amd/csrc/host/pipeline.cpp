@@ -1,5 +1,6 @@
 #include "pipeline.h"
 
+#include "cloud_export.h"
 #include "deskew.h"
 #include "device.h"
 #include "task_pool.h"
@@ -155,6 +156,66 @@ Pipeline::~Pipeline() {  // Frames own their trees; trees release their HBM copi
     dropDeviceLookAhead();
   } catch (...) {
   }
+  dropKeptScan();
+}
+
+// ---- the retained scan (pipeline.h: setKeepScan / registeredScan) ---------------------------------------------------------------
+void Pipeline::dropKeptScan() {
+  if (kept_cloud_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    // (an id belongs to the context generation that issued it: after Device::shutdown() there is nothing to give back)
+    if (madicp_ctx* ctx = Device::current(kept_generation_)) madicp_cloud_release(ctx, kept_cloud_id_);
+    kept_cloud_id_ = -1;
+  }
+  kept_host_.clear();
+  have_kept_ = false;
+  kept_n_ = 0;
+}
+
+void Pipeline::keepHostScan(const ContainerType& c) {
+  if (!keep_scan_) return;
+  dropKeptScan();
+  kept_host_ = c;
+  kept_n_ = c.size();
+  have_kept_ = true;
+}
+
+void Pipeline::setKeepScan(bool on) {
+  if (on == keep_scan_) return;
+  keep_scan_ = on;
+  if (on) {
+    dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
+  } else {
+    dropKeptScan();
+  }
+}
+
+size_t Pipeline::registeredScan(float* out, size_t capacity, double voxel, bool map_frame) {
+  if (!keep_scan_) throw std::logic_error("Pipeline::registeredScan: setKeepScan(true) first");
+  if (!have_kept_) throw std::logic_error("Pipeline::registeredScan: no frame has been computed since setKeepScan(true)");
+  if (!out) throw std::invalid_argument("Pipeline::registeredScan: null buffer");
+  if (!std::isfinite(voxel) || voxel < 0.0) throw std::invalid_argument("Pipeline::registeredScan: voxel must be finite and >= 0");
+  const Pose X = map_frame ? frame_to_map_ : Pose::identity();
+  const int64_t cap = static_cast<int64_t>(std::min<size_t>(capacity, size_t(1) << 40));
+  int64_t rows = 0;
+  int rc;
+  if (kept_cloud_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(kept_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::registeredScan: the device context the scan lived in is gone");
+    MADtree::cancelDeviceBuild(0);  // the export needs the builder's scratch: a look-ahead of another Pipeline gives way
+    rc = madicp_cloud_export_f32(ctx, kept_cloud_id_, X.R, X.t, voxel, out, cap, &rows);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_cloud_export_f32");
+  } else {
+    rc = cloud_export_f32(kept_host_.empty() ? nullptr : kept_host_[0].data(), static_cast<int64_t>(kept_host_.size()), X.R, X.t, voxel,
+                          out, cap, &rows);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY)
+      throw std::runtime_error("Pipeline::registeredScan: the host export refused its arguments");
+  }
+  if (rc == MADICP_ERR_CAPACITY)
+    throw std::invalid_argument("Pipeline::registeredScan: the buffer holds " + std::to_string(capacity) + " rows, the scan needs " +
+                                std::to_string(rows));
+  return static_cast<size_t>(rows);
 }
 
 const std::vector<Matrix4d> Pipeline::trajectory() const {
@@ -202,6 +263,7 @@ void Pipeline::prefetchView(const Vector3d* next_cloud, size_t n) {
     // the tree is built on the GPU — a host build would only compete for the CPU — and the look-ahead is the library's:
     // collect the construction in flight (the scan about to be consumed), start this one beside the coming registration
     if (deskew_) return;  // (the tree needs the previous pose)
+    if (keep_scan_) return;  // (a look-ahead build gives back the tree alone, not the scan: pipeline.h, setKeepScan)
     // begun by the next compute(), behind its registration's submission; assign() into a buffer that lives as long as the
     // Pipeline: after the first frames no allocation, no fresh pages
     dev_next_cloud_.assign(next_cloud, next_cloud + n);
@@ -251,6 +313,7 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
   DeviceLock lock(Device::mutex());
   madicp_ctx* ctx = Device::ctx();
   MADtree::cancelDeviceBuild(0);  // deskew and build need the builder's scratch: a look-ahead of another Pipeline gives way
+  dropKeptScan();                 // (the scan retained for the frame before)
   std::unique_ptr<MADtree> tree;
   try {
     if (is_initialized_ && deskew_ && trajectory_.size() > 1) {
@@ -268,6 +331,15 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
   } catch (...) {
     madicp_cloud_release(ctx, cloud_id);
     throw;
+  }
+  if (keep_scan_) {  // retained instead: the buffer goes back to the pool when the next frame, setKeepScan(false) or the end drops it
+    int64_t n = 0;
+    check(madicp_cloud_size(ctx, cloud_id, &n), "madicp_cloud_size");
+    kept_cloud_id_ = cloud_id;
+    kept_generation_ = Device::generation();
+    kept_n_ = static_cast<size_t>(n);
+    have_kept_ = true;
+    return tree;
   }
   check(madicp_cloud_release(ctx, cloud_id), "madicp_cloud_release");
   return tree;
@@ -460,6 +532,7 @@ void Pipeline::computeStampedView(const double& curr_stamp, const Vector3d* curr
     if (takeLookAhead(deskew_ahead_, curr_cloud, n, &unused) && unused.result.valid()) unused.result.wait();
     ContainerType cloud(curr_cloud, curr_cloud + n);  // (the host builder takes the points over)
     deskew_cloud_stamped(cloud, stamps, trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], sensor_hz_, nullptr);
+    keepHostScan(cloud);
     current_tree = std::make_unique<MADtree>(std::move(cloud), b_max_, b_min_, max_parallel_levels_);
   }
   computeWithTree(curr_stamp, std::move(current_tree), nullptr, t_pre);
@@ -501,6 +574,10 @@ void Pipeline::compute(const double& curr_stamp, ContainerType curr_cloud) {
 void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree> current_tree, ContainerType* cloud,
                                double t_pre) {
   current_leaves_host_ = nullptr;
+  // host front-end, the scan as given (first frame, no deskew due, or a tree built ahead for it): retained before the builder
+  // takes the points over; the deskewed one is retained below
+  const bool deskew_due = is_initialized_ && !current_tree && deskew_ && trajectory_.size() > 1;
+  if (cloud && !deskew_due) keepHostScan(*cloud);
   if (!is_initialized_) {
     if (current_tree) {
       auto frame = std::make_unique<Frame>();
@@ -533,6 +610,7 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
         ++look_ahead_hits_;
       }
       deskew(*cloud, trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], have ? &ahead : nullptr);
+      keepHostScan(*cloud);
     }
     current_tree = std::make_unique<MADtree>(std::move(*cloud), b_max_, b_min_, max_parallel_levels_);
   }

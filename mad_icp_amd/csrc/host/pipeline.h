@@ -112,6 +112,28 @@ class Pipeline {
     device_frontend_ = on;
   }
   bool deviceFrontEnd() const { return device_frontend_; }
+
+  // additive: the REGISTERED SCAN out.  With setKeepScan(true) — default off: nothing changes, not a launch — the cloud the frame's
+  // tree was built from is retained until the next compute*(), setKeepScan(false) or destruction: the cloud after deskew where
+  // deskew is due, the cloud as given (or as ingested: range-filtered, merged over the rig) on the first frames and with
+  // deskew = false; azimuth deskew leaves it in azimuth order.  Every compute* entry point retains.  Device front-end: the frame's
+  // resident cloud is kept instead of going back to the pool after the build (one pool buffer more in use, no copy); host
+  // front-end: a host copy is taken before the builder permutes the points.  While the option is on the device look-ahead is not
+  // begun — prefetch() stays legal and the frame builds synchronously, the restriction stamped and records frames already carry
+  // (a look-ahead build owns its own copy of the scan and gives back only the tree).  Poses, keyframe ids and isMapUpdated()
+  // are the same bit for bit with the option on or off.  A sharded Pipeline keeps and exports its own copy on every rank.
+  void setKeepScan(bool on);
+  bool keepScan() const { return keep_scan_; }
+  size_t registeredScanSize() const { return have_kept_ ? kept_n_ : 0; }  // points of the retained scan (0: none)
+  // The retained scan as float32 rows (x, y, z) into out[0, 3 * capacity): map_frame = true takes it through the pose of the frame
+  // just computed (currentPose()), false through the identity — the sensor frame at the pose's reference time.  voxel == 0: every
+  // point in the cloud's order; voxel > 0: the lowest-index point of every voxel of that edge, in ascending index order (the
+  // rule of madicp_cloud_export_f32, include/madicp_hip.h — device front-end: that call, host front-end: its twin
+  // madicp_host_cloud_export_f32; the same bits for the same cloud and pose).  Returns the rows written; registeredScanSize()
+  // rows always suffice.  std::logic_error when the option is off or no frame has been computed since it was turned on;
+  // std::invalid_argument for a null buffer, a voxel that is negative or not finite, a capacity smaller than the rows needed
+  // (nothing is written then).
+  size_t registeredScan(float* out, size_t capacity, double voxel, bool map_frame);
   // additive: one frame straight from sensor records — float32 (x, y, z, intensity ...) `stride_floats` apart, range
   // filter and optional KITTI correction as in apps/cpp_runners/bin_runner.cpp:126-166 — ingest, deskew, build and
   // registration all on the device (implies the device front-end for this frame)
@@ -244,6 +266,14 @@ class Pipeline {
   std::unique_ptr<MADtree> dev_ready_;
   void collectDeviceLookAhead();  // dev_pending_ -> dev_ready_
   void dropDeviceLookAhead(bool staged_too = true);  // forget both (and the scan staged for the next frame)
+  // the retained scan (setKeepScan): a resident cloud of the context generation that issued its id, or a host copy
+  bool keep_scan_ = false, have_kept_ = false;
+  int kept_cloud_id_ = -1;
+  unsigned kept_generation_ = 0;
+  ContainerType kept_host_;
+  size_t kept_n_ = 0;
+  void dropKeptScan();                        // forget it; the device buffer goes back to the pool
+  void keepHostScan(const ContainerType& c);  // host front-end: the copy, when the option is on
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;
   int last_rounds_ = 0;
   double round_ms_estimate_ = 0.05;  // device time of one GN round, from the previous frame (realtime budget)

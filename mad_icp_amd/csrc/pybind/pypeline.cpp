@@ -2,7 +2,10 @@
 #include "common.h"
 #include "pipeline.h"
 
+#include <algorithm>
+#include <cstring>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 PYBIND11_MODULE(pypeline, m) {
@@ -65,6 +68,25 @@ PYBIND11_MODULE(pypeline, m) {
     // setDeviceFrontEnd(False) keep the host builder
     .def("setDeviceFrontEnd", &Pipeline::setDeviceFrontEnd, py::arg("on"))
     .def("deviceFrontEnd", &Pipeline::deviceFrontEnd)
+    // additive: the registered scan out (Pipeline::setKeepScan / registeredScan).  setKeepScan(True) retains the cloud every frame's
+    // tree was built from — deskewed where deskew is due — until the next compute*(); registeredScan(voxel_size, frame) returns it
+    // as an (M, 3) float32 array in the map frame (frame="map": through currentPose()) or the sensor frame (frame="sensor"), every
+    // point (voxel_size = 0) or the lowest-index point of every voxel.  ValueError for another frame name, a voxel_size that is
+    // negative or not finite; RuntimeError (std::logic_error) when the option is off or no frame has been computed.
+    .def("setKeepScan", &Pipeline::setKeepScan, py::arg("on"))
+    .def("keepScan", &Pipeline::keepScan)
+    .def("registeredScanSize", &Pipeline::registeredScanSize)
+    .def("registeredScan",
+         [](Pipeline& self, double voxel_size, const std::string& frame) {
+           if (frame != "map" && frame != "sensor") throw py::value_error("frame must be \"map\" or \"sensor\"");
+           const size_t cap = self.registeredScanSize();
+           std::vector<float> rows(3 * std::max<size_t>(cap, 1));
+           const size_t m = self.registeredScan(rows.data(), cap, voxel_size, frame == "map");
+           py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
+           if (m) std::memcpy(out.mutable_data(), rows.data(), sizeof(float) * 3 * m);
+           return out;
+         },
+         py::arg("voxel_size") = 0.0, py::arg("frame") = "map")
     // additive: a frame straight from sensor records, (n, >=3) float32 (a KITTI .bin is (n,4)): range filter, optional
     // KITTI correction (apps/cpp_runners/bin_runner.cpp:126-166), deskew, build and registration on the device
     .def("computeRecords",
