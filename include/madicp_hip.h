@@ -304,10 +304,11 @@ int madicp_cloud_deskew_stamped(madicp_ctx* ctx, int cloud_id, const double* sta
  * out_n: the survivors; out_t_range (optional): the t0, t1 used — it travels with the one device-to-host copy of the survivor
  * count (one synchronisation, like madicp_cloud_ingest_f32).  With t_type == MADICP_T_NONE the cloud has no stamps, off_t is
  * ignored and out_t_range is +inf, -inf.  MADICP_ERR_INVALID — before anything is launched or allocated, no cloud created —
- * for a null argument, n_records outside 1 .. 2^30, point_step outside 12 .. 256, a field that does not lie inside
+ * for a null argument, n_records outside 1 .. 2^30 - 1, point_step outside 12 .. 256, a field that does not lie inside
  * [0, point_step), an unknown t_type, a t_range that is not finite and increasing; MADICP_ERR_INVALID as well when no record
  * survives; MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Bit-equal to madicp_host_ingest_records
- * (madicp_host.h). */
+ * (madicp_host.h).  (The call IS madicp_cloud_ingest_sources, below, for one plain source — R the identity, t zero, t_scale 1,
+ * t_offset 0 — behind the refusals above: the same kernels, the same chain.) */
 #define MADICP_T_NONE 0 /* time field types: sensor_msgs/PointField's own codes */
 #define MADICP_T_U32 6
 #define MADICP_T_F32 7
@@ -348,7 +349,7 @@ int madicp_cloud_deskew_own_stamps(madicp_ctx* ctx, int cloud_id, const double v
  *                 (R[3i+1] * o1 + R[3i+2] * o2)) — the evaluation order of pose * point in madicp_cloud_deskew_stamped; a
  *                 source whose R is exactly the identity and whose t is exactly zero skips it.  R is used AS GIVEN: that it is
  *                 orthonormal is the caller's business (a scaled or sheared R scales or shears the points).
- * One source with the identity, t_scale 1 and t_offset 0 is madicp_cloud_ingest_records on the same buffer, bit for bit.
+ * One source with the identity, t_scale 1 and t_offset 0 is what madicp_cloud_ingest_records passes on: the same bits.
  * out_n: all survivors; out_n_per_source (n_sources values, optional): those of every source (they ride in the same one
  * device-to-host copy); out_t_range (optional): the t0, t1 used, +inf, -inf without a time field or a finite time.
  * MADICP_ERR_INVALID — before anything is staged, launched or allocated, no cloud created — for a null argument (a source's

@@ -1,5 +1,5 @@
 // What happens to ONE sensor record on its way into a cloud — ONE source for the device ingest kernels (csrc/hip/frontend.hip.h:
-// ingest_mark / ingest_scatter on float32 rows, records_mark / records_scatter on byte records) and for the host twin
+// ingest_mark / ingest_scatter on float32 rows, sources_mark / sources_scatter on byte records) and for the host twin
 // (csrc/host/ingest_records.cpp), so the three cannot drift apart: the range filter of apps/cpp_runners/bin_runner.cpp:149-151,
 // the "kitti magic correction" of :153-158, and the normalisation of a record's time field.  Every translation unit that
 // includes this is compiled WITHOUT floating-point contraction (-ffp-contract=off; the device header adds the pragma).
@@ -105,7 +105,7 @@ MADICP_HD inline double record_stamp(double t64, double t0, double t1) {
 // ---- several sources into one cloud (include/madicp_hip.h: madicp_record_source) ------------------------------------------------
 // the time of a record on the clock all sources share: tc = t64 * t_scale + t_offset, two roundings (no fma: these translation
 // units are compiled without contraction).  `as_is`: the host found t_scale == 1.0 and t_offset == 0.0 exactly — the time is
-// taken unchanged (x * 1.0 + 0.0 would turn a -0.0 into +0.0), which makes one such source the single-source ingest bit for bit.
+// taken unchanged (x * 1.0 + 0.0 would turn a -0.0 into +0.0), so that a plain source (plain_source) keeps its times bit for bit.
 MADICP_HD inline double source_clock(double t64, int as_is, double t_scale, double t_offset) {
   if (as_is) return t64;
   const double scaled = t64 * t_scale;
@@ -159,6 +159,28 @@ inline RecordSource record_source_of(const CSource& c) {
   S.t_offset = c.t_offset;
   S.kitti = c.kitti_correction;
   return S;
+}
+// (and back)
+template <class CSource>
+inline CSource record_source_to(const RecordSource& S) {
+  CSource c{};
+  c.data = S.data;
+  c.n_records = S.n;
+  c.layout = {S.L.step, S.L.off_x, S.L.off_y, S.L.off_z, S.L.off_t, S.L.t_type};
+  for (int i = 0; i < 9; ++i) c.R[i] = S.R[i];
+  for (int i = 0; i < 3; ++i) c.t[i] = S.t[i];
+  c.min_range = S.min_range;
+  c.max_range = S.max_range;
+  c.t_scale = S.t_scale;
+  c.t_offset = S.t_offset;
+  c.kitti_correction = S.kitti ? 1 : 0;
+  return c;
+}
+// The PLAIN source: one sensor already in the base frame and on the common clock — the identity extrinsic (sensor_to_base is
+// skipped), t_scale 1 and t_offset 0 (source_clock takes the time as it is).  The single-source ingests of every layer
+// (madicp_cloud_ingest_records, ingest_records, Pipeline::computeRecordsStamped) are the sources ingest of this one source.
+inline RecordSource plain_source(const void* data, int64_t n, const RecordLayout& L, double min_range, double max_range, bool kitti) {
+  return RecordSource{data, n, L, {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, 0.0}, min_range, max_range, 1.0, 0.0, kitti ? 1 : 0};
 }
 
 // what every layer refuses before it touches a record (null = nothing to refuse): the device entry, the host twin and Pipeline

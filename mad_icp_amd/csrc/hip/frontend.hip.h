@@ -83,7 +83,7 @@ __global__ void ingest_scatter(const float* __restrict__ rec, long n, int stride
 // The last tile's loads round its length up to a dword: up to 3 bytes past the records, which the caller's buffers cover
 // (madicp_cloud_ingest_records).  Loop bounds come from the record count, never from the tile size.
 constexpr int kRecTileDwords = 4096;  // 16 KiB
-constexpr int kRecMaxBlocks = 4096;   // workgroups of records_mark (one pair of partial extremes each)
+constexpr int kRecMaxBlocks = 4096;   // workgroups of sources_mark (one pair of partial extremes each)
 __host__ __device__ inline int records_per_tile(int step) { return step <= 64 ? 256 : (step <= 128 ? 128 : 64); }
 
 struct RecordsResult {  // what the host reads back after the mark pass, in one copy
@@ -101,39 +101,11 @@ __device__ inline void records_stage(const unsigned char* __restrict__ src, int 
   for (int k = 4 * n_q + threadIdx.x; k < n_dw; k += blockDim.x) s_tile[k] = src_d[k];
 }
 
-// mark pass: keep[i] (entry n: the scan's terminator) and, per workgroup, the min / max of the FINITE times of ALL its records,
-// dropped ones included (the reference's point_cloud2.py:90-93 takes the whole message): part[2 b], part[2 b + 1]; +inf / -inf
-// where a workgroup saw none.  Plain comparisons and a fixed reduction shape, no floating-point atomics: min / max do not depend
-// on the order once the sign of a zero extreme is canonicalised (records_range).
-__global__ __launch_bounds__(256) void records_mark(const unsigned char* __restrict__ rec, long n, madicp_host::RecordLayout L, int per_tile,
-                                                    double min_range, double max_range, uint32_t* __restrict__ keep,
-                                                    double* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
+// The join of a 256-thread workgroup's (mn, mx) pairs, left in thread 0: a 64-lane xor butterfly, four per-wave slots in LDS,
+// lane 0 joins them.  Plain comparisons and a fixed shape, no floating-point atomics: min / max do not depend on the order once
+// the sign of a zero extreme is canonicalised (records_range).
+__device__ inline void block_minmax(double& mn, double& mx) {
   __shared__ double s_mn[4], s_mx[4];
-  const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
-  const long n_tiles = (n + per_tile - 1) / per_tile;
-  double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
-  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long first = tile * per_tile;
-    const int cnt = (int)min((long)per_tile, n - first);
-    records_stage(rec + first * L.step, cnt * L.step, s_tile);
-    __syncthreads();
-    if ((int)threadIdx.x < cnt) {
-      const unsigned char* p = s_bytes + threadIdx.x * L.step;
-      const bool drop = madicp_host::ingest_drops(madicp_host::record_f32(p + L.off_x), madicp_host::record_f32(p + L.off_y),
-                                                  madicp_host::record_f32(p + L.off_z), min_range, max_range);
-      keep[first + threadIdx.x] = drop ? 0u : 1u;
-      if (L.t_type != madicp_host::kTimeNone) {
-        const double t = madicp_host::record_time(p + L.off_t, L.t_type);
-        if (madicp_host::time_is_finite(t)) {
-          if (t < mn) mn = t;
-          if (t > mx) mx = t;
-        }
-      }
-    }
-    __syncthreads();  // (the next trip overwrites the tile)
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) keep[n] = 0;
   for (int m = 32; m > 0; m >>= 1) {
     const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
     if (a < mn) mn = a;
@@ -144,14 +116,11 @@ __global__ __launch_bounds__(256) void records_mark(const unsigned char* __restr
     s_mx[threadIdx.x >> 6] = mx;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0)
     for (int w = 1; w < 4; ++w) {
       if (s_mn[w] < mn) mn = s_mn[w];
       if (s_mx[w] > mx) mx = s_mx[w];
     }
-    part[2 * blockIdx.x] = mn;
-    part[2 * blockIdx.x + 1] = mx;
-  }
 }
 
 // one workgroup: the join of the workgroups' extremes, canonicalised as t + 0.0 (a -0.0 extreme becomes +0.0: which of two equal
@@ -160,7 +129,6 @@ __global__ __launch_bounds__(256) void records_mark(const unsigned char* __restr
 __global__ __launch_bounds__(256) void records_range(const double* __restrict__ part, int n_part, int has_time, int explicit_range,
                                                      double e0, double e1, const int32_t* __restrict__ total,
                                                      RecordsResult* __restrict__ res) {
-  __shared__ double s_mn[4], s_mx[4];
   double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
   if (has_time && !explicit_range)
     for (int k = threadIdx.x; k < n_part; k += blockDim.x) {
@@ -168,21 +136,8 @@ __global__ __launch_bounds__(256) void records_range(const double* __restrict__ 
       if (a < mn) mn = a;
       if (b > mx) mx = b;
     }
-  for (int m = 32; m > 0; m >>= 1) {
-    const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
-    if (a < mn) mn = a;
-    if (b > mx) mx = b;
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_mn[threadIdx.x >> 6] = mn;
-    s_mx[threadIdx.x >> 6] = mx;
-  }
-  __syncthreads();
+  block_minmax(mn, mx);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      if (s_mn[w] < mn) mn = s_mn[w];
-      if (s_mx[w] > mx) mx = s_mx[w];
-    }
     res->t0 = explicit_range ? e0 : mn + 0.0;
     res->t1 = explicit_range ? e1 : mx + 0.0;
     res->kept = *total;
@@ -190,42 +145,15 @@ __global__ __launch_bounds__(256) void records_range(const double* __restrict__ 
   }
 }
 
-// scatter pass: the same staging; the survivors' points (madicp_host::ingest_point, the arithmetic of ingest_scatter) and their
-// normalised stamps (madicp_host::record_stamp over the range records_range left in device memory) to the survivor's position,
-// input order kept.  stamps == nullptr: a layout without a time field.
-__global__ __launch_bounds__(256) void records_scatter(const unsigned char* __restrict__ rec, long n, madicp_host::RecordLayout L, int per_tile,
-                                                       const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos, int kitti,
-                                                       double sin_a, double cos_a, const RecordsResult* __restrict__ res,
-                                                       double* __restrict__ out, double* __restrict__ stamps) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
-  const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
-  const long n_tiles = (n + per_tile - 1) / per_tile;
-  const double t0 = res->t0, t1 = res->t1;
-  for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long first = tile * per_tile;
-    const int cnt = (int)min((long)per_tile, n - first);
-    records_stage(rec + first * L.step, cnt * L.step, s_tile);
-    __syncthreads();
-    if ((int)threadIdx.x < cnt && keep[first + threadIdx.x]) {
-      const unsigned char* p = s_bytes + threadIdx.x * L.step;
-      double o[3];
-      madicp_host::ingest_point(madicp_host::record_f32(p + L.off_x), madicp_host::record_f32(p + L.off_y),
-                                madicp_host::record_f32(p + L.off_z), kitti, sin_a, cos_a, o);
-      const long d = pos[first + threadIdx.x];
-      out[3 * d] = o[0]; out[3 * d + 1] = o[1]; out[3 * d + 2] = o[2];
-      if (stamps) stamps[d] = madicp_host::record_stamp(madicp_host::record_time(p + L.off_t, L.t_type), t0, t1);
-    }
-    __syncthreads();
-  }
-}
-
-// ---- ingest of SEVERAL sources' byte records into one cloud ---------------------------------------------------------------------
+// ---- ... of ONE OR SEVERAL sources' byte records into one cloud: the only mark / scatter pair for byte records -------------------
+// (madicp_cloud_ingest_records is the one PLAIN source, madicp_host::plain_source: a table of one entry whose flags skip
+// sensor_to_base and take the clock as it is, zero trips of source_of_tile's loop.)
 // A multi-head rig delivers S buffers per frame, each in its own sensor frame, often with its own record step and time type, each
 // time field counting from its own message header (madicp_cloud_ingest_sources).  All of them are staged into ONE device buffer,
 // every source at a 64-byte aligned offset, and the two kernels below walk ONE grid-stride loop over the GLOBAL tile index: the
 // tiles of source 0, then those of source 1 ... — a source's tiles hold records_per_tile(its step) records, so the 16 KiB tile and
 // everything said about it above holds unchanged.  keep[] / pos[] are indexed by GLOBAL record (source 0's records, then source
-// 1's ...): the one scan of records_mark's caller gives the concatenated order, keep[total] is its terminator.
+// 1's ...): the one scan of sources_mark's caller gives the concatenated order, keep[total] is its terminator.
 // The table of the sources travels BY VALUE as a kernel argument (1.6 KB of the 4 KB a launch may carry): it is wave-uniform, the
 // workgroup finds the source of its tile with at most kMaxSources - 1 scalar comparisons and reads the entry through scalar loads.
 // Per record, madicp_host's rules (csrc/common/ingest_point.h): the range filter on the raw floats in the SENSOR's frame with the
@@ -258,11 +186,12 @@ __device__ inline int source_of_tile(const SourceTable& T, long tile) {
   return s;
 }
 
-// mark pass: records_mark over the global tile index; the partial extremes are those of the times on the COMMON clock
+// mark pass: keep[g] (entry n_total: the scan's terminator) and, per workgroup, the min / max of the FINITE times — on the COMMON
+// clock — of ALL its records, dropped ones included (the reference's point_cloud2.py:90-93 takes the whole message): part[2 b],
+// part[2 b + 1]; +inf / -inf where a workgroup saw none (block_minmax).
 __global__ __launch_bounds__(256) void sources_mark(const unsigned char* __restrict__ rec, SourceTable T, uint32_t* __restrict__ keep,
                                                     double* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
-  __shared__ double s_mn[4], s_mx[4];
   const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
   double mn = __builtin_huge_val(), mx = -__builtin_huge_val();
   for (long tile = blockIdx.x; tile < T.n_tiles; tile += gridDim.x) {
@@ -289,21 +218,8 @@ __global__ __launch_bounds__(256) void sources_mark(const unsigned char* __restr
     __syncthreads();  // (the next trip overwrites the tile)
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) keep[T.n_total] = 0;
-  for (int m = 32; m > 0; m >>= 1) {
-    const double a = __shfl_xor(mn, m, 64), b = __shfl_xor(mx, m, 64);
-    if (a < mn) mn = a;
-    if (b > mx) mx = b;
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_mn[threadIdx.x >> 6] = mn;
-    s_mx[threadIdx.x >> 6] = mx;
-  }
-  __syncthreads();
+  block_minmax(mn, mx);
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) {
-      if (s_mn[w] < mn) mn = s_mn[w];
-      if (s_mx[w] > mx) mx = s_mx[w];
-    }
     part[2 * blockIdx.x] = mn;
     part[2 * blockIdx.x + 1] = mx;
   }
@@ -323,8 +239,9 @@ __global__ __launch_bounds__(64) void sources_counts(SourceTable T, const uint32
   res->kept_of[s] = (int32_t)(pos[end] - pos[T.src[s].first_rec]);
 }
 
-// scatter pass: records_scatter over the global tile index, the survivor's point taken to the base frame and its stamp normalised
-// on the common clock.  stamps == nullptr: sources without a time field.
+// scatter pass: the same staging; the survivors' points (madicp_host::ingest_point, the arithmetic of ingest_scatter) taken to
+// the base frame and their stamps normalised on the common clock (madicp_host::record_stamp over the range records_range left in
+// device memory) to the survivor's position, input order kept.  stamps == nullptr: sources without a time field.
 __global__ __launch_bounds__(256) void sources_scatter(const unsigned char* __restrict__ rec, SourceTable T, const uint32_t* __restrict__ keep,
                                                        const uint32_t* __restrict__ pos, double sin_a, double cos_a,
                                                        const RecordsResult* __restrict__ res, double* __restrict__ out,

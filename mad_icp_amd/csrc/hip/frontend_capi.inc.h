@@ -39,13 +39,11 @@ struct FrontScratch {
   bool state_stale = false;      // h_state is older than the device State
   double* h_table = nullptr;     // pinned, same layout as `table`
   hipEvent_t h_table_read = nullptr;
-  // ingest of byte records: the workgroups' partial time extremes, the result block and its pinned copy
+  // ingest of byte records: the workgroups' partial time extremes, the result block (range and survivor count, the survivors per
+  // source behind them) and its pinned copy
   double* rec_part = nullptr;    // (2 * fe::kRecMaxBlocks)
-  fe::RecordsResult* rec_res = nullptr;
-  fe::RecordsResult* h_rec_res = nullptr;
-  // ... of several sources' records: the same block with the survivors per source behind it, and its pinned copy
-  fe::SourcesResult* src_res = nullptr;
-  fe::SourcesResult* h_src_res = nullptr;
+  fe::SourcesResult* rec_res = nullptr;
+  fe::SourcesResult* h_rec_res = nullptr;
   // a construction between its two halves (tree_build_begin_on / tree_build_end_on)
   struct InFlight {
     bool active = false;
@@ -144,7 +142,6 @@ size_t carve_scratch(FrontScratch& fs, char* base, int64_t nc) {
   carve(fs.table, kDeskewTableMax * 13);
   carve(fs.rec_part, 2 * fe::kRecMaxBlocks);
   carve(fs.rec_res, 1);
-  carve(fs.src_res, 1);
   fs.sort_tmp_bytes = sort_temp_bytes(nc);
   carve(fs.sort_tmp, fs.sort_tmp_bytes);
   return off;
@@ -159,8 +156,7 @@ int ensure_scratch(madicp_ctx* ctx, int64_t n, FrontScratch** out) {
     std::memset(fs.h_line, 0, sizeof(tb::HostLine));
     HIP_TRY(hipHostMalloc(&fs.h_table, sizeof(double) * kDeskewTableMax * 13, hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&fs.h_table_read, hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc(&fs.h_rec_res, sizeof(fe::RecordsResult), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc(&fs.h_src_res, sizeof(fe::SourcesResult), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&fs.h_rec_res, sizeof(fe::SourcesResult), hipHostMallocDefault));
   }
   if (n <= fs.n_cap) return MADICP_OK;
   if (fs.block) {
@@ -196,7 +192,6 @@ void front_destroy(madicp_ctx* ctx) {  // called by madicp_ctx_destroy (streams 
   if (fs.h_line) hipHostFree(fs.h_line);
   if (fs.h_table) hipHostFree(fs.h_table);
   if (fs.h_rec_res) hipHostFree(fs.h_rec_res);
-  if (fs.h_src_res) hipHostFree(fs.h_src_res);
   if (fs.h_table_read) hipEventDestroy(fs.h_table_read);
   delete ctx->front;
   ctx->front = nullptr;
@@ -367,7 +362,7 @@ int register_cloud(madicp_ctx* ctx, const DevCloud& c, int* out_id) {
   return MADICP_OK;
 }
 
-// the prologue of both ingests: the raw records — `bytes` of them, sent as `padded` >= bytes with the rest zero — go through
+// the prologue of the float32-row ingest: the rows — `bytes` of them, sent as `padded` >= bytes with the rest zero — go through
 // the pinned staging into buf[0] of a scratch sized for them (a point of the scratch is 24 bytes, a KITTI record 16: wider
 // records ask for a scratch laid out for proportionally more points)
 int stage_records(madicp_ctx* ctx, const void* data, int64_t n_records, size_t bytes, size_t padded, FrontScratch** fs, void** d_rec) {
@@ -385,6 +380,102 @@ int stage_records(madicp_ctx* ctx, const void* data, int64_t n_records, size_t b
   HIP_TRY(hipMemcpyAsync(*d_rec, stage, padded, hipMemcpyHostToDevice, ctx->copy));
   HIP_TRY(ctx->staging.sent(hb, ctx->copy));
   return MADICP_OK;
+}
+
+// Byte records -> ONE filtered base-frame cloud with one set of stamps on a common clock: the chain behind
+// madicp_cloud_ingest_sources and madicp_cloud_ingest_records (kernels: fe::sources_mark, fe::records_range, fe::sources_scatter),
+// for sources the caller has VALIDATED (madicp_host::record_sources_refusal).  All sources go through ONE acquisition of the
+// pinned staging and ONE host-to-device copy into buf[0] of the scratch, each at a 64-byte aligned offset (a tile then starts
+// 16-byte aligned whatever the steps in front of it), the gaps zeroed: the last tile of a source loads up to 3 bytes past its
+// records.  Mark, scan, range, one copy of the result block, one synchronisation, scatter — whatever the number of sources.
+int ingest_sources_on(madicp_ctx* ctx, const madicp_host::RecordSource* src, int n_sources, const double* t_range, int* out_cloud_id,
+                      int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]) {
+  // the table of the sources: where each one's bytes, tiles and records begin
+  fe::SourceTable T{};
+  T.n_sources = n_sources;
+  T.has_time = src[0].L.t_type != madicp_host::kTimeNone ? 1 : 0;
+  size_t staged = 0;  // bytes of the one copy
+  for (int s = 0; s < n_sources; ++s) {
+    fe::SourceEntry& E = T.src[s];
+    const size_t bytes = (size_t)src[s].L.step * (size_t)src[s].n;
+    E.byte_off = (long)((staged + 63) & ~(size_t)63);
+    E.first_tile = T.n_tiles;
+    E.first_rec = T.n_total;
+    E.n = (long)src[s].n;
+    E.L = src[s].L;
+    E.per_tile = fe::records_per_tile(E.L.step);
+    E.flags = (src[s].kitti ? fe::kSrcKitti : 0) | (madicp_host::source_extrinsic_is_identity(src[s].R, src[s].t) ? fe::kSrcIdentity : 0) |
+              (madicp_host::source_clock_as_is(src[s].t_scale, src[s].t_offset) ? fe::kSrcClockAsIs : 0);
+    E.min_range = src[s].min_range;
+    E.max_range = src[s].max_range;
+    E.t_scale = src[s].t_scale;
+    E.t_offset = src[s].t_offset;
+    std::memcpy(E.R, src[s].R, sizeof(E.R));
+    std::memcpy(E.t, src[s].t, sizeof(E.t));
+    T.n_tiles += (E.n + E.per_tile - 1) / E.per_tile;
+    T.n_total += E.n;
+    staged = (size_t)E.byte_off + ((bytes + 3) & ~(size_t)3);  // what the source's last tile's dword loads reach
+  }
+  const int64_t n_total = T.n_total;
+  // (a point of the scratch is 24 bytes: wider records ask for a scratch laid out for proportionally more points)
+  const int64_t n_layout = std::max<int64_t>(n_total, (int64_t)((staged + 23) / 24));
+  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
+  RC_TRY(busy_with_lookahead(ctx));
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, n_layout, &fs));
+  {
+    int hb = 0;
+    char* stage = nullptr;
+    RC_TRY(ctx->staging.acquire(staged, &hb, &stage));
+    size_t at = 0;
+    for (int s = 0; s < n_sources; ++s) {
+      const size_t bytes = (size_t)src[s].L.step * (size_t)src[s].n;
+      std::memset(stage + at, 0, (size_t)T.src[s].byte_off - at);
+      std::memcpy(stage + T.src[s].byte_off, src[s].data, bytes);
+      at = (size_t)T.src[s].byte_off + bytes;
+    }
+    std::memset(stage + at, 0, staged - at);
+    HIP_TRY(hipMemcpyAsync(fs->P.buf[0], stage, staged, hipMemcpyHostToDevice, ctx->copy));
+    HIP_TRY(ctx->staging.sent(hb, ctx->copy));
+  }
+  const unsigned char* d_rec = reinterpret_cast<const unsigned char*>(fs->P.buf[0]);
+  uint32_t* keep = fs->P.leaf_start;
+  const int blocks = static_cast<int>(std::min<int64_t>(T.n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
+  hipLaunchKernelGGL(fe::sources_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, keep, fs->rec_part);
+  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_total, &fs->P.st->n_leaves));
+  hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, T.has_time,
+                     (T.has_time && t_range) ? 1 : 0, t_range ? t_range[0] : 0.0, t_range ? t_range[1] : 0.0,
+                     (const int32_t*)&fs->P.st->n_leaves, &fs->rec_res->r);
+  if (out_n_per_source)  // (the survivors per source ride in the same copy)
+    hipLaunchKernelGGL(fe::sources_counts, dim3(1), dim3(64), 0, ctx->copy, T, (const uint32_t*)fs->S, fs->rec_res);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(fs->h_rec_res, fs->rec_res, out_n_per_source ? sizeof(fe::SourcesResult) : sizeof(fe::RecordsResult),
+                         hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the size of the result decides the allocation; the range comes with it
+  const int64_t kept = fs->h_rec_res->r.kept;
+  if (kept < 1) return fail(MADICP_ERR_INVALID, "no point of any source survives the range filter");
+  DevCloud c;
+  RC_TRY(new_cloud(ctx, kept, &c));
+  if (T.has_time) {
+    void* p = nullptr;
+    const int rc = pool_alloc(ctx, sizeof(double) * (size_t)kept, ctx->copy, &p);
+    if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
+    c.stamps = static_cast<double*>(p);
+  }
+  const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
+  hipLaunchKernelGGL(fe::sources_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, (const uint32_t*)keep, (const uint32_t*)fs->S,
+                     std::sin(angle), std::cos(angle), (const fe::RecordsResult*)&fs->rec_res->r, c.xyz, c.stamps);
+  CLOUD_TRY(hipGetLastError());
+  CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
+  *out_n = kept;
+  if (out_n_per_source)
+    for (int s = 0; s < n_sources; ++s) out_n_per_source[s] = fs->h_rec_res->kept_of[s];
+  if (out_t_range) {
+    out_t_range[0] = fs->h_rec_res->r.t0;
+    out_t_range[1] = fs->h_rec_res->r.t1;
+  }
+  return register_cloud(ctx, c, out_cloud_id);
 }
 
 }  // namespace
@@ -469,69 +560,21 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
   return register_cloud(ctx, c, out_cloud_id);
 }
 
-// A driver's byte records -> a filtered cloud with its own normalised stamps (include/madicp_hip.h; kernels: fe::records_mark,
-// fe::records_range, fe::records_scatter).  Like madicp_cloud_ingest_f32 the raw bytes go through the pinned staging into
-// buf[0] of the scratch; BOTH are sized for the length rounded up to a dword, because the last tile's loads are.
+// A driver's byte records -> a filtered cloud with its own normalised stamps (include/madicp_hip.h): the chain above for the one
+// plain source, behind this entry's own refusals.
 int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_records, const madicp_record_layout* layout,
                                 double min_range, double max_range, int kitti_correction, const double* t_range, int* out_cloud_id,
                                 int64_t* out_n, double out_t_range[2]) {
   if (!ctx || !data || !layout || !out_cloud_id || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
   if (n_records < 1 || n_records > 0x3fffffff) return fail(MADICP_ERR_INVALID, "1 .. 2^30 records");
-  const madicp_host::RecordLayout L{layout->point_step, layout->off_x, layout->off_y, layout->off_z, layout->off_t, layout->t_type};
-  if (!madicp_host::record_layout_ok(L))
-    return fail(MADICP_ERR_INVALID, "record layout: point_step 12 .. 256, every field inside the record, t_type one of MADICP_T_*");
-  const bool has_time = L.t_type != madicp_host::kTimeNone;
-  if (t_range && !(std::isfinite(t_range[0]) && std::isfinite(t_range[1]) && t_range[1] > t_range[0]))
-    return fail(MADICP_ERR_INVALID, "t_range: both values finite, t_end > t_begin");
-  FrontScratch* fs = nullptr;
-  void* d_raw = nullptr;
-  const size_t bytes = (size_t)L.step * (size_t)n_records;
-  const size_t padded = (bytes + 3) & ~(size_t)3;  // what the last tile's dword loads reach
-  RC_TRY(stage_records(ctx, data, n_records, bytes, padded, &fs, &d_raw));
-  const unsigned char* d_rec = static_cast<const unsigned char*>(d_raw);
-  uint32_t* keep = fs->P.leaf_start;
-  const int per_tile = fe::records_per_tile(L.step);
-  const int64_t n_tiles = (n_records + per_tile - 1) / per_tile;
-  const int blocks = static_cast<int>(std::min<int64_t>(n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
-  hipLaunchKernelGGL(fe::records_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, L, per_tile,
-                     min_range, max_range, keep, fs->rec_part);
-  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_records, &fs->P.st->n_leaves));
-  hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, has_time ? 1 : 0,
-                     (has_time && t_range) ? 1 : 0, t_range ? t_range[0] : 0.0, t_range ? t_range[1] : 0.0,
-                     (const int32_t*)&fs->P.st->n_leaves, fs->rec_res);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(fs->h_rec_res, fs->rec_res, sizeof(fe::RecordsResult), hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the size of the result decides the allocation; the range comes with it
-  const int64_t kept = fs->h_rec_res->kept;
-  if (kept < 1) return fail(MADICP_ERR_INVALID, "no point survives the range filter");
-  DevCloud c;
-  RC_TRY(new_cloud(ctx, kept, &c));
-  if (has_time) {
-    void* p = nullptr;
-    const int rc = pool_alloc(ctx, sizeof(double) * (size_t)kept, ctx->copy, &p);
-    if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
-    c.stamps = static_cast<double*>(p);
-  }
-  const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
-  hipLaunchKernelGGL(fe::records_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, L, per_tile,
-                     (const uint32_t*)keep, (const uint32_t*)fs->S, kitti_correction ? 1 : 0, std::sin(angle), std::cos(angle),
-                     (const fe::RecordsResult*)fs->rec_res, c.xyz, c.stamps);
-  CLOUD_TRY(hipGetLastError());
-  CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
-  *out_n = kept;
-  if (out_t_range) {
-    out_t_range[0] = fs->h_rec_res->t0;
-    out_t_range[1] = fs->h_rec_res->t1;
-  }
-  return register_cloud(ctx, c, out_cloud_id);
+  const madicp_host::RecordSource src = madicp_host::plain_source(
+      data, n_records, {layout->point_step, layout->off_x, layout->off_y, layout->off_z, layout->off_t, layout->t_type}, min_range,
+      max_range, kitti_correction != 0);
+  if (const char* why = madicp_host::record_sources_refusal(&src, 1, t_range)) return fail(MADICP_ERR_INVALID, why);
+  return ingest_sources_on(ctx, &src, 1, t_range, out_cloud_id, out_n, nullptr, out_t_range);
 }
 
-// Several sources' byte records -> ONE filtered base-frame cloud with one set of stamps on a common clock (include/madicp_hip.h;
-// kernels: fe::sources_mark, fe::records_range, fe::sources_scatter).  All sources go through ONE acquisition of the pinned
-// staging and ONE host-to-device copy into buf[0] of the scratch, each at a 64-byte aligned offset (a tile then starts 16-byte
-// aligned whatever the steps in front of it), the gaps zeroed: the last tile of a source loads up to 3 bytes past its records.
-// The chain — mark, scan, range, one copy of the result block, one synchronisation, scatter — is the single-source ingest's,
-// whatever the number of sources.
+// Several sources' byte records -> one cloud (include/madicp_hip.h): the refusals, then the chain above.
 int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources, const double* t_range,
                                 int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]) {
   if (!ctx || !sources || !out_cloud_id || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
@@ -539,92 +582,7 @@ int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sou
   madicp_host::RecordSource src[MADICP_MAX_SOURCES];
   for (int s = 0; s < n_sources; ++s) src[s] = madicp_host::record_source_of(sources[s]);
   if (const char* why = madicp_host::record_sources_refusal(src, n_sources, t_range)) return fail(MADICP_ERR_INVALID, why);
-  // the table of the sources: where each one's bytes, tiles and records begin
-  fe::SourceTable T{};
-  T.n_sources = n_sources;
-  T.has_time = src[0].L.t_type != madicp_host::kTimeNone ? 1 : 0;
-  size_t staged = 0;  // bytes of the one copy
-  for (int s = 0; s < n_sources; ++s) {
-    fe::SourceEntry& E = T.src[s];
-    const size_t bytes = (size_t)src[s].L.step * (size_t)src[s].n;
-    E.byte_off = (long)((staged + 63) & ~(size_t)63);
-    E.first_tile = T.n_tiles;
-    E.first_rec = T.n_total;
-    E.n = (long)src[s].n;
-    E.L = src[s].L;
-    E.per_tile = fe::records_per_tile(E.L.step);
-    E.flags = (src[s].kitti ? fe::kSrcKitti : 0) | (madicp_host::source_extrinsic_is_identity(src[s].R, src[s].t) ? fe::kSrcIdentity : 0) |
-              (madicp_host::source_clock_as_is(src[s].t_scale, src[s].t_offset) ? fe::kSrcClockAsIs : 0);
-    E.min_range = src[s].min_range;
-    E.max_range = src[s].max_range;
-    E.t_scale = src[s].t_scale;
-    E.t_offset = src[s].t_offset;
-    std::memcpy(E.R, src[s].R, sizeof(E.R));
-    std::memcpy(E.t, src[s].t, sizeof(E.t));
-    T.n_tiles += (E.n + E.per_tile - 1) / E.per_tile;
-    T.n_total += E.n;
-    staged = (size_t)E.byte_off + ((bytes + 3) & ~(size_t)3);  // what the source's last tile's dword loads reach
-  }
-  const int64_t n_total = T.n_total;
-  // (a point of the scratch is 24 bytes: wider records ask for a scratch laid out for proportionally more points)
-  const int64_t n_layout = std::max<int64_t>(n_total, (int64_t)((staged + 23) / 24));
-  if (n_layout > 0x3fffffff) return fail(MADICP_ERR_INVALID, "records too large");
-  RC_TRY(busy_with_lookahead(ctx));
-  HIP_TRY(hipSetDevice(ctx->device));
-  FrontScratch* fs = nullptr;
-  RC_TRY(ensure_scratch(ctx, n_layout, &fs));
-  {
-    int hb = 0;
-    char* stage = nullptr;
-    RC_TRY(ctx->staging.acquire(staged, &hb, &stage));
-    size_t at = 0;
-    for (int s = 0; s < n_sources; ++s) {
-      const size_t bytes = (size_t)src[s].L.step * (size_t)src[s].n;
-      std::memset(stage + at, 0, (size_t)T.src[s].byte_off - at);
-      std::memcpy(stage + T.src[s].byte_off, src[s].data, bytes);
-      at = (size_t)T.src[s].byte_off + bytes;
-    }
-    std::memset(stage + at, 0, staged - at);
-    HIP_TRY(hipMemcpyAsync(fs->P.buf[0], stage, staged, hipMemcpyHostToDevice, ctx->copy));
-    HIP_TRY(ctx->staging.sent(hb, ctx->copy));
-  }
-  const unsigned char* d_rec = reinterpret_cast<const unsigned char*>(fs->P.buf[0]);
-  uint32_t* keep = fs->P.leaf_start;
-  const int blocks = static_cast<int>(std::min<int64_t>(T.n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
-  hipLaunchKernelGGL(fe::sources_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, keep, fs->rec_part);
-  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_total, &fs->P.st->n_leaves));
-  hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, T.has_time,
-                     (T.has_time && t_range) ? 1 : 0, t_range ? t_range[0] : 0.0, t_range ? t_range[1] : 0.0,
-                     (const int32_t*)&fs->P.st->n_leaves, &fs->src_res->r);
-  if (out_n_per_source)  // (the survivors per source ride in the same copy)
-    hipLaunchKernelGGL(fe::sources_counts, dim3(1), dim3(64), 0, ctx->copy, T, (const uint32_t*)fs->S, fs->src_res);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(fs->h_src_res, fs->src_res, out_n_per_source ? sizeof(fe::SourcesResult) : sizeof(fe::RecordsResult),
-                         hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the size of the result decides the allocation; the range comes with it
-  const int64_t kept = fs->h_src_res->r.kept;
-  if (kept < 1) return fail(MADICP_ERR_INVALID, "no point of any source survives the range filter");
-  DevCloud c;
-  RC_TRY(new_cloud(ctx, kept, &c));
-  if (T.has_time) {
-    void* p = nullptr;
-    const int rc = pool_alloc(ctx, sizeof(double) * (size_t)kept, ctx->copy, &p);
-    if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
-    c.stamps = static_cast<double*>(p);
-  }
-  const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
-  hipLaunchKernelGGL(fe::sources_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, (const uint32_t*)keep, (const uint32_t*)fs->S,
-                     std::sin(angle), std::cos(angle), (const fe::RecordsResult*)&fs->src_res->r, c.xyz, c.stamps);
-  CLOUD_TRY(hipGetLastError());
-  CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
-  *out_n = kept;
-  if (out_n_per_source)
-    for (int s = 0; s < n_sources; ++s) out_n_per_source[s] = fs->h_src_res->kept_of[s];
-  if (out_t_range) {
-    out_t_range[0] = fs->h_src_res->r.t0;
-    out_t_range[1] = fs->h_src_res->r.t1;
-  }
-  return register_cloud(ctx, c, out_cloud_id);
+  return ingest_sources_on(ctx, src, n_sources, t_range, out_cloud_id, out_n, out_n_per_source, out_t_range);
 }
 
 }  // extern "C"
@@ -848,7 +806,7 @@ int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int
 // idle parts of the builder's scratch, which this call owns like every other madicp_cloud_* call — the block does not grow:
 //   buf[0]  (24 bytes per point)  the table: 2 n 64-bit keys, behind them 2 n 32-bit owners — exactly 24 n bytes, set to all
 //                                 ones by ONE memset (the empty key and the "no owner yet" index are both all ones)
-//   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->kept  the scan's total
+//   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->r.kept  the scan's total
 //   buf[1]  the float rows (12 of its 24 bytes per point)
 // The scatter is enqueued BEHIND the scan, before the host knows the count: it writes scratch only, so a refusal for capacity
 // still leaves out_xyz alone, and the rows are ready when the count arrives.  Two synchronisations: the count, then the rows
@@ -888,13 +846,13 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
     hipLaunchKernelGGL(fe::export_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, keys, owner, slots,
                        slot_of);
     hipLaunchKernelGGL(fe::export_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)owner, (long)n, mark);
-    RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->kept));
-    HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->kept, &fs->rec_res->kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
+    RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
+    HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
     hipLaunchKernelGGL(fe::export_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, (const uint32_t*)mark,
                        (const uint32_t*)fs->S, d_rows);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count decides whether the caller's buffer is large enough
-    rows = fs->h_rec_res->kept;
+    rows = fs->h_rec_res->r.kept;
     *out_n = rows;
     if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the export needs (*out_n)");
     if (rows == 0) return MADICP_OK;  // (no candidate: every point outside the 2^21 cells per axis, or not finite)

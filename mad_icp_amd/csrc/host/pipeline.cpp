@@ -360,74 +360,59 @@ void Pipeline::ingestPrologue() {
   MADtree::cancelDeviceBuild(0);  //  ... with every Pipeline of the process)
 }
 
-void Pipeline::computeRecords(const double& curr_stamp, const float* records, size_t n_records, int stride_floats,
-                              double min_range, double max_range, bool kitti_correction) {
+// The device half of a frame whose scan is ingested on the device: the builder's scratch is claimed, `ingest` — run under the
+// device lock — returns the cloud's id, then deskew (`own_stamps`: by the stamps the cloud carries), build and registration.
+template <class Ingest>
+void Pipeline::computeIngested(const double& curr_stamp, bool own_stamps, Ingest&& ingest) {
   is_map_updated_ = false;
-  if (!records || n_records == 0) throw std::invalid_argument("Pipeline::computeRecords: no records");
   const double t_pre = now_ms();
   ingestPrologue();
   int cloud_id = -1;
   {
     DeviceLock lock(Device::mutex());
+    cloud_id = ingest();
+  }
+  computeWithTree(curr_stamp, buildOnDevice(cloud_id, nullptr, 0, own_stamps), nullptr, t_pre);
+}
+
+void Pipeline::computeRecords(const double& curr_stamp, const float* records, size_t n_records, int stride_floats,
+                              double min_range, double max_range, bool kitti_correction) {
+  is_map_updated_ = false;
+  if (!records || n_records == 0) throw std::invalid_argument("Pipeline::computeRecords: no records");
+  computeIngested(curr_stamp, false, [&] {
+    int cloud_id = -1;
     int64_t kept = 0;
     check(madicp_cloud_ingest_f32(Device::ctx(), records, static_cast<int64_t>(n_records), stride_floats, min_range, max_range,
                                   kitti_correction ? 1 : 0, &cloud_id, &kept),
           "madicp_cloud_ingest_f32");
-  }
-  computeWithTree(curr_stamp, buildOnDevice(cloud_id), nullptr, t_pre);
+    return cloud_id;
+  });
 }
 
-// A frame from a driver's byte records (pipeline.h).  The time field matters only where stamps can: deskew = true and a layout
-// that has one — everywhere else the layout is taken without it, so nothing is normalised, stored or read.
+// A frame from a driver's byte records (pipeline.h): its own refusals, then the frame of the one plain source.
 void Pipeline::computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout,
                                      double min_range, double max_range, bool kitti_correction, const double* t_range) {
   if (!data || n_records == 0) throw std::invalid_argument("Pipeline::computeRecordsStamped: no records");
-  RecordLayout L = layout;
-  if (!record_layout_ok(L)) throw std::invalid_argument("Pipeline::computeRecordsStamped: bad record layout");
+  if (!record_layout_ok(layout)) throw std::invalid_argument("Pipeline::computeRecordsStamped: bad record layout");
   if (n_records > 0x3fffffff) throw std::invalid_argument("Pipeline::computeRecordsStamped: 1 .. 2^30 records");
   if (t_range && !(std::isfinite(t_range[0]) && std::isfinite(t_range[1]) && t_range[1] > t_range[0]))
     throw std::invalid_argument("Pipeline::computeRecordsStamped: t_range needs two finite values, t_end > t_begin");
-  if (!deskew_) {
-    L.t_type = kTimeNone;
-    t_range = nullptr;
-  }
-  const bool stamped = L.t_type != kTimeNone;
-  const madicp_record_layout cl{L.step, L.off_x, L.off_y, L.off_z, L.off_t, L.t_type};
-  if (device_frontend_) {
-    is_map_updated_ = false;
-    const double t_pre = now_ms();
-    ingestPrologue();
-    int cloud_id = -1;
-    {
-      DeviceLock lock(Device::mutex());
-      int64_t kept = 0;
-      check(madicp_cloud_ingest_records(Device::ctx(), data, static_cast<int64_t>(n_records), &cl, min_range, max_range,
-                                        kitti_correction ? 1 : 0, t_range, &cloud_id, &kept, nullptr),
-            "madicp_cloud_ingest_records");
-    }
-    computeWithTree(curr_stamp, buildOnDevice(cloud_id, nullptr, 0, stamped), nullptr, t_pre);
-    return;
-  }
-  ContainerType cloud(n_records);
-  std::vector<double> stamps(stamped ? n_records : 0);
-  int64_t kept = 0;
-  if (ingest_records(data, static_cast<int64_t>(n_records), L, min_range, max_range, kitti_correction, t_range, cloud[0].data(),
-                     stamped ? stamps.data() : nullptr, &kept, nullptr) != 0)
-    throw std::invalid_argument("Pipeline::computeRecordsStamped: bad arguments (record count or t_range)");
-  if (kept < 1) throw std::invalid_argument("Pipeline::computeRecordsStamped: no point survives the range filter");
-  cloud.resize(static_cast<size_t>(kept));
-  if (stamped) {
-    stamps.resize(static_cast<size_t>(kept));
-    computeStamped(curr_stamp, std::move(cloud), stamps);
-  } else {
-    compute(curr_stamp, std::move(cloud));
-  }
+  const RecordSource S = plain_source(data, static_cast<int64_t>(n_records), layout, min_range, max_range, kitti_correction);
+  computeSources(curr_stamp, &S, 1, t_range, "Pipeline::computeRecordsStamped");
 }
 
-// A frame from several sensors' byte records (pipeline.h): computeRecordsStamped with the multi-source ingest in front.
+// A frame from several sensors' byte records (pipeline.h)
 void Pipeline::computeSourcesStamped(const double& curr_stamp, const RecordSource* sources, int n_sources, const double* t_range) {
   if (const char* why = record_sources_refusal(sources, n_sources, t_range))
     throw std::invalid_argument(std::string("Pipeline::computeSourcesStamped: ") + why);
+  computeSources(curr_stamp, sources, n_sources, t_range, "Pipeline::computeSourcesStamped");
+}
+
+// ... for sources that passed record_sources_refusal (`who`: the entry, for what is still refused).  The time fields matter only
+// where stamps can: deskew = true and layouts that have one — everywhere else the layouts are taken without it, so nothing is
+// normalised, stored or read.
+void Pipeline::computeSources(const double& curr_stamp, const RecordSource* sources, int n_sources, const double* t_range,
+                              const char* who) {
   RecordSource src[kMaxSources];
   int64_t total = 0;
   for (int s = 0; s < n_sources; ++s) {
@@ -436,43 +421,25 @@ void Pipeline::computeSourcesStamped(const double& curr_stamp, const RecordSourc
     total += src[s].n;
   }
   if (!deskew_) t_range = nullptr;
-  const bool stamped = src[0].L.t_type != kTimeNone;
+  const bool stamped = deskew_ && sources[0].L.t_type != kTimeNone;
   if (device_frontend_) {
     madicp_record_source cs[MADICP_MAX_SOURCES];
-    for (int s = 0; s < n_sources; ++s) {
-      const RecordSource& S = src[s];
-      madicp_record_source& c = cs[s];
-      c.data = S.data;
-      c.n_records = S.n;
-      c.layout = madicp_record_layout{S.L.step, S.L.off_x, S.L.off_y, S.L.off_z, S.L.off_t, S.L.t_type};
-      std::copy(S.R, S.R + 9, c.R);
-      std::copy(S.t, S.t + 3, c.t);
-      c.min_range = S.min_range;
-      c.max_range = S.max_range;
-      c.t_scale = S.t_scale;
-      c.t_offset = S.t_offset;
-      c.kitti_correction = S.kitti ? 1 : 0;
-      c.reserved = 0;
-    }
-    is_map_updated_ = false;
-    const double t_pre = now_ms();
-    ingestPrologue();
-    int cloud_id = -1;
-    {
-      DeviceLock lock(Device::mutex());
+    for (int s = 0; s < n_sources; ++s) cs[s] = record_source_to<madicp_record_source>(src[s]);
+    computeIngested(curr_stamp, stamped, [&] {
+      int cloud_id = -1;
       int64_t kept = 0;
       check(madicp_cloud_ingest_sources(Device::ctx(), cs, n_sources, t_range, &cloud_id, &kept, nullptr, nullptr),
             "madicp_cloud_ingest_sources");
-    }
-    computeWithTree(curr_stamp, buildOnDevice(cloud_id, nullptr, 0, stamped), nullptr, t_pre);
+      return cloud_id;
+    });
     return;
   }
   ContainerType cloud(static_cast<size_t>(total));
   std::vector<double> stamps(stamped ? static_cast<size_t>(total) : 0);
   int64_t kept = 0;
   if (ingest_sources(src, n_sources, t_range, cloud[0].data(), stamped ? stamps.data() : nullptr, &kept, nullptr, nullptr) != 0)
-    throw std::invalid_argument("Pipeline::computeSourcesStamped: bad arguments");
-  if (kept < 1) throw std::invalid_argument("Pipeline::computeSourcesStamped: no point survives the range filter");
+    throw std::invalid_argument(std::string(who) + ": bad arguments");
+  if (kept < 1) throw std::invalid_argument(std::string(who) + ": no point survives the range filter");
   cloud.resize(static_cast<size_t>(kept));
   if (stamped) {
     stamps.resize(static_cast<size_t>(kept));

@@ -142,9 +142,10 @@ class Pipeline {
 
   // additive: one frame straight from a driver's BYTE records with a time field (a PointCloud2-style buffer: `layout.step` bytes
   // apart, float32 x / y / z and a uint32 / float32 / float64 time at byte offsets, any alignment — madicp_record_layout).
-  // Device front-end: madicp_cloud_ingest_records — range filter, compaction and the stamps normalised over the scan, on the
-  // device — then, where the reference deskews, madicp_cloud_deskew_own_stamps from the stamps the cloud carries, build and
-  // registration: the time column never exists on the host.  Host front-end: the host twin (ingest_records.h), then
+  // The frame of computeSourcesStamped (below) for ONE plain source — identity extrinsic, the clock as it is — behind this call's
+  // own refusals.  Device front-end: range filter, compaction and the stamps normalised over the scan, on the device — then,
+  // where the reference deskews, madicp_cloud_deskew_own_stamps from the stamps the cloud carries, build and registration: the
+  // time column never exists on the host.  Host front-end: the host twin (ingest_records.h), then
   // deskew_cloud_stamped and the host builder — the same bits.  t_range: null = the min / max time over the message, else
   // {t_begin, t_end}.  With layout.t_type == kTimeNone the frame is computeRecords' on the same coordinates, azimuth deskew
   // included; with deskew = false the time field is ignored entirely.  No look-ahead for records.  std::invalid_argument for
@@ -208,6 +209,10 @@ class Pipeline {
   std::unique_ptr<MADtree> buildOnDevice(int cloud_id, const double* stamps = nullptr, size_t n_stamps = 0, bool own_stamps = false);
   std::unique_ptr<MADtree> uploadAndBuild(const Vector3d* cloud, size_t n, const double* stamps = nullptr);  // madicp_cloud_upload + buildOnDevice
   void ingestPrologue();  // the builder's scratch is this frame's: no look-ahead of this Pipeline or another one holds it
+  template <class Ingest>  // (pipeline.cpp only) the device half of computeRecords / computeSources: `ingest` returns the cloud id
+  void computeIngested(const double& curr_stamp, bool own_stamps, Ingest&& ingest);
+  // computeSourcesStamped behind its refusals; computeRecordsStamped is this for the one plain source
+  void computeSources(const double& curr_stamp, const RecordSource* sources, int n_sources, const double* t_range, const char* who);
   void computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree> current_tree, ContainerType* curr_cloud, double t_pre);
 
   MADicp icp_;

@@ -1,5 +1,6 @@
-"""The device ingest of raw point records with a time field — fe::records_mark / records_range / records_scatter through
-madicp_cloud_ingest_records — with madicp_cloud_stamps and madicp_cloud_deskew_own_stamps on top of it.
+"""The device ingest of raw point records with a time field — fe::sources_mark / records_range / sources_scatter through
+madicp_cloud_ingest_records, the one plain source of the sources ingest — with madicp_cloud_stamps and
+madicp_cloud_deskew_own_stamps on top of it.
 
 Everything is held bit for bit (uint64 views, NaN positions separately) to two references at once: the numpy restatement of
 tests/ingest_records_ref.py and the host twin madicp_host_ingest_records.  No tolerance anywhere.
@@ -233,6 +234,7 @@ def test_refusals(ctx):
     assert call(h=None) == INVALID and call(d=None) == INVALID and call(lay_null=True) == INVALID
     assert call(id_null=True) == INVALID and call(n_null=True) == INVALID
     assert call(count=0) == INVALID and call(count=-1) == INVALID and call(count=2**30 + 1) == INVALID
+    assert call(count=2**30) == INVALID                                # this entry's own bound: the sources rule would allow it
     for bad in [(11, 0, 4, 7, 0, 0), (257, 0, 4, 8, 0, 0), (22, -1, 4, 8, 18, 7), (22, 0, 19, 8, 18, 7), (22, 0, 4, 22, 18, 7),
                 (22, 0, 4, 8, 19, 7), (22, 0, 4, 8, 15, 8), (22, 0, 4, 8, -1, 6), (22, 0, 4, 8, 18, 5), (22, 0, 4, 8, 18, 9)]:
         assert call(layout=bad) == INVALID, bad

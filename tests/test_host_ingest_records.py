@@ -91,6 +91,7 @@ def test_refusals(natives):
     kept.value = -7
     assert call(lay, data=None) == -1 and call(lay, out=None) == -1 and call(lay, lay_null=True) == -1
     assert call(lay, count=0) == -1 and call(lay, count=-1) == -1 and call(lay, count=2**30 + 1) == -1
+    assert call(lay, count=2**30) == -1              # this entry's own bound: the sources rule would allow it
     for bad in [(11, 0, 4, 7, 0, 0), (257, 0, 4, 8, 0, 0), (22, -1, 4, 8, 18, 7), (22, 0, 19, 8, 18, 7), (22, 0, 4, 22, 18, 7),
                 (22, 0, 4, 8, 19, 7), (22, 0, 4, 8, 15, 8), (22, 0, 4, 8, -1, 6), (22, 0, 4, 8, 18, 5), (22, 0, 4, 8, 18, 9)]:
         assert call(bad) == -1, bad
