@@ -392,6 +392,37 @@ int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sou
  * size always suffices).  Bit-equal to madicp_host_cloud_export_f32 (madicp_host.h). */
 int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
                             int64_t capacity_rows, int64_t* out_n);
+/* THE VOXEL MAP — what a mapping consumer wants of a drive, not of one scan: registered scans accumulated on the device into an
+ * append-only set of float32 rows, one per voxel, of which the consumer fetches only what was added since it last looked.
+ * Additive.  Per point the export's rule above, everything in fp64 without contraction (one source:
+ * mad_icp_amd/csrc/common/export_point.h); the KEY of a point comes from its fp64 position, never from the float that is stored.
+ * A map has a voxel size (finite, > 0: no "every point" mode), M rows and the set K of their M keys.  Folding a cloud of n points
+ * through (R, t): point i is a CANDIDATE if all three cells are in range (as for the export), NEW if it is a candidate and its
+ * key is not in K; of the new points that share a key the one with the LOWEST index is kept; kept points are appended as
+ * (float)q[i] in ascending index order and their keys join K.  Rows are never changed or removed by a fold, so rows [0, M) after
+ * any fold are a prefix of the map for ever after, and the map is a function of the sequence of (cloud, pose) alone: launch
+ * geometry, timing, initial_rows and the number of growths do not show.
+ *   madicp_map_create        initial_rows >= 1 sizes the first block (44 bytes per row: float row, key, two table slots); blocks
+ *                            grow geometrically up to 1 <= max_rows <= 2^30.  MADICP_ERR_INVALID for a null argument, a voxel
+ *                            that is not finite or not > 0, rows out of those ranges.
+ *   madicp_map_insert_cloud  folds a resident cloud, which is only read: *out_added rows were appended, the map holds *out_rows.
+ *                            MADICP_ERR_CAPACITY, map unchanged, when rows + n > max_rows (conservative on purpose: decided
+ *                            before any launch), and while a look-ahead build is in flight (the fold's scratch is the builder's).
+ *                            MADICP_ERR_INVALID, nothing changed or written, for a null argument, an unknown id, a non-finite
+ *                            entry of R or t.  One host synchronisation, for the count.
+ *   madicp_map_size          the rows the map holds.
+ *   madicp_map_download_f32  rows [first_row, rows) into out_xyz, their number in *out_n; MADICP_ERR_CAPACITY when capacity_rows
+ *                            is smaller: *out_n is the number needed and out_xyz is not written (the export's convention);
+ *                            MADICP_ERR_INVALID for a null argument, an unknown id, a first_row outside [0, rows].
+ *   madicp_map_clear         forgets the rows, keeps the block.     madicp_map_release  frees everything.
+ * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds. */
+int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
+int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
+                            int64_t* out_rows);
+int madicp_map_size(madicp_ctx* ctx, int map_id, int64_t* out_rows);
+int madicp_map_download_f32(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_clear(madicp_ctx* ctx, int map_id);
+int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes
  * a resident tree exactly like one given to madicp_tree_upload (same node format, madicp_tree_download returns it).
  * Same decisions as the reference node by node, the reference's member order (the permutation utils.h:37-52 leaves), and

@@ -98,6 +98,27 @@ int madicp_host_ingest_sources(const madicp_record_source* sources, int n_source
  * argument, n < 0 or > 2^30, a non-finite entry of R or t, a voxel that is negative or not finite. */
 int madicp_host_cloud_export_f32(const double* xyz, int64_t n, const double R[9], const double t[3], double voxel, float* out_xyz,
                                  int64_t capacity_rows, int64_t* out_n);
+/* The host twin of the device voxel map madicp_map_* (madicp_hip.h: the same rule from the same per-point source
+ * csrc/common/export_point.h, bit-equal for every sequence of folds): an append-only set of float32 rows, the first point ever
+ * to fall into each voxel; what a Pipeline with the host front-end runs for setMapAccumulation().
+ *   _create        voxel finite and > 0, initial_rows >= 1 (a reservation: it never shows in the result), 1 <= max_rows <= 2^30;
+ *                  MADICP_ERR_INVALID otherwise, *out_map not written.
+ *   _insert        folds xyz (n, 3) float64, n >= 0, only read, through (R row-major, t): *out_added rows were appended, the map
+ *                  holds *out_rows.  MADICP_ERR_CAPACITY, map unchanged, when rows + n > max_rows; MADICP_ERR_INVALID, map
+ *                  unchanged and nothing written, for a null argument (xyz may be null when n == 0), n < 0 or > 2^30, a
+ *                  non-finite entry of R or t.
+ *   _download_f32  rows [first_row, rows) into out_xyz, their number in *out_n; MADICP_ERR_CAPACITY when capacity_rows is smaller
+ *                  — *out_n is the number needed, out_xyz is not written; MADICP_ERR_INVALID for a null argument or a first_row
+ *                  outside [0, rows].
+ *   _clear         forgets the rows, keeps the memory.   _destroy  frees everything (null: nothing). */
+typedef struct madicp_host_map madicp_host_map;
+int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
+int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
+                           int64_t* out_rows);
+int madicp_host_map_size(const madicp_host_map* map, int64_t* out_rows);
+int madicp_host_map_download_f32(const madicp_host_map* map, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_clear(madicp_host_map* map);
+void madicp_host_map_destroy(madicp_host_map* map);
 
 /* ---- the keyframe map sharded over the ranks of a node (Pipeline::setShard, csrc/host/pipeline.h) ---- */
 /* The rank that owns the keyframe of ORDINAL k — promotion order: the first scan is 0, every promotion adds 1; not the frame

@@ -158,6 +158,12 @@ def hip_lib():
         L.madicp_cloud_ingest_sources.argtypes = [C.c_void_p, C.POINTER(RecordSourceC), C.c_int, _dp, _ip, _i64p, _i64p, _dp]
         L.madicp_cloud_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64]
         L.madicp_cloud_export_f32.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
+        L.madicp_map_create.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, _ip]
+        L.madicp_map_insert_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _i64p, _i64p]
+        L.madicp_map_size.argtypes = [C.c_void_p, C.c_int, _i64p]
+        L.madicp_map_download_f32.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
+        L.madicp_map_clear.argtypes = [C.c_void_p, C.c_int]
+        L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
@@ -209,6 +215,13 @@ def host_lib():
                                                  _dp, _dp, _i64p, _dp]
         L.madicp_host_ingest_sources.argtypes = [C.POINTER(RecordSourceC), C.c_int, _dp, _dp, _dp, _i64p, _i64p, _dp]
         L.madicp_host_cloud_export_f32.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
+        L.madicp_host_map_create.argtypes = [C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+        L.madicp_host_map_insert.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, _i64p, _i64p]
+        L.madicp_host_map_size.argtypes = [C.c_void_p, _i64p]
+        L.madicp_host_map_download_f32.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
+        L.madicp_host_map_clear.argtypes = [C.c_void_p]
+        L.madicp_host_map_destroy.restype = None
+        L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
         L.madicp_host_debug_partition.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_int]
@@ -486,6 +499,52 @@ def host_cloud_export_f32(xyz, R, t, voxel):
     return out[:m.value].copy()
 
 
+def _host_map_check(rc, what):
+    if rc != 0:
+        raise MadIcpError("%s: error %d (%s)" % (what, rc, "capacity" if rc == -4 else "bad arguments"))
+
+
+def host_map_create(voxel, initial_rows, max_rows):
+    """madicp_host_map_create: the host twin of Context.map_create.  Returns the handle the other host_map_* calls take;
+    host_map_destroy frees it."""
+    h = C.c_void_p()
+    _host_map_check(host_lib().madicp_host_map_create(float(voxel), int(initial_rows), int(max_rows), C.byref(h)), "madicp_host_map_create")
+    return h
+
+
+def host_map_insert(h, xyz, R, t):
+    """Folds xyz (n, 3) float64 through (R (3, 3), t (3,)) into the map.  Returns (rows added, rows the map holds)."""
+    a = _f64(xyz).reshape(-1, 3)
+    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+    added, rows = C.c_int64(0), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_insert(h, a.ctypes.data_as(_dp), a.shape[0], Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp),
+                                                      C.byref(added), C.byref(rows)), "madicp_host_map_insert")
+    return added.value, rows.value
+
+
+def host_map_size(h):
+    rows = C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_size(h, C.byref(rows)), "madicp_host_map_size")
+    return rows.value
+
+
+def host_map_download_f32(h, first_row=0):
+    """Rows [first_row, size) of the map as (M - first_row, 3) float32."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    out, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_download_f32(h, int(first_row), out.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(got)),
+                    "madicp_host_map_download_f32")
+    return out[:got.value].copy()
+
+
+def host_map_clear(h):
+    _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
+
+
+def host_map_destroy(h):
+    host_lib().madicp_host_map_destroy(h)
+
+
 class Context:
     """One device + one stream (include/madicp_hip.h)."""
 
@@ -650,6 +709,40 @@ class Context:
         _check(hip_lib().madicp_cloud_export_f32(self._h, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), float(voxel),
                                                  out.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(m)))
         return out[:m.value].copy()
+
+    def map_create(self, voxel, initial_rows, max_rows):
+        """A device-resident, append-only voxel map (madicp_map_create): one float32 row per voxel, the first point ever to fall
+        into it.  Returns the map id."""
+        mid = C.c_int(0)
+        _check(hip_lib().madicp_map_create(self._h, float(voxel), int(initial_rows), int(max_rows), C.byref(mid)))
+        return mid.value
+
+    def map_insert_cloud(self, mid, cid, R, t):
+        """Folds a resident cloud through (R (3, 3), t (3,)) into the map; the cloud is only read.  Returns (rows added, rows the
+        map holds)."""
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        added, rows = C.c_int64(0), C.c_int64(0)
+        _check(hip_lib().madicp_map_insert_cloud(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), C.byref(added),
+                                                 C.byref(rows)))
+        return added.value, rows.value
+
+    def map_size(self, mid):
+        rows = C.c_int64(0)
+        _check(hip_lib().madicp_map_size(self._h, mid, C.byref(rows)))
+        return rows.value
+
+    def map_download_f32(self, mid, first_row=0):
+        """Rows [first_row, size) of the map as (M - first_row, 3) float32: what was added since the caller last looked."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        out, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
+        _check(hip_lib().madicp_map_download_f32(self._h, mid, int(first_row), out.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(got)))
+        return out[:got.value].copy()
+
+    def map_clear(self, mid):
+        _check(hip_lib().madicp_map_clear(self._h, mid))
+
+    def map_release(self, mid):
+        _check(hip_lib().madicp_map_release(self._h, mid))
 
     def cloud_deskew_own_stamps(self, cid, velocity, sensor_hz, want_chunks=False):
         """cloud_deskew_stamped from the stamps the cloud carries itself.  Returns the chunks (n,) int32 when asked for."""

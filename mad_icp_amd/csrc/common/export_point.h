@@ -53,4 +53,15 @@ inline const char* export_refusal(const double* R, const double* t, double voxel
   return nullptr;
 }
 
+// ---- the voxel map (madicp_map_* / madicp_host_map_*): the same per-point rule, folded into a set of keys that persists ----------
+constexpr int64_t kMapMaxRows = int64_t(1) << 30;               // (the device table has two 32-bit-indexed slots per row)
+
+// what both create entry points refuse (null = nothing to refuse): a map has no "every point" mode
+inline const char* map_create_refusal(double voxel, int64_t initial_rows, int64_t max_rows) {
+  if (!(voxel - voxel == 0.0) || !(voxel > 0.0)) return "voxel: finite and > 0";
+  if (initial_rows < 1) return "initial_rows: at least 1";
+  if (max_rows < 1 || max_rows > kMapMaxRows) return "max_rows: 1 .. 2^30";
+  return nullptr;
+}
+
 }  // namespace madicp_host

@@ -502,5 +502,85 @@ __global__ __launch_bounds__(256) void export_scatter(const double* __restrict__
   }
 }
 
+// ---- the voxel map: registered scans folded into ONE table that persists across frames -------------------------------------------
+// The export's rule per point (export_position, export_value, export_key: the key from the fp64 position, never from the stored
+// float), and the export's table — 64-bit keys, empty = all ones, linear probing from export_slot0, claimed by compare-and-swap —
+// but the table LIVES ON between folds, so a slot's 32-bit owner word has three states:
+//   kMapNever (all ones)   no fold has owned the slot yet — what the memset that empties the table leaves
+//   kMapSettled (0)        the slot's key got its row in an EARLIER fold: its points are not new
+//   1 .. n                 contended in THIS fold: the lowest index + 1 seen so far (atomicMin; i + 1 >= 1, so the settled word can
+//                          never be won, and an atomicMin that meets it leaves it settled)
+//   map_claim   one lane per point: position, key, the key's slot found or claimed, atomicMin(owner, i + 1) unless settled
+//   map_mark    behind a kernel boundary: mark[i] = candidate and owner[slot_of[i]] == i + 1 — the lowest index of a NEW key
+//   tile scan   S[i] = marks before i, the total = rows added
+//   map_append  marked points: the float row and the 64-bit key at row M + S[i] (growth re-inserts from the stored keys: a float
+//               row cannot reproduce its key), and the slot settles.  Every slot claimed in a fold has a lowest-index point, so
+//               none is left contended; between folds every owner is kMapNever or kMapSettled.
+//   map_rehash  growth: the stored keys of rows [0, M) into a fresh, larger table — all distinct, so claim only — owners settled
+// Which lane wins a compare-and-swap decides WHERE a key sits, never WHETHER it is in the table or which index owns it: the rows
+// are a function of the sequence of (cloud, pose) alone, whatever the launch geometry, the table size or the number of growths.
+// Termination: the host grows the table before a fold whenever M + n would exceed half its slots, so a probe always meets an empty
+// slot or its key.  Plain relaxed agent-scope loads in front of the atomics, as in export_claim.
+constexpr uint32_t kMapNever = 0xffffffffu, kMapSettled = 0u;
+__device__ inline uint32_t map_find_or_claim(unsigned long long* __restrict__ keys, uint32_t slots, unsigned long long key) {
+  uint32_t s = export_slot0(key, slots);
+  for (;;) {
+    unsigned long long seen = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (seen == madicp_host::kExportNoKey) seen = atomicCAS(&keys[s], (unsigned long long)madicp_host::kExportNoKey, key);
+    if (seen == madicp_host::kExportNoKey || seen == key) return s;  // claimed now, or this key's already
+    s = (s + 1 == slots) ? 0u : s + 1;
+  }
+}
+__global__ __launch_bounds__(256) void map_claim(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
+                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
+                                                 uint32_t* __restrict__ slot_of) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    double q[3];
+    madicp_host::export_position(p, X.R, X.t, q);
+    const unsigned long long key = madicp_host::export_key(q, voxel);
+    uint32_t s = kExportNoSlot;
+    if (key != madicp_host::kExportNoKey) {
+      s = map_find_or_claim(keys, slots, key);
+      // (kMapSettled is 0 and never above i + 1; owners only fall within a fold, so a stale value only costs the atomic)
+      if (__hip_atomic_load(&owner[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)i + 1u) atomicMin(&owner[s], (uint32_t)i + 1u);
+    }
+    slot_of[i] = s;
+  }
+}
+__global__ __launch_bounds__(256) void map_mark(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ owner, long n,
+                                                uint32_t* __restrict__ mark) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i <= n; i += (long)gridDim.x * blockDim.x) {
+    uint32_t m = 0;
+    if (i < n) {
+      const uint32_t s = slot_of[i];
+      m = (s != kExportNoSlot && owner[s] == (uint32_t)i + 1u) ? 1u : 0u;
+    }
+    mark[i] = m;  // (entry n: the scan needs a terminator)
+  }
+}
+__global__ __launch_bounds__(256) void map_append(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
+                                                  const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
+                                                  const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner, long first_row,
+                                                  float* __restrict__ rows, unsigned long long* __restrict__ row_keys) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    if (!mark[i]) continue;
+    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    double q[3];
+    madicp_host::export_position(p, X.R, X.t, q);
+    const long d = first_row + (long)pos[i];
+    rows[3 * d] = madicp_host::export_value(q[0]);
+    rows[3 * d + 1] = madicp_host::export_value(q[1]);
+    rows[3 * d + 2] = madicp_host::export_value(q[2]);
+    row_keys[d] = madicp_host::export_key(q, voxel);
+    owner[slot_of[i]] = kMapSettled;  // (one marked point per slot: nobody else writes it in this kernel)
+  }
+}
+__global__ __launch_bounds__(256) void map_rehash(const unsigned long long* __restrict__ row_keys, long n_rows,
+                                                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots) {
+  for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n_rows; r += (long)gridDim.x * blockDim.x)
+    owner[map_find_or_claim(keys, slots, row_keys[r])] = kMapSettled;
+}
+
 }  // namespace fe
 }  // namespace madicp

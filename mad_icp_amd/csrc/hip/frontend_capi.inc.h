@@ -17,6 +17,18 @@ struct DevCloud {
   hipEvent_t ready = nullptr;  // recorded on the copy stream behind whatever produced xyz
 };
 
+// a voxel map (madicp_map_*): one device block for `cap` rows and 2 cap table slots — laid out where the entry points are
+struct DevMap {
+  double voxel = 0.0;
+  int64_t max_rows = 0, cap = 0, rows = 0;  // rows: what the map holds — exact, the host reads every fold's count
+  char* block = nullptr;
+  unsigned long long* keys = nullptr;      // (slots) the table's keys, empty = all ones
+  uint32_t* owner = nullptr;               // (slots) fe::kMapNever / kMapSettled / contended
+  unsigned long long* row_keys = nullptr;  // (cap) the key of every row
+  float* xyz = nullptr;                    // (cap, 3)
+  uint32_t slots = 0;
+};
+
 // grow-only scratch of the tree builder / deskew / ingest
 struct FrontScratch {
   char* block = nullptr;
@@ -77,6 +89,7 @@ constexpr int kDeskewTableMax = 1040;  // > CHUNKS + a few: thresholds fall belo
 // per context, so that contexts driven from different host threads share nothing
 struct madicp_ctx::Front {
   std::unordered_map<int, DevCloud> clouds;
+  std::unordered_map<int, DevMap> maps;
   FrontScratch scratch;
 };
 
@@ -182,6 +195,8 @@ void front_destroy(madicp_ctx* ctx) {  // called by madicp_ctx_destroy (streams 
   if (!ctx->front) return;
   for (auto& c : ctx->front->clouds)
     if (c.second.ready) hipEventDestroy(c.second.ready);  // (the device buffers belong to the pool)
+  for (auto& m : ctx->front->maps)
+    if (m.second.block) hipFree(m.second.block);
   FrontScratch& fs = ctx->front->scratch;
   if (fs.fly.pre) {  // (a construction that was begun and never ended: its pre-sized tree block goes back with the pool)
     pool_free(ctx, fs.fly.pre_tree.block, nullptr);
@@ -860,6 +875,177 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
   HIP_TRY(hipMemcpyAsync(out_xyz, d_rows, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
   HIP_TRY(hipStreamSynchronize(ctx->copy));
   *out_n = rows;
+  return MADICP_OK;
+}
+
+}  // extern "C"
+
+// ---- the voxel map: registered scans accumulated on the device (include/madicp_hip.h: madicp_map_*) ---------------------------------
+// Kernels: fe::map_claim, fe::map_mark, the tile scan, fe::map_append, fe::map_rehash (frontend.hip.h has the rule and the
+// determinism argument).  A map owns ONE device block laid out for `cap` rows and 2 cap table slots — 44 bytes per row of capacity:
+//   keys (2 cap x 8) | owner (2 cap x 4)    the table: emptied by ONE memset to all ones (empty key, "never owned")
+//   row_keys (cap x 8) | xyz (cap x 12)     what the rows hold, in row order
+// Growth invariant: before a fold of n points into M rows, M + n <= cap — so the table is never more than half full and every
+// probe ends; where it would not hold, a block for max(M + n, min(2 cap, max_rows)) rows is allocated, rows and keys move by device
+// copy, map_rehash refills the table, the old block is freed.  The host knows M exactly: every fold ends with ONE synchronisation,
+// for the count (none more at a growth but the one in front of freeing the old block).  The per-fold scratch lives in idle parts of
+// the builder's scratch like the export's (idx[0] slot_of, leaf_start the marks, S / tile_sums the scan, rec_res->r.kept the total):
+// a fold is refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
+namespace {
+
+int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m) {
+  const size_t c = (size_t)cap;
+  char* block = nullptr;
+  HIP_TRY(hipMalloc(&block, 44 * c));
+  m->block = block;
+  m->cap = cap;
+  m->slots = static_cast<uint32_t>(2 * c);
+  m->keys = reinterpret_cast<unsigned long long*>(block);
+  m->owner = reinterpret_cast<uint32_t*>(block + 16 * c);
+  m->row_keys = reinterpret_cast<unsigned long long*>(block + 24 * c);
+  m->xyz = reinterpret_cast<float*>(block + 32 * c);
+  hipError_t e = hipMemsetAsync(block, 0xff, 24 * c, ctx->copy);
+  if (e != hipSuccess) {
+    hipFree(block);
+    *m = DevMap{};
+    return fail(MADICP_ERR_DEVICE, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
+  }
+  return MADICP_OK;
+}
+
+// a block that holds `need` rows (<= max_rows): the rows move, the table is refilled from their keys
+int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
+  DevMap g = *m;
+  RC_TRY(map_block_alloc(ctx, std::max(need, std::min(2 * m->cap, m->max_rows)), &g));
+  hipError_t e = hipSuccess;
+  if (m->rows > 0) {
+    const size_t M = (size_t)m->rows;
+    e = hipMemcpyAsync(g.row_keys, m->row_keys, sizeof(unsigned long long) * M, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(g.xyz, m->xyz, sizeof(float) * 3 * M, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess) {
+      const int blocks = static_cast<int>(std::min<int64_t>((m->rows + 255) / 256, (int64_t)ctx->n_cus * 8));
+      hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)m->rows, g.keys,
+                         g.owner, g.slots);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy);  // (the old block is read until here)
+  if (e != hipSuccess) {
+    hipFree(g.block);
+    return fail(MADICP_ERR_DEVICE, std::string("voxel map growth: ") + hipGetErrorString(e));
+  }
+  hipFree(m->block);
+  *m = g;
+  return MADICP_OK;
+}
+
+DevMap* find_map(madicp_ctx* ctx, int id) {
+  if (!ctx->front) return nullptr;
+  auto it = ctx->front->maps.find(id);
+  return it == ctx->front->maps.end() ? nullptr : &it->second;
+}
+
+}  // namespace
+
+extern "C" {
+
+int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id) {
+  if (!ctx || !out_map_id) return fail(MADICP_ERR_INVALID, "null argument");
+  if (const char* why = madicp_host::map_create_refusal(voxel, initial_rows, max_rows)) return fail(MADICP_ERR_INVALID, why);
+  HIP_TRY(hipSetDevice(ctx->device));
+  DevMap m;
+  m.voxel = voxel;
+  m.max_rows = max_rows;
+  RC_TRY(map_block_alloc(ctx, std::min(initial_rows, max_rows), &m));
+  const int id = ctx->next_id++;
+  front_of(ctx).maps[id] = m;
+  *out_map_id = id;
+  return MADICP_OK;
+}
+
+int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
+                            int64_t* out_rows) {
+  if (!ctx || !R || !t || !out_added || !out_rows) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (const char* why = madicp_host::export_refusal(R, t, m->voxel)) return fail(MADICP_ERR_INVALID, why);
+  RC_TRY(busy_with_lookahead(ctx));
+  const int64_t n = c->n;
+  if (m->rows + n > m->max_rows) return fail(MADICP_ERR_CAPACITY, "the map's rows and the cloud's points together exceed max_rows");
+  if (n == 0) {
+    *out_added = 0;
+    *out_rows = m->rows;
+    return MADICP_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, n, &fs));
+  if (m->rows + n > m->cap) RC_TRY(map_grow(ctx, m, m->rows + n));
+  fe::ExportPose X;
+  std::memcpy(X.R, R, sizeof(X.R));
+  std::memcpy(X.t, t, sizeof(X.t));
+  uint32_t* slot_of = fs->idx[0];
+  uint32_t* mark = fs->P.leaf_start;
+  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+  hipLaunchKernelGGL(fe::map_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, m->voxel, m->keys, m->owner,
+                     m->slots, slot_of);
+  hipLaunchKernelGGL(fe::map_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)m->owner, (long)n, mark);
+  RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
+  HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
+  hipLaunchKernelGGL(fe::map_append, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, m->voxel, (const uint32_t*)mark,
+                     (const uint32_t*)fs->S, (const uint32_t*)slot_of, m->owner, (long)m->rows, m->xyz, m->row_keys);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count: the one synchronisation of a fold
+  const int64_t added = fs->h_rec_res->r.kept;
+  m->rows += added;
+  *out_added = added;
+  *out_rows = m->rows;
+  return MADICP_OK;
+}
+
+int madicp_map_size(madicp_ctx* ctx, int map_id, int64_t* out_rows) {
+  if (!ctx || !out_rows) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  *out_rows = m->rows;
+  return MADICP_OK;
+}
+
+int madicp_map_download_f32(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out_xyz, m->xyz + 3 * first_row, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
+}
+
+int madicp_map_clear(madicp_ctx* ctx, int map_id) {
+  if (!ctx) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemsetAsync(m->block, 0xff, 24 * (size_t)m->cap, ctx->copy));
+  m->rows = 0;
+  return MADICP_OK;
+}
+
+int madicp_map_release(madicp_ctx* ctx, int map_id) {
+  if (!ctx) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  HIP_TRY(hipFree(m->block));
+  ctx->front->maps.erase(map_id);
   return MADICP_OK;
 }
 

@@ -157,6 +157,7 @@ Pipeline::~Pipeline() {  // Frames own their trees; trees release their HBM copi
   } catch (...) {
   }
   dropKeptScan();
+  dropMap();
 }
 
 // ---- the retained scan (pipeline.h: setKeepScan / registeredScan) ---------------------------------------------------------------
@@ -173,7 +174,7 @@ void Pipeline::dropKeptScan() {
 }
 
 void Pipeline::keepHostScan(const ContainerType& c) {
-  if (!keep_scan_) return;
+  if (!keep_scan_ && map_voxel_ == 0.0) return;
   dropKeptScan();
   kept_host_ = c;
   kept_n_ = c.size();
@@ -187,6 +188,125 @@ void Pipeline::setKeepScan(bool on) {
     dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
   } else {
     dropKeptScan();
+  }
+}
+
+// ---- map accumulation (pipeline.h: setMapAccumulation) -----------------------------------------------------------------------
+void Pipeline::dropMap() {
+  if (map_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    if (madicp_ctx* ctx = Device::current(map_generation_)) madicp_map_release(ctx, map_id_);  // (as for a kept cloud's id)
+    map_id_ = -1;
+  }
+  map_host_.reset();
+  map_overflowed_ = false;
+}
+
+void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points) {
+  if (!std::isfinite(voxel_size) || voxel_size < 0.0)
+    throw std::invalid_argument("Pipeline::setMapAccumulation: voxel_size must be finite and >= 0 (0 = off)");
+  if (voxel_size > 0.0 && (max_points < 1 || max_points > static_cast<size_t>(kMapMaxRows)))
+    throw std::invalid_argument("Pipeline::setMapAccumulation: max_points must be 1 .. 2^30");
+  if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_))) return;
+  dropMap();
+  const bool was_on = map_voxel_ > 0.0;
+  map_voxel_ = voxel_size;
+  map_keyframes_only_ = keyframes_only;
+  map_max_points_ = max_points;
+  if (voxel_size > 0.0) {
+    if (!was_on) dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
+  } else if (!keep_scan_) {
+    dropKeptScan();
+  }
+}
+
+void Pipeline::foldFrame() {
+  if (map_voxel_ == 0.0) return;
+  if (have_kept_ && !map_overflowed_ && (!map_keyframes_only_ || is_map_updated_)) {
+    const int64_t max_rows = static_cast<int64_t>(map_max_points_);
+    const int64_t first_rows = std::min<int64_t>(max_rows, int64_t(1) << 18);
+    const bool fresh = map_id_ < 0 && !map_host_;
+    int64_t added = 0, rows = 0;
+    int rc;
+    if (fresh ? kept_cloud_id_ >= 0 : map_id_ >= 0) {
+      DeviceLock lock(Device::mutex());
+      madicp_ctx* ctx = fresh ? Device::ctx() : Device::current(map_generation_);
+      if (!ctx) throw std::logic_error("Pipeline: the device context the map lived in is gone");
+      if (fresh) {
+        check(madicp_map_create(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create");
+        map_generation_ = Device::generation();
+      }
+      MADtree::cancelDeviceBuild(0);  // the fold needs the builder's scratch: a look-ahead of another Pipeline gives way
+      int cloud_id = kept_cloud_id_;
+      if (cloud_id < 0)  // (a host-side scan into a device map: the front-end was switched)
+        check(madicp_cloud_upload(ctx, kept_host_[0].data(), static_cast<int64_t>(kept_host_.size()), &cloud_id), "madicp_cloud_upload");
+      rc = madicp_map_insert_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, &added, &rows);
+      if (kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
+      if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_insert_cloud");
+    } else {
+      if (fresh) map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows);
+      ContainerType down;  // (a resident scan into a host map: the front-end was switched)
+      if (kept_cloud_id_ >= 0) {
+        DeviceLock lock(Device::mutex());
+        madicp_ctx* ctx = Device::current(kept_generation_);
+        if (!ctx) throw std::logic_error("Pipeline: the device context the scan lived in is gone");
+        down.resize(kept_n_);
+        check(madicp_cloud_download(ctx, kept_cloud_id_, down[0].data(), static_cast<int64_t>(kept_n_)), "madicp_cloud_download");
+      }
+      const ContainerType& c = kept_cloud_id_ >= 0 ? down : kept_host_;
+      rc = map_host_->insert(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, &added,
+                             &rows);
+      if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline: the host voxel map refused its arguments");
+    }
+    if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
+  }
+  if (!keep_scan_) dropKeptScan();
+}
+
+size_t Pipeline::mapSize() {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapSize: setMapAccumulation(voxel_size > 0) first");
+  if (map_host_) return static_cast<size_t>(map_host_->size());
+  if (map_id_ < 0) return 0;  // (no frame folded yet)
+  DeviceLock lock(Device::mutex());
+  madicp_ctx* ctx = Device::current(map_generation_);
+  if (!ctx) throw std::logic_error("Pipeline::mapSize: the device context the map lived in is gone");
+  int64_t rows = 0;
+  check(madicp_map_size(ctx, map_id_, &rows), "madicp_map_size");
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::mapCloud(float* out, size_t capacity, size_t first_row) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapCloud: setMapAccumulation(voxel_size > 0) first");
+  if (!out) throw std::invalid_argument("Pipeline::mapCloud: null buffer");
+  const size_t size = mapSize();
+  if (first_row > size) throw std::invalid_argument("Pipeline::mapCloud: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (capacity < size - first_row)
+    throw std::invalid_argument("Pipeline::mapCloud: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
+                                std::to_string(size - first_row));
+  if (size == first_row) return 0;
+  int64_t rows = 0;
+  if (map_host_) {
+    if (map_host_->download(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
+      throw std::runtime_error("Pipeline::mapCloud: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapCloud: the device context the map lived in is gone");
+    check(madicp_map_download_f32(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
+          "madicp_map_download_f32");
+  }
+  return static_cast<size_t>(rows);
+}
+
+void Pipeline::clearMap() {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::clearMap: setMapAccumulation(voxel_size > 0) first");
+  map_overflowed_ = false;
+  if (map_host_) map_host_->clear();
+  if (map_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::clearMap: the device context the map lived in is gone");
+    check(madicp_map_clear(ctx, map_id_), "madicp_map_clear");
   }
 }
 
@@ -263,7 +383,7 @@ void Pipeline::prefetchView(const Vector3d* next_cloud, size_t n) {
     // the tree is built on the GPU — a host build would only compete for the CPU — and the look-ahead is the library's:
     // collect the construction in flight (the scan about to be consumed), start this one beside the coming registration
     if (deskew_) return;  // (the tree needs the previous pose)
-    if (keep_scan_) return;  // (a look-ahead build gives back the tree alone, not the scan: pipeline.h, setKeepScan)
+    if (keep_scan_ || map_voxel_ > 0.0) return;  // (a look-ahead build gives back the tree alone, not the scan: pipeline.h, setKeepScan)
     // begun by the next compute(), behind its registration's submission; assign() into a buffer that lives as long as the
     // Pipeline: after the first frames no allocation, no fresh pages
     dev_next_cloud_.assign(next_cloud, next_cloud + n);
@@ -332,7 +452,9 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
     madicp_cloud_release(ctx, cloud_id);
     throw;
   }
-  if (keep_scan_) {  // retained instead: the buffer goes back to the pool when the next frame, setKeepScan(false) or the end drops it
+  // retained instead (map accumulation alone: until the frame's fold): the buffer goes back to the pool when the next frame,
+  // setKeepScan(false) or the end drops it
+  if (keep_scan_ || map_voxel_ > 0.0) {
     int64_t n = 0;
     check(madicp_cloud_size(ctx, cloud_id, &n), "madicp_cloud_size");
     kept_cloud_id_ = cloud_id;
@@ -563,6 +685,7 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
     } else {
       initialize(curr_stamp, *cloud);
     }
+    foldFrame();
     return;
   }
 
@@ -680,6 +803,7 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
     }
   }
   seq_++;
+  foldFrame();
 }
 
 // the reference's current_leaves_ are pointers into the current tree, so after compute() they read map-frame means

@@ -38,6 +38,7 @@
 
 #include "deskew.h"
 #include "ingest_records.h"
+#include "voxel_map.h"
 #include "keyframe_ledger.h"
 #include "linalg.h"
 #include "mad_icp.h"
@@ -134,6 +135,32 @@ class Pipeline {
   // std::invalid_argument for a null buffer, a voxel that is negative or not finite, a capacity smaller than the rows needed
   // (nothing is written then).
   size_t registeredScan(float* out, size_t capacity, double voxel, bool map_frame);
+
+  // additive: MAP ACCUMULATION.  With setMapAccumulation(voxel_size > 0) — default off: nothing changes, not a launch — every
+  // compute* entry point ends by folding the cloud its tree was built from (the cloud registeredScan(0, ...) returns, in that row
+  // order) through the frame's pose (currentPose()) into an append-only voxel map: one float32 row per voxel of edge voxel_size,
+  // the first point ever to fall into it; later arrivals are dropped where the map lives (the rule of madicp_map_insert_cloud,
+  // include/madicp_hip.h).  keyframes_only: only frames that end with isMapUpdated() true are folded.  max_points bounds the
+  // map (default kMapMaxPointsDefault = 2^24 rows: 0.7 GB of device memory at 44 bytes per row of capacity, allocated
+  // geometrically from 2^18 rows up); a fold is refused when the map's rows plus the frame's points would exceed it: compute*
+  // still returns its pose, accumulation stops and mapOverflowed() answers true until clearMap().  voxel_size == 0 turns the
+  // option off and frees the map; another voxel size, keyframes_only or max_points starts a new, empty map.  Device front-end:
+  // the frame's resident cloud is folded on the device, no copy (madicp_map_*); host front-end: the bit-equal host twin
+  // (voxel_map.h).  Independent of setKeepScan; like it, turning the option on drops the device look-ahead and none is begun
+  // while it is on — prefetch() stays legal and the frame builds synchronously: a tree built ahead comes without its scan.
+  // Poses, keyframe ids and isMapUpdated() are the same bit for bit with the option on or off.  A sharded Pipeline holds the
+  // whole map on every rank (poses are bit-equal across ranks, so the maps are).  std::invalid_argument for a voxel_size that
+  // is negative or not finite, max_points outside 1 .. 2^30.
+  static constexpr size_t kMapMaxPointsDefault = size_t(1) << 24;
+  void setMapAccumulation(double voxel_size, bool keyframes_only = false, size_t max_points = kMapMaxPointsDefault);
+  double mapVoxelSize() const { return map_voxel_; }  // 0: off
+  bool mapOverflowed() const { return map_overflowed_; }
+  size_t mapSize();  // rows the map holds; std::logic_error while the option is off (mapCloud and clearMap too)
+  // rows [first_row, mapSize()) as float32 (x, y, z) into out[0, 3 * capacity): rows are never changed or removed by a fold, so
+  // a consumer fetches what was added since it last looked with first_row = the size it saw then.  Returns the rows written;
+  // std::invalid_argument for a null buffer, first_row > mapSize(), a capacity below mapSize() - first_row (nothing written).
+  size_t mapCloud(float* out, size_t capacity, size_t first_row = 0);
+  void clearMap();  // forgets the rows (and the overflow), keeps the memory
   // additive: one frame straight from sensor records — float32 (x, y, z, intensity ...) `stride_floats` apart, range
   // filter and optional KITTI correction as in apps/cpp_runners/bin_runner.cpp:126-166 — ingest, deskew, build and
   // registration all on the device (implies the device front-end for this frame)
@@ -278,7 +305,17 @@ class Pipeline {
   ContainerType kept_host_;
   size_t kept_n_ = 0;
   void dropKeptScan();                        // forget it; the device buffer goes back to the pool
-  void keepHostScan(const ContainerType& c);  // host front-end: the copy, when the option is on
+  void keepHostScan(const ContainerType& c);  // host front-end: the copy, when the option (or map accumulation) is on
+  // map accumulation (setMapAccumulation): the map lives where the first folded cloud did — a device map of the context generation
+  // that issued its id, or the host twin; a cloud from the other side (the front-end was switched) crosses over for its fold
+  double map_voxel_ = 0.0;
+  bool map_keyframes_only_ = false, map_overflowed_ = false;
+  size_t map_max_points_ = kMapMaxPointsDefault;
+  int map_id_ = -1;
+  unsigned map_generation_ = 0;
+  std::unique_ptr<VoxelMap> map_host_;
+  void dropMap();
+  void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;
   int last_rounds_ = 0;
   double round_ms_estimate_ = 0.05;  // device time of one GN round, from the previous frame (realtime budget)

@@ -1,0 +1,52 @@
+// madicp_host_map_* (include/madicp_host.h): the C entry points of the host voxel map (voxel_map.h).  Compiled without
+// floating-point contraction, like everything that includes csrc/common/export_point.h.
+#include "voxel_map.h"
+
+#include <new>
+
+#include "madicp_host.h"
+
+static_assert(madicp_host::kMapOk == MADICP_OK && madicp_host::kMapInvalid == MADICP_ERR_INVALID &&
+                  madicp_host::kMapCapacity == MADICP_ERR_CAPACITY,
+              "voxel_map.h returns the C ABI's codes");
+
+struct madicp_host_map {
+  madicp_host::VoxelMap map;
+};
+
+extern "C" {
+
+int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map) {
+  if (!out_map || madicp_host::map_create_refusal(voxel, initial_rows, max_rows)) return MADICP_ERR_INVALID;
+  madicp_host_map* m = new (std::nothrow) madicp_host_map{madicp_host::VoxelMap(voxel, initial_rows, max_rows)};
+  if (!m) return MADICP_ERR_CAPACITY;
+  *out_map = m;
+  return MADICP_OK;
+}
+
+int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
+                           int64_t* out_rows) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.insert(xyz, n, R, t, out_added, out_rows);
+}
+
+int madicp_host_map_size(const madicp_host_map* map, int64_t* out_rows) {
+  if (!map || !out_rows) return MADICP_ERR_INVALID;
+  *out_rows = map->map.size();
+  return MADICP_OK;
+}
+
+int madicp_host_map_download_f32(const madicp_host_map* map, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download(first_row, out_xyz, capacity_rows, out_n);
+}
+
+int madicp_host_map_clear(madicp_host_map* map) {
+  if (!map) return MADICP_ERR_INVALID;
+  map->map.clear();
+  return MADICP_OK;
+}
+
+void madicp_host_map_destroy(madicp_host_map* map) { delete map; }
+
+}  // extern "C"

@@ -87,6 +87,30 @@ PYBIND11_MODULE(pypeline, m) {
            return out;
          },
          py::arg("voxel_size") = 0.0, py::arg("frame") = "map")
+    // additive: map accumulation (Pipeline::setMapAccumulation).  setMapAccumulation(voxel_size) makes every compute*() end by folding
+    // the frame's scan at the frame's pose into an append-only voxel map — the first point ever to fall into a voxel stays — on the
+    // device (device front-end) or in its bit-equal host twin; voxel_size = 0 turns it off and frees the map.  mapCloud(first_row)
+    // returns rows [first_row, mapSize()) as an (M - first_row, 3) float32 array: what was added since the caller last looked.
+    // ValueError for a voxel_size that is negative or not finite, a max_points outside 1 .. 2^30, a first_row beyond the map;
+    // RuntimeError (std::logic_error) from mapSize / mapCloud / clearMap while the option is off.
+    .def("setMapAccumulation", &Pipeline::setMapAccumulation, py::arg("voxel_size"), py::arg("keyframes_only") = false,
+         py::arg("max_points") = Pipeline::kMapMaxPointsDefault)
+    .def("mapVoxelSize", &Pipeline::mapVoxelSize)
+    .def("mapOverflowed", &Pipeline::mapOverflowed)
+    .def("mapSize", &Pipeline::mapSize)
+    .def("mapCloud",
+         [](Pipeline& self, size_t first_row) {
+           const size_t size = self.mapSize();
+           if (first_row > size) throw py::value_error("first_row is beyond the map's rows");
+           const size_t m = size - first_row;
+           py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
+           float none[3];
+           const size_t got = self.mapCloud(m ? out.mutable_data() : none, m, first_row);
+           if (got != m) throw std::runtime_error("Pipeline::mapCloud: the map changed during the call");
+           return out;
+         },
+         py::arg("first_row") = 0)
+    .def("clearMap", &Pipeline::clearMap)
     // additive: a frame straight from sensor records, (n, >=3) float32 (a KITTI .bin is (n,4)): range filter, optional
     // KITTI correction (apps/cpp_runners/bin_runner.cpp:126-166), deskew, build and registration on the device
     .def("computeRecords",
