@@ -1,5 +1,5 @@
 // What happens to ONE point of a registered scan on its way OUT — ONE source for the device export kernels (csrc/hip/frontend.hip.h:
-// export_claim / export_mark / export_scatter) and for the host twin (csrc/host/cloud_export.cpp), so the two cannot drift apart:
+// voxel_claim / voxel_mark / voxel_rows) and for the host twins (csrc/host/cloud_export.h, voxel_map.h), so they cannot drift apart:
 // the position in the target frame, the float that goes out, and the voxel a position falls in.  Every translation unit that
 // includes this is compiled WITHOUT floating-point contraction (-ffp-contract=off; the device header adds the pragma).
 //

@@ -428,23 +428,36 @@ __global__ __launch_bounds__(256) void deskew_stamped(const double* __restrict__
   }
 }
 
-// ---- export: a resident cloud out, in another frame, as float32, one point per voxel ------------------------------------------
-// The rule is madicp_host's (csrc/common/export_point.h: export_position, export_value, export_key — shared with the host twin).
-// "The lowest index of every voxel" must not depend on which lane arrives first, so it is decided by two integer atomics whose
-// results commute, and read only behind a kernel boundary:
-//   export_claim   one lane per point: position, key; the key's slot in an open-addressing table (`slots` >= 2 n entries of
-//                  64-bit keys, empty = all ones, linear probing from a hash of the key) is found or claimed with a 64-bit
-//                  compare-and-swap — whoever wins, the slot ends up holding that key, and a slot never changes once it is set —
-//                  then atomicMin(owner[slot], index).  At most n distinct keys in >= 2 n slots: a probe always ends.
-//   export_mark    mark[i] = the point is a candidate and owner[slot_of[i]] == i (every claim has finished: kernel boundary)
-//   tile scan      tb_scan_tiles / tb_scan_top / tb_scan_apply: S[i] = marks before i, the total
-//   export_scatter the kept points' positions, recomputed, as three floats at row S[i]; marks == nullptr (voxel == 0): every point
-//                  at row i
-// Contention: a plain (relaxed, device-scope) load in front of each atomic skips it where it can no longer change anything — a
-// slot that already holds the key, an owner that is already <= the index (owners only fall, so a stale value only costs the
-// atomic it would have saved).  All points in ONE voxel is the worst case: one compare-and-swap wins, the lanes of the first
-// wavefronts serialise on one owner word, everybody later reads a smaller owner and passes.  Correct; not tuned for.
-constexpr uint32_t kExportNoSlot = 0xffffffffu;  // slot_of[] of a point that is no candidate; also the initial owner
+// ---- voxel thinning: a resident cloud folded into a table of voxels, one row per NEW voxel ----------------------------------------
+// The rule is madicp_host's (csrc/common/export_point.h: export_position, export_value, export_key — shared with the host twins; the
+// key comes from the fp64 position, never from the stored float).  The table is open addressing over `slots` 64-bit keys, empty =
+// all ones, linear probing from export_slot0, a slot found or claimed with a 64-bit compare-and-swap: whoever wins, the slot ends up
+// holding that key, and a slot never changes once it is set.  Beside every key sits a 32-bit owner word with three states:
+//   kMapNever (all ones)   no fold has owned the slot yet — what the ONE memset that empties the table leaves
+//   kMapSettled (0)        the slot's key got its row in an EARLIER fold: its points are not new
+//   1 .. n                 contended in THIS fold: the lowest index + 1 seen so far (atomicMin; i + 1 >= 1, so the settled word can
+//                          never be won, and an atomicMin that meets it leaves it settled)
+//   voxel_claim  one lane per point: position, key, the key's slot found or claimed, atomicMin(owner, i + 1) unless settled
+//   voxel_mark   behind a kernel boundary (every claim has finished): mark[i] = candidate and owner[slot_of[i]] == i + 1 — the
+//                lowest index of a NEW key
+//   tile scan    tb_scan_tiles / tb_scan_top / tb_scan_apply: S[i] = marks before i, the total = rows added
+//   voxel_rows   marked points: the position, recomputed, as three floats at row first_row + S[i]; where asked for, the row's 64-bit
+//                key beside it and the slot settled.  Every slot claimed in a fold has a lowest-index point, so a settling fold
+//                leaves none contended: between its folds every owner is kMapNever or kMapSettled.
+//   map_rehash   growth: the stored keys of rows [0, M) into a fresh, larger table — all distinct, so claim only — owners settled
+// Determinism: "the lowest index of every new voxel" is decided by two integer atomics whose results commute and is read only behind
+// a kernel boundary.  Which lane wins a compare-and-swap decides WHERE a key sits, never WHETHER it is in the table or which index
+// owns it: the rows are a function of the sequence of (cloud, pose) alone, whatever the launch geometry, the table size or the
+// number of growths.  Termination: the table is never more than half full (the callers see to it), so a probe always meets an empty
+// slot or its key.  Contention: a plain (relaxed, device-scope) load in front of each atomic skips it where it can no longer change
+// anything — a slot that already holds the key, an owner that is already <= i + 1 (owners only fall within a fold, so a stale value
+// only costs the atomic it would have saved).  All points in ONE voxel is the worst case: one compare-and-swap wins, the lanes of
+// the first wavefronts serialise on one owner word, everybody later reads a smaller owner and passes.  Correct; not tuned for.
+// The export (madicp_cloud_export_f32) is the FIRST fold into a scratch table of 2 n slots that the next call wipes: no keys stored,
+// nothing settled; voxel == 0 skips the table and sends every point to row i.  The map (madicp_map_*) keeps its table between folds,
+// stores every row's key (growth re-inserts from them: a float row cannot reproduce its key) and settles what it appended.
+constexpr uint32_t kExportNoSlot = 0xffffffffu;  // slot_of[] of a point that is no candidate
+constexpr uint32_t kMapNever = 0xffffffffu, kMapSettled = 0u;
 struct ExportPose {  // by value, wave-uniform: scalar loads
   double R[9], t[3];
 };
@@ -455,73 +468,6 @@ __device__ inline uint32_t export_slot0(uint64_t key, uint32_t slots) {
   h ^= h >> 33;
   return __umulhi((uint32_t)(h >> 32), slots);  // [0, slots) without a division
 }
-__global__ __launch_bounds__(256) void export_claim(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
-                                                    unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
-                                                    uint32_t* __restrict__ slot_of) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-    double q[3];
-    madicp_host::export_position(p, X.R, X.t, q);
-    const unsigned long long key = madicp_host::export_key(q, voxel);
-    uint32_t s = kExportNoSlot;
-    if (key != madicp_host::kExportNoKey) {
-      s = export_slot0(key, slots);
-      for (;;) {
-        unsigned long long seen = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (seen == madicp_host::kExportNoKey) seen = atomicCAS(&keys[s], (unsigned long long)madicp_host::kExportNoKey, key);
-        if (seen == madicp_host::kExportNoKey || seen == key) break;  // claimed now, or this key's already
-        s = (s + 1 == slots) ? 0u : s + 1;
-      }
-      if (__hip_atomic_load(&owner[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)i) atomicMin(&owner[s], (uint32_t)i);
-    }
-    slot_of[i] = s;
-  }
-}
-__global__ __launch_bounds__(256) void export_mark(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ owner, long n,
-                                                   uint32_t* __restrict__ mark) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i <= n; i += (long)gridDim.x * blockDim.x) {
-    uint32_t m = 0;
-    if (i < n) {
-      const uint32_t s = slot_of[i];
-      m = (s != kExportNoSlot && owner[s] == (uint32_t)i) ? 1u : 0u;
-    }
-    mark[i] = m;  // (entry n: the scan needs a terminator)
-  }
-}
-__global__ __launch_bounds__(256) void export_scatter(const double* __restrict__ xyz, long n, ExportPose X, const uint32_t* __restrict__ mark,
-                                                      const uint32_t* __restrict__ pos, float* __restrict__ out) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    if (mark && !mark[i]) continue;
-    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-    double q[3];
-    madicp_host::export_position(p, X.R, X.t, q);
-    const long d = mark ? (long)pos[i] : i;
-    out[3 * d] = madicp_host::export_value(q[0]);
-    out[3 * d + 1] = madicp_host::export_value(q[1]);
-    out[3 * d + 2] = madicp_host::export_value(q[2]);
-  }
-}
-
-// ---- the voxel map: registered scans folded into ONE table that persists across frames -------------------------------------------
-// The export's rule per point (export_position, export_value, export_key: the key from the fp64 position, never from the stored
-// float), and the export's table — 64-bit keys, empty = all ones, linear probing from export_slot0, claimed by compare-and-swap —
-// but the table LIVES ON between folds, so a slot's 32-bit owner word has three states:
-//   kMapNever (all ones)   no fold has owned the slot yet — what the memset that empties the table leaves
-//   kMapSettled (0)        the slot's key got its row in an EARLIER fold: its points are not new
-//   1 .. n                 contended in THIS fold: the lowest index + 1 seen so far (atomicMin; i + 1 >= 1, so the settled word can
-//                          never be won, and an atomicMin that meets it leaves it settled)
-//   map_claim   one lane per point: position, key, the key's slot found or claimed, atomicMin(owner, i + 1) unless settled
-//   map_mark    behind a kernel boundary: mark[i] = candidate and owner[slot_of[i]] == i + 1 — the lowest index of a NEW key
-//   tile scan   S[i] = marks before i, the total = rows added
-//   map_append  marked points: the float row and the 64-bit key at row M + S[i] (growth re-inserts from the stored keys: a float
-//               row cannot reproduce its key), and the slot settles.  Every slot claimed in a fold has a lowest-index point, so
-//               none is left contended; between folds every owner is kMapNever or kMapSettled.
-//   map_rehash  growth: the stored keys of rows [0, M) into a fresh, larger table — all distinct, so claim only — owners settled
-// Which lane wins a compare-and-swap decides WHERE a key sits, never WHETHER it is in the table or which index owns it: the rows
-// are a function of the sequence of (cloud, pose) alone, whatever the launch geometry, the table size or the number of growths.
-// Termination: the host grows the table before a fold whenever M + n would exceed half its slots, so a probe always meets an empty
-// slot or its key.  Plain relaxed agent-scope loads in front of the atomics, as in export_claim.
-constexpr uint32_t kMapNever = 0xffffffffu, kMapSettled = 0u;
 __device__ inline uint32_t map_find_or_claim(unsigned long long* __restrict__ keys, uint32_t slots, unsigned long long key) {
   uint32_t s = export_slot0(key, slots);
   for (;;) {
@@ -531,9 +477,9 @@ __device__ inline uint32_t map_find_or_claim(unsigned long long* __restrict__ ke
     s = (s + 1 == slots) ? 0u : s + 1;
   }
 }
-__global__ __launch_bounds__(256) void map_claim(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
-                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
-                                                 uint32_t* __restrict__ slot_of) {
+__global__ __launch_bounds__(256) void voxel_claim(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
+                                                   unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
+                                                   uint32_t* __restrict__ slot_of) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     double q[3];
@@ -542,14 +488,14 @@ __global__ __launch_bounds__(256) void map_claim(const double* __restrict__ xyz,
     uint32_t s = kExportNoSlot;
     if (key != madicp_host::kExportNoKey) {
       s = map_find_or_claim(keys, slots, key);
-      // (kMapSettled is 0 and never above i + 1; owners only fall within a fold, so a stale value only costs the atomic)
+      // (kMapSettled is 0 and never above i + 1)
       if (__hip_atomic_load(&owner[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)i + 1u) atomicMin(&owner[s], (uint32_t)i + 1u);
     }
     slot_of[i] = s;
   }
 }
-__global__ __launch_bounds__(256) void map_mark(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ owner, long n,
-                                                uint32_t* __restrict__ mark) {
+__global__ __launch_bounds__(256) void voxel_mark(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ owner, long n,
+                                                  uint32_t* __restrict__ mark) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i <= n; i += (long)gridDim.x * blockDim.x) {
     uint32_t m = 0;
     if (i < n) {
@@ -559,21 +505,23 @@ __global__ __launch_bounds__(256) void map_mark(const uint32_t* __restrict__ slo
     mark[i] = m;  // (entry n: the scan needs a terminator)
   }
 }
-__global__ __launch_bounds__(256) void map_append(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
+// Null arguments (kernel arguments: the branches are wave-uniform) switch parts off.  mark / pos: every point, at row first_row + i.
+// row_keys: no key is stored, and none is recomputed (three fp64 divisions per row).  owner / slot_of: nothing settles.
+__global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
                                                   const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
                                                   const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner, long first_row,
                                                   float* __restrict__ rows, unsigned long long* __restrict__ row_keys) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    if (!mark[i]) continue;
+    if (mark && !mark[i]) continue;
     const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     double q[3];
     madicp_host::export_position(p, X.R, X.t, q);
-    const long d = first_row + (long)pos[i];
+    const long d = first_row + (mark ? (long)pos[i] : i);
     rows[3 * d] = madicp_host::export_value(q[0]);
     rows[3 * d + 1] = madicp_host::export_value(q[1]);
     rows[3 * d + 2] = madicp_host::export_value(q[2]);
-    row_keys[d] = madicp_host::export_key(q, voxel);
-    owner[slot_of[i]] = kMapSettled;  // (one marked point per slot: nobody else writes it in this kernel)
+    if (row_keys) row_keys[d] = madicp_host::export_key(q, voxel);
+    if (owner) owner[slot_of[i]] = kMapSettled;  // (one marked point per slot: nobody else writes it in this kernel)
   }
 }
 __global__ __launch_bounds__(256) void map_rehash(const unsigned long long* __restrict__ row_keys, long n_rows,

@@ -556,7 +556,7 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
   RC_TRY(stage_records(ctx, records, n_records, bytes, bytes, &fs, &d_raw));
   const float* d_rec = static_cast<const float*>(d_raw);
   uint32_t* keep = fs->P.leaf_start;
-  const int blocks = static_cast<int>(std::min<int64_t>((n_records + 255) / 256, (int64_t)ctx->n_cus * 8));
+  const int blocks = grid_256(ctx, n_records);
   hipLaunchKernelGGL(fe::ingest_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, stride_floats,
                      min_range, max_range, keep);
   RC_TRY(scan_marks(ctx->copy, *fs, keep, n_records, &fs->P.st->n_leaves));
@@ -728,7 +728,7 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   int n_thr = 0;
   RC_TRY(send_deskew_table(ctx, fs, velocity, sensor_hz, kDeskewTableMax, true, &n_thr));
   const int n_poses = std::min(n_thr + 1, kDeskewTableMax);
-  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+  const int blocks = grid_256(ctx, n);
   hipLaunchKernelGGL(fe::deskew_keys, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, fs->key[0], fs->idx[0]);
   HIP_TRY(hipGetLastError());
   size_t tmp_bytes = fs->sort_tmp_bytes;
@@ -761,11 +761,52 @@ int deskew_stamped_on(madicp_ctx* ctx, DevCloud* c, FrontScratch* fs, const doub
   RC_TRY(send_deskew_table(ctx, fs, velocity, sensor_hz, fe::kStampChunks, false, &n_thr));
   const double* d_poses = fs->table + kDeskewTableMax;
   int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;  // (input order)
-  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+  const int blocks = grid_256(ctx, n);
   return replace_points(ctx, c, "deskew_stamped", false, out_chunks, d_chunks, [&](double* fresh) {
     hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, d_stamps, (long)n, d_poses, fresh,
                        d_chunks);
   });
+}
+
+fe::ExportPose export_pose(const double R[9], const double t[3]) {
+  fe::ExportPose X;
+  std::memcpy(X.R, R, sizeof(X.R));
+  std::memcpy(X.t, t, sizeof(X.t));
+  return X;
+}
+
+// a voxel table (frontend.hip.h) where it lies: a map's own block, or buf[0] of the scratch for an export
+struct VoxelTable {
+  unsigned long long* keys;  // (slots) empty = all ones
+  uint32_t* owner;           // (slots) fe::kMapNever / kMapSettled / contended
+  uint32_t slots;
+};
+
+// One fold of a resident cloud (n >= 1 points) through X into table T, on the copy stream: fe::voxel_claim, fe::voxel_mark, the
+// tile scan, fe::voxel_rows — the lowest-index point of every voxel T has not settled yet, as float rows from `first_row` of `rows`
+// on, in input order.  row_keys: where the rows' keys go, or null; settle: whether the rows' slots settle (a table that lives on).
+// The caller keeps T at most half full.  The per-fold scratch lives in idle parts of the builder's scratch, which the caller owns
+// (busy_with_lookahead, ensure_scratch for n) and which does not grow:
+//   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->r.kept  the scan's total
+// The rows are enqueued BEHIND the scan, before the host knows the count, and they are ready when it arrives: ONE synchronisation.
+int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::ExportPose& X, double voxel, VoxelTable T, bool settle,
+               float* rows, int64_t first_row, unsigned long long* row_keys, int64_t* out_added) {
+  const int64_t n = c->n;
+  uint32_t* slot_of = fs->idx[0];
+  uint32_t* mark = fs->P.leaf_start;
+  const int blocks = grid_256(ctx, n);
+  hipLaunchKernelGGL(fe::voxel_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, T.keys, T.owner,
+                     T.slots, slot_of);
+  hipLaunchKernelGGL(fe::voxel_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)T.owner, (long)n, mark);
+  RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
+  HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
+  hipLaunchKernelGGL(fe::voxel_rows, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, (const uint32_t*)mark,
+                     (const uint32_t*)fs->S, (const uint32_t*)(settle ? slot_of : nullptr), settle ? T.owner : nullptr, (long)first_row,
+                     rows, row_keys);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count
+  *out_added = fs->h_rec_res->r.kept;
+  return MADICP_OK;
 }
 }  // namespace
 
@@ -816,16 +857,14 @@ int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int
   return MADICP_OK;
 }
 
-// A resident cloud OUT: through (R, t), as float32 rows, thinned to the lowest-index point of every voxel (include/madicp_hip.h;
-// kernels: fe::export_claim, fe::export_mark, the tile scan, fe::export_scatter).  The cloud is only read.  Everything lives in
-// idle parts of the builder's scratch, which this call owns like every other madicp_cloud_* call — the block does not grow:
+// A resident cloud OUT: through (R, t), as float32 rows, thinned to the lowest-index point of every voxel (include/madicp_hip.h):
+// the first fold (voxel_fold) of the cloud into an empty table, nothing kept afterwards.  The cloud is only read.  Table and rows
+// live in idle parts of the builder's scratch too, which this call owns like every other madicp_cloud_* call:
 //   buf[0]  (24 bytes per point)  the table: 2 n 64-bit keys, behind them 2 n 32-bit owners — exactly 24 n bytes, set to all
-//                                 ones by ONE memset (the empty key and the "no owner yet" index are both all ones)
-//   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->r.kept  the scan's total
+//                                 ones by ONE memset (the empty key and the never-owned word are both all ones)
 //   buf[1]  the float rows (12 of its 24 bytes per point)
-// The scatter is enqueued BEHIND the scan, before the host knows the count: it writes scratch only, so a refusal for capacity
-// still leaves out_xyz alone, and the rows are ready when the count arrives.  Two synchronisations: the count, then the rows
-// (voxel == 0: the count is the cloud's size — one).
+// The fold writes scratch only, so a refusal for capacity still leaves out_xyz alone.  Two synchronisations: the count, then the
+// rows (voxel == 0: no table, every point a row, the count is the cloud's size — one).
 int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
                             int64_t capacity_rows, int64_t* out_n) {
   if (!ctx || !R || !t || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
@@ -841,34 +880,22 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
   HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
   RC_TRY(ensure_scratch(ctx, n, &fs));
-  fe::ExportPose X;
-  std::memcpy(X.R, R, sizeof(X.R));
-  std::memcpy(X.t, t, sizeof(X.t));
+  const fe::ExportPose X = export_pose(R, t);
   float* d_rows = reinterpret_cast<float*>(fs->P.buf[1]);
-  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
   int64_t rows = n;
   if (voxel == 0.0) {
-    hipLaunchKernelGGL(fe::export_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, d_rows);
+    hipLaunchKernelGGL(fe::voxel_rows, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0L, d_rows,
+                       (unsigned long long*)nullptr);
     HIP_TRY(hipGetLastError());
   } else {
-    const uint32_t slots = static_cast<uint32_t>(2 * n);  // (n <= 2^30)
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(fs->P.buf[0]);
-    uint32_t* owner = reinterpret_cast<uint32_t*>(keys + slots);
-    uint32_t* slot_of = fs->idx[0];
-    uint32_t* mark = fs->P.leaf_start;
-    HIP_TRY(hipMemsetAsync(keys, 0xff, (sizeof(unsigned long long) + sizeof(uint32_t)) * (size_t)slots, ctx->copy));
-    hipLaunchKernelGGL(fe::export_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, keys, owner, slots,
-                       slot_of);
-    hipLaunchKernelGGL(fe::export_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)owner, (long)n, mark);
-    RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
-    HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
-    hipLaunchKernelGGL(fe::export_scatter, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, (const uint32_t*)mark,
-                       (const uint32_t*)fs->S, d_rows);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count decides whether the caller's buffer is large enough
-    rows = fs->h_rec_res->r.kept;
-    *out_n = rows;
+    VoxelTable T;
+    T.slots = static_cast<uint32_t>(2 * n);  // (n <= 2^30)
+    T.keys = reinterpret_cast<unsigned long long*>(fs->P.buf[0]);
+    T.owner = reinterpret_cast<uint32_t*>(T.keys + T.slots);
+    HIP_TRY(hipMemsetAsync(T.keys, 0xff, (sizeof(unsigned long long) + sizeof(uint32_t)) * (size_t)T.slots, ctx->copy));
+    RC_TRY(voxel_fold(ctx, fs, c, X, voxel, T, false, d_rows, 0, nullptr, &rows));
+    *out_n = rows;  // the count decides whether the caller's buffer is large enough
     if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the export needs (*out_n)");
     if (rows == 0) return MADICP_OK;  // (no candidate: every point outside the 2^21 cells per axis, or not finite)
   }
@@ -881,16 +908,15 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
 }  // extern "C"
 
 // ---- the voxel map: registered scans accumulated on the device (include/madicp_hip.h: madicp_map_*) ---------------------------------
-// Kernels: fe::map_claim, fe::map_mark, the tile scan, fe::map_append, fe::map_rehash (frontend.hip.h has the rule and the
-// determinism argument).  A map owns ONE device block laid out for `cap` rows and 2 cap table slots — 44 bytes per row of capacity:
+// Every insert is one voxel_fold into a table that persists; fe::map_rehash refills it at a growth (frontend.hip.h has the rule and
+// the determinism argument).  A map owns ONE device block laid out for `cap` rows and 2 cap table slots — 44 bytes per row of capacity:
 //   keys (2 cap x 8) | owner (2 cap x 4)    the table: emptied by ONE memset to all ones (empty key, "never owned")
 //   row_keys (cap x 8) | xyz (cap x 12)     what the rows hold, in row order
 // Growth invariant: before a fold of n points into M rows, M + n <= cap — so the table is never more than half full and every
 // probe ends; where it would not hold, a block for max(M + n, min(2 cap, max_rows)) rows is allocated, rows and keys move by device
 // copy, map_rehash refills the table, the old block is freed.  The host knows M exactly: every fold ends with ONE synchronisation,
-// for the count (none more at a growth but the one in front of freeing the old block).  The per-fold scratch lives in idle parts of
-// the builder's scratch like the export's (idx[0] slot_of, leaf_start the marks, S / tile_sums the scan, rec_res->r.kept the total):
-// a fold is refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
+// for the count (none more at a growth but the one in front of freeing the old block).  A fold uses the builder's scratch: it is
+// refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
 namespace {
 
 int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m) {
@@ -923,7 +949,7 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
     e = hipMemcpyAsync(g.row_keys, m->row_keys, sizeof(unsigned long long) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) e = hipMemcpyAsync(g.xyz, m->xyz, sizeof(float) * 3 * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) {
-      const int blocks = static_cast<int>(std::min<int64_t>((m->rows + 255) / 256, (int64_t)ctx->n_cus * 8));
+      const int blocks = grid_256(ctx, m->rows);
       hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)m->rows, g.keys,
                          g.owner, g.slots);
       e = hipGetLastError();
@@ -983,22 +1009,9 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
   FrontScratch* fs = nullptr;
   RC_TRY(ensure_scratch(ctx, n, &fs));
   if (m->rows + n > m->cap) RC_TRY(map_grow(ctx, m, m->rows + n));
-  fe::ExportPose X;
-  std::memcpy(X.R, R, sizeof(X.R));
-  std::memcpy(X.t, t, sizeof(X.t));
-  uint32_t* slot_of = fs->idx[0];
-  uint32_t* mark = fs->P.leaf_start;
-  const int blocks = static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
-  hipLaunchKernelGGL(fe::map_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, m->voxel, m->keys, m->owner,
-                     m->slots, slot_of);
-  hipLaunchKernelGGL(fe::map_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)m->owner, (long)n, mark);
-  RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
-  HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
-  hipLaunchKernelGGL(fe::map_append, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, m->voxel, (const uint32_t*)mark,
-                     (const uint32_t*)fs->S, (const uint32_t*)slot_of, m->owner, (long)m->rows, m->xyz, m->row_keys);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count: the one synchronisation of a fold
-  const int64_t added = fs->h_rec_res->r.kept;
+  int64_t added = 0;
+  RC_TRY(voxel_fold(ctx, fs, c, export_pose(R, t), m->voxel, VoxelTable{m->keys, m->owner, m->slots}, true, m->xyz, m->rows, m->row_keys,
+                    &added));
   m->rows += added;
   *out_added = added;
   *out_rows = m->rows;

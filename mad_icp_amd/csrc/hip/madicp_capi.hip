@@ -270,6 +270,9 @@ namespace {
 
 void front_destroy(madicp_ctx* ctx);  // frontend_capi.inc.h
 
+// the grid of a one-lane-per-element, grid-stride kernel of 256 threads: eight workgroups per CU at the most
+int grid_256(const madicp_ctx* ctx, int64_t n) { return static_cast<int>(std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8)); }
+
 constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 
@@ -1530,8 +1533,7 @@ int madicp_nn_search_device_enqueue(madicp_ctx* ctx, int tree_id, const double* 
     hipLaunchKernelGGL(nn_descend_top, dim3((unsigned)blocks), dim3(1024), kTopLdsBytes, ctx->stream, it->second.desc, d_queries,
                        (long long)n, d_out_leaf_id, d_out_node, d_out_dist, d_out_depth);
   } else {
-    const long long blocks = std::min<long long>((n + 255) / 256, (long long)ctx->n_cus * 8);
-    hipLaunchKernelGGL(nn_descend, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, it->second.desc, d_queries,
+    hipLaunchKernelGGL(nn_descend, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->stream, it->second.desc, d_queries,
                        (long long)n, d_out_leaf_id, d_out_node, d_out_dist, d_out_depth);
   }
   HIP_TRY(hipGetLastError());

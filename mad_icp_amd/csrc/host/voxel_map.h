@@ -1,10 +1,11 @@
-// The host twin of the device voxel map (csrc/hip/frontend.hip.h: map_claim / map_mark / map_append / map_rehash): an append-only
+// The host twin of the device voxel map (csrc/hip/frontend.hip.h: voxel_claim / voxel_mark / voxel_rows / map_rehash): an append-only
 // set of float32 rows, one per voxel, the first point ever to fall into a voxel.  The per-point arithmetic is
 // csrc/common/export_point.h, shared with the device kernels and the export — the KEY comes from the fp64 position, never from the
 // float that is stored.  "Lowest index of the new points of a key" is the order of one sequential pass here, two integer atomics
 // behind a kernel boundary there: the map is a function of the sequence of (cloud, pose) alone either way.  Header-only, like
-// cloud_export.h: Pipeline (host front-end) and the C entry points madicp_host_map_* (voxel_map.cpp) use the one class.  Every
-// translation unit that includes this is compiled without floating-point contraction.
+// ingest_records.h: Pipeline (host front-end), the C entry points madicp_host_map_* (voxel_map.cpp) and the thinned export
+// (cloud_export.h: one fold into a temporary map) use the one class.  Every translation unit that includes this is compiled without
+// floating-point contraction.
 #pragma once
 #include <algorithm>
 #include <cstdint>

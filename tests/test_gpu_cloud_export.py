@@ -1,4 +1,4 @@
-"""Context.cloud_export_f32 (madicp_cloud_export_f32: fe::export_claim / export_mark / the tile scan / export_scatter) on uploaded
+"""Context.cloud_export_f32 (madicp_cloud_export_f32: fe::voxel_claim / voxel_mark / the tile scan / voxel_rows) on uploaded
 clouds against BOTH the numpy restatement of tests/cloud_export_ref.py and the host twin, bit for bit, over the input sets of the
 host test; the sizes cover the wavefront, the workgroup, the 1 024-mark scan tile and many workgroups racing on one table."""
 import ctypes as C

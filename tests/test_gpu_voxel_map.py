@@ -1,4 +1,4 @@
-"""Context.map_* (madicp_map_*: fe::map_claim / map_mark / the tile scan / map_append / map_rehash) on uploaded clouds against BOTH
+"""Context.map_* (madicp_map_*: fe::voxel_claim / voxel_mark / the tile scan / voxel_rows / map_rehash) on uploaded clouds against BOTH
 the numpy restatement of tests/voxel_map_ref.py and the host twin, bit for bit after every fold, over the sequences of the host
 test; the sizes cover the wavefront, the workgroup, the 1 024-mark scan tile and many workgroups racing on one persistent table."""
 import ctypes as C
@@ -253,3 +253,60 @@ def test_full_size_count(ctx, maps):
         assert 120000 < total == ctx.map_size(mid) < 360000
     finally:
         capi.host_map_destroy(twin)
+
+
+FOLD_SIZES = [1, 63, 64, 65, 257, 1025, 4097]
+FOLD_VOXELS = [1e-3, 0.1, 0.5, 50.0, 1e6]
+FOLD_POSES = {"identity": E.IDENTITY, "random": E.random_pose(11)}
+
+
+@pytest.mark.parametrize("n", FOLD_SIZES)
+def test_thinned_export_is_a_first_fold(ctx, n):
+    """cloud_export_f32 at voxel > 0: the bytes of a fresh map's first fold of the same cloud, downloaded"""
+    for name, pts in E.input_sets(n, 100 + n):
+        cid = ctx.cloud_upload(pts)
+        try:
+            for pose in sorted(FOLD_POSES):
+                R, t = FOLD_POSES[pose]
+                for voxel in FOLD_VOXELS:
+                    mid = ctx.map_create(voxel, n, 1 << 24)
+                    try:
+                        ctx.map_insert_cloud(mid, cid, R, t)
+                        want = ctx.map_download_f32(mid)
+                    finally:
+                        ctx.map_release(mid)
+                    assert ctx.cloud_export_f32(cid, R, t, voxel).tobytes() == want.tobytes(), (name, pose, voxel)
+        finally:
+            ctx.cloud_release(cid)
+
+
+def test_exports_between_folds_do_not_show(ctx, maps):
+    """fold A, export B (voxel 0.5 and 0), fold B, export A, fold C on a map that grows: the map equals a restatement that never saw
+    an export after every fold, every export its own — the shared scratch carries nothing from one call into the next, and an export
+    settles nothing in a live table"""
+    mid = maps(initial_rows=1)
+    ref = V.RefMap(V.VOXEL)
+    clouds = [(E.gaussian(4097, 500 + k, scale=5.0 + k), E.random_pose(70 + k)) for k in range(3)]
+    cids = [ctx.cloud_upload(pts) for pts, _ in clouds]
+
+    def fold_k(k):
+        pts, (R, t) = clouds[k]
+        added = ref.insert(pts, R, t)
+        assert ctx.map_insert_cloud(mid, cids[k], R, t) == (added, ref.size)
+        assert E.same_bits(ctx.map_download_f32(mid), ref.rows())
+
+    def export_k(k, voxel):
+        pts, (R, t) = clouds[k]
+        assert E.same_bits(ctx.cloud_export_f32(cids[k], R, t, voxel), E.export_f32(pts, R, t, voxel))
+
+    try:
+        fold_k(0)
+        export_k(1, 0.5)
+        export_k(1, 0.0)
+        fold_k(1)
+        export_k(0, 0.5)
+        fold_k(2)
+        assert ref.size > 4097
+    finally:
+        for cid in cids:
+            ctx.cloud_release(cid)

@@ -12,6 +12,9 @@ SIZES = [1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 5000]
 VOXELS = [0.0, 1e-3, 0.1, 0.5, 50.0, 1e6]
 POSES = {"identity": E.IDENTITY, "random": E.random_pose(11)}
 
+FOLD_SIZES = [1, 63, 64, 65, 257, 1025, 4097]
+FOLD_VOXELS = [1e-3, 0.1, 0.5, 50.0, 1e6]
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 
@@ -130,3 +133,36 @@ def test_refusals_leave_the_output_alone(natives):
     assert _raw(pts, 0, R, t, 0.5, out, 0, m) == 0 and m.value == 0
     far = np.full((3, 3), 1e30)
     assert _raw(far, 3, R, t, 0.5, out, 0, m) == 0 and m.value == 0
+
+
+def first_fold(points, R, t, voxel):
+    """a fresh host map's first fold of the cloud, downloaded"""
+    h = capi.host_map_create(voxel, max(points.shape[0], 1), 1 << 24)
+    try:
+        capi.host_map_insert(h, points, R, t)
+        return capi.host_map_download_f32(h)
+    finally:
+        capi.host_map_destroy(h)
+
+
+@pytest.mark.parametrize("n", FOLD_SIZES)
+def test_thinned_export_is_a_first_fold(natives, n):
+    """voxel > 0: the bytes of a fresh map's first fold of the same cloud, downloaded"""
+    for name, pts in E.input_sets(n, 100 + n):
+        for pose in sorted(POSES):
+            R, t = POSES[pose]
+            for voxel in FOLD_VOXELS:
+                got = capi.host_cloud_export_f32(pts, R, t, voxel)
+                assert got.tobytes() == first_fold(pts, R, t, voxel).tobytes(), (name, pose, voxel)
+
+
+def test_first_fold_capacity_leaves_the_output_alone(natives):
+    pts = E.gaussian(1025, 9)
+    R, t = E.random_pose(11)
+    need = first_fold(pts, R, t, 0.5).shape[0]
+    assert 1 < need < 1025
+    sentinel = np.float32(-77.5)
+    out = np.full((1025, 3), sentinel, np.float32)
+    m = C.c_int64(-7)
+    Rf = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+    assert _raw(pts, 1025, Rf, t, 0.5, out, need - 1, m) == -4 and m.value == need and (out == sentinel).all()
