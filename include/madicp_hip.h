@@ -267,7 +267,8 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
  * leaves them (it is not stable), and the device atan2 may differ from libm's in the last bit: the result is the
  * reference's up to the order of such ties.  out_chunks (n, optional): the time chunk of every point in walk order
  * (largest azimuth first) — synchronises when given.  A cloud that carries stamps (madicp_cloud_ingest_records) LOSES them
- * here: the points are sorted, the stamps would no longer line up. */
+ * here: the points are sorted, the stamps would no longer line up.  An attribute column (madicp_cloud_set_attr, below) is KEPT:
+ * it is re-ordered with the points. */
 int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6], double sensor_hz, int32_t* out_chunks);
 /* Motion compensation from PER-POINT TIMESTAMPS, for callers whose driver delivers them (a PointCloud2 `t` / `timestamp` /
  * `time` field): additive, the reference has no such path — its azimuth guess above fits a single 360-degree head that starts
@@ -372,6 +373,44 @@ int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sou
                                 const double* t_range /* NULL: min / max over all records; else {t_begin, t_end} */,
                                 int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source /* n_sources, optional */,
                                 double out_t_range[2] /* optional */);
+/* A PER-POINT ATTRIBUTE — every real record carries more than x y z t (intensity, reflectivity, ring, a label), and a consumer of
+ * the exported scan or of the map wants it on the points it gets back.  Additive and default off.  The attribute is ONE 32-bit word
+ * per point: the bytes of one named record field, little-endian, zero-extended to 32 bits.  Nothing converts, scales or interprets
+ * it: a FLOAT32 keeps its bits (NaN payloads and -0.0 included), an INT16 of -1 is the word 0x0000ffff.  It belongs to the point
+ * and travels with it: through the range filter and the compaction of the ingest, the merge of several sources, the re-ordering
+ * of madicp_cloud_deskew (the column is replaced by its gather in the sorted order — unlike the stamps it is NOT dropped; the
+ * stamped deskews keep input order and leave it alone), the voxel thinning of the export and the folds of a map.  A row's word is
+ * its OWNING point's, the lowest index of its voxel: nothing is averaged.
+ *   madicp_cloud_ingest_sources_attr  madicp_cloud_ingest_sources with `fields`, one per source: the cloud carries the column, filled
+ *                                     by the same launches.  fields == NULL: no attribute — that IS madicp_cloud_ingest_sources.
+ *                                     Further refusals (MADICP_ERR_INVALID, nothing staged): a field that does not lie inside
+ *                                     [0, point_step) or whose type is none of MADICP_A_INT8 .. MADICP_A_FLOAT32, sources with
+ *                                     AND without an attribute (type MADICP_A_NONE: all or none), differing types over the sources.
+ *   madicp_cloud_set_attr             gives ANY resident cloud (madicp_cloud_upload ...) a column, or its column new words; n = the
+ *                                     cloud's size.  Returns once `attr` has been staged.
+ *   madicp_cloud_attr                 the column, in the cloud's order; MADICP_ERR_INVALID when the cloud carries none.
+ *   madicp_cloud_export_f32_attr      madicp_cloud_export_f32 — the same rule, refusals and synchronisation count, the same rows —
+ *                                     with out_attr[r] the word of row r (capacity_rows words).  MADICP_ERR_INVALID, nothing
+ *                                     written, when the cloud carries no column.
+ * Bit-equal to madicp_host_ingest_sources_attr / madicp_host_cloud_export_f32_attr (madicp_host.h). */
+#define MADICP_A_NONE 0 /* attribute field types: sensor_msgs/PointField's own codes */
+#define MADICP_A_INT8 1
+#define MADICP_A_UINT8 2
+#define MADICP_A_INT16 3
+#define MADICP_A_UINT16 4
+#define MADICP_A_INT32 5
+#define MADICP_A_UINT32 6
+#define MADICP_A_FLOAT32 7
+typedef struct madicp_attr_field {
+  int32_t offset; /* byte offset of the field in the record, any alignment */
+  int32_t type;   /* MADICP_A_* */
+} madicp_attr_field;
+int madicp_cloud_ingest_sources_attr(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources,
+                                     const madicp_attr_field* fields /* n_sources, or NULL: no attribute */,
+                                     const double* t_range, int* out_cloud_id, int64_t* out_n,
+                                     int64_t* out_n_per_source /* n_sources, optional */, double out_t_range[2] /* optional */);
+int madicp_cloud_set_attr(madicp_ctx* ctx, int cloud_id, const uint32_t* attr, int64_t n);
+int madicp_cloud_attr(madicp_ctx* ctx, int cloud_id, uint32_t* out_attr, int64_t n);
 /* A RESIDENT CLOUD OUT — what a mapping, loop-closure or visualisation consumer wants of a registered scan: the points in
  * another frame (the map's), as float32, thinned to one point per voxel.  Additive.  The rule, everything in fp64 without
  * contraction (one source for the device and the host twin: mad_icp_amd/csrc/common/export_point.h):
@@ -392,6 +431,8 @@ int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sou
  * size always suffices).  Bit-equal to madicp_host_cloud_export_f32 (madicp_host.h). */
 int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
                             int64_t capacity_rows, int64_t* out_n);
+int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
+                                 uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
 /* THE VOXEL MAP — what a mapping consumer wants of a drive, not of one scan: registered scans accumulated on the device into an
  * append-only set of float32 rows, one per voxel, of which the consumer fetches only what was added since it last looked.
  * Additive.  Per point the export's rule above, everything in fp64 without contraction (one source:
@@ -405,6 +446,10 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
  *   madicp_map_create        initial_rows >= 1 sizes the first block (44 bytes per row: float row, key, two table slots); blocks
  *                            grow geometrically up to 1 <= max_rows <= 2^30.  MADICP_ERR_INVALID for a null argument, a voxel
  *                            that is not finite or not > 0, rows out of those ranges.
+ *   madicp_map_create_attr   the same map with a fifth column, the ATTRIBUTE word of every row (above: a per-point attribute): 48
+ *                            bytes per row of capacity instead of 44.  madicp_map_insert_cloud appends the owning point's word
+ *                            with its row, or the word 0 when the cloud carries no column; a growth moves the column with the
+ *                            rows.  The rows are those of a map of madicp_map_create on the same folds, bit for bit.
  *   madicp_map_insert_cloud  folds a resident cloud, which is only read: *out_added rows were appended, the map holds *out_rows.
  *                            MADICP_ERR_CAPACITY, map unchanged, when rows + n > max_rows (conservative on purpose: decided
  *                            before any launch), and while a look-ahead build is in flight (the fold's scratch is the builder's).
@@ -414,6 +459,8 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
  *   madicp_map_download_f32  rows [first_row, rows) into out_xyz, their number in *out_n; MADICP_ERR_CAPACITY when capacity_rows
  *                            is smaller: *out_n is the number needed and out_xyz is not written (the export's convention);
  *                            MADICP_ERR_INVALID for a null argument, an unknown id, a first_row outside [0, rows].
+ *   madicp_map_download_attr the words of rows [first_row, rows), madicp_map_download_f32's conventions; MADICP_ERR_INVALID as well
+ *                            on a map made without the column, out_attr not written.
  *   madicp_map_clear         forgets the rows, keeps the block.     madicp_map_release  frees everything.
  * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
@@ -421,6 +468,8 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
                             int64_t* out_rows);
 int madicp_map_size(madicp_ctx* ctx, int map_id, int64_t* out_rows);
 int madicp_map_download_f32(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_create_attr(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
+int madicp_map_download_attr(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

@@ -89,6 +89,14 @@ int madicp_host_ingest_records(const void* data, int64_t n_records, const madicp
  * written. */
 int madicp_host_ingest_sources(const madicp_record_source* sources, int n_sources, const double* t_range, double* out_xyz,
                                double* out_stamps01, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]);
+/* The host twin of madicp_cloud_ingest_sources_attr (madicp_hip.h: a per-point attribute — the same word per record from the same
+ * csrc/common/ingest_point.h: record_attr, bit-equal): madicp_host_ingest_sources with `fields`, one per source, and the survivors'
+ * words in out_attr (room for one per record of all sources; the first *out_n are written).  fields == NULL: no attribute,
+ * out_attr is not written and may be null — madicp_host_ingest_sources.  -1, nothing written, as well for what
+ * madicp_cloud_ingest_sources_attr refuses and for a null out_attr with fields that name an attribute. */
+int madicp_host_ingest_sources_attr(const madicp_record_source* sources, int n_sources, const madicp_attr_field* fields,
+                                    const double* t_range, double* out_xyz, double* out_stamps01, uint32_t* out_attr, int64_t* out_n,
+                                    int64_t* out_n_per_source, double out_t_range[2]);
 /* The host twin of madicp_cloud_export_f32 (madicp_hip.h: the same rule from the same per-point source
  * csrc/common/export_point.h, bit-equal): xyz (n, 3) float64, n >= 0, taken through (R row-major, t) and written as float32
  * rows, every point in cloud order (voxel == 0) or the lowest-index point of every voxel in ascending index order (voxel > 0);
@@ -98,6 +106,11 @@ int madicp_host_ingest_sources(const madicp_record_source* sources, int n_source
  * argument, n < 0 or > 2^30, a non-finite entry of R or t, a voxel that is negative or not finite. */
 int madicp_host_cloud_export_f32(const double* xyz, int64_t n, const double R[9], const double t[3], double voxel, float* out_xyz,
                                  int64_t capacity_rows, int64_t* out_n);
+/* ... and of madicp_cloud_export_f32_attr: attr (n words) is the cloud's attribute column, out_attr (capacity_rows words) gets the
+ * word of every row written — its owning point's.  The rows are madicp_host_cloud_export_f32's.  MADICP_ERR_INVALID as well for a
+ * null attr or out_attr; on MADICP_ERR_CAPACITY neither buffer is written. */
+int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, int64_t n, const double R[9], const double t[3],
+                                      double voxel, float* out_xyz, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
 /* The host twin of the device voxel map madicp_map_* (madicp_hip.h: the same rule from the same per-point source
  * csrc/common/export_point.h, bit-equal for every sequence of folds): an append-only set of float32 rows, the first point ever
  * to fall into each voxel; what a Pipeline with the host front-end runs for setMapAccumulation().
@@ -110,13 +123,22 @@ int madicp_host_cloud_export_f32(const double* xyz, int64_t n, const double R[9]
  *   _download_f32  rows [first_row, rows) into out_xyz, their number in *out_n; MADICP_ERR_CAPACITY when capacity_rows is smaller
  *                  — *out_n is the number needed, out_xyz is not written; MADICP_ERR_INVALID for a null argument or a first_row
  *                  outside [0, rows].
- *   _clear         forgets the rows, keeps the memory.   _destroy  frees everything (null: nothing). */
+ *   _clear         forgets the rows, keeps the memory.   _destroy  frees everything (null: nothing).
+ *   _create_attr   the same map with the attribute column (madicp_map_create_attr): every row has a 32-bit word, its owning point's.
+ *   _insert_attr   _insert with the cloud's column attr (n words; null: the cloud carries none, its rows get the word 0 — what
+ *                  _insert does on such a map).  On a map made without the column attr is ignored.
+ *   _download_attr the words of rows [first_row, rows), _download_f32's conventions; MADICP_ERR_INVALID on a map made without
+ *                  the column, out_attr not written. */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
                            int64_t* out_rows);
 int madicp_host_map_size(const madicp_host_map* map, int64_t* out_rows);
 int madicp_host_map_download_f32(const madicp_host_map* map, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_create_attr(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
+int madicp_host_map_insert_attr(madicp_host_map* map, const double* xyz, const uint32_t* attr, int64_t n, const double R[9],
+                                const double t[3], int64_t* out_added, int64_t* out_rows);
+int madicp_host_map_download_attr(const madicp_host_map* map, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

@@ -42,6 +42,11 @@ class RecordSourceC(C.Structure):
                 ("kitti_correction", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AttrFieldC(C.Structure):
+    """madicp_attr_field (include/madicp_hip.h)"""
+    _fields_ = [("offset", C.c_int32), ("type", C.c_int32)]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _u8p = C.POINTER(C.c_uint8)
@@ -157,6 +162,13 @@ def hip_lib():
                                                   C.c_int, _dp, _ip, _i64p, _dp]
         L.madicp_cloud_ingest_sources.argtypes = [C.c_void_p, C.POINTER(RecordSourceC), C.c_int, _dp, _ip, _i64p, _i64p, _dp]
         L.madicp_cloud_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64]
+        L.madicp_cloud_ingest_sources_attr.argtypes = [C.c_void_p, C.POINTER(RecordSourceC), C.c_int, C.POINTER(AttrFieldC), _dp, _ip, _i64p,
+                                                       _i64p, _dp]
+        L.madicp_cloud_set_attr.argtypes = [C.c_void_p, C.c_int, _u32p, C.c_int64]
+        L.madicp_cloud_attr.argtypes = [C.c_void_p, C.c_int, _u32p, C.c_int64]
+        L.madicp_cloud_export_f32_attr.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
+        L.madicp_map_create_attr.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, _ip]
+        L.madicp_map_download_attr.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u32p, C.c_int64, _i64p]
         L.madicp_cloud_export_f32.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_map_create.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, _ip]
         L.madicp_map_insert_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _i64p, _i64p]
@@ -220,6 +232,13 @@ def host_lib():
         L.madicp_host_map_size.argtypes = [C.c_void_p, _i64p]
         L.madicp_host_map_download_f32.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_host_map_clear.argtypes = [C.c_void_p]
+        L.madicp_host_ingest_sources_attr.argtypes = [C.POINTER(RecordSourceC), C.c_int, C.POINTER(AttrFieldC), _dp, _dp, _dp, _u32p, _i64p,
+                                                      _i64p, _dp]
+        L.madicp_host_cloud_export_f32_attr.argtypes = [_dp, _u32p, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), _u32p, C.c_int64,
+                                                        _i64p]
+        L.madicp_host_map_create_attr.argtypes = [C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+        L.madicp_host_map_insert_attr.argtypes = [C.c_void_p, _dp, _u32p, C.c_int64, _dp, _dp, _i64p, _i64p]
+        L.madicp_host_map_download_attr.argtypes = [C.c_void_p, C.c_int64, _u32p, C.c_int64, _i64p]
         L.madicp_host_map_destroy.restype = None
         L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
@@ -485,6 +504,64 @@ def host_ingest_sources(sources, t_range=None):
     return xyz[:k].copy(), (st[:k].copy() if timed else None), (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]]
 
 
+def _attr_fields(sources):
+    """The AttrFieldC array of a sources call, or None when no source names an attribute.  A Source's `attribute` is a field name
+    or an (offset, type code) pair (mad_icp_amd.records.resolve_attribute); a source WITHOUT one among sources with one travels as
+    type 0, so that the native refusal ("an attribute in every source or in none") is what the caller meets.  Like _sources_args
+    nothing else is validated here."""
+    from mad_icp_amd import records as _records
+
+    if not any(getattr(s, "attribute", None) is not None for s in sources):
+        return None
+    arr = (AttrFieldC * len(sources))()
+    for k, src in enumerate(sources):
+        if src.attribute is None:
+            arr[k].offset, arr[k].type = 0, 0
+        elif isinstance(src.attribute, str):
+            arr[k].offset, arr[k].type = _records.resolve_attribute(src.records, src.attribute)[:2]
+        else:
+            arr[k].offset, arr[k].type = (int(v) for v in src.attribute)
+    return arr
+
+
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+
+
+def host_ingest_sources_attr(sources, t_range=None):
+    """madicp_host_ingest_sources_attr: the host twin of Context.cloud_ingest_sources_attr.  Returns (points, stamps or None,
+    (t0, t1), survivors per source, words (kept,) uint32 or None when no source names an attribute)."""
+    alive, arr, total, timed, tr = _sources_args(sources, t_range)
+    fields = _attr_fields(sources)
+    xyz, st, words = np.empty((max(total, 1), 3)), np.empty(max(total, 1)), np.empty(max(total, 1), np.uint32)
+    kept, rng, per = C.c_int64(0), np.empty(2), np.zeros(max(len(sources), 1), np.int64)
+    rc = host_lib().madicp_host_ingest_sources_attr(arr, len(sources), fields, tr.ctypes.data_as(_dp) if tr is not None else None,
+                                                    xyz.ctypes.data_as(_dp), st.ctypes.data_as(_dp), words.ctypes.data_as(_u32p),
+                                                    C.byref(kept), per.ctypes.data_as(_i64p), rng.ctypes.data_as(_dp))
+    if rc != 0:
+        raise MadIcpError("madicp_host_ingest_sources_attr: bad arguments")
+    k = kept.value
+    return (xyz[:k].copy(), (st[:k].copy() if timed else None), (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]],
+            (words[:k].copy() if fields is not None else None))
+
+
+def host_cloud_export_f32_attr(xyz, attr, R, t, voxel):
+    """madicp_host_cloud_export_f32_attr: host_cloud_export_f32 with the cloud's attribute column (n words).  Returns ((M, 3)
+    float32 rows, (M,) uint32 words)."""
+    a, w = _f64(xyz).reshape(-1, 3), _u32(attr)
+    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+    n = a.shape[0]
+    if w.shape[0] != n:
+        raise ValueError("one attribute word per point")
+    out, ow, m = np.empty((max(n, 1), 3), np.float32), np.empty(max(n, 1), np.uint32), C.c_int64(0)
+    rc = host_lib().madicp_host_cloud_export_f32_attr(a.ctypes.data_as(_dp), w.ctypes.data_as(_u32p), n, Rm.ctypes.data_as(_dp),
+                                                      tv.ctypes.data_as(_dp), float(voxel), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      ow.ctypes.data_as(_u32p), n, C.byref(m))
+    if rc != 0:
+        raise MadIcpError("madicp_host_cloud_export_f32_attr: error %d (bad arguments)" % rc)
+    return out[:m.value].copy(), ow[:m.value].copy()
+
+
 def host_cloud_export_f32(xyz, R, t, voxel):
     """madicp_host_cloud_export_f32: the host twin of Context.cloud_export_f32.  xyz (n, 3) float64 through (R (3, 3), t (3,)) as
     float32 rows: every point (voxel = 0) or the lowest-index point of every voxel.  Returns (M, 3) float32."""
@@ -510,6 +587,37 @@ def host_map_create(voxel, initial_rows, max_rows):
     h = C.c_void_p()
     _host_map_check(host_lib().madicp_host_map_create(float(voxel), int(initial_rows), int(max_rows), C.byref(h)), "madicp_host_map_create")
     return h
+
+
+def host_map_create_attr(voxel, initial_rows, max_rows):
+    """madicp_host_map_create_attr: a host map with the attribute column (the twin of Context.map_create_attr)."""
+    h = C.c_void_p()
+    _host_map_check(host_lib().madicp_host_map_create_attr(float(voxel), int(initial_rows), int(max_rows), C.byref(h)),
+                    "madicp_host_map_create_attr")
+    return h
+
+
+def host_map_insert_attr(h, xyz, attr, R, t):
+    """host_map_insert with the cloud's attribute column (n words, or None: the cloud carries none)."""
+    a = _f64(xyz).reshape(-1, 3)
+    w = None if attr is None else _u32(attr)
+    if w is not None and w.shape[0] != a.shape[0]:
+        raise ValueError("one attribute word per point")
+    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+    added, rows = C.c_int64(0), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_insert_attr(h, a.ctypes.data_as(_dp), w.ctypes.data_as(_u32p) if w is not None else None,
+                                                           a.shape[0], Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), C.byref(added),
+                                                           C.byref(rows)), "madicp_host_map_insert_attr")
+    return added.value, rows.value
+
+
+def host_map_download_attr(h, first_row=0):
+    """The attribute words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_download_attr(h, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)),
+                    "madicp_host_map_download_attr")
+    return out[:got.value].copy()
 
 
 def host_map_insert(h, xyz, R, t):
@@ -692,6 +800,50 @@ class Context:
         _check(hip_lib().madicp_cloud_ingest_sources(self._h, arr, len(sources), tr.ctypes.data_as(_dp) if tr is not None else None,
                                                      C.byref(cid), C.byref(kept), per.ctypes.data_as(_i64p), rng.ctypes.data_as(_dp)))
         return cid.value, kept.value, (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]]
+
+    def cloud_ingest_sources_attr(self, sources, t_range=None):
+        """cloud_ingest_sources for Sources that name an `attribute` (see _attr_fields): the cloud carries the attribute column
+        as well.  Returns what cloud_ingest_sources returns."""
+        alive, arr, _, _, tr = _sources_args(sources, t_range)
+        fields = _attr_fields(sources)
+        cid, kept, rng, per = C.c_int(0), C.c_int64(0), np.empty(2), np.zeros(max(len(sources), 1), np.int64)
+        _check(hip_lib().madicp_cloud_ingest_sources_attr(self._h, arr, len(sources), fields, tr.ctypes.data_as(_dp) if tr is not None else None,
+                                                          C.byref(cid), C.byref(kept), per.ctypes.data_as(_i64p), rng.ctypes.data_as(_dp)))
+        return cid.value, kept.value, (float(rng[0]), float(rng[1])), [int(v) for v in per[:len(sources)]]
+
+    def cloud_set_attr(self, cid, attr):
+        """Gives a resident cloud an attribute column (one uint32 word per point), or its column new words."""
+        w = _u32(attr)
+        _check(hip_lib().madicp_cloud_set_attr(self._h, cid, w.ctypes.data_as(_u32p), w.shape[0]))
+
+    def cloud_attr(self, cid):
+        """The attribute column a cloud carries, (n,) uint32 in the cloud's order; MadIcpError when it has none."""
+        n = self.cloud_size(cid)
+        out = np.empty(n, np.uint32)
+        _check(hip_lib().madicp_cloud_attr(self._h, cid, out.ctypes.data_as(_u32p), n))
+        return out
+
+    def cloud_export_f32_attr(self, cid, R, t, voxel):
+        """cloud_export_f32 with the rows' attribute words.  Returns ((M, 3) float32, (M,) uint32)."""
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        n = self.cloud_size(cid)
+        out, ow, m = np.empty((max(n, 1), 3), np.float32), np.empty(max(n, 1), np.uint32), C.c_int64(0)
+        _check(hip_lib().madicp_cloud_export_f32_attr(self._h, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), float(voxel),
+                                                      out.ctypes.data_as(C.POINTER(C.c_float)), ow.ctypes.data_as(_u32p), n, C.byref(m)))
+        return out[:m.value].copy(), ow[:m.value].copy()
+
+    def map_create_attr(self, voxel, initial_rows, max_rows):
+        """map_create with the attribute column: every row keeps its owning point's word (0 for clouds that carry none)."""
+        mid = C.c_int(0)
+        _check(hip_lib().madicp_map_create_attr(self._h, float(voxel), int(initial_rows), int(max_rows), C.byref(mid)))
+        return mid.value
+
+    def map_download_attr(self, mid, first_row=0):
+        """The attribute words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
+        _check(hip_lib().madicp_map_download_attr(self._h, mid, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)))
+        return out[:got.value].copy()
 
     def cloud_stamps(self, cid):
         """The stamps a cloud of cloud_ingest_records carries, (n,) float64 in the cloud's order; MadIcpError when it has none."""

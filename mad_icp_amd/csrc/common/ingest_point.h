@@ -94,6 +94,27 @@ MADICP_HD inline double record_time(const unsigned char* p, int t_type) {
 }
 MADICP_HD inline bool time_is_finite(double t) { return t - t == 0.0; }  // (inf - inf and NaN - NaN are NaN)
 
+// ---- the attribute: ONE more field of the record (intensity, reflectivity, ring, a label ...) carried beside the point as a 32-bit
+// word — the field's bytes, little-endian, zero-extended.  Nothing converts, scales or interprets it: an INT16 of -1 is the word
+// 0x0000ffff, a FLOAT32 keeps its bits (NaN payloads and -0.0 included).  Types are sensor_msgs/PointField's codes (MADICP_A_*).
+constexpr int kAttrNone = 0, kAttrI8 = 1, kAttrU8 = 2, kAttrI16 = 3, kAttrU16 = 4, kAttrI32 = 5, kAttrU32 = 6, kAttrF32 = 7;
+struct AttrField {  // madicp_attr_field
+  int32_t off, type;
+};
+MADICP_HD inline int attr_width(int type) { return type <= kAttrU8 ? 1 : (type <= kAttrU16 ? 2 : 4); }
+MADICP_HD inline uint32_t record_attr(const unsigned char* p, int type) {
+  uint32_t w = 0;
+  if (type <= kAttrU8) __builtin_memcpy(&w, p, 1);
+  else if (type <= kAttrU16) __builtin_memcpy(&w, p, 2);
+  else __builtin_memcpy(&w, p, 4);
+  return w;
+}
+// the field lies inside the record and its type is known
+inline bool attr_field_ok(const RecordLayout& L, const AttrField& A) {
+  if (A.type < kAttrI8 || A.type > kAttrF32) return false;
+  return A.off >= 0 && A.off <= L.step - attr_width(A.type);
+}
+
 // the stamp of a record, normalised over [t0, t1]: NaN unless the span is positive (all times equal, or no finite time at all);
 // +-inf and values outside [0, 1] are left as IEEE produces them — stamp_chunk() clamps them
 MADICP_HD inline double record_stamp(double t64, double t0, double t1) {
@@ -143,6 +164,7 @@ struct RecordSource {           // madicp_record_source with its layout as a Rec
   double min_range, max_range;
   double t_scale, t_offset;
   int32_t kitti;
+  AttrField A;  // the attribute field; type kAttrNone (what value-initialisation leaves): none is carried
 };
 // (from the C ABI's madicp_record_source: a template, so that this header needs none of the C headers)
 template <class CSource>
@@ -158,6 +180,7 @@ inline RecordSource record_source_of(const CSource& c) {
   S.t_scale = c.t_scale;
   S.t_offset = c.t_offset;
   S.kitti = c.kitti_correction;
+  S.A = AttrField{0, kAttrNone};  // (the C struct has none: madicp_cloud_ingest_sources_attr passes the fields beside the sources)
   return S;
 }
 // (and back)
@@ -180,7 +203,8 @@ inline CSource record_source_to(const RecordSource& S) {
 // skipped), t_scale 1 and t_offset 0 (source_clock takes the time as it is).  The single-source ingests of every layer
 // (madicp_cloud_ingest_records, ingest_records, Pipeline::computeRecordsStamped) are the sources ingest of this one source.
 inline RecordSource plain_source(const void* data, int64_t n, const RecordLayout& L, double min_range, double max_range, bool kitti) {
-  return RecordSource{data, n, L, {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, 0.0}, min_range, max_range, 1.0, 0.0, kitti ? 1 : 0};
+  return RecordSource{data, n, L, {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, 0.0}, min_range, max_range, 1.0, 0.0, kitti ? 1 : 0,
+                      AttrField{0, kAttrNone}};
 }
 
 // what every layer refuses before it touches a record (null = nothing to refuse): the device entry, the host twin and Pipeline
@@ -201,6 +225,9 @@ inline const char* record_sources_refusal(const RecordSource* src, int n_sources
       if (!time_is_finite(v)) return "R and t: finite entries";
     if (!time_is_finite(S.t_scale) || !(S.t_scale > 0.0) || !time_is_finite(S.t_offset)) return "t_scale finite and > 0, t_offset finite";
     if ((S.L.t_type != kTimeNone) != (src[0].L.t_type != kTimeNone)) return "a time field in every source or in none";
+    if (S.A.type != kAttrNone && !attr_field_ok(S.L, S.A)) return "attribute field: inside the record, type one of MADICP_A_*";
+    if ((S.A.type != kAttrNone) != (src[0].A.type != kAttrNone)) return "an attribute in every source or in none";
+    if (S.A.type != src[0].A.type) return "the same attribute type in every source";
   }
   if (total > 0x40000000) return "every source holds at least one record, all of them together at most 2^30";
   if (t_range && !(time_is_finite(t_range[0]) && time_is_finite(t_range[1]) && t_range[1] > t_range[0]))

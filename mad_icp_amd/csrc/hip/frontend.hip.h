@@ -166,6 +166,7 @@ struct SourceEntry {
   long first_rec;   // global index of its first record: the base into keep[] / pos[]
   long n;           // records
   madicp_host::RecordLayout L;
+  madicp_host::AttrField A;  // read by sources_scatter only, and only where it is given an attribute column
   int32_t per_tile, flags;
   double min_range, max_range;
   double t_scale, t_offset;
@@ -241,11 +242,13 @@ __global__ __launch_bounds__(64) void sources_counts(SourceTable T, const uint32
 
 // scatter pass: the same staging; the survivors' points (madicp_host::ingest_point, the arithmetic of ingest_scatter) taken to
 // the base frame and their stamps normalised on the common clock (madicp_host::record_stamp over the range records_range left in
-// device memory) to the survivor's position, input order kept.  stamps == nullptr: sources without a time field.
+// device memory) to the survivor's position, input order kept.  stamps == nullptr: sources without a time field.  attr == nullptr
+// (a kernel argument: the branch is wave-uniform): no attribute is carried; else the survivor's word (madicp_host::record_attr of
+// the source's field, from the tile already staged in LDS) goes to the survivor's position too.
 __global__ __launch_bounds__(256) void sources_scatter(const unsigned char* __restrict__ rec, SourceTable T, const uint32_t* __restrict__ keep,
                                                        const uint32_t* __restrict__ pos, double sin_a, double cos_a,
                                                        const RecordsResult* __restrict__ res, double* __restrict__ out,
-                                                       double* __restrict__ stamps) {
+                                                       double* __restrict__ stamps, uint32_t* __restrict__ attr) {
   __shared__ __attribute__((aligned(16))) uint32_t s_tile[kRecTileDwords];
   const unsigned char* s_bytes = reinterpret_cast<const unsigned char*>(s_tile);
   const double t0 = res->t0, t1 = res->t1;
@@ -270,6 +273,7 @@ __global__ __launch_bounds__(256) void sources_scatter(const unsigned char* __re
                                                     E.t_offset);
         stamps[d] = madicp_host::record_stamp(tc, t0, t1);
       }
+      if (attr) attr[d] = madicp_host::record_attr(p + E.A.off, E.A.type);
     }
     __syncthreads();
   }
@@ -390,6 +394,11 @@ __global__ __launch_bounds__(256) void deskew_apply(const double* __restrict__ x
     if (chunk_of) chunk_of[d] = kd;
   }
 }
+// the attribute column of a cloud that deskew_apply re-orders, taken along: deskew_apply leaves point idx_sorted[j] at position j
+__global__ __launch_bounds__(256) void attr_gather(const uint32_t* __restrict__ attr_in, const uint32_t* __restrict__ idx_sorted, long n,
+                                                   uint32_t* __restrict__ attr_out) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n; j += (long)gridDim.x * blockDim.x) attr_out[j] = attr_in[idx_sorted[j]];
+}
 
 // ---- deskew from per-point timestamps ---------------------------------------------------------------------------------
 // For sensors whose driver delivers the acquisition time of every point (a PointCloud2 `t` / `timestamp` / `time` field,
@@ -507,10 +516,13 @@ __global__ __launch_bounds__(256) void voxel_mark(const uint32_t* __restrict__ s
 }
 // Null arguments (kernel arguments: the branches are wave-uniform) switch parts off.  mark / pos: every point, at row first_row + i.
 // row_keys: no key is stored, and none is recomputed (three fp64 divisions per row).  owner / slot_of: nothing settles.
+// row_attr: no attribute column beside the rows; else every row written gets its owning point's word, or 0 where the cloud carries
+// none (attr == nullptr).
 __global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
                                                   const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
                                                   const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner, long first_row,
-                                                  float* __restrict__ rows, unsigned long long* __restrict__ row_keys) {
+                                                  float* __restrict__ rows, unsigned long long* __restrict__ row_keys,
+                                                  const uint32_t* __restrict__ attr, uint32_t* __restrict__ row_attr) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     if (mark && !mark[i]) continue;
     const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
@@ -521,6 +533,7 @@ __global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz
     rows[3 * d + 1] = madicp_host::export_value(q[1]);
     rows[3 * d + 2] = madicp_host::export_value(q[2]);
     if (row_keys) row_keys[d] = madicp_host::export_key(q, voxel);
+    if (row_attr) row_attr[d] = attr ? attr[i] : 0u;
     if (owner) owner[slot_of[i]] = kMapSettled;  // (one marked point per slot: nobody else writes it in this kernel)
   }
 }

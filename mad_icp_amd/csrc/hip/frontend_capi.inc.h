@@ -13,6 +13,7 @@ namespace {
 struct DevCloud {
   double* xyz = nullptr;  // (n,3)
   double* stamps = nullptr;  // (n) normalised acquisition times, the cloud's order: clouds of madicp_cloud_ingest_records only (pooled)
+  uint32_t* attr = nullptr;  // (n) one 32-bit attribute word per point, the cloud's order: madicp_cloud_ingest_sources_attr / _set_attr (pooled)
   int64_t n = 0;
   hipEvent_t ready = nullptr;  // recorded on the copy stream behind whatever produced xyz
 };
@@ -26,6 +27,8 @@ struct DevMap {
   uint32_t* owner = nullptr;               // (slots) fe::kMapNever / kMapSettled / contended
   unsigned long long* row_keys = nullptr;  // (cap) the key of every row
   float* xyz = nullptr;                    // (cap, 3)
+  uint32_t* attr = nullptr;                // (cap) the rows' attribute words: maps of madicp_map_create_attr only
+  bool with_attr = false;
   uint32_t slots = 0;
 };
 
@@ -233,6 +236,7 @@ int drop_cloud(madicp_ctx* ctx, DevCloud& c, int rc) {
   if (fence_event(ctx, &after) != MADICP_OK) after = nullptr;
   pool_free(ctx, c.xyz, after);
   pool_free(ctx, c.stamps, after);
+  pool_free(ctx, c.attr, after);
   if (c.ready) hipEventDestroy(c.ready);
   c = DevCloud{};
   return rc;
@@ -403,6 +407,8 @@ int stage_records(madicp_ctx* ctx, const void* data, int64_t n_records, size_t b
 // pinned staging and ONE host-to-device copy into buf[0] of the scratch, each at a 64-byte aligned offset (a tile then starts
 // 16-byte aligned whatever the steps in front of it), the gaps zeroed: the last tile of a source loads up to 3 bytes past its
 // records.  Mark, scan, range, one copy of the result block, one synchronisation, scatter — whatever the number of sources.
+// Sources that name an attribute field (RecordSource::A, all of them or none) give the cloud its attribute column, allocated from
+// the pool beside the stamps and filled by the same scatter: no further launch.
 int ingest_sources_on(madicp_ctx* ctx, const madicp_host::RecordSource* src, int n_sources, const double* t_range, int* out_cloud_id,
                       int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]) {
   // the table of the sources: where each one's bytes, tiles and records begin
@@ -418,6 +424,7 @@ int ingest_sources_on(madicp_ctx* ctx, const madicp_host::RecordSource* src, int
     E.first_rec = T.n_total;
     E.n = (long)src[s].n;
     E.L = src[s].L;
+    E.A = src[s].A;
     E.per_tile = fe::records_per_tile(E.L.step);
     E.flags = (src[s].kitti ? fe::kSrcKitti : 0) | (madicp_host::source_extrinsic_is_identity(src[s].R, src[s].t) ? fe::kSrcIdentity : 0) |
               (madicp_host::source_clock_as_is(src[s].t_scale, src[s].t_offset) ? fe::kSrcClockAsIs : 0);
@@ -478,9 +485,15 @@ int ingest_sources_on(madicp_ctx* ctx, const madicp_host::RecordSource* src, int
     if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
     c.stamps = static_cast<double*>(p);
   }
+  if (src[0].A.type != madicp_host::kAttrNone) {
+    void* p = nullptr;
+    const int rc = pool_alloc(ctx, sizeof(uint32_t) * (size_t)kept, ctx->copy, &p);
+    if (rc != MADICP_OK) return drop_cloud(ctx, c, rc);
+    c.attr = static_cast<uint32_t*>(p);
+  }
   const double angle = madicp_host::ingest_kitti_angle();  // libm sin / cos like Eigen::AngleAxisd
   hipLaunchKernelGGL(fe::sources_scatter, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, (const uint32_t*)keep, (const uint32_t*)fs->S,
-                     std::sin(angle), std::cos(angle), (const fe::RecordsResult*)&fs->rec_res->r, c.xyz, c.stamps);
+                     std::sin(angle), std::cos(angle), (const fe::RecordsResult*)&fs->rec_res->r, c.xyz, c.stamps, c.attr);
   CLOUD_TRY(hipGetLastError());
   CLOUD_TRY(hipEventRecord(c.ready, ctx->copy));
   *out_n = kept;
@@ -521,6 +534,7 @@ int madicp_cloud_release(madicp_ctx* ctx, int cloud_id) {
   RC_TRY(fence_event(ctx, &after));
   pool_free(ctx, c->xyz, after);
   pool_free(ctx, c->stamps, after);
+  pool_free(ctx, c->attr, after);
   if (c->ready) hipEventDestroy(c->ready);
   ctx->front->clouds.erase(cloud_id);
   return MADICP_OK;
@@ -589,15 +603,58 @@ int madicp_cloud_ingest_records(madicp_ctx* ctx, const void* data, int64_t n_rec
   return ingest_sources_on(ctx, &src, 1, t_range, out_cloud_id, out_n, nullptr, out_t_range);
 }
 
-// Several sources' byte records -> one cloud (include/madicp_hip.h): the refusals, then the chain above.
-int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources, const double* t_range,
-                                int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]) {
+// Several sources' byte records -> one cloud (include/madicp_hip.h): the refusals, then the chain above.  `fields`: one attribute
+// field per source, or null — no attribute is carried.
+int madicp_cloud_ingest_sources_attr(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources, const madicp_attr_field* fields,
+                                     const double* t_range, int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source,
+                                     double out_t_range[2]) {
   if (!ctx || !sources || !out_cloud_id || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
   if (n_sources < 1 || n_sources > MADICP_MAX_SOURCES) return fail(MADICP_ERR_INVALID, "1 .. 8 sources");
   madicp_host::RecordSource src[MADICP_MAX_SOURCES];
-  for (int s = 0; s < n_sources; ++s) src[s] = madicp_host::record_source_of(sources[s]);
+  for (int s = 0; s < n_sources; ++s) {
+    src[s] = madicp_host::record_source_of(sources[s]);
+    if (fields) src[s].A = madicp_host::AttrField{fields[s].offset, fields[s].type};
+  }
   if (const char* why = madicp_host::record_sources_refusal(src, n_sources, t_range)) return fail(MADICP_ERR_INVALID, why);
   return ingest_sources_on(ctx, src, n_sources, t_range, out_cloud_id, out_n, out_n_per_source, out_t_range);
+}
+int madicp_cloud_ingest_sources(madicp_ctx* ctx, const madicp_record_source* sources, int n_sources, const double* t_range,
+                                int* out_cloud_id, int64_t* out_n, int64_t* out_n_per_source, double out_t_range[2]) {
+  return madicp_cloud_ingest_sources_attr(ctx, sources, n_sources, nullptr, t_range, out_cloud_id, out_n, out_n_per_source, out_t_range);
+}
+
+// a resident cloud gets an attribute column (or its column new words): through the pinned staging, on the copy stream
+int madicp_cloud_set_attr(madicp_ctx* ctx, int cloud_id, const uint32_t* attr, int64_t n) {
+  if (!ctx || !attr) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (n != c->n) return fail(MADICP_ERR_INVALID, "n mismatch: one word per point of the cloud");
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(uint32_t) * (size_t)n;
+  if (!c->attr) {
+    void* p = nullptr;
+    RC_TRY(pool_alloc(ctx, bytes, ctx->copy, &p));
+    c->attr = static_cast<uint32_t*>(p);
+  }
+  int hb = 0;
+  char* stage = nullptr;
+  RC_TRY(ctx->staging.acquire(bytes, &hb, &stage));
+  std::memcpy(stage, attr, bytes);
+  HIP_TRY(hipMemcpyAsync(c->attr, stage, bytes, hipMemcpyHostToDevice, ctx->copy));
+  HIP_TRY(ctx->staging.sent(hb, ctx->copy));
+  return MADICP_OK;
+}
+
+int madicp_cloud_attr(madicp_ctx* ctx, int cloud_id, uint32_t* out_attr, int64_t n) {
+  if (!ctx || !out_attr) return fail(MADICP_ERR_INVALID, "null argument");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (!c->attr) return fail(MADICP_ERR_INVALID, "the cloud carries no attribute");
+  if (n != c->n) return fail(MADICP_ERR_INVALID, "n mismatch");
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out_attr, c->attr, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
 }
 
 }  // extern "C"
@@ -684,13 +741,25 @@ int send_deskew_table(madicp_ctx* ctx, FrontScratch* fs, const double velocity[6
 
 // The compensated cloud replaces the input: `launch(fresh)` enqueues the kernel that writes the points into a fresh buffer, the
 // old one goes back to the pool behind it — with the cloud's stamps (`drop_stamps`) where the new order no longer lines up
-// with them.  `out_chunks` (debugging / parity aid): the time chunk of every point, which the kernel left in `d_chunks`.
+// with them.  The attribute column is never dropped: a `reorders` launch gets a fresh column as well, which it fills with the
+// words in the new order and which replaces the old one together with the points (null when the cloud carries none); a launch
+// that keeps the input order leaves the column alone.  `out_chunks` (debugging / parity aid): the time chunk of every point,
+// which the kernel left in `d_chunks`.
 template <class Launch>
-int replace_points(madicp_ctx* ctx, DevCloud* c, const char* what, bool drop_stamps, int32_t* out_chunks, const int32_t* d_chunks,
+int replace_points(madicp_ctx* ctx, DevCloud* c, const char* what, bool reorders, int32_t* out_chunks, const int32_t* d_chunks,
                    Launch launch) {
+  const bool drop_stamps = reorders;
   void* fresh = nullptr;
   RC_TRY(pool_alloc(ctx, sizeof(double) * 3 * (size_t)c->n, ctx->copy, &fresh));
-  launch(static_cast<double*>(fresh));
+  void* fresh_attr = nullptr;
+  if (reorders && c->attr) {
+    const int rc = pool_alloc(ctx, sizeof(uint32_t) * (size_t)c->n, ctx->copy, &fresh_attr);
+    if (rc != MADICP_OK) {
+      pool_free(ctx, fresh, nullptr);
+      return rc;
+    }
+  }
+  launch(static_cast<double*>(fresh), static_cast<uint32_t*>(fresh_attr));
   EventRef after;
   {  // a failure from here on must not leak the fresh buffer: the cloud keeps its old points
     const hipError_t le = hipGetLastError();
@@ -698,6 +767,7 @@ int replace_points(madicp_ctx* ctx, DevCloud* c, const char* what, bool drop_sta
     if (le != hipSuccess || frc != MADICP_OK) {
       hipStreamSynchronize(ctx->copy);
       pool_free(ctx, fresh, nullptr);
+      pool_free(ctx, fresh_attr, nullptr);
       return le != hipSuccess ? fail(MADICP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(le)) : frc;
     }
   }
@@ -706,6 +776,10 @@ int replace_points(madicp_ctx* ctx, DevCloud* c, const char* what, bool drop_sta
   if (drop_stamps) {
     pool_free(ctx, c->stamps, after);
     c->stamps = nullptr;
+  }
+  if (fresh_attr) {
+    pool_free(ctx, c->attr, after);
+    c->attr = static_cast<uint32_t*>(fresh_attr);
   }
   HIP_TRY(hipEventRecord(c->ready, ctx->copy));
   if (out_chunks) {
@@ -742,10 +816,13 @@ int madicp_cloud_deskew(madicp_ctx* ctx, int cloud_id, const double velocity[6],
   // (the points end up in azimuth order — the chunks, when asked for, in walk order, largest azimuth first — and stamps in
   // input order would no longer line up)
   int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;
-  return replace_points(ctx, c, "deskew", true, out_chunks, d_chunks, [&](double* fresh) {
+  return replace_points(ctx, c, "deskew", true, out_chunks, d_chunks, [&](double* fresh, uint32_t* fresh_attr) {
     hipLaunchKernelGGL(fe::deskew_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const double*)c->xyz, (const uint32_t*)fs->idx[1], (long)n,
                        (const int32_t*)fs->g, (const int32_t*)fs->tile_min, (const double*)(fs->table + kDeskewTableMax), n_poses, fresh,
                        d_chunks);
+    if (fresh_attr)  // (the sorted index is still in the scratch)
+      hipLaunchKernelGGL(fe::attr_gather, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)c->attr, (const uint32_t*)fs->idx[1], (long)n,
+                         fresh_attr);
   });
 }
 
@@ -762,7 +839,7 @@ int deskew_stamped_on(madicp_ctx* ctx, DevCloud* c, FrontScratch* fs, const doub
   const double* d_poses = fs->table + kDeskewTableMax;
   int32_t* d_chunks = out_chunks ? reinterpret_cast<int32_t*>(fs->P.small[0]) : nullptr;  // (input order)
   const int blocks = grid_256(ctx, n);
-  return replace_points(ctx, c, "deskew_stamped", false, out_chunks, d_chunks, [&](double* fresh) {
+  return replace_points(ctx, c, "deskew_stamped", false, out_chunks, d_chunks, [&](double* fresh, uint32_t*) {
     hipLaunchKernelGGL(fe::deskew_stamped, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, d_stamps, (long)n, d_poses, fresh,
                        d_chunks);
   });
@@ -785,12 +862,13 @@ struct VoxelTable {
 // One fold of a resident cloud (n >= 1 points) through X into table T, on the copy stream: fe::voxel_claim, fe::voxel_mark, the
 // tile scan, fe::voxel_rows — the lowest-index point of every voxel T has not settled yet, as float rows from `first_row` of `rows`
 // on, in input order.  row_keys: where the rows' keys go, or null; settle: whether the rows' slots settle (a table that lives on).
+// row_attr: where the rows' attribute words go (the owning point's, 0 where the cloud carries no column), or null.
 // The caller keeps T at most half full.  The per-fold scratch lives in idle parts of the builder's scratch, which the caller owns
 // (busy_with_lookahead, ensure_scratch for n) and which does not grow:
 //   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->r.kept  the scan's total
 // The rows are enqueued BEHIND the scan, before the host knows the count, and they are ready when it arrives: ONE synchronisation.
 int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::ExportPose& X, double voxel, VoxelTable T, bool settle,
-               float* rows, int64_t first_row, unsigned long long* row_keys, int64_t* out_added) {
+               float* rows, int64_t first_row, unsigned long long* row_keys, uint32_t* row_attr, int64_t* out_added) {
   const int64_t n = c->n;
   uint32_t* slot_of = fs->idx[0];
   uint32_t* mark = fs->P.leaf_start;
@@ -802,7 +880,7 @@ int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::E
   HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
   hipLaunchKernelGGL(fe::voxel_rows, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, (const uint32_t*)mark,
                      (const uint32_t*)fs->S, (const uint32_t*)(settle ? slot_of : nullptr), settle ? T.owner : nullptr, (long)first_row,
-                     rows, row_keys);
+                     rows, row_keys, (const uint32_t*)c->attr, row_attr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count
   *out_added = fs->h_rec_res->r.kept;
@@ -863,13 +941,17 @@ int madicp_cloud_stamps(madicp_ctx* ctx, int cloud_id, double* out_stamps01, int
 //   buf[0]  (24 bytes per point)  the table: 2 n 64-bit keys, behind them 2 n 32-bit owners — exactly 24 n bytes, set to all
 //                                 ones by ONE memset (the empty key and the never-owned word are both all ones)
 //   buf[1]  the float rows (12 of its 24 bytes per point)
+//           madicp_cloud_export_f32_attr: behind the rows, in 4 of buf[1]'s 12 idle bytes per point, the rows' attribute words
 // The fold writes scratch only, so a refusal for capacity still leaves out_xyz alone.  Two synchronisations: the count, then the
 // rows (voxel == 0: no table, every point a row, the count is the cloud's size — one).
-int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
-                            int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !R || !t || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+}  // extern "C"
+namespace {
+int cloud_export_on(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz, bool want_attr,
+                    uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !R || !t || !out_xyz || !out_n || (want_attr && !out_attr)) return fail(MADICP_ERR_INVALID, "null argument");
   DevCloud* c = find_cloud(ctx, cloud_id);
   if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (want_attr && !c->attr) return fail(MADICP_ERR_INVALID, "the cloud carries no attribute");
   if (const char* why = madicp_host::export_refusal(R, t, voxel)) return fail(MADICP_ERR_INVALID, why);
   RC_TRY(busy_with_lookahead(ctx));
   const int64_t n = c->n;
@@ -882,11 +964,12 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
   RC_TRY(ensure_scratch(ctx, n, &fs));
   const fe::ExportPose X = export_pose(R, t);
   float* d_rows = reinterpret_cast<float*>(fs->P.buf[1]);
+  uint32_t* d_row_attr = want_attr ? reinterpret_cast<uint32_t*>(d_rows + 3 * n) : nullptr;
   int64_t rows = n;
   if (voxel == 0.0) {
     hipLaunchKernelGGL(fe::voxel_rows, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel,
                        (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0L, d_rows,
-                       (unsigned long long*)nullptr);
+                       (unsigned long long*)nullptr, (const uint32_t*)c->attr, d_row_attr);
     HIP_TRY(hipGetLastError());
   } else {
     VoxelTable T;
@@ -894,15 +977,27 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
     T.keys = reinterpret_cast<unsigned long long*>(fs->P.buf[0]);
     T.owner = reinterpret_cast<uint32_t*>(T.keys + T.slots);
     HIP_TRY(hipMemsetAsync(T.keys, 0xff, (sizeof(unsigned long long) + sizeof(uint32_t)) * (size_t)T.slots, ctx->copy));
-    RC_TRY(voxel_fold(ctx, fs, c, X, voxel, T, false, d_rows, 0, nullptr, &rows));
+    RC_TRY(voxel_fold(ctx, fs, c, X, voxel, T, false, d_rows, 0, nullptr, d_row_attr, &rows));
     *out_n = rows;  // the count decides whether the caller's buffer is large enough
     if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the export needs (*out_n)");
     if (rows == 0) return MADICP_OK;  // (no candidate: every point outside the 2^21 cells per axis, or not finite)
   }
   HIP_TRY(hipMemcpyAsync(out_xyz, d_rows, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  if (want_attr) HIP_TRY(hipMemcpyAsync(out_attr, d_row_attr, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
   HIP_TRY(hipStreamSynchronize(ctx->copy));
   *out_n = rows;
   return MADICP_OK;
+}
+}  // namespace
+extern "C" {
+int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
+                            int64_t capacity_rows, int64_t* out_n) {
+  return cloud_export_on(ctx, cloud_id, R, t, voxel, out_xyz, false, nullptr, capacity_rows, out_n);
+}
+// ... with the attribute word of every row beside it (the cloud must carry a column)
+int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9], const double t[3], double voxel, float* out_xyz,
+                                 uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
+  return cloud_export_on(ctx, cloud_id, R, t, voxel, out_xyz, true, out_attr, capacity_rows, out_n);
 }
 
 }  // extern "C"
@@ -914,7 +1009,8 @@ int madicp_cloud_export_f32(madicp_ctx* ctx, int cloud_id, const double R[9], co
 //   row_keys (cap x 8) | xyz (cap x 12)     what the rows hold, in row order
 // Growth invariant: before a fold of n points into M rows, M + n <= cap — so the table is never more than half full and every
 // probe ends; where it would not hold, a block for max(M + n, min(2 cap, max_rows)) rows is allocated, rows and keys move by device
-// copy, map_rehash refills the table, the old block is freed.  The host knows M exactly: every fold ends with ONE synchronisation,
+// copy, map_rehash refills the table, the old block is freed.  A map of madicp_map_create_attr has a fifth column
+// behind these — attr (cap x 4), the rows' attribute words: 48 bytes per row of capacity — that moves with the rows.  The host knows M exactly: every fold ends with ONE synchronisation,
 // for the count (none more at a growth but the one in front of freeing the old block).  A fold uses the builder's scratch: it is
 // refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
 namespace {
@@ -922,7 +1018,7 @@ namespace {
 int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m) {
   const size_t c = (size_t)cap;
   char* block = nullptr;
-  HIP_TRY(hipMalloc(&block, 44 * c));
+  HIP_TRY(hipMalloc(&block, (m->with_attr ? 48 : 44) * c));
   m->block = block;
   m->cap = cap;
   m->slots = static_cast<uint32_t>(2 * c);
@@ -930,6 +1026,7 @@ int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m) {
   m->owner = reinterpret_cast<uint32_t*>(block + 16 * c);
   m->row_keys = reinterpret_cast<unsigned long long*>(block + 24 * c);
   m->xyz = reinterpret_cast<float*>(block + 32 * c);
+  m->attr = m->with_attr ? reinterpret_cast<uint32_t*>(block + 44 * c) : nullptr;
   hipError_t e = hipMemsetAsync(block, 0xff, 24 * c, ctx->copy);
   if (e != hipSuccess) {
     hipFree(block);
@@ -948,6 +1045,7 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
     const size_t M = (size_t)m->rows;
     e = hipMemcpyAsync(g.row_keys, m->row_keys, sizeof(unsigned long long) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) e = hipMemcpyAsync(g.xyz, m->xyz, sizeof(float) * 3 * M, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess && m->with_attr) e = hipMemcpyAsync(g.attr, m->attr, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) {
       const int blocks = grid_256(ctx, m->rows);
       hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)m->rows, g.keys,
@@ -971,22 +1069,27 @@ DevMap* find_map(madicp_ctx* ctx, int id) {
   return it == ctx->front->maps.end() ? nullptr : &it->second;
 }
 
-}  // namespace
-
-extern "C" {
-
-int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id) {
+int map_create_on(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr, int* out_map_id) {
   if (!ctx || !out_map_id) return fail(MADICP_ERR_INVALID, "null argument");
   if (const char* why = madicp_host::map_create_refusal(voxel, initial_rows, max_rows)) return fail(MADICP_ERR_INVALID, why);
   HIP_TRY(hipSetDevice(ctx->device));
   DevMap m;
   m.voxel = voxel;
   m.max_rows = max_rows;
+  m.with_attr = with_attr;
   RC_TRY(map_block_alloc(ctx, std::min(initial_rows, max_rows), &m));
   const int id = ctx->next_id++;
   front_of(ctx).maps[id] = m;
   *out_map_id = id;
   return MADICP_OK;
+}
+}  // namespace
+extern "C" {
+int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id) {
+  return map_create_on(ctx, voxel, initial_rows, max_rows, false, out_map_id);
+}
+int madicp_map_create_attr(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id) {
+  return map_create_on(ctx, voxel, initial_rows, max_rows, true, out_map_id);
 }
 
 int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
@@ -1011,7 +1114,7 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
   if (m->rows + n > m->cap) RC_TRY(map_grow(ctx, m, m->rows + n));
   int64_t added = 0;
   RC_TRY(voxel_fold(ctx, fs, c, export_pose(R, t), m->voxel, VoxelTable{m->keys, m->owner, m->slots}, true, m->xyz, m->rows, m->row_keys,
-                    &added));
+                    m->attr, &added));
   m->rows += added;
   *out_added = added;
   *out_rows = m->rows;
@@ -1037,6 +1140,22 @@ int madicp_map_download_f32(madicp_ctx* ctx, int map_id, int64_t first_row, floa
   if (rows == 0) return MADICP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipMemcpyAsync(out_xyz, m->xyz + 3 * first_row, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
+}
+
+int madicp_map_download_attr(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_attr || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!m->with_attr) return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_attr holds fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out_attr, m->attr + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
   HIP_TRY(hipStreamSynchronize(ctx->copy));
   return MADICP_OK;
 }

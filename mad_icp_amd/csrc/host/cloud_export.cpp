@@ -12,3 +12,9 @@ extern "C" int madicp_host_cloud_export_f32(const double* xyz, int64_t n, const 
                                             float* out_xyz, int64_t capacity_rows, int64_t* out_n) {
   return madicp_host::cloud_export_f32(xyz, n, R, t, voxel, out_xyz, capacity_rows, out_n);
 }
+
+extern "C" int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, int64_t n, const double R[9], const double t[3],
+                                                 double voxel, float* out_xyz, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
+  if (!attr || !out_attr) return MADICP_ERR_INVALID;
+  return madicp_host::cloud_export_f32_attr(xyz, attr, n, R, t, voxel, out_xyz, out_attr, capacity_rows, out_n);
+}

@@ -23,10 +23,15 @@ namespace madicp_host {
 // ones included, each canonicalised as t + 0.0; else {t_begin, t_end}.  out_t_range: the range used (+inf, -inf without a time
 // field or a finite time).  Returns 0; -1 for what record_sources_refusal refuses or a null out_xyz / out_n, nothing
 // written.  No survivor is NOT an error here: *out_n = 0.  Nothing past data[n * step) of any source is touched.
-inline int ingest_sources(const RecordSource* src, int n_sources, const double* t_range, double* out_xyz, double* out_stamps01,
-                          int64_t* out_n, int64_t* out_n_per_source, double* out_t_range) {
+// ingest_sources_attr — the twin of madicp_cloud_ingest_sources_attr — is the loop nest: sources that name an attribute field
+// (RecordSource::A, all or none) leave every survivor's word (ingest_point.h: record_attr) in out_attr, room for one per record;
+// -1 as well for a null out_attr with such sources.  ingest_sources is the same call for sources that name none.
+inline int ingest_sources_attr(const RecordSource* src, int n_sources, const double* t_range, double* out_xyz, double* out_stamps01,
+                               uint32_t* out_attr, int64_t* out_n, int64_t* out_n_per_source, double* out_t_range) {
   if (!out_xyz || !out_n) return -1;
   if (record_sources_refusal(src, n_sources, t_range)) return -1;
+  const bool has_attr = src[0].A.type != kAttrNone;
+  if (has_attr && !out_attr) return -1;
   const bool has_time = src[0].L.t_type != kTimeNone;
   bool as_is[kMaxSources];
   for (int s = 0; s < n_sources; ++s) as_is[s] = source_clock_as_is(src[s].t_scale, src[s].t_offset);
@@ -67,6 +72,7 @@ inline int ingest_sources(const RecordSource* src, int n_sources, const double* 
       if (!identity) sensor_to_base(S.R, S.t, o);
       if (has_time && out_stamps01)
         out_stamps01[kept] = record_stamp(source_clock(record_time(p + L.off_t, L.t_type), as_is[s] ? 1 : 0, S.t_scale, S.t_offset), t0, t1);
+      if (has_attr) out_attr[kept] = record_attr(p + S.A.off, S.A.type);
       ++kept;
     }
     if (out_n_per_source) out_n_per_source[s] = kept - before;
@@ -77,6 +83,11 @@ inline int ingest_sources(const RecordSource* src, int n_sources, const double* 
     out_t_range[1] = t1;
   }
   return 0;
+}
+
+inline int ingest_sources(const RecordSource* src, int n_sources, const double* t_range, double* out_xyz, double* out_stamps01,
+                          int64_t* out_n, int64_t* out_n_per_source, double* out_t_range) {
+  return ingest_sources_attr(src, n_sources, t_range, out_xyz, out_stamps01, nullptr, out_n, out_n_per_source, out_t_range);
 }
 
 // ... and of madicp_cloud_ingest_records: ingest_sources of the one plain source (ingest_point.h: plain_source), so out_xyz has

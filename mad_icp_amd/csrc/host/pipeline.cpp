@@ -169,16 +169,48 @@ void Pipeline::dropKeptScan() {
     kept_cloud_id_ = -1;
   }
   kept_host_.clear();
+  kept_attr_.clear();
+  kept_has_attr_ = false;
+  kept_attr_type_ = kAttrNone;
   have_kept_ = false;
   kept_n_ = 0;
 }
 
 void Pipeline::keepHostScan(const ContainerType& c) {
+  // (the column the frame announced is taken over here, or let go with the scan)
+  const int attr_type = frame_attr_type_;
+  std::vector<uint32_t> attr = std::move(frame_attr_);
+  frame_attr_type_ = kAttrNone;
+  frame_attr_.clear();
   if (!keep_scan_ && map_voxel_ == 0.0) return;
   dropKeptScan();
   kept_host_ = c;
   kept_n_ = c.size();
   have_kept_ = true;
+  if (attr_type != kAttrNone && attr.size() == c.size()) {
+    kept_attr_ = std::move(attr);
+    kept_has_attr_ = true;
+    kept_attr_type_ = attr_type;
+  }
+}
+
+// The host azimuth deskew leaves the point with the i-th smallest azimuth at position i (deskew.h): the frame's column follows.
+// With ties the order is std::sort's own of (azimuth, point) pairs; sorting (azimuth, index) pairs with the same comparator makes
+// the same comparisons in the same sequence — the algorithm never looks at the payload — and so leaves the same permutation.
+void Pipeline::permuteFrameAttr(const DeskewOrder& order) {
+  const size_t n = frame_attr_.size();
+  if (order.azimuth.size() != n) return;
+  std::vector<uint32_t> out(n);
+  if (!order.ties && order.order.size() == n) {
+    for (size_t i = 0; i < n; ++i) out[i] = frame_attr_[order.order[i]];
+  } else {
+    std::vector<std::pair<double, uint32_t>> sorted(n);
+    for (size_t i = 0; i < n; ++i) sorted[i] = std::make_pair(order.azimuth[i], frame_attr_[i]);
+    std::sort(sorted.begin(), sorted.end(),
+              [](const std::pair<double, uint32_t>& a, const std::pair<double, uint32_t>& b) -> bool { return a.first < b.first; });
+    for (size_t i = 0; i < n; ++i) out[i] = sorted[i].second;
+  }
+  frame_attr_.swap(out);
 }
 
 void Pipeline::setKeepScan(bool on) {
@@ -202,17 +234,20 @@ void Pipeline::dropMap() {
   map_overflowed_ = false;
 }
 
-void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points) {
+void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute) {
   if (!std::isfinite(voxel_size) || voxel_size < 0.0)
     throw std::invalid_argument("Pipeline::setMapAccumulation: voxel_size must be finite and >= 0 (0 = off)");
   if (voxel_size > 0.0 && (max_points < 1 || max_points > static_cast<size_t>(kMapMaxRows)))
     throw std::invalid_argument("Pipeline::setMapAccumulation: max_points must be 1 .. 2^30");
-  if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_))) return;
+  if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_ && with_attribute == map_with_attr_)))
+    return;
   dropMap();
   const bool was_on = map_voxel_ > 0.0;
   map_voxel_ = voxel_size;
   map_keyframes_only_ = keyframes_only;
   map_max_points_ = max_points;
+  map_with_attr_ = voxel_size > 0.0 && with_attribute;
+  map_attr_type_ = kAttrNone;
   if (voxel_size > 0.0) {
     if (!was_on) dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
   } else if (!keep_scan_) {
@@ -233,32 +268,50 @@ void Pipeline::foldFrame() {
       madicp_ctx* ctx = fresh ? Device::ctx() : Device::current(map_generation_);
       if (!ctx) throw std::logic_error("Pipeline: the device context the map lived in is gone");
       if (fresh) {
-        check(madicp_map_create(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create");
+        if (map_with_attr_)
+          check(madicp_map_create_attr(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create_attr");
+        else
+          check(madicp_map_create(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create");
         map_generation_ = Device::generation();
       }
       MADtree::cancelDeviceBuild(0);  // the fold needs the builder's scratch: a look-ahead of another Pipeline gives way
       int cloud_id = kept_cloud_id_;
-      if (cloud_id < 0)  // (a host-side scan into a device map: the front-end was switched)
+      if (cloud_id < 0) {  // (a host-side scan into a device map: the front-end was switched — its column crosses with it)
         check(madicp_cloud_upload(ctx, kept_host_[0].data(), static_cast<int64_t>(kept_host_.size()), &cloud_id), "madicp_cloud_upload");
+        if (map_with_attr_ && kept_has_attr_) {
+          const int arc = madicp_cloud_set_attr(ctx, cloud_id, kept_attr_.data(), static_cast<int64_t>(kept_attr_.size()));
+          if (arc != MADICP_OK) {
+            madicp_cloud_release(ctx, cloud_id);
+            check(arc, "madicp_cloud_set_attr");
+          }
+        }
+      }
       rc = madicp_map_insert_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, &added, &rows);
       if (kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_insert_cloud");
     } else {
-      if (fresh) map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows);
-      ContainerType down;  // (a resident scan into a host map: the front-end was switched)
+      if (fresh) map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_);
+      ContainerType down;  // (a resident scan into a host map: the front-end was switched — its column crosses with it)
+      std::vector<uint32_t> down_attr;
       if (kept_cloud_id_ >= 0) {
         DeviceLock lock(Device::mutex());
         madicp_ctx* ctx = Device::current(kept_generation_);
         if (!ctx) throw std::logic_error("Pipeline: the device context the scan lived in is gone");
         down.resize(kept_n_);
         check(madicp_cloud_download(ctx, kept_cloud_id_, down[0].data(), static_cast<int64_t>(kept_n_)), "madicp_cloud_download");
+        if (map_with_attr_ && kept_has_attr_) {
+          down_attr.resize(kept_n_);
+          check(madicp_cloud_attr(ctx, kept_cloud_id_, down_attr.data(), static_cast<int64_t>(kept_n_)), "madicp_cloud_attr");
+        }
       }
       const ContainerType& c = kept_cloud_id_ >= 0 ? down : kept_host_;
+      const std::vector<uint32_t>& a = kept_cloud_id_ >= 0 ? down_attr : kept_attr_;
       rc = map_host_->insert(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, &added,
-                             &rows);
+                             &rows, (kept_has_attr_ && a.size() == c.size()) ? a.data() : nullptr);
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline: the host voxel map refused its arguments");
     }
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
+    if (rc == MADICP_OK && map_with_attr_ && kept_has_attr_) map_attr_type_ = kept_attr_type_;
   }
   if (!keep_scan_) dropKeptScan();
 }
@@ -294,6 +347,30 @@ size_t Pipeline::mapCloud(float* out, size_t capacity, size_t first_row) {
     if (!ctx) throw std::logic_error("Pipeline::mapCloud: the device context the map lived in is gone");
     check(madicp_map_download_f32(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
           "madicp_map_download_f32");
+  }
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::mapAttribute(uint32_t* out, size_t capacity, size_t first_row) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapAttribute: setMapAccumulation(voxel_size > 0) first");
+  if (!map_with_attr_) throw std::logic_error("Pipeline::mapAttribute: the map was made without the attribute (setMapAccumulation's with_attribute)");
+  if (!out) throw std::invalid_argument("Pipeline::mapAttribute: null buffer");
+  const size_t size = mapSize();
+  if (first_row > size) throw std::invalid_argument("Pipeline::mapAttribute: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (capacity < size - first_row)
+    throw std::invalid_argument("Pipeline::mapAttribute: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
+                                std::to_string(size - first_row));
+  if (size == first_row) return 0;
+  int64_t rows = 0;
+  if (map_host_) {
+    if (map_host_->download_attr(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
+      throw std::runtime_error("Pipeline::mapAttribute: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapAttribute: the device context the map lived in is gone");
+    check(madicp_map_download_attr(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
+          "madicp_map_download_attr");
   }
   return static_cast<size_t>(rows);
 }
@@ -334,6 +411,41 @@ size_t Pipeline::registeredScan(float* out, size_t capacity, double voxel, bool 
   }
   if (rc == MADICP_ERR_CAPACITY)
     throw std::invalid_argument("Pipeline::registeredScan: the buffer holds " + std::to_string(capacity) + " rows, the scan needs " +
+                                std::to_string(rows));
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::registeredScanAttribute(uint32_t* out, size_t capacity, double voxel, bool map_frame) {
+  // (the rows themselves into a buffer of its own: no more of them than the scan has points)
+  std::vector<float> xyz(3 * std::max<size_t>(std::min(capacity, registeredScanSize()), 1));
+  return registeredScanWithAttribute(xyz.data(), out, std::min(capacity, xyz.size() / 3), voxel, map_frame);
+}
+
+size_t Pipeline::registeredScanWithAttribute(float* out_xyz, uint32_t* out, size_t capacity, double voxel, bool map_frame) {
+  if (!keep_scan_) throw std::logic_error("Pipeline::registeredScanAttribute: setKeepScan(true) first");
+  if (!have_kept_) throw std::logic_error("Pipeline::registeredScanAttribute: no frame has been computed since setKeepScan(true)");
+  if (!kept_has_attr_) throw std::logic_error("Pipeline::registeredScanAttribute: the retained scan carries no attribute");
+  if (!out || !out_xyz) throw std::invalid_argument("Pipeline::registeredScanAttribute: null buffer");
+  if (!std::isfinite(voxel) || voxel < 0.0) throw std::invalid_argument("Pipeline::registeredScanAttribute: voxel must be finite and >= 0");
+  const Pose X = map_frame ? frame_to_map_ : Pose::identity();
+  const int64_t cap_rows = static_cast<int64_t>(std::min<size_t>(capacity, size_t(1) << 40));
+  int64_t rows = 0;
+  int rc;
+  if (kept_cloud_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(kept_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::registeredScanAttribute: the device context the scan lived in is gone");
+    MADtree::cancelDeviceBuild(0);  // the export needs the builder's scratch: a look-ahead of another Pipeline gives way
+    rc = madicp_cloud_export_f32_attr(ctx, kept_cloud_id_, X.R, X.t, voxel, out_xyz, out, cap_rows, &rows);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_cloud_export_f32_attr");
+  } else {
+    rc = cloud_export_f32_attr(kept_host_.empty() ? nullptr : kept_host_[0].data(), kept_attr_.data(), static_cast<int64_t>(kept_host_.size()),
+                               X.R, X.t, voxel, out_xyz, out, cap_rows, &rows);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY)
+      throw std::runtime_error("Pipeline::registeredScanAttribute: the host export refused its arguments");
+  }
+  if (rc == MADICP_ERR_CAPACITY)
+    throw std::invalid_argument("Pipeline::registeredScanAttribute: the buffer holds " + std::to_string(capacity) + " rows, the scan needs " +
                                 std::to_string(rows));
   return static_cast<size_t>(rows);
 }
@@ -434,6 +546,8 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
   madicp_ctx* ctx = Device::ctx();
   MADtree::cancelDeviceBuild(0);  // deskew and build need the builder's scratch: a look-ahead of another Pipeline gives way
   dropKeptScan();                 // (the scan retained for the frame before)
+  const int attr_type = frame_attr_type_;  // (the column the frame announced lives in the cloud: both deskews keep it aligned)
+  frame_attr_type_ = kAttrNone;
   std::unique_ptr<MADtree> tree;
   try {
     if (is_initialized_ && deskew_ && trajectory_.size() > 1) {
@@ -461,6 +575,8 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
     kept_generation_ = Device::generation();
     kept_n_ = static_cast<size_t>(n);
     have_kept_ = true;
+    kept_has_attr_ = attr_type != kAttrNone;
+    kept_attr_type_ = attr_type;
     return tree;
   }
   check(madicp_cloud_release(ctx, cloud_id), "madicp_cloud_release");
@@ -523,6 +639,17 @@ void Pipeline::computeRecordsStamped(const double& curr_stamp, const void* data,
   computeSources(curr_stamp, &S, 1, t_range, "Pipeline::computeRecordsStamped");
 }
 
+void Pipeline::computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout,
+                                     double min_range, double max_range, bool kitti_correction, const double* t_range,
+                                     const AttrField& attribute) {
+  if (!data || n_records == 0) throw std::invalid_argument("Pipeline::computeRecordsStamped: no records");
+  if (n_records > 0x3fffffff) throw std::invalid_argument("Pipeline::computeRecordsStamped: 1 .. 2^30 records");
+  RecordSource S = plain_source(data, static_cast<int64_t>(n_records), layout, min_range, max_range, kitti_correction);
+  S.A = attribute;
+  if (const char* why = record_sources_refusal(&S, 1, t_range)) throw std::invalid_argument(std::string("Pipeline::computeRecordsStamped: ") + why);
+  computeSources(curr_stamp, &S, 1, t_range, "Pipeline::computeRecordsStamped");
+}
+
 // A frame from several sensors' byte records (pipeline.h)
 void Pipeline::computeSourcesStamped(const double& curr_stamp, const RecordSource* sources, int n_sources, const double* t_range) {
   if (const char* why = record_sources_refusal(sources, n_sources, t_range))
@@ -544,13 +671,29 @@ void Pipeline::computeSources(const double& curr_stamp, const RecordSource* sour
   }
   if (!deskew_) t_range = nullptr;
   const bool stamped = deskew_ && sources[0].L.t_type != kTimeNone;
+  // The attribute column (sources that name a field: all of them or none): announced to whoever retains the frame's scan
+  // (buildOnDevice / keepHostScan take it over) and forgotten again however the frame ends.
+  const int attr_type = sources[0].A.type;
+  struct FrameAttr {
+    Pipeline* p;
+    ~FrameAttr() {
+      p->frame_attr_type_ = kAttrNone;
+      p->frame_attr_.clear();
+    }
+  } frame_attr{this};
   if (device_frontend_) {
     madicp_record_source cs[MADICP_MAX_SOURCES];
-    for (int s = 0; s < n_sources; ++s) cs[s] = record_source_to<madicp_record_source>(src[s]);
+    madicp_attr_field fields[MADICP_MAX_SOURCES];
+    for (int s = 0; s < n_sources; ++s) {
+      cs[s] = record_source_to<madicp_record_source>(src[s]);
+      fields[s] = madicp_attr_field{src[s].A.off, src[s].A.type};
+    }
+    frame_attr_type_ = attr_type;
     computeIngested(curr_stamp, stamped, [&] {
       int cloud_id = -1;
       int64_t kept = 0;
-      check(madicp_cloud_ingest_sources(Device::ctx(), cs, n_sources, t_range, &cloud_id, &kept, nullptr, nullptr),
+      check(madicp_cloud_ingest_sources_attr(Device::ctx(), cs, n_sources, attr_type != kAttrNone ? fields : nullptr, t_range, &cloud_id,
+                                             &kept, nullptr, nullptr),
             "madicp_cloud_ingest_sources");
       return cloud_id;
     });
@@ -558,11 +701,18 @@ void Pipeline::computeSources(const double& curr_stamp, const RecordSource* sour
   }
   ContainerType cloud(static_cast<size_t>(total));
   std::vector<double> stamps(stamped ? static_cast<size_t>(total) : 0);
+  std::vector<uint32_t> words(attr_type != kAttrNone ? static_cast<size_t>(total) : 0);
   int64_t kept = 0;
-  if (ingest_sources(src, n_sources, t_range, cloud[0].data(), stamped ? stamps.data() : nullptr, &kept, nullptr, nullptr) != 0)
+  if (ingest_sources_attr(src, n_sources, t_range, cloud[0].data(), stamped ? stamps.data() : nullptr,
+                          attr_type != kAttrNone ? words.data() : nullptr, &kept, nullptr, nullptr) != 0)
     throw std::invalid_argument(std::string(who) + ": bad arguments");
   if (kept < 1) throw std::invalid_argument(std::string(who) + ": no point survives the range filter");
   cloud.resize(static_cast<size_t>(kept));
+  if (attr_type != kAttrNone) {
+    words.resize(static_cast<size_t>(kept));
+    frame_attr_ = std::move(words);
+    frame_attr_type_ = attr_type;
+  }
   if (stamped) {
     stamps.resize(static_cast<size_t>(kept));
     computeStamped(curr_stamp, std::move(cloud), stamps);
@@ -694,10 +844,17 @@ void Pipeline::computeWithTree(const double& curr_stamp, std::unique_ptr<MADtree
       // the azimuth order computed ahead for exactly this scan, if there is one (older ones: scans that never came)
       DeskewOrder ahead;
       DeskewAhead a;
-      const bool have = takeLookAhead(deskew_ahead_, cloud->data(), cloud->size(), &a);
+      bool have = takeLookAhead(deskew_ahead_, cloud->data(), cloud->size(), &a);
       if (have) {
         ahead = a.result.get();
         ++look_ahead_hits_;
+      }
+      if (frame_attr_type_ != kAttrNone) {  // the frame's attribute column follows the points into azimuth order
+        if (!have) {
+          ahead = deskew_order(*cloud);
+          have = true;
+        }
+        permuteFrameAttr(ahead);
       }
       deskew(*cloud, trajectory_[trajectory_.size() - 2], trajectory_[trajectory_.size() - 1], have ? &ahead : nullptr);
       keepHostScan(*cloud);

@@ -135,6 +135,16 @@ class Pipeline {
   // std::invalid_argument for a null buffer, a voxel that is negative or not finite, a capacity smaller than the rows needed
   // (nothing is written then).
   size_t registeredScan(float* out, size_t capacity, double voxel, bool map_frame);
+  // additive: the per-point ATTRIBUTE (include/madicp_hip.h: one 32-bit word per point, the bytes of one record field zero-extended,
+  // never converted).  A frame whose sources name an attribute field (RecordSource::A — computeSourcesStamped, or
+  // computeRecordsStamped's overload with a field) carries the column beside its points through the ingest and both deskews (the
+  // azimuth deskew permutes it with the points), on either front-end; the retained scan keeps it.  registeredScanAttribute returns
+  // the words of exactly the rows registeredScan(…, voxel, map_frame) returns (which points own a voxel depends on the frame the
+  // voxels are cut in; at voxel 0 it does not matter); registeredScanWithAttribute returns rows and words from ONE export.  Same
+  // refusals as registeredScan; std::logic_error as well when the retained scan carries no attribute.
+  size_t registeredScanAttribute(uint32_t* out, size_t capacity, double voxel, bool map_frame = true);
+  size_t registeredScanWithAttribute(float* out_xyz, uint32_t* out_attr, size_t capacity, double voxel, bool map_frame);
+  int registeredScanAttributeType() const { return have_kept_ && kept_has_attr_ ? kept_attr_type_ : kAttrNone; }  // kAttr*: the field's type
 
   // additive: MAP ACCUMULATION.  With setMapAccumulation(voxel_size > 0) — default off: nothing changes, not a launch — every
   // compute* entry point ends by folding the cloud its tree was built from (the cloud registeredScan(0, ...) returns, in that row
@@ -152,7 +162,14 @@ class Pipeline {
   // whole map on every rank (poses are bit-equal across ranks, so the maps are).  std::invalid_argument for a voxel_size that
   // is negative or not finite, max_points outside 1 .. 2^30.
   static constexpr size_t kMapMaxPointsDefault = size_t(1) << 24;
-  void setMapAccumulation(double voxel_size, bool keyframes_only = false, size_t max_points = kMapMaxPointsDefault);
+  // with_attribute: the map is made with the attribute column (madicp_map_create_attr / VoxelMap's) — a row keeps its owning
+  // point's word; frames that arrive without an attribute (compute, computeRecords ...) contribute the word 0.  mapAttribute
+  // runs beside mapCloud: the words of rows [first_row, mapSize()), the same refusals; std::logic_error without the column.
+  void setMapAccumulation(double voxel_size, bool keyframes_only = false, size_t max_points = kMapMaxPointsDefault,
+                          bool with_attribute = false);
+  bool mapWithAttribute() const { return map_voxel_ > 0.0 && map_with_attr_; }
+  int mapAttributeType() const { return map_attr_type_; }  // the field type of the last attribute frame folded (kAttrNone: none yet)
+  size_t mapAttribute(uint32_t* out, size_t capacity, size_t first_row = 0);
   double mapVoxelSize() const { return map_voxel_; }  // 0: off
   bool mapOverflowed() const { return map_overflowed_; }
   size_t mapSize();  // rows the map holds; std::logic_error while the option is off (mapCloud and clearMap too)
@@ -179,6 +196,9 @@ class Pipeline {
   // no records or a layout / t_range the ingest refuses.
   void computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout, double min_range,
                              double max_range, bool kitti_correction, const double* t_range);
+  // ... with one more field of the record carried as the points' attribute (above: registeredScanAttribute)
+  void computeRecordsStamped(const double& curr_stamp, const void* data, size_t n_records, const RecordLayout& layout, double min_range,
+                             double max_range, bool kitti_correction, const double* t_range, const AttrField& attribute);
 
   // additive: one frame from SEVERAL sensors' byte records (a multi-head rig: every source in its own sensor frame, with its own
   // layout, range bounds, sensor -> base extrinsic and time scale / offset onto one common clock — RecordSource, ingest_point.h).
@@ -304,12 +324,21 @@ class Pipeline {
   unsigned kept_generation_ = 0;
   ContainerType kept_host_;
   size_t kept_n_ = 0;
+  // its attribute column: inside the resident cloud, or kept_attr_ beside the host copy.  A records frame announces its column
+  // (frame_attr_type_, host front-end: the words in frame_attr_) before it enters compute*; whoever retains the scan takes it over
+  bool kept_has_attr_ = false;
+  int kept_attr_type_ = 0;
+  std::vector<uint32_t> kept_attr_;
+  int frame_attr_type_ = 0;  // kAttrNone: the frame being computed carries no attribute
+  std::vector<uint32_t> frame_attr_;
+  void permuteFrameAttr(const DeskewOrder& order);  // host azimuth deskew: the column follows the points
   void dropKeptScan();                        // forget it; the device buffer goes back to the pool
   void keepHostScan(const ContainerType& c);  // host front-end: the copy, when the option (or map accumulation) is on
   // map accumulation (setMapAccumulation): the map lives where the first folded cloud did — a device map of the context generation
   // that issued its id, or the host twin; a cloud from the other side (the front-end was switched) crosses over for its fold
   double map_voxel_ = 0.0;
-  bool map_keyframes_only_ = false, map_overflowed_ = false;
+  bool map_keyframes_only_ = false, map_overflowed_ = false, map_with_attr_ = false;
+  int map_attr_type_ = 0;
   size_t map_max_points_ = kMapMaxPointsDefault;
   int map_id_ = -1;
   unsigned map_generation_ = 0;

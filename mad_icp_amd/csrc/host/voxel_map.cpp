@@ -24,10 +24,29 @@ int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows,
   return MADICP_OK;
 }
 
+int madicp_host_map_create_attr(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map) {
+  if (!out_map || madicp_host::map_create_refusal(voxel, initial_rows, max_rows)) return MADICP_ERR_INVALID;
+  madicp_host_map* m = new (std::nothrow) madicp_host_map{madicp_host::VoxelMap(voxel, initial_rows, max_rows, true)};
+  if (!m) return MADICP_ERR_CAPACITY;
+  *out_map = m;
+  return MADICP_OK;
+}
+
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
                            int64_t* out_rows) {
   if (!map) return MADICP_ERR_INVALID;
   return map->map.insert(xyz, n, R, t, out_added, out_rows);
+}
+
+int madicp_host_map_insert_attr(madicp_host_map* map, const double* xyz, const uint32_t* attr, int64_t n, const double R[9],
+                                const double t[3], int64_t* out_added, int64_t* out_rows) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.insert(xyz, n, R, t, out_added, out_rows, attr);
+}
+
+int madicp_host_map_download_attr(const madicp_host_map* map, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_attr(first_row, out_attr, capacity_rows, out_n);
 }
 
 int madicp_host_map_size(const madicp_host_map* map, int64_t* out_rows) {

@@ -6,6 +6,8 @@
 // ingest_records.h: Pipeline (host front-end), the C entry points madicp_host_map_* (voxel_map.cpp) and the thinned export
 // (cloud_export.h: one fold into a temporary map) use the one class.  Every translation unit that includes this is compiled without
 // floating-point contraction.
+// A map made `with_attr` holds one more column: the 32-bit attribute word of every row — its OWNING point's, 0 where the folded
+// cloud carries none (madicp_map_create_attr).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -21,16 +23,20 @@ constexpr int kMapOk = 0, kMapInvalid = -1, kMapCapacity = -4;  // MADICP_OK, MA
 
 class VoxelMap {
  public:
-  VoxelMap(double voxel, int64_t initial_rows, int64_t max_rows) : voxel_(voxel), max_rows_(max_rows) {
+  VoxelMap(double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr = false)
+      : voxel_(voxel), max_rows_(max_rows), with_attr_(with_attr) {
     const size_t first = static_cast<size_t>(std::min(initial_rows, max_rows));
     rows_.reserve(3 * first);
     keys_.reserve(first);
+    if (with_attr_) attr_.reserve(first);
   }
   double voxel() const { return voxel_; }
+  bool with_attr() const { return with_attr_; }
   int64_t size() const { return static_cast<int64_t>(rows_.size() / 3); }
 
-  // include/madicp_host.h: madicp_host_map_insert
-  int insert(const double* xyz, int64_t n, const double* R, const double* t, int64_t* out_added, int64_t* out_rows) {
+  // include/madicp_host.h: madicp_host_map_insert / _insert_attr — attr: one word per point, or null (the rows' words are 0)
+  int insert(const double* xyz, int64_t n, const double* R, const double* t, int64_t* out_added, int64_t* out_rows,
+             const uint32_t* attr = nullptr) {
     if (!out_added || !out_rows || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
     if (export_refusal(R, t, voxel_)) return kMapInvalid;
     if (size() + n > max_rows_) return kMapCapacity;  // (conservative: decided before a point is looked at, as on the device)
@@ -41,6 +47,7 @@ class VoxelMap {
       const uint64_t key = export_key(q, voxel_);
       if (key == kExportNoKey || !keys_.insert(key).second) continue;
       for (int k = 0; k < 3; ++k) rows_.push_back(export_value(q[k]));
+      if (with_attr_) attr_.push_back(attr ? attr[i] : 0u);
     }
     *out_added = size() - before;
     *out_rows = size();
@@ -56,16 +63,28 @@ class VoxelMap {
     if (m > 0) std::memcpy(out, rows_.data() + 3 * first_row, sizeof(float) * 3 * static_cast<size_t>(m));
     return kMapOk;
   }
+  // include/madicp_host.h: madicp_host_map_download_attr — the words of rows [first_row, size()); invalid on a map without the column
+  int download_attr(int64_t first_row, uint32_t* out, int64_t capacity_rows, int64_t* out_n) const {
+    if (!with_attr_ || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
+    const int64_t m = size() - first_row;
+    *out_n = m;
+    if (capacity_rows < m) return kMapCapacity;
+    if (m > 0) std::memcpy(out, attr_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
+    return kMapOk;
+  }
 
   void clear() {  // (keeps the memory, forgets the rows)
     rows_.clear();
     keys_.clear();
+    attr_.clear();
   }
 
  private:
   double voxel_;
   int64_t max_rows_;
+  bool with_attr_;
   std::vector<float> rows_;
+  std::vector<uint32_t> attr_;
   std::unordered_set<uint64_t> keys_;
 };
 

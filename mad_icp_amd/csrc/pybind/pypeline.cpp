@@ -76,40 +76,60 @@ PYBIND11_MODULE(pypeline, m) {
     .def("setKeepScan", &Pipeline::setKeepScan, py::arg("on"))
     .def("keepScan", &Pipeline::keepScan)
     .def("registeredScanSize", &Pipeline::registeredScanSize)
+    // ... with_attribute=True: (rows, attr) — attr[j] the attribute of row j, the words the frame carried (computeRecordsStamped's /
+    // Source's `attribute`) viewed back as the field's dtype.  RuntimeError (std::logic_error) when the retained scan carries none.
     .def("registeredScan",
-         [](Pipeline& self, double voxel_size, const std::string& frame) {
+         [](Pipeline& self, double voxel_size, const std::string& frame, bool with_attribute) -> py::object {
            if (frame != "map" && frame != "sensor") throw py::value_error("frame must be \"map\" or \"sensor\"");
            const size_t cap = self.registeredScanSize();
            std::vector<float> rows(3 * std::max<size_t>(cap, 1));
-           const size_t m = self.registeredScan(rows.data(), cap, voxel_size, frame == "map");
+           std::vector<uint32_t> words(std::max<size_t>(cap, 1));
+           const size_t m = with_attribute ? self.registeredScanWithAttribute(rows.data(), words.data(), cap, voxel_size, frame == "map")
+                                           : self.registeredScan(rows.data(), cap, voxel_size, frame == "map");
            py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
            if (m) std::memcpy(out.mutable_data(), rows.data(), sizeof(float) * 3 * m);
-           return out;
+           if (!with_attribute) return std::move(out);
+           py::array_t<uint32_t> w(static_cast<py::ssize_t>(m));
+           if (m) std::memcpy(w.mutable_data(), words.data(), sizeof(uint32_t) * m);
+           const py::module_ rec = py::module_::import("mad_icp_amd.records");
+           return py::make_tuple(out, rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(self.registeredScanAttributeType())]));
          },
-         py::arg("voxel_size") = 0.0, py::arg("frame") = "map")
+         py::arg("voxel_size") = 0.0, py::arg("frame") = "map", py::arg("with_attribute") = false)
     // additive: map accumulation (Pipeline::setMapAccumulation).  setMapAccumulation(voxel_size) makes every compute*() end by folding
     // the frame's scan at the frame's pose into an append-only voxel map — the first point ever to fall into a voxel stays — on the
     // device (device front-end) or in its bit-equal host twin; voxel_size = 0 turns it off and frees the map.  mapCloud(first_row)
     // returns rows [first_row, mapSize()) as an (M - first_row, 3) float32 array: what was added since the caller last looked.
     // ValueError for a voxel_size that is negative or not finite, a max_points outside 1 .. 2^30, a first_row beyond the map;
     // RuntimeError (std::logic_error) from mapSize / mapCloud / clearMap while the option is off.
+    // with_attribute: the map keeps every row's attribute too; mapCloud(first_row, with_attribute=True) returns (rows, attr), attr
+    // viewed as the dtype of the last attribute frame folded (uint32 words before there is one; frames without an attribute
+    // contribute zeros).
     .def("setMapAccumulation", &Pipeline::setMapAccumulation, py::arg("voxel_size"), py::arg("keyframes_only") = false,
-         py::arg("max_points") = Pipeline::kMapMaxPointsDefault)
+         py::arg("max_points") = Pipeline::kMapMaxPointsDefault, py::arg("with_attribute") = false)
+    .def("mapWithAttribute", &Pipeline::mapWithAttribute)
     .def("mapVoxelSize", &Pipeline::mapVoxelSize)
     .def("mapOverflowed", &Pipeline::mapOverflowed)
     .def("mapSize", &Pipeline::mapSize)
     .def("mapCloud",
-         [](Pipeline& self, size_t first_row) {
+         [](Pipeline& self, size_t first_row, bool with_attribute) -> py::object {
            const size_t size = self.mapSize();
            if (first_row > size) throw py::value_error("first_row is beyond the map's rows");
            const size_t m = size - first_row;
            py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
            float none[3];
-           const size_t got = self.mapCloud(m ? out.mutable_data() : none, m, first_row);
-           if (got != m) throw std::runtime_error("Pipeline::mapCloud: the map changed during the call");
-           return out;
+           if (self.mapCloud(m ? out.mutable_data() : none, m, first_row) != m)
+             throw std::runtime_error("Pipeline::mapCloud: the map changed during the call");
+           if (!with_attribute) return std::move(out);
+           py::array_t<uint32_t> w(static_cast<py::ssize_t>(m));
+           uint32_t no_word[1];
+           if (self.mapAttribute(m ? w.mutable_data() : no_word, m, first_row) != m)
+             throw std::runtime_error("Pipeline::mapCloud: the map changed during the call");
+           const int type = self.mapAttributeType();
+           if (type == madicp_host::kAttrNone) return py::make_tuple(out, w);
+           const py::module_ rec = py::module_::import("mad_icp_amd.records");
+           return py::make_tuple(out, rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]));
          },
-         py::arg("first_row") = 0)
+         py::arg("first_row") = 0, py::arg("with_attribute") = false)
     .def("clearMap", &Pipeline::clearMap)
     // additive: a frame straight from sensor records, (n, >=3) float32 (a KITTI .bin is (n,4)): range filter, optional
     // KITTI correction (apps/cpp_runners/bin_runner.cpp:126-166), deskew, build and registration on the device
@@ -129,7 +149,7 @@ PYBIND11_MODULE(pypeline, m) {
     // helper or the ingest refuses.
     .def("computeRecordsStamped",
          [](Pipeline& self, double stamp, py::array rec, double min_range, double max_range, bool kitti, py::object time_field,
-            py::object time_range, py::object layout) {
+            py::object time_range, py::object layout, py::object attribute) {
            const py::tuple r = py::module_::import("mad_icp_amd.records").attr("resolve")(rec, time_field, layout);
            const size_t n = r[0].cast<size_t>();
            const py::tuple l = r[1];
@@ -143,14 +163,23 @@ PYBIND11_MODULE(pypeline, m) {
              range[0] = tr[0].cast<double>();
              range[1] = tr[1].cast<double>();
            }
+           madicp_host::AttrField A{0, madicp_host::kAttrNone};
+           if (!attribute.is_none()) {  // (a field's name, or (offset, type code) for raw records: mad_icp_amd.records.resolve_attribute)
+             const py::tuple a = py::module_::import("mad_icp_amd.records").attr("resolve_attribute")(rec, attribute);
+             A = madicp_host::AttrField{a[0].cast<int32_t>(), a[1].cast<int32_t>()};
+           }
            try {
-             self.computeRecordsStamped(stamp, rec.data(), n, L, min_range, max_range, kitti, have_range ? range : nullptr);
+             if (!attribute.is_none())
+               self.computeRecordsStamped(stamp, rec.data(), n, L, min_range, max_range, kitti, have_range ? range : nullptr, A);
+             else
+               self.computeRecordsStamped(stamp, rec.data(), n, L, min_range, max_range, kitti, have_range ? range : nullptr);
            } catch (const std::invalid_argument& e) {
              throw py::value_error(e.what());
            }
          },
          py::arg("stamp"), py::arg("records"), py::arg("min_range"), py::arg("max_range"), py::arg("kitti_correction") = false,
-         py::arg("time_field") = py::none(), py::arg("time_range") = py::none(), py::arg("layout") = py::none())
+         py::arg("time_field") = py::none(), py::arg("time_range") = py::none(), py::arg("layout") = py::none(),
+         py::arg("attribute") = py::none())
     // additive: a frame from SEVERAL sensors' byte records (Pipeline::computeSourcesStamped): a sequence of
     // mad_icp_amd.records.Source — the buffer as computeRecordsStamped takes it, the range bounds in the sensor's frame, the 4x4
     // sensor_to_base and the time field's scale / offset onto the common clock.  The arrays are read in place.  time_range:
@@ -178,6 +207,8 @@ PYBIND11_MODULE(pypeline, m) {
              S.t_scale = r[7].cast<double>();
              S.t_offset = r[8].cast<double>();
              S.kitti = r[9].cast<bool>() ? 1 : 0;
+             const py::tuple a = r[10];
+             S.A = madicp_host::AttrField{a[0].cast<int32_t>(), a[1].cast<int32_t>()};
            }
            double range[2];
            const bool have_range = !time_range.is_none();

@@ -14,6 +14,12 @@ and, for a rig of several sensors (Pipeline.computeSourcesStamped, madicp_cloud_
            time_field=None, layout=None)                                           one sensor's buffer and how to read it
     resolve_sources(sources) -> [ResolvedSource(...)]                              what Pipeline.computeSourcesStamped calls
 
+and, for a per-point ATTRIBUTE carried from the records to the exported scan and the map (one more field of the record — intensity,
+reflectivity, ring, a label — as a 32-bit word per point, its bytes zero-extended, never converted):
+
+    attribute_of(dtype, name) -> (offset, type code A_*, numpy dtype)               the field as madicp_attr_field takes it
+    attribute_view(words, dtype) -> the uint32 words viewed back as the field's dtype
+
 `time_field=None` takes the first of `t`, `timestamp`, `time` that the dtype has (point_cloud2.py:72), and no time field at
 all (t_type = T_NONE) when it has none; `time_field=False` ignores a time field that is there.
 """
@@ -69,6 +75,53 @@ def layout_of(dtype, time_field=None):
     return RecordLayout(dtype.itemsize, offs[0], offs[1], offs[2], int(off), t_type)
 
 
+A_NONE, A_INT8, A_UINT8, A_INT16, A_UINT16, A_INT32, A_UINT32, A_FLOAT32 = range(8)  # sensor_msgs/PointField's codes (MADICP_A_*)
+_ATTR_TYPES = {("i", 1): A_INT8, ("u", 1): A_UINT8, ("i", 2): A_INT16, ("u", 2): A_UINT16, ("i", 4): A_INT32, ("u", 4): A_UINT32,
+               ("f", 4): A_FLOAT32}
+ATTR_DTYPE = {code: np.dtype("<" + kind + str(size)) for (kind, size), code in _ATTR_TYPES.items()}
+
+
+def attribute_of(dtype, name):
+    """(byte offset, type code, little-endian numpy dtype) of the field `name` of a structured dtype: what the native layers take as
+    a madicp_attr_field, and what the words they return are viewed back as.  ValueError for: no fields, a missing field, a
+    big-endian one, a dtype that is not int8 / uint8 / int16 / uint16 / int32 / uint32 / float32."""
+    dtype = np.dtype(dtype)
+    if dtype.fields is None:
+        raise ValueError("a structured dtype is needed to name an attribute field, got %r" % (dtype,))
+    if name not in dtype.fields:
+        raise ValueError("the records have no attribute field %r" % (name,))
+    dt, off = dtype.fields[name][:2]
+    code = _ATTR_TYPES.get((dt.kind, dt.itemsize)) if dt.shape == () else None
+    if code is None:
+        raise ValueError("attribute field %r: unsupported dtype %r (int8 .. uint32 or float32)" % (name, dt))
+    if not _little_endian(dt):
+        raise ValueError("attribute field %r is big-endian: little-endian records only" % (name,))
+    return int(off), code, ATTR_DTYPE[code]
+
+
+def resolve_attribute(records, attribute):
+    """(offset, type code, numpy dtype) of what a caller passed as `attribute`: a field name of structured records
+    (attribute_of), or — the only way for raw (n, point_step) uint8 records — an explicit (offset, type code) pair.  ValueError
+    for what attribute_of refuses and for an unknown type code; the offset is the native layers' to judge."""
+    if isinstance(attribute, str):
+        return attribute_of(np.asarray(records).dtype, attribute)
+    try:
+        off, code = (int(v) for v in attribute)
+    except (TypeError, ValueError):
+        raise ValueError("attribute: a field name or an (offset, type code) pair, got %r" % (attribute,)) from None
+    if code not in ATTR_DTYPE:
+        raise ValueError("attribute: unknown type code %d" % code)
+    return off, code, ATTR_DTYPE[code]
+
+
+def attribute_view(words, dtype):
+    """The native layers' uint32 words as the field's dtype: the low bytes of every word, reinterpreted (an INT16 of -1 travels as
+    0x0000ffff and comes back as -1; a float32 keeps its bits)."""
+    w = np.ascontiguousarray(words, dtype="<u4")
+    dt = np.dtype(dtype)
+    return w.astype("<u%d" % dt.itemsize).view(dt.newbyteorder("<"))
+
+
 def check_layout(layout):
     """An explicit layout (six integers) as a RecordLayout; ValueError where the native layers would refuse it."""
     lay = RecordLayout(*(int(v) for v in layout))
@@ -115,16 +168,16 @@ MAX_RECORDS = 2 ** 30
 
 class Source:
     """One sensor's records in a frame of several (madicp_record_source): the buffer as resolve() takes it, the range bounds IN
-    THE SENSOR'S FRAME, `sensor_to_base` (4x4, None = identity: the upper 3x4 is used as given, orthonormality is the caller's
+    THE SENSOR'S FRAME, `attribute` (None, or the field carried as the points' attribute: resolve_attribute), `sensor_to_base` (4x4, None = identity: the upper 3x4 is used as given, orthonormality is the caller's
     business) and the time field's way onto the clock all sources share: common = field * time_scale + time_offset (uint32
     nanoseconds: time_scale=1e-9, time_offset = the message's header stamp RELATIVE TO THE FRAME'S START — an absolute epoch
     as offset eats the nanoseconds)."""
 
     __slots__ = ("records", "min_range", "max_range", "sensor_to_base", "time_scale", "time_offset", "kitti_correction",
-                 "time_field", "layout")
+                 "time_field", "layout", "attribute")
 
     def __init__(self, records, min_range, max_range, sensor_to_base=None, time_scale=1.0, time_offset=0.0, kitti_correction=False,
-                 time_field=None, layout=None):
+                 time_field=None, layout=None, attribute=None):
         self.records = records
         self.min_range = min_range
         self.max_range = max_range
@@ -134,10 +187,12 @@ class Source:
         self.kitti_correction = kitti_correction
         self.time_field = time_field
         self.layout = layout
+        self.attribute = attribute  # None, a field's name, or (offset, type code): resolve_attribute
 
 
 ResolvedSource = collections.namedtuple(
-    "ResolvedSource", "records n_records layout R t min_range max_range time_scale time_offset kitti_correction")
+    "ResolvedSource", "records n_records layout R t min_range max_range time_scale time_offset kitti_correction attribute")
+# (attribute: (offset, type code) — (0, A_NONE) for a source that names none)
 
 
 def resolve_sources(sources):
@@ -145,7 +200,7 @@ def resolve_sources(sources):
     of sensor_to_base.  ValueError where the native layers would refuse: no source or more than MAX_SOURCES, a source that is not
     a Source, what resolve() refuses, an empty source or more than 2^30 records in all, a sensor_to_base that is not 4x4 or not
     finite in its upper 3x4, a time_scale that is not finite and > 0, a non-finite time_offset, sources with and without a time
-    field."""
+    field; what resolve_attribute refuses, sources with and without an attribute, attribute dtypes that differ over the sources."""
     sources = list(sources)
     if not 1 <= len(sources) <= MAX_SOURCES:
         raise ValueError("1 .. %d sources, got %d" % (MAX_SOURCES, len(sources)))
@@ -171,9 +226,14 @@ def resolve_sources(sources):
             raise ValueError("source %d: time_offset must be finite" % k)
         out.append(ResolvedSource(src.records, n, lay, tuple(float(v) for v in T[:3, :3].reshape(-1)),
                                   tuple(float(v) for v in T[:3, 3]), float(src.min_range), float(src.max_range), scale, offset,
-                                  bool(src.kitti_correction)))
+                                  bool(src.kitti_correction),
+                                  (0, A_NONE) if src.attribute is None else resolve_attribute(src.records, src.attribute)[:2]))
     if sum(r.n_records for r in out) > MAX_RECORDS:
         raise ValueError("more than 2^30 records in all")
     if len({r.layout.t_type != T_NONE for r in out}) != 1:
         raise ValueError("a time field in every source or in none")
+    if len({r.attribute[1] != A_NONE for r in out}) != 1:
+        raise ValueError("an attribute in every source or in none")
+    if len({r.attribute[1] for r in out}) != 1:
+        raise ValueError("the same attribute dtype in every source")
     return out
