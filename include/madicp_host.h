@@ -128,7 +128,12 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *   _insert_attr   _insert with the cloud's column attr (n words; null: the cloud carries none, its rows get the word 0 — what
  *                  _insert does on such a map).  On a map made without the column attr is ignored.
  *   _download_attr the words of rows [first_row, rows), _download_f32's conventions; MADICP_ERR_INVALID on a map made without
- *                  the column, out_attr not written. */
+ *                  the column, out_attr not written.
+ *   _prune         the twin of madicp_map_prune (madicp_hip.h has the rule): rows farther than `radius` from `center` leave, with
+ *                  their keys; the kept rows close up in order.  *out_removed rows left, the map holds *out_rows, *out_watermark
+ *                  is the number of kept rows among rows [0, watermark).  MADICP_ERR_INVALID, map unchanged and nothing written,
+ *                  for a null argument, a non-finite center, a radius that is not finite and > 0 or whose square is not finite,
+ *                  a watermark outside [0, rows].  One sequential pass. */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -139,6 +144,8 @@ int madicp_host_map_create_attr(double voxel, int64_t initial_rows, int64_t max_
 int madicp_host_map_insert_attr(madicp_host_map* map, const double* xyz, const uint32_t* attr, int64_t n, const double R[9],
                                 const double t[3], int64_t* out_added, int64_t* out_rows);
 int madicp_host_map_download_attr(const madicp_host_map* map, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_prune(madicp_host_map* map, const double center[3], double radius, int64_t watermark, int64_t* out_removed,
+                          int64_t* out_rows, int64_t* out_watermark);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

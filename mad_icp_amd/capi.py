@@ -175,6 +175,7 @@ def hip_lib():
         L.madicp_map_size.argtypes = [C.c_void_p, C.c_int, _i64p]
         L.madicp_map_download_f32.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_map_clear.argtypes = [C.c_void_p, C.c_int]
+        L.madicp_map_prune.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
@@ -232,6 +233,7 @@ def host_lib():
         L.madicp_host_map_size.argtypes = [C.c_void_p, _i64p]
         L.madicp_host_map_download_f32.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_host_map_clear.argtypes = [C.c_void_p]
+        L.madicp_host_map_prune.argtypes = [C.c_void_p, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_host_ingest_sources_attr.argtypes = [C.POINTER(RecordSourceC), C.c_int, C.POINTER(AttrFieldC), _dp, _dp, _dp, _u32p, _i64p,
                                                       _i64p, _dp]
         L.madicp_host_cloud_export_f32_attr.argtypes = [_dp, _u32p, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), _u32p, C.c_int64,
@@ -645,6 +647,16 @@ def host_map_download_f32(h, first_row=0):
     return out[:got.value].copy()
 
 
+def host_map_prune(h, center, radius, watermark=0):
+    """madicp_host_map_prune: the host twin of Context.map_prune.  Returns (rows removed, rows the map holds, the kept rows among
+    rows [0, watermark))."""
+    c = _f64(center, (3,))
+    removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_prune(h, c.ctypes.data_as(_dp), float(radius), int(watermark), C.byref(removed),
+                                                     C.byref(rows), C.byref(mark)), "madicp_host_map_prune")
+    return removed.value, rows.value, mark.value
+
+
 def host_map_clear(h):
     _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
 
@@ -889,6 +901,16 @@ class Context:
         out, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
         _check(hip_lib().madicp_map_download_f32(self._h, mid, int(first_row), out.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(got)))
         return out[:got.value].copy()
+
+    def map_prune(self, mid, center, radius, watermark=0):
+        """Removes the rows whose stored float position is farther than radius from center (3,), with their voxels; the kept rows
+        close up in order (madicp_map_prune).  Returns (rows removed, rows the map holds, the kept rows among rows [0, watermark)):
+        a consumer that had fetched rows [0, watermark) has fetched exactly rows [0, that) of the pruned map."""
+        c = _f64(center, (3,))
+        removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(hip_lib().madicp_map_prune(self._h, mid, c.ctypes.data_as(_dp), float(radius), int(watermark), C.byref(removed),
+                                          C.byref(rows), C.byref(mark)))
+        return removed.value, rows.value, mark.value
 
     def map_clear(self, mid):
         _check(hip_lib().madicp_map_clear(self._h, mid))

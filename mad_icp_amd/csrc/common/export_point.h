@@ -64,4 +64,24 @@ inline const char* map_create_refusal(double voxel, int64_t initial_rows, int64_
   return nullptr;
 }
 
+// ---- pruning the map (madicp_map_prune / madicp_host_map_prune): rows beyond `radius` of `center` leave, with their keys ------------
+// what both prune entry points refuse (null = nothing to refuse)
+inline const char* map_prune_refusal(const double* center, double radius) {
+  if (!center) return "null argument";
+  for (int i = 0; i < 3; ++i)
+    if (!(center[i] - center[i] == 0.0)) return "center: finite entries";
+  if (!(radius - radius == 0.0) || !(radius > 0.0)) return "radius: finite and > 0";
+  if (!(radius * radius - radius * radius == 0.0)) return "radius: its square must be finite";
+  return nullptr;
+}
+
+// whether a row stays: fp64, from the STORED float row (all a map keeps of a position); r2 = radius * radius, computed once by the
+// caller.  A distance of exactly `radius` stays; a row that fails the comparison for any reason (a NaN or infinite float) leaves.
+MADICP_HD inline bool map_row_kept(const float* row, const double* c, double r2) {
+  const double dx = static_cast<double>(row[0]) - c[0];
+  const double dy = static_cast<double>(row[1]) - c[1];
+  const double dz = static_cast<double>(row[2]) - c[2];
+  return sum3s(dx * dx, dy * dy, dz * dz) <= r2;
+}
+
 }  // namespace madicp_host

@@ -543,5 +543,47 @@ __global__ __launch_bounds__(256) void map_rehash(const unsigned long long* __re
     owner[map_find_or_claim(keys, slots, row_keys[r])] = kMapSettled;
 }
 
+// ---- pruning the map: rows beyond a radius of a centre leave, the kept ones close up in order (madicp_map_prune) -------------------
+// The rule is madicp_host::map_row_kept (csrc/common/export_point.h, shared with the host twin): fp64, from the STORED float row.
+//   map_prune_mark  one lane per row: mark[j] = the row stays; mark[M] = 0, the scan's terminator (as in voxel_mark)
+//   tile scan       over marks and positions of the prune's own (a map is many clouds: not the builder's S / tile_sums)
+//   map_compact     one lane per row: a kept row's stored key, three floats and, where the column exists, its word to row S[j] of the
+//                   DESTINATION block — coalesced reads, monotone writes; whether row j stays is read off the scan, S[j + 1] != S[j],
+//                   so the marks are dead by now and the lane of row 0 leaves {S[M], S[watermark]} in `res` (the caller lays it over
+//                   them): both answers of a prune in one small copy
+// The table is then emptied by the one memset and refilled by map_rehash over the kept keys, which leaves every owner kMapNever or
+// kMapSettled — what the folds rely on.  Determinism: a comparison per row and an exclusive scan; nothing depends on the geometry.
+struct PruneSphere {  // by value, wave-uniform: scalar loads
+  double c[3], r2;
+};
+__global__ __launch_bounds__(256) void map_prune_mark(const float* __restrict__ rows, long n_rows, PruneSphere Q, uint32_t* __restrict__ mark) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j <= n_rows; j += (long)gridDim.x * blockDim.x) {
+    uint32_t m = 0;
+    if (j < n_rows) {
+      const float row[3] = {rows[3 * j], rows[3 * j + 1], rows[3 * j + 2]};
+      m = madicp_host::map_row_kept(row, Q.c, Q.r2) ? 1u : 0u;
+    }
+    mark[j] = m;  // (entry n_rows: the scan needs a terminator)
+  }
+}
+__global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ pos, long n_rows, long watermark,
+                                                   const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
+                                                   const uint32_t* __restrict__ attr, unsigned long long* __restrict__ out_keys,
+                                                   float* __restrict__ out_rows, uint32_t* __restrict__ out_attr, uint32_t* __restrict__ res) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_rows; j += (long)gridDim.x * blockDim.x) {
+    if (j == 0) {
+      res[0] = pos[n_rows];
+      res[1] = pos[watermark];
+    }
+    const long d = pos[j];
+    if ((long)pos[j + 1] == d) continue;
+    out_keys[d] = row_keys[j];
+    out_rows[3 * d] = rows[3 * j];
+    out_rows[3 * d + 1] = rows[3 * j + 1];
+    out_rows[3 * d + 2] = rows[3 * j + 2];
+    if (attr) out_attr[d] = attr[j];
+  }
+}
+
 }  // namespace fe
 }  // namespace madicp

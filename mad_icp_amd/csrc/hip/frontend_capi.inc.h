@@ -1015,7 +1015,7 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
 // refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
 namespace {
 
-int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m) {
+int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
   const size_t c = (size_t)cap;
   char* block = nullptr;
   HIP_TRY(hipMalloc(&block, (m->with_attr ? 48 : 44) * c));
@@ -1027,7 +1027,7 @@ int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m) {
   m->row_keys = reinterpret_cast<unsigned long long*>(block + 24 * c);
   m->xyz = reinterpret_cast<float*>(block + 32 * c);
   m->attr = m->with_attr ? reinterpret_cast<uint32_t*>(block + 44 * c) : nullptr;
-  hipError_t e = hipMemsetAsync(block, 0xff, 24 * c, ctx->copy);
+  hipError_t e = wipe ? hipMemsetAsync(block, 0xff, 24 * c, ctx->copy) : hipSuccess;  // (a prune wipes the table itself, later)
   if (e != hipSuccess) {
     hipFree(block);
     *m = DevMap{};
@@ -1060,6 +1060,56 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
   }
   hipFree(m->block);
   *m = g;
+  return MADICP_OK;
+}
+
+// The rows of *m that stay within sphere Q, closed up in order in a FRESH block of the same capacity — the shape of a growth, and its
+// transient cost: one more block.  The fresh block's table region (24 cap bytes, not yet a table) holds the prune's scratch until
+// the memset that makes it one:   mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)   — 8 (M + 1) + 4 tiles + 4
+// bytes, within 24 cap for every 1 <= M <= cap; the builder's scratch (sized by the largest CLOUD) is not touched.  map_compact
+// leaves {rows kept, kept below the watermark} over the first two marks, which nobody reads after the scan: ONE small copy, ONE
+// synchronisation.  Behind it nothing reads the old block any more: it is freed, the table wiped and refilled from the kept keys
+// on the stream, in front of whatever fold comes next.  Nothing removed: the fresh block is dropped, the map is not touched at all.
+int map_prune_on(madicp_ctx* ctx, DevMap* m, const fe::PruneSphere& Q, int64_t watermark, int64_t* out_kept, int64_t* out_watermark) {
+  const int64_t M = m->rows;
+  DevMap g = *m;
+  RC_TRY(map_block_alloc(ctx, m->cap, &g, false));
+  const int tiles = static_cast<int>((M + 1 + tb::kScanTile - 1) / tb::kScanTile);
+  uint32_t* mark = reinterpret_cast<uint32_t*>(g.block);
+  uint32_t* S = mark + (M + 1);
+  uint32_t* tile_sums = S + (M + 1);
+  int32_t* total = reinterpret_cast<int32_t*>(tile_sums + tiles);
+  const int blocks = grid_256(ctx, M + 1);
+  hipLaunchKernelGGL(fe::map_prune_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const float*)m->xyz, (long)M, Q, mark);
+  hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, tile_sums);
+  hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, ctx->copy, tile_sums, tiles, total);
+  hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
+  hipLaunchKernelGGL(fe::map_compact, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
+                     (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark);
+  uint32_t res[2] = {0, 0};
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(res, mark, sizeof(res), hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy);  // the counts (the old block is read until here)
+  const int64_t kept = res[0];
+  if (e == hipSuccess && kept < M) {
+    e = hipMemsetAsync(g.block, 0xff, 24 * (size_t)g.cap, ctx->copy);
+    if (e == hipSuccess && kept > 0) {
+      hipLaunchKernelGGL(fe::map_rehash, dim3(grid_256(ctx, kept)), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)kept,
+                         g.keys, g.owner, g.slots);
+      e = hipGetLastError();
+    }
+  }
+  if (e != hipSuccess || kept == M) {
+    if (e != hipSuccess) hipStreamSynchronize(ctx->copy);
+    hipFree(g.block);
+    if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map prune: ") + hipGetErrorString(e));
+  } else {
+    hipFree(m->block);
+    g.rows = kept;
+    *m = g;
+  }
+  *out_kept = kept;
+  *out_watermark = res[1];
   return MADICP_OK;
 }
 
@@ -1157,6 +1207,28 @@ int madicp_map_download_attr(madicp_ctx* ctx, int map_id, int64_t first_row, uin
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipMemcpyAsync(out_attr, m->attr + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
   HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
+}
+
+int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double radius, int64_t watermark, int64_t* out_removed,
+                     int64_t* out_rows, int64_t* out_watermark) {
+  if (!ctx || !center || !out_removed || !out_rows || !out_watermark) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (const char* why = madicp_host::map_prune_refusal(center, radius)) return fail(MADICP_ERR_INVALID, why);
+  if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
+  const int64_t before = m->rows;
+  int64_t kept = 0, mark = 0;
+  if (before > 0) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    fe::PruneSphere Q;
+    std::memcpy(Q.c, center, sizeof(Q.c));
+    Q.r2 = radius * radius;
+    RC_TRY(map_prune_on(ctx, m, Q, watermark, &kept, &mark));
+  }
+  *out_removed = before - kept;
+  *out_rows = kept;
+  *out_watermark = mark;
   return MADICP_OK;
 }
 

@@ -232,6 +232,8 @@ void Pipeline::dropMap() {
   }
   map_host_.reset();
   map_overflowed_ = false;
+  map_have_center_ = map_have_last_ = false;
+  map_cursor_ = map_removed_ = 0;
 }
 
 void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute) {
@@ -261,6 +263,12 @@ void Pipeline::foldFrame() {
     const int64_t max_rows = static_cast<int64_t>(map_max_points_);
     const int64_t first_rows = std::min<int64_t>(max_rows, int64_t(1) << 18);
     const bool fresh = map_id_ < 0 && !map_host_;
+    // (b) a fold the capacity rule would refuse: the rows out of range of the frame before this one give way first, once
+    if (map_range_ > 0.0 && !fresh && map_have_last_ && mapSize() + kept_n_ > map_max_points_) {
+      pruneMapAt(map_last_position_, map_range_);
+      std::copy(map_last_position_, map_last_position_ + 3, map_prune_center_);
+      map_have_center_ = true;
+    }
     int64_t added = 0, rows = 0;
     int rc;
     if (fresh ? kept_cloud_id_ >= 0 : map_id_ >= 0) {
@@ -312,8 +320,73 @@ void Pipeline::foldFrame() {
     }
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
     if (rc == MADICP_OK && map_with_attr_ && kept_has_attr_) map_attr_type_ = kept_attr_type_;
+    // (a) the vehicle has moved a quarter of the range since the last prune: squared distances, fp64 — the poses alone decide
+    if (rc == MADICP_OK && map_range_ > 0.0) {
+      const double* p = frame_to_map_.t;
+      const double dx = p[0] - map_prune_center_[0], dy = p[1] - map_prune_center_[1], dz = p[2] - map_prune_center_[2];
+      const double step = map_range_ / 4.0;
+      const bool due = map_have_center_ && dx * dx + (dy * dy + dz * dz) >= step * step;
+      if (due) pruneMapAt(p, map_range_);
+      if (due || !map_have_center_) std::copy(p, p + 3, map_prune_center_);
+      map_have_center_ = true;
+    }
   }
+  std::copy(frame_to_map_.t, frame_to_map_.t + 3, map_last_position_);
+  map_have_last_ = true;
   if (!keep_scan_) dropKeptScan();
+}
+
+void Pipeline::setMapRange(double radius) {
+  if (!std::isfinite(radius) || radius < 0.0 || !std::isfinite(radius * radius))
+    throw std::invalid_argument("Pipeline::setMapRange: radius must be finite and >= 0 (0 = off), and so must its square");
+  map_range_ = radius;
+}
+
+size_t Pipeline::pruneMapAt(const double center[3], double radius) {
+  int64_t removed = 0, rows = 0, mark = 0;
+  if (map_host_) {
+    if (map_host_->prune(center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark) != MADICP_OK)
+      throw std::invalid_argument("Pipeline::mapPrune: center must be finite, radius finite and > 0 with a finite square");
+  } else if (map_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapPrune: the device context the map lived in is gone");
+    const int rc = madicp_map_prune(ctx, map_id_, center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+    if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapPrune: ") + madicp_last_error());
+    check(rc, "madicp_map_prune");
+  } else {  // (no frame folded yet: nothing to remove, but the arguments are held to the same rule)
+    if (map_prune_refusal(center, radius))
+      throw std::invalid_argument("Pipeline::mapPrune: center must be finite, radius finite and > 0 with a finite square");
+  }
+  map_cursor_ = static_cast<size_t>(mark);
+  map_removed_ += static_cast<size_t>(removed);
+  return static_cast<size_t>(removed);
+}
+
+size_t Pipeline::mapPrune(const double center[3], double radius) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapPrune: setMapAccumulation(voxel_size > 0) first");
+  if (!center) throw std::invalid_argument("Pipeline::mapPrune: null center");
+  return pruneMapAt(center, radius);
+}
+
+size_t Pipeline::mapNewRowCount() {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapNewRows: setMapAccumulation(voxel_size > 0) first");
+  return mapSize() - map_cursor_;
+}
+
+size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr) {
+  const size_t m = mapNewRowCount();
+  if (!out) throw std::invalid_argument("Pipeline::mapNewRows: null buffer");
+  if (out_attr && !map_with_attr_)
+    throw std::logic_error("Pipeline::mapNewRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
+  if (capacity < m)
+    throw std::invalid_argument("Pipeline::mapNewRows: the buffer holds " + std::to_string(capacity) + " rows, " + std::to_string(m) +
+                                " are new");
+  if (m == 0) return 0;
+  const size_t got = mapCloud(out, capacity, map_cursor_);
+  if (out_attr) mapAttribute(out_attr, capacity, map_cursor_);
+  map_cursor_ += got;
+  return got;
 }
 
 size_t Pipeline::mapSize() {
@@ -378,6 +451,8 @@ size_t Pipeline::mapAttribute(uint32_t* out, size_t capacity, size_t first_row) 
 void Pipeline::clearMap() {
   if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::clearMap: setMapAccumulation(voxel_size > 0) first");
   map_overflowed_ = false;
+  map_have_center_ = false;
+  map_cursor_ = map_removed_ = 0;
   if (map_host_) map_host_->clear();
   if (map_id_ >= 0) {
     DeviceLock lock(Device::mutex());

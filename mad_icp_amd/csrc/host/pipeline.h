@@ -174,10 +174,36 @@ class Pipeline {
   bool mapOverflowed() const { return map_overflowed_; }
   size_t mapSize();  // rows the map holds; std::logic_error while the option is off (mapCloud and clearMap too)
   // rows [first_row, mapSize()) as float32 (x, y, z) into out[0, 3 * capacity): rows are never changed or removed by a fold, so
-  // a consumer fetches what was added since it last looked with first_row = the size it saw then.  Returns the rows written;
+  // a consumer fetches what was added since it last looked with first_row = the size it saw then (across prunes — setMapRange,
+  // mapPrune — rows move down: mapNewRows below keeps the place instead).  Returns the rows written;
   // std::invalid_argument for a null buffer, first_row > mapSize(), a capacity below mapSize() - first_row (nothing written).
   size_t mapCloud(float* out, size_t capacity, size_t first_row = 0);
-  void clearMap();  // forgets the rows (and the overflow), keeps the memory
+  void clearMap();  // forgets the rows (and the overflow), keeps the memory; mapRemoved() and mapNewRows' cursor start again at 0
+  // additive: A MAP THAT FOLLOWS THE VEHICLE.  setMapRange(radius > 0) — default 0, off: not a launch, not an allocation — lets
+  // foldFrame() PRUNE the map (madicp_map_prune / VoxelMap::prune: rows whose stored float position is farther than radius from
+  // a centre leave, with their voxels, and the kept rows close up in order) at the translation of the frame's pose:
+  //   (a) after a successful fold, when that position is at least radius / 4 from the centre of the last prune (squared
+  //       distances, fp64); the position of the first frame folded while a range is set counts as a prune centre, so a parked
+  //       vehicle never prunes;
+  //   (b) before a fold that the capacity rule would refuse (rows + n > max_points), once, at the position of the frame before
+  //       it; only if the fold is still refused does mapOverflowed() become true.
+  // The policy is a function of the poses alone: both front-ends and every rank of a sharded Pipeline prune identically.  It has
+  // an effect only while setMapAccumulation is on.  std::invalid_argument for a radius that is negative or not finite or whose
+  // square is not finite.  mapPrune: the same operation by hand, returns the rows removed (0 before the first fold);
+  // std::logic_error while accumulation is off, std::invalid_argument for what madicp_map_prune refuses.  mapRemoved(): rows
+  // removed since the map was made or cleared.
+  // mapCloud(first_row) and mapAttribute index the map AS IT IS NOW: a prune moves rows down, so a consumer that streams the map
+  // incrementally across prunes uses mapNewRows instead — the rows (and with out_attr, on a map with the column, their words)
+  // added since its previous call, mapNewRowCount() of them.  The Pipeline keeps that consumer's cursor and hands it through every
+  // prune as the watermark: every row is delivered at most once, whatever was pruned in between.  A row that is added AND pruned
+  // between two calls is never delivered — that happens only with a radius below the sensor's range.  Returns the rows written;
+  // std::invalid_argument for a null buffer or a capacity below mapNewRowCount() (nothing written, the cursor stays).
+  void setMapRange(double radius);
+  double mapRange() const { return map_range_; }  // 0: off
+  size_t mapPrune(const double center[3], double radius);
+  size_t mapRemoved() const { return map_removed_; }
+  size_t mapNewRowCount();
+  size_t mapNewRows(float* out, size_t capacity, uint32_t* out_attr = nullptr);
   // additive: one frame straight from sensor records — float32 (x, y, z, intensity ...) `stride_floats` apart, range
   // filter and optional KITTI correction as in apps/cpp_runners/bin_runner.cpp:126-166 — ingest, deskew, build and
   // registration all on the device (implies the device front-end for this frame)
@@ -344,6 +370,13 @@ class Pipeline {
   unsigned map_generation_ = 0;
   std::unique_ptr<VoxelMap> map_host_;
   void dropMap();
+  // setMapRange: the centre of the last prune and the position of the frame before this one (foldFrame's policy), the consumer's
+  // cursor (mapNewRows) and the rows removed so far
+  double map_range_ = 0.0;
+  double map_prune_center_[3] = {0.0, 0.0, 0.0}, map_last_position_[3] = {0.0, 0.0, 0.0};
+  bool map_have_center_ = false, map_have_last_ = false;
+  size_t map_cursor_ = 0, map_removed_ = 0;
+  size_t pruneMapAt(const double center[3], double radius);  // madicp_map_prune / VoxelMap::prune with the cursor as watermark
   void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;
   int last_rounds_ = 0;

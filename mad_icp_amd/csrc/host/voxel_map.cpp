@@ -60,6 +60,12 @@ int madicp_host_map_download_f32(const madicp_host_map* map, int64_t first_row, 
   return map->map.download(first_row, out_xyz, capacity_rows, out_n);
 }
 
+int madicp_host_map_prune(madicp_host_map* map, const double center[3], double radius, int64_t watermark, int64_t* out_removed,
+                          int64_t* out_rows, int64_t* out_watermark) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.prune(center, radius, watermark, out_removed, out_rows, out_watermark);
+}
+
 int madicp_host_map_clear(madicp_host_map* map) {
   if (!map) return MADICP_ERR_INVALID;
   map->map.clear();

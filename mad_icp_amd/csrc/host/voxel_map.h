@@ -1,5 +1,5 @@
-// The host twin of the device voxel map (csrc/hip/frontend.hip.h: voxel_claim / voxel_mark / voxel_rows / map_rehash): an append-only
-// set of float32 rows, one per voxel, the first point ever to fall into a voxel.  The per-point arithmetic is
+// The host twin of the device voxel map (csrc/hip/frontend.hip.h: voxel_claim / voxel_mark / voxel_rows / map_rehash; map_prune_mark /
+// map_compact): a set of float32 rows that folds append to and prune alone removes from, one per voxel, the first point ever to fall into a voxel.  The per-point arithmetic is
 // csrc/common/export_point.h, shared with the device kernels and the export — the KEY comes from the fp64 position, never from the
 // float that is stored.  "Lowest index of the new points of a key" is the order of one sequential pass here, two integer atomics
 // behind a kernel boundary there: the map is a function of the sequence of (cloud, pose) alone either way.  Header-only, like
@@ -28,6 +28,7 @@ class VoxelMap {
     const size_t first = static_cast<size_t>(std::min(initial_rows, max_rows));
     rows_.reserve(3 * first);
     keys_.reserve(first);
+    row_keys_.reserve(first);
     if (with_attr_) attr_.reserve(first);
   }
   double voxel() const { return voxel_; }
@@ -47,6 +48,7 @@ class VoxelMap {
       const uint64_t key = export_key(q, voxel_);
       if (key == kExportNoKey || !keys_.insert(key).second) continue;
       for (int k = 0; k < 3; ++k) rows_.push_back(export_value(q[k]));
+      row_keys_.push_back(key);
       if (with_attr_) attr_.push_back(attr ? attr[i] : 0u);
     }
     *out_added = size() - before;
@@ -73,9 +75,43 @@ class VoxelMap {
     return kMapOk;
   }
 
+  // include/madicp_host.h: madicp_host_map_prune — rows beyond `radius` of `center` leave (map_row_kept, from the stored float row),
+  // their keys leave the set; the kept rows close up in order, keys and attribute words with them: one sequential stable pass.
+  // *out_watermark: the kept rows among [0, watermark).
+  int prune(const double* center, double radius, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) {
+    if (!center || !out_removed || !out_rows || !out_watermark) return kMapInvalid;
+    if (map_prune_refusal(center, radius)) return kMapInvalid;
+    if (watermark < 0 || watermark > size()) return kMapInvalid;
+    const double r2 = radius * radius;
+    const int64_t m = size();
+    int64_t d = 0, mark = 0;
+    for (int64_t j = 0; j < m; ++j) {
+      if (j == watermark) mark = d;
+      if (!map_row_kept(rows_.data() + 3 * j, center, r2)) {
+        keys_.erase(row_keys_[j]);
+        continue;
+      }
+      if (d != j) {
+        for (int k = 0; k < 3; ++k) rows_[3 * d + k] = rows_[3 * j + k];
+        row_keys_[d] = row_keys_[j];
+        if (with_attr_) attr_[d] = attr_[j];
+      }
+      ++d;
+    }
+    if (watermark == m) mark = d;
+    rows_.resize(3 * static_cast<size_t>(d));
+    row_keys_.resize(static_cast<size_t>(d));
+    if (with_attr_) attr_.resize(static_cast<size_t>(d));
+    *out_removed = m - d;
+    *out_rows = d;
+    *out_watermark = mark;
+    return kMapOk;
+  }
+
   void clear() {  // (keeps the memory, forgets the rows)
     rows_.clear();
     keys_.clear();
+    row_keys_.clear();
     attr_.clear();
   }
 
@@ -85,6 +121,7 @@ class VoxelMap {
   bool with_attr_;
   std::vector<float> rows_;
   std::vector<uint32_t> attr_;
+  std::vector<uint64_t> row_keys_;  // the key of every row (prune erases by it: a float row cannot reproduce its key)
   std::unordered_set<uint64_t> keys_;
 };
 

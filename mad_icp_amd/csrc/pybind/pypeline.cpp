@@ -131,6 +131,40 @@ PYBIND11_MODULE(pypeline, m) {
          },
          py::arg("first_row") = 0, py::arg("with_attribute") = false)
     .def("clearMap", &Pipeline::clearMap)
+    // additive: a map that follows the vehicle (Pipeline::setMapRange).  setMapRange(radius) lets every fold prune the rows farther
+    // than radius from the vehicle once it has moved radius / 4 since the last prune, and before a fold that max_points would
+    // refuse; 0 (the default) turns it off.  mapPrune(center, radius) does it by hand and returns the rows removed; mapRemoved()
+    // counts them.  mapNewRows(with_attribute=False) returns the rows added since the previous call as (M, 3) float32, or
+    // (rows, attr): the incremental consumer's call — across prunes every row is delivered at most once (a row added and pruned
+    // between two calls: never).  ValueError for a radius that is negative or not finite or whose square is not finite, a
+    // non-finite center; RuntimeError (std::logic_error) from mapPrune / mapNewRows while accumulation is off.
+    .def("setMapRange", &Pipeline::setMapRange, py::arg("radius"))
+    .def("mapRange", &Pipeline::mapRange)
+    .def("mapRemoved", &Pipeline::mapRemoved)
+    .def("mapPrune",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> center, double radius) {
+           if (center.size() != 3) throw py::value_error("center must hold 3 values");
+           return self.mapPrune(center.data(), radius);
+         },
+         py::arg("center"), py::arg("radius"))
+    .def("mapNewRows",
+         [](Pipeline& self, bool with_attribute) -> py::object {
+           const size_t m = self.mapNewRowCount();
+           if (with_attribute && !self.mapWithAttribute())
+             throw std::logic_error("Pipeline::mapNewRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
+           py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
+           py::array_t<uint32_t> w(static_cast<py::ssize_t>(with_attribute ? m : 0));
+           float none[3];
+           uint32_t no_word[1];
+           if (self.mapNewRows(m ? out.mutable_data() : none, m, with_attribute ? (m ? w.mutable_data() : no_word) : nullptr) != m)
+             throw std::runtime_error("Pipeline::mapNewRows: the map changed during the call");
+           if (!with_attribute) return std::move(out);
+           const int type = self.mapAttributeType();
+           if (type == madicp_host::kAttrNone) return py::make_tuple(out, w);
+           const py::module_ rec = py::module_::import("mad_icp_amd.records");
+           return py::make_tuple(out, rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]));
+         },
+         py::arg("with_attribute") = false)
     // additive: a frame straight from sensor records, (n, >=3) float32 (a KITTI .bin is (n,4)): range filter, optional
     // KITTI correction (apps/cpp_runners/bin_runner.cpp:126-166), deskew, build and registration on the device
     .def("computeRecords",
