@@ -441,7 +441,7 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  * through (R, t): point i is a CANDIDATE if all three cells are in range (as for the export), NEW if it is a candidate and its
  * key is not in K; of the new points that share a key the one with the LOWEST index is kept; kept points are appended as
  * (float)q[i] in ascending index order and their keys join K.  Rows are never changed or removed by a fold, so rows [0, M) after
- * any fold stay a prefix of the map until a prune (madicp_map_prune, below), and the map is a function of the sequence of (cloud, pose) alone: launch
+ * any fold stay a prefix of the map until a prune or a clearing (madicp_map_prune, madicp_map_clear_rays, below), and the map is a function of the sequence of (cloud, pose) alone: launch
  * geometry, timing, initial_rows and the number of growths do not show.
  *   madicp_map_create        initial_rows >= 1 sizes the first block (44 bytes per row: float row, key, two table slots); blocks
  *                            grow geometrically up to 1 <= max_rows <= 2^30.  MADICP_ERR_INVALID for a null argument, a voxel
@@ -462,7 +462,7 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *   madicp_map_download_attr the words of rows [first_row, rows), madicp_map_download_f32's conventions; MADICP_ERR_INVALID as well
  *                            on a map made without the column, out_attr not written.
  *   madicp_map_clear         forgets the rows, keeps the block.     madicp_map_release  frees everything.
- *   madicp_map_prune         the ONE call that removes rows: row j stays iff its STORED float row is within `radius` of `center` —
+ *   madicp_map_prune         removes rows by RANGE: row j stays iff its STORED float row is within `radius` of `center` —
  *                            dx = (double)row[0] - center[0] ..., dx dx + (dy dy + dz dz) <= radius radius in fp64 without
  *                            contraction (export_point.h: map_row_kept); exactly `radius` stays, a row that fails the comparison
  *                            for any reason leaves.  Kept rows keep their relative order (a stable compaction), their keys and
@@ -477,7 +477,26 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                            not finite, a watermark outside [0, rows].  An empty map answers 0, 0, 0.  The builder's scratch is
  *                            not touched (legal while a look-ahead build is in flight); transiently one more block of the map's
  *                            capacity, as for a growth.  One host synchronisation, whatever the size of the map.
- * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds and prunes. */
+ *   madicp_map_clear_rays    the OTHER call that removes rows: free-space clearing by the rays of a scan.  With qo and q[i] the
+ *                            sensor origin and point i of the cloud taken into the map frame by (R, t) (the export's position rule),
+ *                            d = q[i] - qo per axis and L = sqrt(dx dx + (dy dy + dz dz)), ray i is SAMPLED one voxel edge apart:
+ *                            K = min(floor((L - margin) / voxel), 4096) samples if L is finite and L - margin >= voxel, else none;
+ *                            sample k = 1 .. K is s = qo + d * f per axis, f = (k * voxel) / L — fp64 without contraction
+ *                            (export_point.h: ray_length, ray_sample_count, ray_sample).  The candidate keys of the samples are
+ *                            TRAVERSED, the candidate keys of the end points q[i] are OCCUPIED by this scan — also those of rays
+ *                            that walk nothing (a NaN or infinite point has no key and protects nothing); a sample outside the
+ *                            key range is skipped and the walk goes on.  Row j leaves iff its STORED key is traversed and not
+ *                            occupied.  Sampling is not an exact voxel traversal — a ray can cut a corner between two samples —
+ *                            and a ray ends 4096 samples from the origin: what lies beyond stays.  Kept rows, keys, attribute
+ *                            words, the three answers and the watermark exactly as for madicp_map_prune; the result is a function
+ *                            of (map, cloud, pose, origin, margin) alone.  The cloud is only read.  MADICP_ERR_INVALID, map
+ *                            unchanged and nothing launched, for a null argument, an unknown id, a non-finite R, t or origin, a
+ *                            margin that is not finite and >= 0, a watermark outside [0, rows].  An empty map or an empty cloud
+ *                            answers 0, rows, watermark without a launch.  The builder's scratch is neither used nor grown (legal
+ *                            while a look-ahead build is in flight, and in a context that has only seen small clouds);
+ *                            transiently one more block of the map's capacity.  One host synchronisation, whatever M and n.
+ * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes and
+ * clearings. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
 int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
                             int64_t* out_rows);
@@ -487,6 +506,8 @@ int madicp_map_create_attr(madicp_ctx* ctx, double voxel, int64_t initial_rows, 
 int madicp_map_download_attr(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double radius, int64_t watermark, int64_t* out_removed,
                      int64_t* out_rows, int64_t* out_watermark);
+int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], const double origin[3],
+                          double margin, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

@@ -133,7 +133,12 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  their keys; the kept rows close up in order.  *out_removed rows left, the map holds *out_rows, *out_watermark
  *                  is the number of kept rows among rows [0, watermark).  MADICP_ERR_INVALID, map unchanged and nothing written,
  *                  for a null argument, a non-finite center, a radius that is not finite and > 0 or whose square is not finite,
- *                  a watermark outside [0, rows].  One sequential pass. */
+ *                  a watermark outside [0, rows].  One sequential pass.
+ *   _clear_rays    the twin of madicp_map_clear_rays (madicp_hip.h has the rule): the rays from `origin` to the n points of xyz,
+ *                  all taken into the map frame by (R, t), are sampled one voxel edge apart; a row leaves iff its stored key is
+ *                  the key of a sample and not the key of an end point.  Answers as for _prune.  MADICP_ERR_INVALID, map
+ *                  unchanged and nothing written, for a null argument (xyz may be null when n == 0), n < 0, a non-finite R, t or
+ *                  origin, a margin that is not finite and >= 0, a watermark outside [0, rows].  Two sets and one pass. */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -146,6 +151,9 @@ int madicp_host_map_insert_attr(madicp_host_map* map, const double* xyz, const u
 int madicp_host_map_download_attr(const madicp_host_map* map, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_prune(madicp_host_map* map, const double center[3], double radius, int64_t watermark, int64_t* out_removed,
                           int64_t* out_rows, int64_t* out_watermark);
+int madicp_host_map_clear_rays(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
+                               const double origin[3], double margin, int64_t watermark, int64_t* out_removed, int64_t* out_rows,
+                               int64_t* out_watermark);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

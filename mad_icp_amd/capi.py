@@ -176,6 +176,7 @@ def hip_lib():
         L.madicp_map_download_f32.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_map_clear.argtypes = [C.c_void_p, C.c_int]
         L.madicp_map_prune.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
+        L.madicp_map_clear_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
@@ -234,6 +235,7 @@ def host_lib():
         L.madicp_host_map_download_f32.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
         L.madicp_host_map_clear.argtypes = [C.c_void_p]
         L.madicp_host_map_prune.argtypes = [C.c_void_p, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
+        L.madicp_host_map_clear_rays.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_host_ingest_sources_attr.argtypes = [C.POINTER(RecordSourceC), C.c_int, C.POINTER(AttrFieldC), _dp, _dp, _dp, _u32p, _i64p,
                                                       _i64p, _dp]
         L.madicp_host_cloud_export_f32_attr.argtypes = [_dp, _u32p, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), _u32p, C.c_int64,
@@ -657,6 +659,18 @@ def host_map_prune(h, center, radius, watermark=0):
     return removed.value, rows.value, mark.value
 
 
+def host_map_clear_rays(h, xyz, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, watermark=0):
+    """madicp_host_map_clear_rays: the host twin of Context.map_clear_rays over xyz (n, 3) float64.  Returns (rows removed, rows
+    the map holds, the kept rows among rows [0, watermark))."""
+    a = _f64(xyz).reshape(-1, 3)
+    Rm, tv, o = _f64(R, (9,)), _f64(t, (3,)), _f64(origin, (3,))
+    removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_clear_rays(h, a.ctypes.data_as(_dp), a.shape[0], Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp),
+                                                          o.ctypes.data_as(_dp), float(margin), int(watermark), C.byref(removed),
+                                                          C.byref(rows), C.byref(mark)), "madicp_host_map_clear_rays")
+    return removed.value, rows.value, mark.value
+
+
 def host_map_clear(h):
     _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
 
@@ -910,6 +924,17 @@ class Context:
         removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _check(hip_lib().madicp_map_prune(self._h, mid, c.ctypes.data_as(_dp), float(radius), int(watermark), C.byref(removed),
                                           C.byref(rows), C.byref(mark)))
+        return removed.value, rows.value, mark.value
+
+    def map_clear_rays(self, mid, cid, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, watermark=0):
+        """Free-space clearing (madicp_map_clear_rays): the rays from origin (3,) to the points of resident cloud cid, taken into
+        the map frame by (R (3, 3), t (3,)), are sampled one voxel edge apart, stopping margin short of the point; the rows whose
+        voxel a sample falls in and no point of the cloud lies in leave, the kept rows close up in order.  The cloud is only read.
+        Returns (rows removed, rows the map holds, the kept rows among rows [0, watermark))."""
+        Rm, tv, o = _f64(R, (9,)), _f64(t, (3,)), _f64(origin, (3,))
+        removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _check(hip_lib().madicp_map_clear_rays(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), o.ctypes.data_as(_dp),
+                                               float(margin), int(watermark), C.byref(removed), C.byref(rows), C.byref(mark)))
         return removed.value, rows.value, mark.value
 
     def map_clear(self, mid):

@@ -84,4 +84,50 @@ MADICP_HD inline bool map_row_kept(const float* row, const double* c, double r2)
   return sum3s(dx * dx, dy * dy, dz * dz) <= r2;
 }
 
+// ---- clearing the map by a scan's rays (madicp_map_clear_rays / madicp_host_map_clear_rays): rows that a ray passes through leave ---
+// A ray runs from the sensor origin qo to a point q of the scan, both in the map frame (export_position).  It is SAMPLED one voxel
+// edge apart — sample k = 1 .. K sits k * voxel along it — which is not an exact voxel traversal: a ray can cut a voxel's corner
+// between two samples.  That is the rule.  Everything fp64, no contraction:
+//   d[a] = q[a] - qo[a],  L = sqrt(dx dx + (dy dy + dz dz))
+//   K    = min(floor((L - margin) / voxel), kRayMaxSamples) if L is finite and L - margin >= voxel, else 0 (ray_sample_count)
+//   s[a] = qo[a] + d[a] * f,  f = (k * voxel) / L — three separate operations per axis (ray_sample)
+// The candidate keys of the samples are TRAVERSED (T), the candidate keys of the end points are OCCUPIED by this scan (O); a row
+// leaves iff its STORED key is in T \ O.  A sample outside the key range is skipped, the walk goes on behind it.
+constexpr int kRayMaxSamples = 4096;  // bounds the work of one ray: the voxels beyond kRayMaxSamples * voxel of the origin stay
+
+// what both entry points refuse (null = nothing to refuse): export_refusal's conditions on R and t, a finite origin and margin >= 0
+inline const char* map_clear_refusal(const double* R, const double* t, const double* origin, double margin) {
+  if (!R || !t || !origin) return "null argument";
+  if (const char* why = export_refusal(R, t, 1.0)) return why;
+  for (int i = 0; i < 3; ++i)
+    if (!(origin[i] - origin[i] == 0.0)) return "origin: finite entries";
+  if (!(margin - margin == 0.0) || margin < 0.0) return "margin: finite and >= 0";
+  return nullptr;
+}
+
+// d = q - qo and the length of the ray
+MADICP_HD inline double ray_length(const double* qo, const double* q, double* d) {
+  d[0] = q[0] - qo[0];
+  d[1] = q[1] - qo[1];
+  d[2] = q[2] - qo[2];
+  return sqrt(sum3s(d[0] * d[0], d[1] * d[1], d[2] * d[2]));
+}
+
+// samples a ray of length L walks: 0 for a NaN or infinite length and for one below voxel + margin
+MADICP_HD inline int ray_sample_count(double L, double margin, double voxel) {
+  if (!(L - L == 0.0)) return 0;
+  const double reach = L - margin;
+  if (!(reach >= voxel)) return 0;
+  const double k = floor(reach / voxel);
+  return k < static_cast<double>(kRayMaxSamples) ? static_cast<int>(k) : kRayMaxSamples;
+}
+
+// sample k (1 .. K) of the ray
+MADICP_HD inline void ray_sample(const double* qo, const double* d, double L, int k, double voxel, double* s) {
+  const double f = (static_cast<double>(k) * voxel) / L;
+  s[0] = qo[0] + d[0] * f;
+  s[1] = qo[1] + d[1] * f;
+  s[2] = qo[2] + d[2] * f;
+}
+
 }  // namespace madicp_host

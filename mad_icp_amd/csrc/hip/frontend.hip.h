@@ -585,5 +585,87 @@ __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ 
   }
 }
 
+// ---- clearing the map by a scan's rays: rows whose voxel a ray passes through and no point of the scan lies in leave ----------------
+// (madicp_map_clear_rays).  The rule is csrc/common/export_point.h's, shared with the host twin: ray_length, ray_sample_count,
+// ray_sample, export_key.  A second way to produce the marks of a prune; behind them everything is the prune's.
+//   ray_flags       ONE WAVEFRONT PER RAY: lane l takes the samples k = l + 1, l + 65, ... of the ray, so a wavefront's time is its own
+//                   ray's length / 64 and rays of 2 m and 80 m side by side in the cloud do not wait for each other; lane 0 also takes
+//                   the end point.  A key is looked up in the LIVE table with map_find — the table is only read: a key that is not in
+//                   it owns no row and is skipped — and its bit set in `flags`, one 32-bit word per table slot in scratch of the call's
+//                   own: bit 0 traversed, bit 1 occupied.  A lane whose key equals its left neighbour's (sample k - 1; lane 0: lane 63
+//                   of the pass before) skips the probe: that lane does it.
+//   map_clear_mark  one lane per row: the slot of the row's stored key (always present), mark[j] = the row stays = its flags are not
+//                   exactly "traversed"; mark[M] = 0, the scan's terminator
+// Determinism: the flags are ORs of bits, which commute, read only behind a kernel boundary; the table is not written.  Nothing
+// depends on the geometry or on timing.  Contention: a relaxed agent-scope load in front of each atomicOr skips it once the bit is
+// there (bits are only ever set, so a stale value costs one atomic and nothing else); all rays through ONE voxel serialise on one
+// word for the first wavefronts and read the bit afterwards.  Termination: the table is at most half full, so a probe meets an empty
+// slot or its key; a ray walks at most kRayMaxSamples samples.
+constexpr uint32_t kRayTraversed = 1u, kRayOccupied = 2u;
+__device__ inline uint32_t map_find(const unsigned long long* __restrict__ keys, uint32_t slots, unsigned long long key) {
+  uint32_t s = export_slot0(key, slots);
+  for (;;) {
+    const unsigned long long seen = keys[s];
+    if (seen == key) return s;
+    if (seen == madicp_host::kExportNoKey) return kExportNoSlot;
+    s = (s + 1 == slots) ? 0u : s + 1;
+  }
+}
+__device__ inline void ray_flag(uint32_t* __restrict__ flags, uint32_t slot, uint32_t bit) {
+  if (!(__hip_atomic_load(&flags[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(&flags[slot], bit);
+}
+struct RayFrame {  // by value, wave-uniform: scalar loads
+  ExportPose X;
+  double o[3], margin;  // the sensor origin in the cloud's frame
+};
+__global__ __launch_bounds__(256) void ray_flags(const double* __restrict__ xyz, long n, RayFrame F, double voxel,
+                                                 const unsigned long long* __restrict__ keys, uint32_t slots, uint32_t* __restrict__ flags) {
+  const int lane = threadIdx.x & 63;
+  const long waves = ((long)gridDim.x * blockDim.x) >> 6;
+  double qo[3];
+  madicp_host::export_position(F.o, F.X.R, F.X.t, qo);
+  for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n; i += waves) {  // (wave-uniform)
+    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    double q[3], d[3];
+    madicp_host::export_position(p, F.X.R, F.X.t, q);
+    if (lane == 0) {
+      const unsigned long long end = madicp_host::export_key(q, voxel);
+      const uint32_t s = end != madicp_host::kExportNoKey ? map_find(keys, slots, end) : kExportNoSlot;
+      if (s != kExportNoSlot) ray_flag(flags, s, kRayOccupied);
+    }
+    const double L = madicp_host::ray_length(qo, q, d);
+    const int K = madicp_host::ray_sample_count(L, F.margin, voxel);
+    unsigned long long carry = madicp_host::kExportNoKey;  // the key of sample k0 (lane 63 of the pass before)
+    for (int k0 = 0; k0 < K; k0 += 64) {  // (wave-uniform bounds: the shuffles below see every lane)
+      const int k = k0 + lane + 1;
+      unsigned long long key = madicp_host::kExportNoKey;
+      if (k <= K) {
+        double s[3];
+        madicp_host::ray_sample(qo, d, L, k, voxel, s);
+        key = madicp_host::export_key(s, voxel);
+      }
+      unsigned long long left = __shfl_up(key, 1);
+      if (lane == 0) left = carry;
+      carry = __shfl(key, 63);
+      if (key != madicp_host::kExportNoKey && key != left) {
+        const uint32_t slot = map_find(keys, slots, key);
+        if (slot != kExportNoSlot) ray_flag(flags, slot, kRayTraversed);
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void map_clear_mark(const unsigned long long* __restrict__ row_keys, long n_rows,
+                                                      const unsigned long long* __restrict__ keys, uint32_t slots,
+                                                      const uint32_t* __restrict__ flags, uint32_t* __restrict__ mark) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j <= n_rows; j += (long)gridDim.x * blockDim.x) {
+    uint32_t m = 0;
+    if (j < n_rows) {
+      const uint32_t s = map_find(keys, slots, row_keys[j]);
+      m = (s == kExportNoSlot || (flags[s] & (kRayTraversed | kRayOccupied)) != kRayTraversed) ? 1u : 0u;
+    }
+    mark[j] = m;  // (entry n_rows: the scan needs a terminator)
+  }
+}
+
 }  // namespace fe
 }  // namespace madicp

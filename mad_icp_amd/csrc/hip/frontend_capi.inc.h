@@ -1063,28 +1063,21 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
   return MADICP_OK;
 }
 
-// The rows of *m that stay within sphere Q, closed up in order in a FRESH block of the same capacity — the shape of a growth, and its
-// transient cost: one more block.  The fresh block's table region (24 cap bytes, not yet a table) holds the prune's scratch until
-// the memset that makes it one:   mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)   — 8 (M + 1) + 4 tiles + 4
-// bytes, within 24 cap for every 1 <= M <= cap; the builder's scratch (sized by the largest CLOUD) is not touched.  map_compact
-// leaves {rows kept, kept below the watermark} over the first two marks, which nobody reads after the scan: ONE small copy, ONE
-// synchronisation.  Behind it nothing reads the old block any more: it is freed, the table wiped and refilled from the kept keys
-// on the stream, in front of whatever fold comes next.  Nothing removed: the fresh block is dropped, the map is not touched at all.
-int map_prune_on(madicp_ctx* ctx, DevMap* m, const fe::PruneSphere& Q, int64_t watermark, int64_t* out_kept, int64_t* out_watermark) {
+// The tail every removal shares (madicp_map_prune, madicp_map_clear_rays).  The caller has allocated the FRESH block g of the same
+// capacity — the shape of a growth, and its transient cost: one more block — and enqueued the kernel that leaves mark[0 .. M] in g's
+// table region (24 cap bytes, not yet a table); here: the tile scan of the marks into S, map_compact into g, which leaves {rows kept,
+// kept below the watermark} over the first two marks, which nobody reads after the scan: ONE small copy, ONE synchronisation.
+// Behind it nothing reads the old block any more: it is freed, the table wiped and refilled from the kept keys on the stream, in
+// front of whatever fold comes next.  Nothing removed: the fresh block is dropped, the map is not touched at all.
+int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uint32_t* S, uint32_t* tile_sums, int64_t watermark,
+                      const char* what, int64_t* out_kept, int64_t* out_watermark) {
   const int64_t M = m->rows;
-  DevMap g = *m;
-  RC_TRY(map_block_alloc(ctx, m->cap, &g, false));
   const int tiles = static_cast<int>((M + 1 + tb::kScanTile - 1) / tb::kScanTile);
-  uint32_t* mark = reinterpret_cast<uint32_t*>(g.block);
-  uint32_t* S = mark + (M + 1);
-  uint32_t* tile_sums = S + (M + 1);
   int32_t* total = reinterpret_cast<int32_t*>(tile_sums + tiles);
-  const int blocks = grid_256(ctx, M + 1);
-  hipLaunchKernelGGL(fe::map_prune_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const float*)m->xyz, (long)M, Q, mark);
   hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, tile_sums);
   hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, ctx->copy, tile_sums, tiles, total);
   hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
-  hipLaunchKernelGGL(fe::map_compact, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
+  hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
                      (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark);
   uint32_t res[2] = {0, 0};
   hipError_t e = hipGetLastError();
@@ -1102,7 +1095,7 @@ int map_prune_on(madicp_ctx* ctx, DevMap* m, const fe::PruneSphere& Q, int64_t w
   if (e != hipSuccess || kept == M) {
     if (e != hipSuccess) hipStreamSynchronize(ctx->copy);
     hipFree(g.block);
-    if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map prune: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string(what) + hipGetErrorString(e));
   } else {
     hipFree(m->block);
     g.rows = kept;
@@ -1111,6 +1104,43 @@ int map_prune_on(madicp_ctx* ctx, DevMap* m, const fe::PruneSphere& Q, int64_t w
   *out_kept = kept;
   *out_watermark = res[1];
   return MADICP_OK;
+}
+
+// The rows of *m that stay within sphere Q.  The fresh block's table region holds the prune's scratch until the memset that makes
+// it a table:   mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)   — 8 (M + 1) + 4 tiles + 4 bytes, within 24 cap
+// for every 1 <= M <= cap; the builder's scratch (sized by the largest CLOUD) is not touched.
+int map_prune_on(madicp_ctx* ctx, DevMap* m, const fe::PruneSphere& Q, int64_t watermark, int64_t* out_kept, int64_t* out_watermark) {
+  const int64_t M = m->rows;
+  DevMap g = *m;
+  RC_TRY(map_block_alloc(ctx, m->cap, &g, false));
+  uint32_t* mark = reinterpret_cast<uint32_t*>(g.block);
+  uint32_t* S = mark + (M + 1);
+  hipLaunchKernelGGL(fe::map_prune_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const float*)m->xyz, (long)M, Q, mark);
+  return map_remove_marked(ctx, m, g, mark, S, S + (M + 1), watermark, "voxel map prune: ", out_kept, out_watermark);
+}
+
+// The rows of *m that the rays of cloud c do not clear.  The fresh block's table region, until the memset that makes it a table:
+//   flags (2 cap words: one per slot of the LIVE table, zeroed by the one memset) | mark (M + 1) | tile_sums (tiles) | total (1)
+// and S (M + 1 <= 2 cap words) is laid over the flags, which are dead once map_clear_mark has run: 8 cap + 4 (M + 1) + 4 tiles + 4
+// bytes, within 24 cap for every 1 <= M <= cap (cap = 1: 8 + 8 + 4 + 4 = 24).  The live table is only read; the builder's scratch
+// is not touched.
+int map_clear_rays_on(madicp_ctx* ctx, DevMap* m, const DevCloud* c, const fe::RayFrame& F, int64_t watermark, int64_t* out_kept,
+                      int64_t* out_watermark) {
+  const int64_t M = m->rows;
+  DevMap g = *m;
+  RC_TRY(map_block_alloc(ctx, m->cap, &g, false));
+  uint32_t* flags = reinterpret_cast<uint32_t*>(g.block);
+  uint32_t* mark = flags + 2 * (size_t)m->cap;
+  const hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * 2 * (size_t)m->cap, ctx->copy);
+  if (e != hipSuccess) {
+    hipFree(g.block);
+    return fail(MADICP_ERR_DEVICE, std::string("voxel map clearing: ") + hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(fe::ray_flags, dim3(grid_256(ctx, 64 * c->n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)c->n, F, m->voxel,
+                     (const unsigned long long*)m->keys, m->slots, flags);
+  hipLaunchKernelGGL(fe::map_clear_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys, (long)M,
+                     (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, mark);
+  return map_remove_marked(ctx, m, g, mark, flags, mark + (M + 1), watermark, "voxel map clearing: ", out_kept, out_watermark);
 }
 
 DevMap* find_map(madicp_ctx* ctx, int id) {
@@ -1225,6 +1255,31 @@ int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double
     std::memcpy(Q.c, center, sizeof(Q.c));
     Q.r2 = radius * radius;
     RC_TRY(map_prune_on(ctx, m, Q, watermark, &kept, &mark));
+  }
+  *out_removed = before - kept;
+  *out_rows = kept;
+  *out_watermark = mark;
+  return MADICP_OK;
+}
+
+int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], const double origin[3],
+                          double margin, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) {
+  if (!ctx || !R || !t || !origin || !out_removed || !out_rows || !out_watermark) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (const char* why = madicp_host::map_clear_refusal(R, t, origin, margin)) return fail(MADICP_ERR_INVALID, why);
+  if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
+  const int64_t before = m->rows;
+  int64_t kept = before, mark = watermark;
+  if (before > 0 && c->n > 0) {  // (an empty map or an empty cloud: nothing can leave, nothing is launched)
+    HIP_TRY(hipSetDevice(ctx->device));
+    fe::RayFrame F;
+    F.X = export_pose(R, t);
+    std::memcpy(F.o, origin, sizeof(F.o));
+    F.margin = margin;
+    RC_TRY(map_clear_rays_on(ctx, m, c, F, watermark, &kept, &mark));
   }
   *out_removed = before - kept;
   *out_rows = kept;

@@ -295,8 +295,19 @@ void Pipeline::foldFrame() {
         }
       }
       rc = madicp_map_insert_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, &added, &rows);
+      // setMapClearing: what the cloud just folded sees through leaves, before the range prune below
+      int64_t removed = 0, mark = 0;
+      int crc = MADICP_OK;
+      if (rc == MADICP_OK && map_clearing_)
+        crc = madicp_map_clear_rays(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, map_clear_origin_, map_clear_margin_,
+                                    static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
       if (kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_insert_cloud");
+      check(crc, "madicp_map_clear_rays");
+      if (rc == MADICP_OK && map_clearing_) {
+        map_cursor_ = static_cast<size_t>(mark);
+        map_removed_ += static_cast<size_t>(removed);
+      }
     } else {
       if (fresh) map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_);
       ContainerType down;  // (a resident scan into a host map: the front-end was switched — its column crosses with it)
@@ -317,6 +328,14 @@ void Pipeline::foldFrame() {
       rc = map_host_->insert(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, &added,
                              &rows, (kept_has_attr_ && a.size() == c.size()) ? a.data() : nullptr);
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline: the host voxel map refused its arguments");
+      if (rc == MADICP_OK && map_clearing_) {
+        int64_t removed = 0, mark = 0;
+        if (map_host_->clearRays(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t,
+                                 map_clear_origin_, map_clear_margin_, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark) != MADICP_OK)
+          throw std::runtime_error("Pipeline: the host voxel map refused the clearing's arguments");
+        map_cursor_ = static_cast<size_t>(mark);
+        map_removed_ += static_cast<size_t>(removed);
+      }
     }
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
     if (rc == MADICP_OK && map_with_attr_ && kept_has_attr_) map_attr_type_ = kept_attr_type_;
@@ -367,6 +386,42 @@ size_t Pipeline::mapPrune(const double center[3], double radius) {
   if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapPrune: setMapAccumulation(voxel_size > 0) first");
   if (!center) throw std::invalid_argument("Pipeline::mapPrune: null center");
   return pruneMapAt(center, radius);
+}
+
+void Pipeline::setMapClearing(bool on, double margin, const double origin[3]) {
+  const double zero[3] = {0.0, 0.0, 0.0};
+  const double* o = origin ? origin : zero;
+  if (!std::isfinite(margin) || margin < 0.0) throw std::invalid_argument("Pipeline::setMapClearing: margin must be finite and >= 0");
+  if (!std::isfinite(o[0]) || !std::isfinite(o[1]) || !std::isfinite(o[2]))
+    throw std::invalid_argument("Pipeline::setMapClearing: origin must be finite");
+  map_clearing_ = on;
+  map_clear_margin_ = margin;
+  std::copy(o, o + 3, map_clear_origin_);
+}
+
+size_t Pipeline::mapClearRays(const double* xyz, size_t n, const double R[9], const double t[3], const double origin[3], double margin) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapClearRays: setMapAccumulation(voxel_size > 0) first");
+  if ((!xyz && n > 0) || !R || !t || !origin) throw std::invalid_argument("Pipeline::mapClearRays: null argument");
+  if (const char* why = map_clear_refusal(R, t, origin, margin)) throw std::invalid_argument(std::string("Pipeline::mapClearRays: ") + why);
+  int64_t removed = 0, rows = 0, mark = static_cast<int64_t>(map_cursor_);
+  if (map_host_) {
+    if (map_host_->clearRays(xyz, static_cast<int64_t>(n), R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark) !=
+        MADICP_OK)
+      throw std::invalid_argument("Pipeline::mapClearRays: the host voxel map refused its arguments");
+  } else if (map_id_ >= 0 && n > 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapClearRays: the device context the map lived in is gone");
+    int cloud_id = -1;
+    check(madicp_cloud_upload(ctx, xyz, static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
+    const int rc = madicp_map_clear_rays(ctx, map_id_, cloud_id, R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+    madicp_cloud_release(ctx, cloud_id);
+    if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapClearRays: ") + madicp_last_error());
+    check(rc, "madicp_map_clear_rays");
+  }  // (no frame folded yet, or no ray: nothing to remove)
+  map_cursor_ = static_cast<size_t>(mark);
+  map_removed_ += static_cast<size_t>(removed);
+  return static_cast<size_t>(removed);
 }
 
 size_t Pipeline::mapNewRowCount() {

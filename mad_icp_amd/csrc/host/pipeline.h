@@ -204,6 +204,20 @@ class Pipeline {
   size_t mapRemoved() const { return map_removed_; }
   size_t mapNewRowCount();
   size_t mapNewRows(float* out, size_t capacity, uint32_t* out_attr = nullptr);
+  // additive: FREE-SPACE CLEARING.  setMapClearing(true) — default off: not a launch, not an allocation, the same pose bits — lets
+  // foldFrame() call madicp_map_clear_rays / VoxelMap::clearRays after every successful fold and before the range prune (a), with
+  // the cloud it has just folded, the frame's pose and `origin`, the sensor's position in the cloud's frame: the rows whose voxel a
+  // ray of the scan is sampled in (one voxel edge apart, stopping `margin` metres short of the point) and no point of the scan lies
+  // in leave, with their voxels — what moved through the scene does not stay in the map.  mapNewRows' cursor is the watermark, as
+  // for a prune; mapRemoved() counts both kinds of removal.  It has an effect only while setMapAccumulation is on.  The rule
+  // samples, it does not traverse: shallow rays over ground that the scan samples sparsely remove ground voxels between the rings —
+  // margin and the voxel size are the consumer's knobs.  std::invalid_argument for a margin that is negative or not finite, a
+  // non-finite origin (null: the cloud's origin).  mapClearRays: the same operation by hand over n points xyz (n, 3) at pose
+  // (R, t), returns the rows removed (0 before the first fold); std::logic_error while accumulation is off, std::invalid_argument
+  // for what madicp_map_clear_rays refuses.
+  void setMapClearing(bool on, double margin = 0.0, const double origin[3] = nullptr);
+  bool mapClearing() const { return map_clearing_; }
+  size_t mapClearRays(const double* xyz, size_t n, const double R[9], const double t[3], const double origin[3], double margin = 0.0);
   // additive: one frame straight from sensor records — float32 (x, y, z, intensity ...) `stride_floats` apart, range
   // filter and optional KITTI correction as in apps/cpp_runners/bin_runner.cpp:126-166 — ingest, deskew, build and
   // registration all on the device (implies the device front-end for this frame)
@@ -376,6 +390,8 @@ class Pipeline {
   double map_prune_center_[3] = {0.0, 0.0, 0.0}, map_last_position_[3] = {0.0, 0.0, 0.0};
   bool map_have_center_ = false, map_have_last_ = false;
   size_t map_cursor_ = 0, map_removed_ = 0;
+  bool map_clearing_ = false;  // setMapClearing
+  double map_clear_margin_ = 0.0, map_clear_origin_[3] = {0.0, 0.0, 0.0};
   size_t pruneMapAt(const double center[3], double radius);  // madicp_map_prune / VoxelMap::prune with the cursor as watermark
   void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;

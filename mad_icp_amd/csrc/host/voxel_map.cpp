@@ -66,6 +66,13 @@ int madicp_host_map_prune(madicp_host_map* map, const double center[3], double r
   return map->map.prune(center, radius, watermark, out_removed, out_rows, out_watermark);
 }
 
+int madicp_host_map_clear_rays(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
+                               const double origin[3], double margin, int64_t watermark, int64_t* out_removed, int64_t* out_rows,
+                               int64_t* out_watermark) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.clearRays(xyz, n, R, t, origin, margin, watermark, out_removed, out_rows, out_watermark);
+}
+
 int madicp_host_map_clear(madicp_host_map* map) {
   if (!map) return MADICP_ERR_INVALID;
   map->map.clear();

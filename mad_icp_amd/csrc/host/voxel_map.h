@@ -1,5 +1,5 @@
 // The host twin of the device voxel map (csrc/hip/frontend.hip.h: voxel_claim / voxel_mark / voxel_rows / map_rehash; map_prune_mark /
-// map_compact): a set of float32 rows that folds append to and prune alone removes from, one per voxel, the first point ever to fall into a voxel.  The per-point arithmetic is
+// map_compact; ray_flags / map_clear_mark): a set of float32 rows that folds append to and prune and clearRays alone remove from, one per voxel, the first point ever to fall into a voxel.  The per-point arithmetic is
 // csrc/common/export_point.h, shared with the device kernels and the export — the KEY comes from the fp64 position, never from the
 // float that is stored.  "Lowest index of the new points of a key" is the order of one sequential pass here, two integer atomics
 // behind a kernel boundary there: the map is a function of the sequence of (cloud, pose) alone either way.  Header-only, like
@@ -83,11 +83,62 @@ class VoxelMap {
     if (map_prune_refusal(center, radius)) return kMapInvalid;
     if (watermark < 0 || watermark > size()) return kMapInvalid;
     const double r2 = radius * radius;
+    close_up([&](int64_t j) { return map_row_kept(rows_.data() + 3 * j, center, r2); }, watermark, out_removed, out_rows, out_watermark);
+    return kMapOk;
+  }
+
+  // include/madicp_host.h: madicp_host_map_clear_rays — the rays of a scan (export_point.h: ray_length / ray_sample_count / ray_sample)
+  // from `origin` to every point of the cloud, both taken into the map frame by (R, t): the candidate keys of the samples are
+  // traversed, those of the end points occupied; a row leaves iff its STORED key is traversed and not occupied.  Two sets, then
+  // prune's stable pass.
+  int clearRays(const double* xyz, int64_t n, const double* R, const double* t, const double* origin, double margin, int64_t watermark,
+                int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) {
+    if (!out_removed || !out_rows || !out_watermark || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
+    if (map_clear_refusal(R, t, origin, margin)) return kMapInvalid;
+    if (watermark < 0 || watermark > size()) return kMapInvalid;
+    std::unordered_set<uint64_t> traversed, occupied;
+    if (size() > 0 && n > 0) {
+      double qo[3];
+      export_position(origin, R, t, qo);
+      for (int64_t i = 0; i < n; ++i) {
+        double q[3], d[3], s[3];
+        export_position(xyz + 3 * i, R, t, q);
+        const uint64_t end = export_key(q, voxel_);
+        if (end != kExportNoKey) occupied.insert(end);
+        const double L = ray_length(qo, q, d);
+        const int K = ray_sample_count(L, margin, voxel_);
+        uint64_t last = kExportNoKey;
+        for (int k = 1; k <= K; ++k) {
+          ray_sample(qo, d, L, k, voxel_, s);
+          const uint64_t key = export_key(s, voxel_);
+          if (key == last || key == kExportNoKey) continue;
+          last = key;
+          if (keys_.count(key)) traversed.insert(key);  // (a key that owns no row cannot remove one)
+        }
+      }
+    }
+    close_up([&](int64_t j) { return !traversed.count(row_keys_[j]) || occupied.count(row_keys_[j]); }, watermark, out_removed, out_rows,
+             out_watermark);
+    return kMapOk;
+  }
+
+  void clear() {  // (keeps the memory, forgets the rows)
+    rows_.clear();
+    keys_.clear();
+    row_keys_.clear();
+    attr_.clear();
+  }
+
+ private:
+  // the one way rows leave: row j stays iff kept(j); the kept rows close up in order, keys and attribute words with them, the keys
+  // of the others leave the set.  *out_watermark: the kept rows among [0, watermark).
+  template <class Kept>
+  void close_up(Kept kept, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) {
     const int64_t m = size();
     int64_t d = 0, mark = 0;
     for (int64_t j = 0; j < m; ++j) {
       if (j == watermark) mark = d;
-      if (!map_row_kept(rows_.data() + 3 * j, center, r2)) {
+      if (!kept(j)) {
         keys_.erase(row_keys_[j]);
         continue;
       }
@@ -105,17 +156,8 @@ class VoxelMap {
     *out_removed = m - d;
     *out_rows = d;
     *out_watermark = mark;
-    return kMapOk;
   }
 
-  void clear() {  // (keeps the memory, forgets the rows)
-    rows_.clear();
-    keys_.clear();
-    row_keys_.clear();
-    attr_.clear();
-  }
-
- private:
   double voxel_;
   int64_t max_rows_;
   bool with_attr_;

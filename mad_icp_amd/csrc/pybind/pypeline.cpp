@@ -147,6 +147,31 @@ PYBIND11_MODULE(pypeline, m) {
            return self.mapPrune(center.data(), radius);
          },
          py::arg("center"), py::arg("radius"))
+    // additive: free-space clearing (Pipeline::setMapClearing).  setMapClearing(on, margin=0, origin=(0, 0, 0)) lets every fold
+    // remove the rows whose voxel a ray of the folded scan is sampled in and no point of that scan lies in; off by default.
+    // mapClearRays(cloud (n, 3), pose (4, 4), origin=(0, 0, 0), margin=0) does it by hand and returns the rows removed;
+    // mapRemoved() counts prunes and clearings together.  ValueError for a margin that is negative or not finite, a non-finite
+    // origin or pose; RuntimeError (std::logic_error) from mapClearRays while accumulation is off.
+    .def("setMapClearing",
+         [](Pipeline& self, bool on, double margin, py::array_t<double, py::array::c_style | py::array::forcecast> origin) {
+           if (origin.size() != 3) throw py::value_error("origin must hold 3 values");
+           self.setMapClearing(on, margin, origin.data());
+         },
+         py::arg("on"), py::arg("margin") = 0.0, py::arg("origin") = std::vector<double>{0.0, 0.0, 0.0})
+    .def("mapClearing", &Pipeline::mapClearing)
+    .def("mapClearRays",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> pose,
+            py::array_t<double, py::array::c_style | py::array::forcecast> origin, double margin) {
+           if (cloud.ndim() != 2 || cloud.shape(1) != 3) throw py::value_error("cloud must be (n, 3)");
+           if (pose.ndim() != 2 || pose.shape(0) != 4 || pose.shape(1) != 4) throw py::value_error("pose must be (4, 4)");
+           if (origin.size() != 3) throw py::value_error("origin must hold 3 values");
+           const double* T = pose.data();
+           const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+           const double t[3] = {T[3], T[7], T[11]};
+           return self.mapClearRays(cloud.data(), static_cast<size_t>(cloud.shape(0)), R, t, origin.data(), margin);
+         },
+         py::arg("cloud"), py::arg("pose"), py::arg("origin") = std::vector<double>{0.0, 0.0, 0.0}, py::arg("margin") = 0.0)
     .def("mapNewRows",
          [](Pipeline& self, bool with_attribute) -> py::object {
            const size_t m = self.mapNewRowCount();
