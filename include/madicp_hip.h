@@ -495,8 +495,38 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                            answers 0, rows, watermark without a launch.  The builder's scratch is neither used nor grown (legal
  *                            while a look-ahead build is in flight, and in a context that has only seen small clouds);
  *                            transiently one more block of the map's capacity.  One host synchronisation, whatever M and n.
- * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes and
- * clearings. */
+ * THE REMOVAL LOG — how a consumer that mirrors the map learns which rows have left.  A map is TRACKING REMOVALS or not (not: the
+ * default, and everything above as it is: no launch, no allocation, no synchronisation more).  On a tracking map every
+ * madicp_map_prune or madicp_map_clear_rays that removes rows appends the removed rows with index below `watermark` — exactly the
+ * rows that the consumer who passed this watermark has fetched — to the map's removal log, in row order: one entry is the row's
+ * stored key (uint64: unique among live rows, the identity a consumer can hold — an index moves at a prune, equal float rows can
+ * have different keys), its three stored floats and, on a map with the attribute column, its word.  Removed rows at or above the
+ * watermark are not logged: they were never delivered.  The call adds exactly watermark - *out_watermark entries, so the host
+ * knows the log's length from answers it already reads: no new synchronisation.  The map after the call, the three answers and
+ * the watermark are what they are without tracking, bit for bit; a removal that removes nothing logs nothing.  TAKING copies
+ * all entries out, oldest first, and empties the log (its memory is kept); madicp_map_clear empties it too, madicp_map_release
+ * frees it.  CAPACITY: a prune or a clearing on a tracking map whose log already holds >= max_rows entries is refused with
+ * MADICP_ERR_CAPACITY, map and log unchanged, nothing launched, nothing written (decided without looking at a row, after the
+ * arguments are found valid); before a launch, memory for log_n + min(watermark, rows) entries is ensured, so the log never
+ * holds memory for more than 2 max_rows entries (20 bytes each, 24 with the column), in a block of its own that grows
+ * geometrically.  THE INVARIANT: a consumer that keeps key -> (row, word), at every poll first deletes the taken log's keys (each
+ * is present, within one poll they are distinct) and then inserts the new rows [its watermark, rows) by key (none is present),
+ * holds exactly the device map, for any polling cadence.  Removals first: a voxel cleared and refilled between two polls is in
+ * both lists.
+ *   madicp_map_track_removed  on != 0: the map tracks removals from now on; 0: it does not, and the log is freed.  Legal at any
+ *                             time.  MADICP_ERR_INVALID for a null ctx or an unknown id.
+ *   madicp_map_removed_count  the entries the log holds (0 on a map that is not tracking).
+ *   madicp_map_take_removed   all entries into out_keys (n), out_xyz (n, 3) and, where out_attr is not null, out_attr (n), their
+ *                             number in *out_n; then the log is empty.  MADICP_ERR_CAPACITY when capacity is smaller: *out_n is
+ *                             the number needed, nothing is written, the log is kept.  MADICP_ERR_INVALID, nothing written, for
+ *                             a null argument (out_attr may be null), an unknown id, a map that is not tracking, an out_attr on
+ *                             a map without the column.  All copies in front of ONE host synchronisation.
+ *   madicp_map_download_keys  the stored keys of rows [first_row, rows), madicp_map_download_f32's conventions.
+ *   madicp_map_download_rows  the columns of rows [first_row, rows) — out_xyz, and out_keys and out_attr where not null — with
+ *                             their copies in front of ONE host synchronisation; madicp_map_download_f32's conventions, and
+ *                             MADICP_ERR_INVALID for an out_attr on a map without the column.
+ * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes,
+ * clearings and takes. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
 int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
                             int64_t* out_rows);
@@ -508,6 +538,13 @@ int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double
                      int64_t* out_rows, int64_t* out_watermark);
 int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], const double origin[3],
                           double margin, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark);
+int madicp_map_track_removed(madicp_ctx* ctx, int map_id, int on);
+int madicp_map_removed_count(madicp_ctx* ctx, int map_id, int64_t* out_n);
+int madicp_map_take_removed(madicp_ctx* ctx, int map_id, uint64_t* out_keys, float* out_xyz, uint32_t* out_attr, int64_t capacity,
+                            int64_t* out_n);
+int madicp_map_download_keys(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_download_rows(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                             int64_t capacity_rows, int64_t* out_n);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

@@ -138,7 +138,12 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  all taken into the map frame by (R, t), are sampled one voxel edge apart; a row leaves iff its stored key is
  *                  the key of a sample and not the key of an end point.  Answers as for _prune.  MADICP_ERR_INVALID, map
  *                  unchanged and nothing written, for a null argument (xyz may be null when n == 0), n < 0, a non-finite R, t or
- *                  origin, a margin that is not finite and >= 0, a watermark outside [0, rows].  Two sets and one pass. */
+ *                  origin, a margin that is not finite and >= 0, a watermark outside [0, rows].  Two sets and one pass.
+ *   _track_removed / _removed_count / _take_removed / _download_keys / _download_rows
+ *                  the twins of madicp_map_track_removed and its neighbours (madicp_hip.h has the rule of the removal log): on a
+ *                  tracking map _prune and _clear_rays append the rows they remove from below the watermark — stored key, float
+ *                  row, word — to the log, in the one stable pass; they are refused with MADICP_ERR_CAPACITY, nothing changed,
+ *                  while the log holds >= max_rows entries.  Codes and "nothing written" as on the device. */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -154,6 +159,13 @@ int madicp_host_map_prune(madicp_host_map* map, const double center[3], double r
 int madicp_host_map_clear_rays(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
                                const double origin[3], double margin, int64_t watermark, int64_t* out_removed, int64_t* out_rows,
                                int64_t* out_watermark);
+int madicp_host_map_track_removed(madicp_host_map* map, int on);
+int madicp_host_map_removed_count(const madicp_host_map* map, int64_t* out_n);
+int madicp_host_map_take_removed(madicp_host_map* map, uint64_t* out_keys, float* out_xyz, uint32_t* out_attr, int64_t capacity,
+                                 int64_t* out_n);
+int madicp_host_map_download_keys(const madicp_host_map* map, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_download_rows(const madicp_host_map* map, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                                  int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

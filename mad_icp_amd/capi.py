@@ -178,6 +178,11 @@ def hip_lib():
         L.madicp_map_prune.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_map_clear_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
+        L.madicp_map_track_removed.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.madicp_map_removed_count.argtypes = [C.c_void_p, C.c_int, _i64p]
+        L.madicp_map_take_removed.argtypes = [C.c_void_p, C.c_int, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
+        L.madicp_map_download_keys.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u64p, C.c_int64, _i64p]
+        L.madicp_map_download_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), _u64p, _u32p, C.c_int64, _i64p]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
@@ -243,6 +248,11 @@ def host_lib():
         L.madicp_host_map_create_attr.argtypes = [C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
         L.madicp_host_map_insert_attr.argtypes = [C.c_void_p, _dp, _u32p, C.c_int64, _dp, _dp, _i64p, _i64p]
         L.madicp_host_map_download_attr.argtypes = [C.c_void_p, C.c_int64, _u32p, C.c_int64, _i64p]
+        L.madicp_host_map_track_removed.argtypes = [C.c_void_p, C.c_int]
+        L.madicp_host_map_removed_count.argtypes = [C.c_void_p, _i64p]
+        L.madicp_host_map_take_removed.argtypes = [C.c_void_p, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
+        L.madicp_host_map_download_keys.argtypes = [C.c_void_p, C.c_int64, _u64p, C.c_int64, _i64p]
+        L.madicp_host_map_download_rows.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), _u64p, _u32p, C.c_int64, _i64p]
         L.madicp_host_map_destroy.restype = None
         L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
@@ -671,6 +681,53 @@ def host_map_clear_rays(h, xyz, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, waterm
     return removed.value, rows.value, mark.value
 
 
+def host_map_track_removed(h, on=True):
+    """madicp_host_map_track_removed: the host twin of Context.map_track_removed."""
+    _host_map_check(host_lib().madicp_host_map_track_removed(h, 1 if on else 0), "madicp_host_map_track_removed")
+
+
+def host_map_removed_count(h):
+    n = C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_removed_count(h, C.byref(n)), "madicp_host_map_removed_count")
+    return n.value
+
+
+def host_map_take_removed(h, with_attr=False):
+    """madicp_host_map_take_removed: the host twin of Context.map_take_removed.  Returns (keys (n,) uint64, rows (n, 3) float32
+    [, words (n,) uint32]) and empties the log."""
+    n = host_map_removed_count(h)
+    keys, xyz, got = np.empty(max(n, 1), np.uint64), np.empty((max(n, 1), 3), np.float32), C.c_int64(0)
+    w = np.empty(max(n, 1), np.uint32) if with_attr else None
+    _host_map_check(host_lib().madicp_host_map_take_removed(h, keys.ctypes.data_as(_u64p), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                            w.ctypes.data_as(_u32p) if with_attr else None, n, C.byref(got)),
+                    "madicp_host_map_take_removed")
+    m = got.value
+    return (keys[:m].copy(), xyz[:m].copy()) + ((w[:m].copy(),) if with_attr else ())
+
+
+def host_map_download_keys(h, first_row=0):
+    """The stored voxel keys of rows [first_row, size) as (M - first_row,) uint64."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    out, got = np.empty(max(m, 1), np.uint64), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_download_keys(h, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)),
+                    "madicp_host_map_download_keys")
+    return out[:got.value].copy()
+
+
+def host_map_download_rows(h, first_row=0, with_keys=True, with_attr=False):
+    """madicp_host_map_download_rows: the columns of rows [first_row, size): (rows (M, 3) float32[, keys uint64][, words uint32])."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
+    k = np.empty(max(m, 1), np.uint64) if with_keys else None
+    w = np.empty(max(m, 1), np.uint32) if with_attr else None
+    _host_map_check(host_lib().madicp_host_map_download_rows(h, int(first_row), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                             k.ctypes.data_as(_u64p) if with_keys else None,
+                                                             w.ctypes.data_as(_u32p) if with_attr else None, m, C.byref(got)),
+                    "madicp_host_map_download_rows")
+    g = got.value
+    return (xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ())
+
+
 def host_map_clear(h):
     _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
 
@@ -936,6 +993,47 @@ class Context:
         _check(hip_lib().madicp_map_clear_rays(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), o.ctypes.data_as(_dp),
                                                float(margin), int(watermark), C.byref(removed), C.byref(rows), C.byref(mark)))
         return removed.value, rows.value, mark.value
+
+    def map_track_removed(self, mid, on=True):
+        """madicp_map_track_removed: from now on the map logs the rows that map_prune and map_clear_rays remove from below their
+        watermark (key, float row, word) until map_take_removed fetches them; on=False stops that and frees the log."""
+        _check(hip_lib().madicp_map_track_removed(self._h, mid, 1 if on else 0))
+
+    def map_removed_count(self, mid):
+        n = C.c_int64(0)
+        _check(hip_lib().madicp_map_removed_count(self._h, mid, C.byref(n)))
+        return n.value
+
+    def map_take_removed(self, mid, with_attr=False):
+        """madicp_map_take_removed: the removal log, oldest first, as (keys (n,) uint64, rows (n, 3) float32[, words (n,) uint32]);
+        the log is empty afterwards.  One host synchronisation."""
+        n = self.map_removed_count(mid)
+        keys, xyz, got = np.empty(max(n, 1), np.uint64), np.empty((max(n, 1), 3), np.float32), C.c_int64(0)
+        w = np.empty(max(n, 1), np.uint32) if with_attr else None
+        _check(hip_lib().madicp_map_take_removed(self._h, mid, keys.ctypes.data_as(_u64p), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 w.ctypes.data_as(_u32p) if with_attr else None, n, C.byref(got)))
+        m = got.value
+        return (keys[:m].copy(), xyz[:m].copy()) + ((w[:m].copy(),) if with_attr else ())
+
+    def map_download_keys(self, mid, first_row=0):
+        """The stored voxel keys of rows [first_row, size) as (M - first_row,) uint64: a row's identity across prunes."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        out, got = np.empty(max(m, 1), np.uint64), C.c_int64(0)
+        _check(hip_lib().madicp_map_download_keys(self._h, mid, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)))
+        return out[:got.value].copy()
+
+    def map_download_rows(self, mid, first_row=0, with_keys=True, with_attr=False):
+        """madicp_map_download_rows: the columns of rows [first_row, size) behind ONE host synchronisation:
+        (rows (M, 3) float32[, keys (M,) uint64][, words (M,) uint32])."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
+        k = np.empty(max(m, 1), np.uint64) if with_keys else None
+        w = np.empty(max(m, 1), np.uint32) if with_attr else None
+        _check(hip_lib().madicp_map_download_rows(self._h, mid, int(first_row), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                  k.ctypes.data_as(_u64p) if with_keys else None,
+                                                  w.ctypes.data_as(_u32p) if with_attr else None, m, C.byref(got)))
+        g = got.value
+        return (xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ())
 
     def map_clear(self, mid):
         _check(hip_lib().madicp_map_clear(self._h, mid))

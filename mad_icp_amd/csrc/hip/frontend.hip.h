@@ -584,6 +584,27 @@ __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ 
     if (attr) out_attr[d] = attr[j];
   }
 }
+// The removal log of a tracking map (madicp_map_track_removed): map_compact's complement over the rows below the watermark, beside it
+// behind the same scan.  One lane per row j < n_below = min(watermark, M): row j leaves iff pos[j + 1] == pos[j], and its place in
+// the log is base + (j - pos[j]) — the rows removed before j, behind the `base` entries the log already holds: no second scan, no
+// atomics, coalesced reads, monotone writes.  Reads the scan and the OLD block only, never the marks (in the clearing path the scan
+// lies over the dead ray flags, and map_compact's lane 0 writes its two answers over the first marks).  At most n_below entries are
+// written: the caller has ensured base + n_below.
+__global__ __launch_bounds__(256) void map_log_removed(const uint32_t* __restrict__ pos, long n_below, long base,
+                                                       const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
+                                                       const uint32_t* __restrict__ attr, unsigned long long* __restrict__ log_keys,
+                                                       float* __restrict__ log_rows, uint32_t* __restrict__ log_attr) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_below; j += (long)gridDim.x * blockDim.x) {
+    const long d = pos[j];
+    if ((long)pos[j + 1] != d) continue;
+    const long e = base + (j - d);
+    log_keys[e] = row_keys[j];
+    log_rows[3 * e] = rows[3 * j];
+    log_rows[3 * e + 1] = rows[3 * j + 1];
+    log_rows[3 * e + 2] = rows[3 * j + 2];
+    if (attr) log_attr[e] = attr[j];
+  }
+}
 
 // ---- clearing the map by a scan's rays: rows whose voxel a ray passes through and no point of the scan lies in leave ----------------
 // (madicp_map_clear_rays).  The rule is csrc/common/export_point.h's, shared with the host twin: ray_length, ray_sample_count,

@@ -30,6 +30,15 @@ struct DevMap {
   uint32_t* attr = nullptr;                // (cap) the rows' attribute words: maps of madicp_map_create_attr only
   bool with_attr = false;
   uint32_t slots = 0;
+  // the removal log (madicp_map_track_removed): a block of its own — the map's is swapped by every prune and growth —
+  //   keys (log_cap x 8) | xyz (log_cap x 12) | attr (log_cap x 4, attribute maps only)
+  // of which the first log_n entries are live; allocated at the first removal that can log
+  bool track = false;
+  char* log_block = nullptr;
+  int64_t log_cap = 0, log_n = 0;
+  unsigned long long* log_keys() const { return reinterpret_cast<unsigned long long*>(log_block); }
+  float* log_xyz() const { return reinterpret_cast<float*>(log_block + 8 * (size_t)log_cap); }
+  uint32_t* log_attr() const { return with_attr ? reinterpret_cast<uint32_t*>(log_block + 20 * (size_t)log_cap) : nullptr; }
 };
 
 // grow-only scratch of the tree builder / deskew / ingest
@@ -198,8 +207,10 @@ void front_destroy(madicp_ctx* ctx) {  // called by madicp_ctx_destroy (streams 
   if (!ctx->front) return;
   for (auto& c : ctx->front->clouds)
     if (c.second.ready) hipEventDestroy(c.second.ready);  // (the device buffers belong to the pool)
-  for (auto& m : ctx->front->maps)
+  for (auto& m : ctx->front->maps) {
     if (m.second.block) hipFree(m.second.block);
+    if (m.second.log_block) hipFree(m.second.log_block);
+  }
   FrontScratch& fs = ctx->front->scratch;
   if (fs.fly.pre) {  // (a construction that was begun and never ended: its pre-sized tree block goes back with the pool)
     pool_free(ctx, fs.fly.pre_tree.block, nullptr);
@@ -1063,12 +1074,53 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
   return MADICP_OK;
 }
 
+// Memory for `need` log entries in front of a removal on a tracking map: a block for max(need, min(2 log_cap, 2 max_rows)) entries, the
+// live entries moved by device copy on the copy stream.  The block it replaces is handed back in *old_block: the caller frees it
+// behind the removal's own one wait (map_log_settle), so a log growth adds no synchronisation.  log_n is not touched.
+int map_log_reserve(madicp_ctx* ctx, DevMap* m, int64_t need, char** old_block) {
+  *old_block = nullptr;
+  if (need <= m->log_cap) return MADICP_OK;
+  DevMap g = *m;
+  g.log_cap = std::max(need, std::min(2 * m->log_cap, 2 * m->max_rows));
+  g.log_block = nullptr;
+  HIP_TRY(hipMalloc(&g.log_block, (m->with_attr ? 24 : 20) * (size_t)g.log_cap));
+  hipError_t e = hipSuccess;
+  if (m->log_n > 0) {
+    const size_t n = (size_t)m->log_n;
+    e = hipMemcpyAsync(g.log_keys(), m->log_keys(), sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess) e = hipMemcpyAsync(g.log_xyz(), m->log_xyz(), sizeof(float) * 3 * n, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess && m->with_attr) e = hipMemcpyAsync(g.log_attr(), m->log_attr(), sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, ctx->copy);
+  }
+  if (e != hipSuccess) {
+    hipStreamSynchronize(ctx->copy);
+    hipFree(g.log_block);
+    return fail(MADICP_ERR_DEVICE, std::string("voxel map removal log: ") + hipGetErrorString(e));
+  }
+  *old_block = m->log_block;
+  m->log_block = g.log_block;
+  m->log_cap = g.log_cap;
+  return MADICP_OK;
+}
+
+// behind a removal (rc: what it returned, logged: the entries it added): the replaced log block is freed — behind the removal's
+// wait; an error may have returned in front of it — and the log's length moves only on success
+void map_log_settle(madicp_ctx* ctx, DevMap* m, char* old_block, int rc, int64_t logged) {
+  if (old_block) {
+    if (rc != MADICP_OK) hipStreamSynchronize(ctx->copy);
+    hipFree(old_block);
+  }
+  if (rc == MADICP_OK && m->track) m->log_n += logged;
+}
+
 // The tail every removal shares (madicp_map_prune, madicp_map_clear_rays).  The caller has allocated the FRESH block g of the same
 // capacity — the shape of a growth, and its transient cost: one more block — and enqueued the kernel that leaves mark[0 .. M] in g's
 // table region (24 cap bytes, not yet a table); here: the tile scan of the marks into S, map_compact into g, which leaves {rows kept,
 // kept below the watermark} over the first two marks, which nobody reads after the scan: ONE small copy, ONE synchronisation.
 // Behind it nothing reads the old block any more: it is freed, the table wiped and refilled from the kept keys on the stream, in
 // front of whatever fold comes next.  Nothing removed: the fresh block is dropped, the map is not touched at all.
+// A tracking map (the caller has ensured its log, map_log_reserve) has map_log_removed beside map_compact: behind the scan, in front
+// of the one wait and of the wipe.  It reads S and the old block only — in the clearing path S lies over the dead ray flags, and
+// map_compact leaves its answers over the first marks — and writes the log; the caller moves log_n (map_log_settle).
 int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uint32_t* S, uint32_t* tile_sums, int64_t watermark,
                       const char* what, int64_t* out_kept, int64_t* out_watermark) {
   const int64_t M = m->rows;
@@ -1079,6 +1131,10 @@ int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uin
   hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
   hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
                      (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark);
+  if (const int64_t below = std::min(watermark, M); m->track && below > 0)
+    hipLaunchKernelGGL(fe::map_log_removed, dim3(grid_256(ctx, below)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)below, (long)m->log_n,
+                       (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, m->log_keys(), m->log_xyz(),
+                       m->log_attr());
   uint32_t res[2] = {0, 0};
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(res, mark, sizeof(res), hipMemcpyDeviceToHost, ctx->copy);
@@ -1142,6 +1198,8 @@ int map_clear_rays_on(madicp_ctx* ctx, DevMap* m, const DevCloud* c, const fe::R
                      (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, mark);
   return map_remove_marked(ctx, m, g, mark, flags, mark + (M + 1), watermark, "voxel map clearing: ", out_kept, out_watermark);
 }
+
+constexpr const char* kMapLogFull = "the map's removal log holds max_rows entries or more (madicp_map_take_removed empties it)";
 
 DevMap* find_map(madicp_ctx* ctx, int id) {
   if (!ctx->front) return nullptr;
@@ -1240,6 +1298,92 @@ int madicp_map_download_attr(madicp_ctx* ctx, int map_id, int64_t first_row, uin
   return MADICP_OK;
 }
 
+int madicp_map_download_keys(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_keys || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_keys holds fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out_keys, m->row_keys + first_row, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
+}
+
+// the columns of a window of rows with their copies in front of ONE wait (each of the single-column downloads above has its own)
+int madicp_map_download_rows(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                             int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (out_attr && !m->with_attr)
+    return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "the buffers hold fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipError_t e = hipMemcpyAsync(out_xyz, m->xyz + 3 * first_row, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess && out_keys)
+    e = hipMemcpyAsync(out_keys, m->row_keys + first_row, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess && out_attr)
+    e = hipMemcpyAsync(out_attr, m->attr + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+  const hipError_t w = hipStreamSynchronize(ctx->copy);
+  if (e == hipSuccess) e = w;
+  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map download: ") + hipGetErrorString(e));
+  return MADICP_OK;
+}
+
+int madicp_map_track_removed(madicp_ctx* ctx, int map_id, int on) {
+  if (!ctx) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  m->track = on != 0;
+  if (!m->track && m->log_block) {  // (every call that wrote or read the log has ended with a wait: nothing is in flight on it)
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipFree(m->log_block);
+    m->log_block = nullptr;
+    m->log_cap = 0;
+  }
+  if (!m->track) m->log_n = 0;
+  return MADICP_OK;
+}
+
+int madicp_map_removed_count(madicp_ctx* ctx, int map_id, int64_t* out_n) {
+  if (!ctx || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  *out_n = m->log_n;
+  return MADICP_OK;
+}
+
+int madicp_map_take_removed(madicp_ctx* ctx, int map_id, uint64_t* out_keys, float* out_xyz, uint32_t* out_attr, int64_t capacity,
+                            int64_t* out_n) {
+  if (!ctx || !out_keys || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!m->track) return fail(MADICP_ERR_INVALID, "the map does not track removals (madicp_map_track_removed)");
+  if (out_attr && !m->with_attr)
+    return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
+  const int64_t n = m->log_n;
+  *out_n = n;
+  if (capacity < n) return fail(MADICP_ERR_CAPACITY, "the buffers hold fewer entries than the removal log has (*out_n)");
+  if (n == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipError_t e = hipMemcpyAsync(out_keys, m->log_keys(), sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_xyz, m->log_xyz(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess && out_attr) e = hipMemcpyAsync(out_attr, m->log_attr(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy);
+  const hipError_t w = hipStreamSynchronize(ctx->copy);
+  if (e == hipSuccess) e = w;
+  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map removal log: ") + hipGetErrorString(e));
+  m->log_n = 0;  // (the memory is kept)
+  return MADICP_OK;
+}
+
 int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double radius, int64_t watermark, int64_t* out_removed,
                      int64_t* out_rows, int64_t* out_watermark) {
   if (!ctx || !center || !out_removed || !out_rows || !out_watermark) return fail(MADICP_ERR_INVALID, "null argument");
@@ -1247,6 +1391,7 @@ int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double
   if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
   if (const char* why = madicp_host::map_prune_refusal(center, radius)) return fail(MADICP_ERR_INVALID, why);
   if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
+  if (m->track && m->log_n >= m->max_rows) return fail(MADICP_ERR_CAPACITY, kMapLogFull);
   const int64_t before = m->rows;
   int64_t kept = 0, mark = 0;
   if (before > 0) {
@@ -1254,7 +1399,11 @@ int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double
     fe::PruneSphere Q;
     std::memcpy(Q.c, center, sizeof(Q.c));
     Q.r2 = radius * radius;
-    RC_TRY(map_prune_on(ctx, m, Q, watermark, &kept, &mark));
+    char* old_log = nullptr;
+    if (m->track && watermark > 0) RC_TRY(map_log_reserve(ctx, m, m->log_n + watermark, &old_log));
+    const int rc = map_prune_on(ctx, m, Q, watermark, &kept, &mark);
+    map_log_settle(ctx, m, old_log, rc, watermark - mark);
+    RC_TRY(rc);
   }
   *out_removed = before - kept;
   *out_rows = kept;
@@ -1271,6 +1420,7 @@ int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const doubl
   if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
   if (const char* why = madicp_host::map_clear_refusal(R, t, origin, margin)) return fail(MADICP_ERR_INVALID, why);
   if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
+  if (m->track && m->log_n >= m->max_rows) return fail(MADICP_ERR_CAPACITY, kMapLogFull);
   const int64_t before = m->rows;
   int64_t kept = before, mark = watermark;
   if (before > 0 && c->n > 0) {  // (an empty map or an empty cloud: nothing can leave, nothing is launched)
@@ -1279,7 +1429,11 @@ int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const doubl
     F.X = export_pose(R, t);
     std::memcpy(F.o, origin, sizeof(F.o));
     F.margin = margin;
-    RC_TRY(map_clear_rays_on(ctx, m, c, F, watermark, &kept, &mark));
+    char* old_log = nullptr;
+    if (m->track && watermark > 0) RC_TRY(map_log_reserve(ctx, m, m->log_n + watermark, &old_log));
+    const int rc = map_clear_rays_on(ctx, m, c, F, watermark, &kept, &mark);
+    map_log_settle(ctx, m, old_log, rc, watermark - mark);
+    RC_TRY(rc);
   }
   *out_removed = before - kept;
   *out_rows = kept;
@@ -1294,6 +1448,7 @@ int madicp_map_clear(madicp_ctx* ctx, int map_id) {
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipMemsetAsync(m->block, 0xff, 24 * (size_t)m->cap, ctx->copy));
   m->rows = 0;
+  m->log_n = 0;  // (the log's memory is kept)
   return MADICP_OK;
 }
 
@@ -1304,6 +1459,7 @@ int madicp_map_release(madicp_ctx* ctx, int map_id) {
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->copy));
   HIP_TRY(hipFree(m->block));
+  if (m->log_block) hipFree(m->log_block);
   ctx->front->maps.erase(map_id);
   return MADICP_OK;
 }

@@ -234,6 +234,7 @@ void Pipeline::dropMap() {
   map_overflowed_ = false;
   map_have_center_ = map_have_last_ = false;
   map_cursor_ = map_removed_ = 0;
+  map_log_full_ = false;
 }
 
 void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute) {
@@ -252,8 +253,9 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
   map_attr_type_ = kAttrNone;
   if (voxel_size > 0.0) {
     if (!was_on) dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
-  } else if (!keep_scan_) {
-    dropKeptScan();
+  } else {
+    map_track_removed_ = false;  // (setMapTrackRemoved is an option of the accumulation: off with it)
+    if (!keep_scan_) dropKeptScan();
   }
 }
 
@@ -281,6 +283,7 @@ void Pipeline::foldFrame() {
         else
           check(madicp_map_create(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create");
         map_generation_ = Device::generation();
+        if (map_track_removed_) check(madicp_map_track_removed(ctx, map_id_, 1), "madicp_map_track_removed");
       }
       MADtree::cancelDeviceBuild(0);  // the fold needs the builder's scratch: a look-ahead of another Pipeline gives way
       int cloud_id = kept_cloud_id_;
@@ -303,13 +306,20 @@ void Pipeline::foldFrame() {
                                     static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
       if (kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_insert_cloud");
-      check(crc, "madicp_map_clear_rays");
-      if (rc == MADICP_OK && map_clearing_) {
+      if (crc == MADICP_ERR_CAPACITY && map_track_removed_) {  // (the removal log is full: this clearing is skipped, map and mirror agree)
+        map_log_full_ = true;
+      } else {
+        check(crc, "madicp_map_clear_rays");
+      }
+      if (rc == MADICP_OK && map_clearing_ && crc == MADICP_OK) {
         map_cursor_ = static_cast<size_t>(mark);
         map_removed_ += static_cast<size_t>(removed);
       }
     } else {
-      if (fresh) map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_);
+      if (fresh) {
+        map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_);
+        map_host_->track_removed(map_track_removed_);
+      }
       ContainerType down;  // (a resident scan into a host map: the front-end was switched — its column crosses with it)
       std::vector<uint32_t> down_attr;
       if (kept_cloud_id_ >= 0) {
@@ -330,11 +340,16 @@ void Pipeline::foldFrame() {
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline: the host voxel map refused its arguments");
       if (rc == MADICP_OK && map_clearing_) {
         int64_t removed = 0, mark = 0;
-        if (map_host_->clearRays(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t,
-                                 map_clear_origin_, map_clear_margin_, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark) != MADICP_OK)
+        const int crc = map_host_->clearRays(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t,
+                                             map_clear_origin_, map_clear_margin_, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+        if (crc == MADICP_ERR_CAPACITY && map_track_removed_) {  // (the removal log is full: this clearing is skipped)
+          map_log_full_ = true;
+        } else if (crc != MADICP_OK) {
           throw std::runtime_error("Pipeline: the host voxel map refused the clearing's arguments");
-        map_cursor_ = static_cast<size_t>(mark);
-        map_removed_ += static_cast<size_t>(removed);
+        } else {
+          map_cursor_ = static_cast<size_t>(mark);
+          map_removed_ += static_cast<size_t>(removed);
+        }
       }
     }
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
@@ -363,19 +378,26 @@ void Pipeline::setMapRange(double radius) {
 
 size_t Pipeline::pruneMapAt(const double center[3], double radius) {
   int64_t removed = 0, rows = 0, mark = 0;
+  int rc = MADICP_OK;
   if (map_host_) {
-    if (map_host_->prune(center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark) != MADICP_OK)
+    rc = map_host_->prune(center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY)
       throw std::invalid_argument("Pipeline::mapPrune: center must be finite, radius finite and > 0 with a finite square");
   } else if (map_id_ >= 0) {
     DeviceLock lock(Device::mutex());
     madicp_ctx* ctx = Device::current(map_generation_);
     if (!ctx) throw std::logic_error("Pipeline::mapPrune: the device context the map lived in is gone");
-    const int rc = madicp_map_prune(ctx, map_id_, center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+    rc = madicp_map_prune(ctx, map_id_, center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
     if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapPrune: ") + madicp_last_error());
-    check(rc, "madicp_map_prune");
+    if (!(rc == MADICP_ERR_CAPACITY && map_track_removed_)) check(rc, "madicp_map_prune");
   } else {  // (no frame folded yet: nothing to remove, but the arguments are held to the same rule)
     if (map_prune_refusal(center, radius))
       throw std::invalid_argument("Pipeline::mapPrune: center must be finite, radius finite and > 0 with a finite square");
+    mark = static_cast<int64_t>(map_cursor_);
+  }
+  if (rc == MADICP_ERR_CAPACITY) {  // (the removal log is full: this prune is skipped, map and mirror agree)
+    map_log_full_ = true;
+    return 0;
   }
   map_cursor_ = static_cast<size_t>(mark);
   map_removed_ += static_cast<size_t>(removed);
@@ -404,9 +426,10 @@ size_t Pipeline::mapClearRays(const double* xyz, size_t n, const double R[9], co
   if ((!xyz && n > 0) || !R || !t || !origin) throw std::invalid_argument("Pipeline::mapClearRays: null argument");
   if (const char* why = map_clear_refusal(R, t, origin, margin)) throw std::invalid_argument(std::string("Pipeline::mapClearRays: ") + why);
   int64_t removed = 0, rows = 0, mark = static_cast<int64_t>(map_cursor_);
+  int rc = MADICP_OK;
   if (map_host_) {
-    if (map_host_->clearRays(xyz, static_cast<int64_t>(n), R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark) !=
-        MADICP_OK)
+    rc = map_host_->clearRays(xyz, static_cast<int64_t>(n), R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY)
       throw std::invalid_argument("Pipeline::mapClearRays: the host voxel map refused its arguments");
   } else if (map_id_ >= 0 && n > 0) {
     DeviceLock lock(Device::mutex());
@@ -414,11 +437,15 @@ size_t Pipeline::mapClearRays(const double* xyz, size_t n, const double R[9], co
     if (!ctx) throw std::logic_error("Pipeline::mapClearRays: the device context the map lived in is gone");
     int cloud_id = -1;
     check(madicp_cloud_upload(ctx, xyz, static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
-    const int rc = madicp_map_clear_rays(ctx, map_id_, cloud_id, R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+    rc = madicp_map_clear_rays(ctx, map_id_, cloud_id, R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
     madicp_cloud_release(ctx, cloud_id);
     if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapClearRays: ") + madicp_last_error());
-    check(rc, "madicp_map_clear_rays");
+    if (!(rc == MADICP_ERR_CAPACITY && map_track_removed_)) check(rc, "madicp_map_clear_rays");
   }  // (no frame folded yet, or no ray: nothing to remove)
+  if (rc == MADICP_ERR_CAPACITY) {  // (the removal log is full: this clearing is skipped)
+    map_log_full_ = true;
+    return 0;
+  }
   map_cursor_ = static_cast<size_t>(mark);
   map_removed_ += static_cast<size_t>(removed);
   return static_cast<size_t>(removed);
@@ -429,7 +456,7 @@ size_t Pipeline::mapNewRowCount() {
   return mapSize() - map_cursor_;
 }
 
-size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr) {
+size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr, uint64_t* out_keys) {
   const size_t m = mapNewRowCount();
   if (!out) throw std::invalid_argument("Pipeline::mapNewRows: null buffer");
   if (out_attr && !map_with_attr_)
@@ -438,10 +465,100 @@ size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr) {
     throw std::invalid_argument("Pipeline::mapNewRows: the buffer holds " + std::to_string(capacity) + " rows, " + std::to_string(m) +
                                 " are new");
   if (m == 0) return 0;
-  const size_t got = mapCloud(out, capacity, map_cursor_);
-  if (out_attr) mapAttribute(out_attr, capacity, map_cursor_);
+  size_t got = 0;
+  if (out_keys || out_attr) {  // more than one column: through the one call — on the device, their copies in front of ONE wait
+    int64_t rows = 0;
+    if (map_host_) {
+      if (map_host_->download_rows(static_cast<int64_t>(map_cursor_), out, out_keys, out_attr, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
+        throw std::runtime_error("Pipeline::mapNewRows: the host voxel map refused its arguments");
+    } else {
+      DeviceLock lock(Device::mutex());
+      madicp_ctx* ctx = Device::current(map_generation_);
+      if (!ctx) throw std::logic_error("Pipeline::mapNewRows: the device context the map lived in is gone");
+      check(madicp_map_download_rows(ctx, map_id_, static_cast<int64_t>(map_cursor_), out, out_keys, out_attr, static_cast<int64_t>(capacity),
+                                     &rows),
+            "madicp_map_download_rows");
+    }
+    got = static_cast<size_t>(rows);
+  } else {
+    got = mapCloud(out, capacity, map_cursor_);
+  }
   map_cursor_ += got;
   return got;
+}
+
+size_t Pipeline::mapKeys(uint64_t* out, size_t capacity, size_t first_row) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapKeys: setMapAccumulation(voxel_size > 0) first");
+  if (!out) throw std::invalid_argument("Pipeline::mapKeys: null buffer");
+  const size_t size = mapSize();
+  if (first_row > size) throw std::invalid_argument("Pipeline::mapKeys: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (capacity < size - first_row)
+    throw std::invalid_argument("Pipeline::mapKeys: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
+                                std::to_string(size - first_row));
+  if (size == first_row) return 0;
+  int64_t rows = 0;
+  if (map_host_) {
+    if (map_host_->download_keys(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
+      throw std::runtime_error("Pipeline::mapKeys: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapKeys: the device context the map lived in is gone");
+    check(madicp_map_download_keys(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
+          "madicp_map_download_keys");
+  }
+  return static_cast<size_t>(rows);
+}
+
+// ---- the removal log (pipeline.h: setMapTrackRemoved) -------------------------------------------------------------------------
+void Pipeline::setMapTrackRemoved(bool on) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::setMapTrackRemoved: setMapAccumulation(voxel_size > 0) first");
+  if (on == map_track_removed_) return;
+  if (map_host_) map_host_->track_removed(on);
+  if (map_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::setMapTrackRemoved: the device context the map lived in is gone");
+    check(madicp_map_track_removed(ctx, map_id_, on ? 1 : 0), "madicp_map_track_removed");
+  }
+  map_track_removed_ = on;
+  if (!on) map_log_full_ = false;
+}
+
+size_t Pipeline::mapRemovedRowCount() {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapRemovedRows: setMapAccumulation(voxel_size > 0) first");
+  if (map_host_) return static_cast<size_t>(map_host_->removed_count());
+  if (map_id_ < 0) return 0;  // (no frame folded yet)
+  DeviceLock lock(Device::mutex());
+  madicp_ctx* ctx = Device::current(map_generation_);
+  if (!ctx) throw std::logic_error("Pipeline::mapRemovedRows: the device context the map lived in is gone");
+  int64_t n = 0;
+  check(madicp_map_removed_count(ctx, map_id_, &n), "madicp_map_removed_count");
+  return static_cast<size_t>(n);
+}
+
+size_t Pipeline::mapRemovedRows(uint64_t* keys, float* rows, uint32_t* attr, size_t capacity) {
+  const size_t m = mapRemovedRowCount();
+  if (!map_track_removed_) throw std::logic_error("Pipeline::mapRemovedRows: setMapTrackRemoved(true) first");
+  if (!keys || !rows) throw std::invalid_argument("Pipeline::mapRemovedRows: null buffer");
+  if (attr && !map_with_attr_)
+    throw std::logic_error("Pipeline::mapRemovedRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
+  if (capacity < m)
+    throw std::invalid_argument("Pipeline::mapRemovedRows: the buffers hold " + std::to_string(capacity) + " rows, the log has " +
+                                std::to_string(m));
+  map_log_full_ = false;
+  if (m == 0) return 0;
+  int64_t n = 0;
+  if (map_host_) {
+    if (map_host_->take_removed(keys, rows, attr, static_cast<int64_t>(capacity), &n) != MADICP_OK)
+      throw std::runtime_error("Pipeline::mapRemovedRows: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapRemovedRows: the device context the map lived in is gone");
+    check(madicp_map_take_removed(ctx, map_id_, keys, rows, attr, static_cast<int64_t>(capacity), &n), "madicp_map_take_removed");
+  }
+  return static_cast<size_t>(n);
 }
 
 size_t Pipeline::mapSize() {
@@ -508,6 +625,7 @@ void Pipeline::clearMap() {
   map_overflowed_ = false;
   map_have_center_ = false;
   map_cursor_ = map_removed_ = 0;
+  map_log_full_ = false;
   if (map_host_) map_host_->clear();
   if (map_id_ >= 0) {
     DeviceLock lock(Device::mutex());

@@ -203,7 +203,28 @@ class Pipeline {
   size_t mapPrune(const double center[3], double radius);
   size_t mapRemoved() const { return map_removed_; }
   size_t mapNewRowCount();
-  size_t mapNewRows(float* out, size_t capacity, uint32_t* out_attr = nullptr);
+  size_t mapNewRows(float* out, size_t capacity, uint32_t* out_attr = nullptr, uint64_t* out_keys = nullptr);
+  // additive: A MAP THAT A CONSUMER CAN MIRROR.  Every row has an identity that survives prunes: its stored 64-bit voxel key, unique
+  // among the rows the map holds (mapKeys: the keys of rows [first_row, mapSize()), mapCloud's refusals; mapNewRows' out_keys: the
+  // keys of the new rows; with keys or words the columns come through madicp_map_download_rows, their copies before one wait).
+  // setMapTrackRemoved(true) — default off: not a launch, not an allocation, the same pose and map bits — makes the map keep a
+  // REMOVAL LOG (include/madicp_hip.h has the rule): foldFrame, mapPrune and mapClearRays pass mapNewRows' cursor as watermark, so
+  // the log holds exactly the rows that were delivered and have left since — key, float row and, on a map with the column, word.
+  // mapRemovedRows takes it (mapRemovedRowCount() entries, oldest first; attr may be null), and a consumer that at every poll
+  // first deletes the removed keys and then inserts mapNewRows' rows by key holds exactly the map (mad_icp_amd/map_mirror.py).  It
+  // takes effect on the current map and on any made later, and survives a front-end switch as the map does; clearMap() empties
+  // the log.  The log is bounded by max_points: once it holds that many entries, foldFrame, mapPrune and mapClearRays SKIP their
+  // removal — map and mirror stay consistent, mapRemovedLogFull() answers true until the next mapRemovedRows() — and a skipped range
+  // prune before a fold the capacity rule refuses ends in mapOverflowed(), as without a range: asking for removals and never
+  // fetching them ends there.  std::logic_error while accumulation is off; mapRemovedRows: also while tracking is off, or with
+  // attr on a map without the column; std::invalid_argument for a null buffer or a capacity below mapRemovedRowCount() (nothing
+  // written, the log is kept).
+  void setMapTrackRemoved(bool on);
+  bool mapTrackRemoved() const { return map_track_removed_; }
+  size_t mapRemovedRowCount();
+  size_t mapRemovedRows(uint64_t* keys, float* rows, uint32_t* attr, size_t capacity);
+  bool mapRemovedLogFull() const { return map_log_full_; }
+  size_t mapKeys(uint64_t* out, size_t capacity, size_t first_row = 0);
   // additive: FREE-SPACE CLEARING.  setMapClearing(true) — default off: not a launch, not an allocation, the same pose bits — lets
   // foldFrame() call madicp_map_clear_rays / VoxelMap::clearRays after every successful fold and before the range prune (a), with
   // the cloud it has just folded, the frame's pose and `origin`, the sensor's position in the cloud's frame: the rows whose voxel a
@@ -391,6 +412,7 @@ class Pipeline {
   bool map_have_center_ = false, map_have_last_ = false;
   size_t map_cursor_ = 0, map_removed_ = 0;
   bool map_clearing_ = false;  // setMapClearing
+  bool map_track_removed_ = false, map_log_full_ = false;  // setMapTrackRemoved; a removal was skipped because the log is full
   double map_clear_margin_ = 0.0, map_clear_origin_[3] = {0.0, 0.0, 0.0};
   size_t pruneMapAt(const double center[3], double radius);  // madicp_map_prune / VoxelMap::prune with the cursor as watermark
   void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it

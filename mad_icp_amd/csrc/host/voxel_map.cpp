@@ -73,6 +73,35 @@ int madicp_host_map_clear_rays(madicp_host_map* map, const double* xyz, int64_t 
   return map->map.clearRays(xyz, n, R, t, origin, margin, watermark, out_removed, out_rows, out_watermark);
 }
 
+int madicp_host_map_track_removed(madicp_host_map* map, int on) {
+  if (!map) return MADICP_ERR_INVALID;
+  map->map.track_removed(on != 0);
+  return MADICP_OK;
+}
+
+int madicp_host_map_removed_count(const madicp_host_map* map, int64_t* out_n) {
+  if (!map || !out_n) return MADICP_ERR_INVALID;
+  *out_n = map->map.removed_count();
+  return MADICP_OK;
+}
+
+int madicp_host_map_take_removed(madicp_host_map* map, uint64_t* out_keys, float* out_xyz, uint32_t* out_attr, int64_t capacity,
+                                 int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.take_removed(out_keys, out_xyz, out_attr, capacity, out_n);
+}
+
+int madicp_host_map_download_keys(const madicp_host_map* map, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_keys(first_row, out_keys, capacity_rows, out_n);
+}
+
+int madicp_host_map_download_rows(const madicp_host_map* map, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                                  int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_rows(first_row, out_xyz, out_keys, out_attr, capacity_rows, out_n);
+}
+
 int madicp_host_map_clear(madicp_host_map* map) {
   if (!map) return MADICP_ERR_INVALID;
   map->map.clear();

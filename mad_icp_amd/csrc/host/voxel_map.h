@@ -75,6 +75,56 @@ class VoxelMap {
     return kMapOk;
   }
 
+  // include/madicp_host.h: madicp_host_map_download_keys — the stored keys of rows [first_row, size())
+  int download_keys(int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) const {
+    if (!out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
+    const int64_t m = size() - first_row;
+    *out_n = m;
+    if (capacity_rows < m) return kMapCapacity;
+    if (m > 0) std::memcpy(out, row_keys_.data() + first_row, sizeof(uint64_t) * static_cast<size_t>(m));
+    return kMapOk;
+  }
+  // include/madicp_host.h: madicp_host_map_download_rows — the columns of rows [first_row, size()): keys and words where asked for
+  int download_rows(int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) const {
+    if (!out_xyz || !out_n || first_row < 0 || first_row > size() || (out_attr && !with_attr_)) return kMapInvalid;
+    const int64_t m = size() - first_row;
+    *out_n = m;
+    if (capacity_rows < m) return kMapCapacity;
+    if (m == 0) return kMapOk;
+    std::memcpy(out_xyz, rows_.data() + 3 * first_row, sizeof(float) * 3 * static_cast<size_t>(m));
+    if (out_keys) std::memcpy(out_keys, row_keys_.data() + first_row, sizeof(uint64_t) * static_cast<size_t>(m));
+    if (out_attr) std::memcpy(out_attr, attr_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
+    return kMapOk;
+  }
+
+  // include/madicp_host.h: madicp_host_map_track_removed / _removed_count / _take_removed — the removal log (madicp_hip.h has the
+  // rule): what prune and clearRays remove below their watermark, oldest first, until it is taken.  Turning it off frees the log.
+  void track_removed(bool on) {
+    track_ = on;
+    if (!on) {
+      std::vector<uint64_t>().swap(log_keys_);
+      std::vector<float>().swap(log_rows_);
+      std::vector<uint32_t>().swap(log_attr_);
+    }
+  }
+  bool tracking() const { return track_; }
+  int64_t removed_count() const { return static_cast<int64_t>(log_keys_.size()); }
+  int take_removed(uint64_t* out_keys, float* out_xyz, uint32_t* out_attr, int64_t capacity, int64_t* out_n) {
+    if (!track_ || !out_keys || !out_xyz || !out_n || (out_attr && !with_attr_)) return kMapInvalid;
+    const int64_t n = removed_count();
+    *out_n = n;
+    if (capacity < n) return kMapCapacity;
+    if (n > 0) {
+      std::memcpy(out_keys, log_keys_.data(), sizeof(uint64_t) * static_cast<size_t>(n));
+      std::memcpy(out_xyz, log_rows_.data(), sizeof(float) * 3 * static_cast<size_t>(n));
+      if (out_attr) std::memcpy(out_attr, log_attr_.data(), sizeof(uint32_t) * static_cast<size_t>(n));
+    }
+    log_keys_.clear();  // (keeps the memory)
+    log_rows_.clear();
+    log_attr_.clear();
+    return kMapOk;
+  }
+
   // include/madicp_host.h: madicp_host_map_prune — rows beyond `radius` of `center` leave (map_row_kept, from the stored float row),
   // their keys leave the set; the kept rows close up in order, keys and attribute words with them: one sequential stable pass.
   // *out_watermark: the kept rows among [0, watermark).
@@ -82,6 +132,7 @@ class VoxelMap {
     if (!center || !out_removed || !out_rows || !out_watermark) return kMapInvalid;
     if (map_prune_refusal(center, radius)) return kMapInvalid;
     if (watermark < 0 || watermark > size()) return kMapInvalid;
+    if (log_full()) return kMapCapacity;
     const double r2 = radius * radius;
     close_up([&](int64_t j) { return map_row_kept(rows_.data() + 3 * j, center, r2); }, watermark, out_removed, out_rows, out_watermark);
     return kMapOk;
@@ -96,6 +147,7 @@ class VoxelMap {
     if (!out_removed || !out_rows || !out_watermark || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
     if (map_clear_refusal(R, t, origin, margin)) return kMapInvalid;
     if (watermark < 0 || watermark > size()) return kMapInvalid;
+    if (log_full()) return kMapCapacity;
     std::unordered_set<uint64_t> traversed, occupied;
     if (size() > 0 && n > 0) {
       double qo[3];
@@ -127,11 +179,18 @@ class VoxelMap {
     keys_.clear();
     row_keys_.clear();
     attr_.clear();
+    log_keys_.clear();
+    log_rows_.clear();
+    log_attr_.clear();
   }
 
  private:
+  // a removal on a tracking map whose log holds max_rows entries or more is refused: decided without looking at a row
+  bool log_full() const { return track_ && removed_count() >= max_rows_; }
+
   // the one way rows leave: row j stays iff kept(j); the kept rows close up in order, keys and attribute words with them, the keys
-  // of the others leave the set.  *out_watermark: the kept rows among [0, watermark).
+  // of the others leave the set.  *out_watermark: the kept rows among [0, watermark).  On a tracking map the rows that leave from
+  // below the watermark go to the removal log, in row order.
   template <class Kept>
   void close_up(Kept kept, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) {
     const int64_t m = size();
@@ -140,6 +199,11 @@ class VoxelMap {
       if (j == watermark) mark = d;
       if (!kept(j)) {
         keys_.erase(row_keys_[j]);
+        if (track_ && j < watermark) {
+          log_keys_.push_back(row_keys_[j]);
+          for (int k = 0; k < 3; ++k) log_rows_.push_back(rows_[3 * j + k]);
+          if (with_attr_) log_attr_.push_back(attr_[j]);
+        }
         continue;
       }
       if (d != j) {
@@ -165,6 +229,10 @@ class VoxelMap {
   std::vector<uint32_t> attr_;
   std::vector<uint64_t> row_keys_;  // the key of every row (prune erases by it: a float row cannot reproduce its key)
   std::unordered_set<uint64_t> keys_;
+  bool track_ = false;  // the removal log: entries of (key, float row, word), oldest first
+  std::vector<uint64_t> log_keys_;
+  std::vector<float> log_rows_;
+  std::vector<uint32_t> log_attr_;
 };
 
 }  // namespace madicp_host

@@ -173,23 +173,74 @@ PYBIND11_MODULE(pypeline, m) {
          },
          py::arg("cloud"), py::arg("pose"), py::arg("origin") = std::vector<double>{0.0, 0.0, 0.0}, py::arg("margin") = 0.0)
     .def("mapNewRows",
-         [](Pipeline& self, bool with_attribute) -> py::object {
+         [](Pipeline& self, bool with_attribute, bool with_keys) -> py::object {
            const size_t m = self.mapNewRowCount();
            if (with_attribute && !self.mapWithAttribute())
              throw std::logic_error("Pipeline::mapNewRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
            py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
            py::array_t<uint32_t> w(static_cast<py::ssize_t>(with_attribute ? m : 0));
+           py::array_t<uint64_t> k(static_cast<py::ssize_t>(with_keys ? m : 0));
            float none[3];
            uint32_t no_word[1];
-           if (self.mapNewRows(m ? out.mutable_data() : none, m, with_attribute ? (m ? w.mutable_data() : no_word) : nullptr) != m)
+           uint64_t no_key[1];
+           if (self.mapNewRows(m ? out.mutable_data() : none, m, with_attribute ? (m ? w.mutable_data() : no_word) : nullptr,
+                               with_keys ? (m ? k.mutable_data() : no_key) : nullptr) != m)
              throw std::runtime_error("Pipeline::mapNewRows: the map changed during the call");
-           if (!with_attribute) return std::move(out);
+           if (!with_attribute && !with_keys) return std::move(out);
+           py::object words = w;
+           if (const int type = self.mapAttributeType(); with_attribute && type != madicp_host::kAttrNone) {
+             const py::module_ rec = py::module_::import("mad_icp_amd.records");
+             words = rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]);
+           }
+           if (!with_keys) return py::make_tuple(out, words);
+           if (!with_attribute) return py::make_tuple(out, k);
+           return py::make_tuple(out, words, k);
+         },
+         py::arg("with_attribute") = false, py::arg("with_keys") = false)
+    // additive: a map that a consumer can mirror (Pipeline::setMapTrackRemoved).  mapKeys(first_row=0): the stored 64-bit voxel keys of
+    // rows [first_row, mapSize()), uint64 (M,) — a row's identity across prunes; mapNewRows(with_keys=True) puts the new rows' keys
+    // last in the tuple.  setMapTrackRemoved(True) makes the map log the rows that were delivered through mapNewRows and have left
+    // since; mapRemovedRows(with_attribute=False) takes the log as (keys uint64 (n,), rows float32 (n, 3)[, attr]), attr viewed as the
+    // field's dtype as in mapNewRows.  mapRemovedLogFull(): a removal was skipped because the log held max_points entries — true
+    // until the next mapRemovedRows().  mad_icp_amd.map_mirror.MapMirror is the reference consumer.  RuntimeError (std::logic_error)
+    // while accumulation is off, from mapRemovedRows while tracking is off.
+    .def("setMapTrackRemoved", &Pipeline::setMapTrackRemoved, py::arg("on"))
+    .def("mapTrackRemoved", &Pipeline::mapTrackRemoved)
+    .def("mapRemovedRowCount", &Pipeline::mapRemovedRowCount)
+    .def("mapRemovedLogFull", &Pipeline::mapRemovedLogFull)
+    .def("mapRemovedRows",
+         [](Pipeline& self, bool with_attribute) -> py::object {
+           const size_t m = self.mapRemovedRowCount();
+           if (with_attribute && !self.mapWithAttribute())
+             throw std::logic_error("Pipeline::mapRemovedRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
+           py::array_t<uint64_t> k(static_cast<py::ssize_t>(m));
+           py::array_t<float> out({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(3)});
+           py::array_t<uint32_t> w(static_cast<py::ssize_t>(with_attribute ? m : 0));
+           uint64_t no_key[1];
+           float none[3];
+           uint32_t no_word[1];
+           if (self.mapRemovedRows(m ? k.mutable_data() : no_key, m ? out.mutable_data() : none,
+                                   with_attribute ? (m ? w.mutable_data() : no_word) : nullptr, m) != m)
+             throw std::runtime_error("Pipeline::mapRemovedRows: the log changed during the call");
+           if (!with_attribute) return py::make_tuple(k, out);
            const int type = self.mapAttributeType();
-           if (type == madicp_host::kAttrNone) return py::make_tuple(out, w);
+           if (type == madicp_host::kAttrNone) return py::make_tuple(k, out, w);
            const py::module_ rec = py::module_::import("mad_icp_amd.records");
-           return py::make_tuple(out, rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]));
+           return py::make_tuple(k, out, rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]));
          },
          py::arg("with_attribute") = false)
+    .def("mapKeys",
+         [](Pipeline& self, size_t first_row) {
+           const size_t size = self.mapSize();
+           if (first_row > size) throw py::value_error("first_row is beyond the map's rows");
+           const size_t m = size - first_row;
+           py::array_t<uint64_t> k(static_cast<py::ssize_t>(m));
+           uint64_t no_key[1];
+           if (self.mapKeys(m ? k.mutable_data() : no_key, m, first_row) != m)
+             throw std::runtime_error("Pipeline::mapKeys: the map changed during the call");
+           return k;
+         },
+         py::arg("first_row") = 0)
     // additive: a frame straight from sensor records, (n, >=3) float32 (a KITTI .bin is (n,4)): range filter, optional
     // KITTI correction (apps/cpp_runners/bin_runner.cpp:126-166), deskew, build and registration on the device
     .def("computeRecords",
