@@ -525,6 +525,33 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *   madicp_map_download_rows  the columns of rows [first_row, rows) — out_xyz, and out_keys and out_attr where not null — with
  *                             their copies in front of ONE host synchronisation; madicp_map_download_f32's conventions, and
  *                             MADICP_ERR_INVALID for an out_attr on a map without the column.
+ * EVIDENCE.  A map of madicp_map_create_ev keeps a hit/miss count per row: one more 32-bit word e, 1 <= e <= cap, under three
+ * parameters fixed at creation, hit >= 1, miss >= 1, hit <= cap <= 2^31 - 1 (the rule, integers only, is
+ * csrc/common/export_point.h's, shared with the host twin).  With N the candidate keys of a folded cloud:
+ *   fold      a row the fold creates gets e = hit; a row that was there before the fold and whose stored key is in N gets
+ *             e = min(e + hit, cap) — ONCE per fold, however many points fall into the voxel; other rows are not touched
+ *   clearing  madicp_map_clear_rays: a row whose stored key is in T \ O is MISSED — e > miss: it stays with e - miss; else it
+ *             leaves, through the same close-up, watermark and removal log as on a plain map.  Every row is covered, below and above
+ *             the watermark; rows in O and rows not in T are not touched; the decrements hold even when no row leaves
+ *   prune, growth: the word travels with its row; madicp_map_clear forgets it with the rows.  The removal log's entries carry none.
+ * With hit = miss = cap = 1 the map is the plain map in every row, key, count and log entry.  A fold's hits are found by one more
+ * kernel behind the claim (fe::map_hit: one lane per point, one elected per voxel and fold by an integer exchange on a stamp word
+ * of the voxel's table slot), the misses by the mark kernel of the clearing itself (fe::map_clear_mark_ev, one lane per row): no
+ * host synchronisation is added to either call, and the result is a function of the sequence of (cloud, pose) alone.
+ *   madicp_map_create_ev            madicp_map_create's arguments, with_attr != 0 for the attribute column as well, and the three
+ *                                   parameters; MADICP_ERR_INVALID for what map_evidence_refusal refuses.  The block gains the
+ *                                   column ev (cap x 4 bytes) and two 32-bit words per table slot (the slot's row, the slot's fold
+ *                                   stamp): 20 more bytes per row of capacity — 64 instead of 44, 68 instead of 48.
+ *   madicp_map_download_evidence    the words of rows [first_row, rows), madicp_map_download_attr's conventions: *out_n set,
+ *                                   MADICP_ERR_CAPACITY when capacity_rows is smaller, MADICP_ERR_INVALID on a map made without
+ *                                   the column.  One host synchronisation.
+ *   madicp_map_download_min_evidence the rows with e >= min_e, in row order, compacted on the device (a mark kernel, the tile scan
+ *                                   and one gather into a transient block of the call's own; the builder's scratch is not
+ *                                   touched): out_xyz, and out_keys, out_attr, out_ev where not null.  *out_n is always set to
+ *                                   their number; MADICP_ERR_CAPACITY, nothing written, when capacity_rows is smaller;
+ *                                   MADICP_ERR_INVALID on a map without the column or for an out_attr on a map without that
+ *                                   one.  TWO host synchronisations: the count, then the rows (none on an empty map, one where
+ *                                   no row qualifies or the buffer is short).
  * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes,
  * clearings and takes. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
@@ -545,6 +572,11 @@ int madicp_map_take_removed(madicp_ctx* ctx, int map_id, uint64_t* out_keys, flo
 int madicp_map_download_keys(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_download_rows(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
                              int64_t capacity_rows, int64_t* out_n);
+int madicp_map_create_ev(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, uint32_t hit, uint32_t miss,
+                         uint32_t cap, int* out_map_id);
+int madicp_map_download_evidence(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_download_min_evidence(madicp_ctx* ctx, int map_id, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                                     uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

@@ -143,7 +143,16 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  the twins of madicp_map_track_removed and its neighbours (madicp_hip.h has the rule of the removal log): on a
  *                  tracking map _prune and _clear_rays append the rows they remove from below the watermark — stored key, float
  *                  row, word — to the log, in the one stable pass; they are refused with MADICP_ERR_CAPACITY, nothing changed,
- *                  while the log holds >= max_rows entries.  Codes and "nothing written" as on the device. */
+ *                  while the log holds >= max_rows entries.  Codes and "nothing written" as on the device.
+ *   _create_ev / _download_evidence / _download_min_evidence
+ *                  the twins of madicp_map_create_ev and its neighbours (madicp_hip.h has the rule of the evidence column): a map
+ *                  with one more 32-bit word per row, 1 .. cap — a fold gives hit to the rows it creates and adds hit, once per
+ *                  fold and saturating at cap, to the older rows it falls into; _clear_rays takes miss from a row it would
+ *                  otherwise remove and removes it only when that uses the word up.  with_attr != 0: the attribute column as
+ *                  well.  MADICP_ERR_INVALID for hit < 1, miss < 1, cap < hit, cap > 2^31 - 1, and for both downloads on a map
+ *                  made without the column.  _download_min_evidence: the rows with word >= min_e in row order, out_keys /
+ *                  out_attr / out_ev null where not wanted; *out_n is always their number, MADICP_ERR_CAPACITY, nothing
+ *                  written, when capacity_rows is smaller. */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -166,6 +175,11 @@ int madicp_host_map_take_removed(madicp_host_map* map, uint64_t* out_keys, float
 int madicp_host_map_download_keys(const madicp_host_map* map, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_download_rows(const madicp_host_map* map, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
                                   int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_create_ev(double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, uint32_t hit, uint32_t miss, uint32_t cap,
+                              madicp_host_map** out_map);
+int madicp_host_map_download_evidence(const madicp_host_map* map, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_download_min_evidence(const madicp_host_map* map, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                                          uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

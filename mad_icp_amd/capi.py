@@ -183,6 +183,10 @@ def hip_lib():
         L.madicp_map_take_removed.argtypes = [C.c_void_p, C.c_int, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
         L.madicp_map_download_keys.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u64p, C.c_int64, _i64p]
         L.madicp_map_download_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), _u64p, _u32p, C.c_int64, _i64p]
+        L.madicp_map_create_ev.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _ip]
+        L.madicp_map_download_evidence.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u32p, C.c_int64, _i64p]
+        L.madicp_map_download_min_evidence.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_float), _u64p, _u32p, _u32p, C.c_int64,
+                                                       _i64p]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
@@ -253,6 +257,10 @@ def host_lib():
         L.madicp_host_map_take_removed.argtypes = [C.c_void_p, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
         L.madicp_host_map_download_keys.argtypes = [C.c_void_p, C.c_int64, _u64p, C.c_int64, _i64p]
         L.madicp_host_map_download_rows.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), _u64p, _u32p, C.c_int64, _i64p]
+        L.madicp_host_map_create_ev.argtypes = [C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_void_p)]
+        L.madicp_host_map_download_evidence.argtypes = [C.c_void_p, C.c_int64, _u32p, C.c_int64, _i64p]
+        L.madicp_host_map_download_min_evidence.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), _u64p, _u32p, _u32p, C.c_int64, _i64p]
         L.madicp_host_map_destroy.restype = None
         L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
@@ -728,6 +736,41 @@ def host_map_download_rows(h, first_row=0, with_keys=True, with_attr=False):
     return (xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ())
 
 
+def host_map_create_ev(voxel, initial_rows, max_rows, hit, miss, cap, with_attr=False):
+    """madicp_host_map_create_ev: a host map with the evidence column (the twin of Context.map_create_ev)."""
+    h = C.c_void_p()
+    _host_map_check(host_lib().madicp_host_map_create_ev(float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0, int(hit),
+                                                         int(miss), int(cap), C.byref(h)), "madicp_host_map_create_ev")
+    return h
+
+
+def host_map_download_evidence(h, first_row=0):
+    """The evidence words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_download_evidence(h, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)),
+                    "madicp_host_map_download_evidence")
+    return out[:got.value].copy()
+
+
+def host_map_download_min_evidence(h, min_e, with_keys=False, with_attr=False, with_ev=False):
+    """madicp_host_map_download_min_evidence: the rows whose evidence word is >= min_e, in row order:
+    (rows (n, 3) float32[, keys uint64][, words uint32][, evidence uint32])."""
+    m = host_map_size(h)
+    xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
+    k = np.empty(max(m, 1), np.uint64) if with_keys else None
+    w = np.empty(max(m, 1), np.uint32) if with_attr else None
+    e = np.empty(max(m, 1), np.uint32) if with_ev else None
+    _host_map_check(host_lib().madicp_host_map_download_min_evidence(h, int(min_e), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                     k.ctypes.data_as(_u64p) if with_keys else None,
+                                                                     w.ctypes.data_as(_u32p) if with_attr else None,
+                                                                     e.ctypes.data_as(_u32p) if with_ev else None, m, C.byref(got)),
+                    "madicp_host_map_download_min_evidence")
+    g = got.value
+    return ((xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ()) +
+            ((e[:g].copy(),) if with_ev else ()))
+
+
 def host_map_clear(h):
     _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
 
@@ -1034,6 +1077,38 @@ class Context:
                                                   w.ctypes.data_as(_u32p) if with_attr else None, m, C.byref(got)))
         g = got.value
         return (xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ())
+
+    def map_create_ev(self, voxel, initial_rows, max_rows, hit, miss, cap, with_attr=False):
+        """madicp_map_create_ev: a map with the evidence column — a fold gives `hit` to the rows it creates and adds `hit`, once per
+        fold and saturating at `cap`, to the older rows it falls into; map_clear_rays takes `miss` from a row it sees through and
+        removes it only when that uses the word up.  with_attr: the attribute column as well.  Returns the map id."""
+        mid = C.c_int(0)
+        _check(hip_lib().madicp_map_create_ev(self._h, float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0, int(hit),
+                                              int(miss), int(cap), C.byref(mid)))
+        return mid.value
+
+    def map_download_evidence(self, mid, first_row=0):
+        """The evidence words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
+        _check(hip_lib().madicp_map_download_evidence(self._h, mid, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)))
+        return out[:got.value].copy()
+
+    def map_download_min_evidence(self, mid, min_e, with_keys=False, with_attr=False, with_ev=False):
+        """madicp_map_download_min_evidence: the rows whose evidence word is >= min_e, in row order, compacted on the device:
+        (rows (n, 3) float32[, keys uint64][, words uint32][, evidence uint32])."""
+        m = self.map_size(mid)
+        xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
+        k = np.empty(max(m, 1), np.uint64) if with_keys else None
+        w = np.empty(max(m, 1), np.uint32) if with_attr else None
+        e = np.empty(max(m, 1), np.uint32) if with_ev else None
+        _check(hip_lib().madicp_map_download_min_evidence(self._h, mid, int(min_e), xyz.ctypes.data_as(C.POINTER(C.c_float)),
+                                                          k.ctypes.data_as(_u64p) if with_keys else None,
+                                                          w.ctypes.data_as(_u32p) if with_attr else None,
+                                                          e.ctypes.data_as(_u32p) if with_ev else None, m, C.byref(got)))
+        g = got.value
+        return ((xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ()) +
+                ((e[:g].copy(),) if with_ev else ()))
 
     def map_clear(self, mid):
         _check(hip_lib().madicp_map_clear(self._h, mid))

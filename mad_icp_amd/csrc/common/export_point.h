@@ -130,4 +130,35 @@ MADICP_HD inline void ray_sample(const double* qo, const double* d, double L, in
   s[2] = qo[2] + d[2] * f;
 }
 
+// ---- evidence (madicp_map_create_ev / madicp_host_map_create_ev): a hit/miss count per row, integers only ---------------------------
+// A map made with evidence has three parameters fixed at creation — hit, miss, cap — and one 32-bit word e per row, 1 <= e <= cap:
+//   fold      a row the fold creates gets e = hit; a row that was there before it and whose STORED key is a candidate key of the
+//             folded cloud gets e = min(e + hit, cap) — once per fold, however many points fall into the voxel
+//   clearing  a row whose stored key is in T \ O is MISSED: e > miss -> it stays with e - miss, else it leaves (the prune's close-up,
+//             watermark and removal log); the rule covers every row, and the decrements hold even when no row leaves
+// hit = miss = cap = 1 is the plain map: every row holds 1, a hit saturates at once, a miss removes.
+constexpr uint32_t kMapEvidenceCapMax = 0x7fffffffu;  // e + hit <= 2 cap stays within 32 bits
+
+// what both create entry points refuse (null = nothing to refuse)
+inline const char* map_evidence_refusal(uint32_t hit, uint32_t miss, uint32_t cap) {
+  if (hit < 1) return "evidence: hit at least 1";
+  if (miss < 1) return "evidence: miss at least 1";
+  if (cap < hit) return "evidence: cap at least hit";
+  if (cap > kMapEvidenceCapMax) return "evidence: cap at most 2^31 - 1";
+  return nullptr;
+}
+
+// the word of a row after a fold that hit it
+MADICP_HD inline uint32_t map_evidence_hit(uint32_t e, uint32_t hit, uint32_t cap) {
+  const uint32_t s = e + hit;  // (e <= cap, hit <= cap, cap < 2^31: no wrap)
+  return s < cap ? s : cap;
+}
+
+// a clearing that missed the row: whether it stays; *e is its word afterwards (unchanged where it leaves)
+MADICP_HD inline bool map_evidence_miss(uint32_t* e, uint32_t miss) {
+  if (*e <= miss) return false;
+  *e -= miss;
+  return true;
+}
+
 }  // namespace madicp_host

@@ -517,12 +517,13 @@ __global__ __launch_bounds__(256) void voxel_mark(const uint32_t* __restrict__ s
 // Null arguments (kernel arguments: the branches are wave-uniform) switch parts off.  mark / pos: every point, at row first_row + i.
 // row_keys: no key is stored, and none is recomputed (three fp64 divisions per row).  owner / slot_of: nothing settles.
 // row_attr: no attribute column beside the rows; else every row written gets its owning point's word, or 0 where the cloud carries
-// none (attr == nullptr).
+// none (attr == nullptr).  row_ev: no evidence column; else every row written gets `hit` and slot_row learns the row of its slot.
 __global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
                                                   const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
                                                   const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner, long first_row,
                                                   float* __restrict__ rows, unsigned long long* __restrict__ row_keys,
-                                                  const uint32_t* __restrict__ attr, uint32_t* __restrict__ row_attr) {
+                                                  const uint32_t* __restrict__ attr, uint32_t* __restrict__ row_attr,
+                                                  uint32_t* __restrict__ row_ev, uint32_t hit, uint32_t* __restrict__ slot_row) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     if (mark && !mark[i]) continue;
     const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
@@ -534,13 +535,47 @@ __global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz
     rows[3 * d + 2] = madicp_host::export_value(q[2]);
     if (row_keys) row_keys[d] = madicp_host::export_key(q, voxel);
     if (row_attr) row_attr[d] = attr ? attr[i] : 0u;
+    if (row_ev) {  // (an evidence map: the new row's word, and where its slot's row is — what map_hit reads in later folds)
+      row_ev[d] = hit;
+      slot_row[slot_of[i]] = (uint32_t)d;
+    }
     if (owner) owner[slot_of[i]] = kMapSettled;  // (one marked point per slot: nobody else writes it in this kernel)
   }
 }
 __global__ __launch_bounds__(256) void map_rehash(const unsigned long long* __restrict__ row_keys, long n_rows,
-                                                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots) {
-  for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n_rows; r += (long)gridDim.x * blockDim.x)
-    owner[map_find_or_claim(keys, slots, row_keys[r])] = kMapSettled;
+                                                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
+                                                  uint32_t* __restrict__ slot_row /* evidence maps, else null */) {
+  for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n_rows; r += (long)gridDim.x * blockDim.x) {
+    const uint32_t s = map_find_or_claim(keys, slots, row_keys[r]);
+    owner[s] = kMapSettled;
+    if (slot_row) slot_row[s] = (uint32_t)r;
+  }
+}
+
+// ---- evidence: the hits of a fold (madicp_map_create_ev; the rule is csrc/common/export_point.h's map_evidence_hit) -----------------
+// An evidence map has two more 32-bit words beside every table slot: slot_row, the row of the slot's key — written where a slot
+// settles (voxel_rows) and where the table is refilled (map_rehash: at a growth and behind every removal, so it follows its row
+// through both) — and stamp, the number of the last fold that hit the slot (all ones: none since the table was last emptied; the
+// host counts the folds from 0 again at every wipe and wipes before the count could reach all ones).
+//   map_hit  behind voxel_claim's kernel boundary, one lane per point: a slot whose owner is kMapSettled belongs to a row OLDER than
+//            this fold (the fold's own slots are contended until voxel_rows settles them, which runs behind this kernel);
+//            atomicExch(stamp[s], fold_no) hands the previous stamp to every lane and exactly ONE of a voxel's lanes sees another
+//            fold's: that lane does the plain saturating add on ev[slot_row[s]] — no other lane touches that word in this kernel.
+// Determinism: who is elected does not matter, only that one is — the result is "+ hit once per voxel and fold", a function of the
+// sequence of (cloud, pose) alone.  Contention: a relaxed agent-scope load in front of the exchange skips it once the stamp is this
+// fold's (within a fold a stamp only ever becomes fold_no, so a stale value costs one exchange); all points in ONE voxel serialise
+// on one word for the first wavefronts and read the stamp afterwards.
+__global__ __launch_bounds__(256) void map_hit(const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ owner, long n,
+                                               const uint32_t* __restrict__ slot_row, uint32_t* __restrict__ stamp, uint32_t fold_no,
+                                               uint32_t* __restrict__ ev, uint32_t hit, uint32_t cap) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const uint32_t s = slot_of[i];
+    if (s == kExportNoSlot || owner[s] != kMapSettled) continue;
+    if (__hip_atomic_load(&stamp[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == fold_no) continue;
+    if (atomicExch(&stamp[s], fold_no) == fold_no) continue;
+    const uint32_t r = slot_row[s];
+    ev[r] = madicp_host::map_evidence_hit(ev[r], hit, cap);
+  }
 }
 
 // ---- pruning the map: rows beyond a radius of a centre leave, the kept ones close up in order (madicp_map_prune) -------------------
@@ -550,7 +585,7 @@ __global__ __launch_bounds__(256) void map_rehash(const unsigned long long* __re
 //   map_compact     one lane per row: a kept row's stored key, three floats and, where the column exists, its word to row S[j] of the
 //                   DESTINATION block — coalesced reads, monotone writes; whether row j stays is read off the scan, S[j + 1] != S[j],
 //                   so the marks are dead by now and the lane of row 0 leaves {S[M], S[watermark]} in `res` (the caller lays it over
-//                   them): both answers of a prune in one small copy
+//                   them): both answers of a prune in one small copy.  ev / out_ev: the evidence column, a null-able pair like attr
 // The table is then emptied by the one memset and refilled by map_rehash over the kept keys, which leaves every owner kMapNever or
 // kMapSettled — what the folds rely on.  Determinism: a comparison per row and an exclusive scan; nothing depends on the geometry.
 struct PruneSphere {  // by value, wave-uniform: scalar loads
@@ -569,7 +604,8 @@ __global__ __launch_bounds__(256) void map_prune_mark(const float* __restrict__ 
 __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ pos, long n_rows, long watermark,
                                                    const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
                                                    const uint32_t* __restrict__ attr, unsigned long long* __restrict__ out_keys,
-                                                   float* __restrict__ out_rows, uint32_t* __restrict__ out_attr, uint32_t* __restrict__ res) {
+                                                   float* __restrict__ out_rows, uint32_t* __restrict__ out_attr, uint32_t* __restrict__ res,
+                                                   const uint32_t* __restrict__ ev, uint32_t* __restrict__ out_ev) {
   for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_rows; j += (long)gridDim.x * blockDim.x) {
     if (j == 0) {
       res[0] = pos[n_rows];
@@ -582,6 +618,7 @@ __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ 
     out_rows[3 * d + 1] = rows[3 * j + 1];
     out_rows[3 * d + 2] = rows[3 * j + 2];
     if (attr) out_attr[d] = attr[j];
+    if (ev) out_ev[d] = ev[j];
   }
 }
 // The removal log of a tracking map (madicp_map_track_removed): map_compact's complement over the rows below the watermark, beside it
@@ -686,6 +723,33 @@ __global__ __launch_bounds__(256) void map_clear_mark(const unsigned long long* 
     }
     mark[j] = m;  // (entry n_rows: the scan needs a terminator)
   }
+}
+// The mark of a clearing on an EVIDENCE map (madicp_map_create_ev), in map_clear_mark's place: one lane per row, so no two lanes
+// meet on a word.  A row whose flags are exactly "traversed" is MISSED (csrc/common/export_point.h: map_evidence_miss): it loses
+// `miss` in place, on the live column, and stays unless that uses its word up — the decrements hold whether or not any row leaves,
+// and map_compact, behind the scan, copies the words as they are then.  ray_flags is the plain map's.
+__global__ __launch_bounds__(256) void map_clear_mark_ev(const unsigned long long* __restrict__ row_keys, long n_rows,
+                                                         const unsigned long long* __restrict__ keys, uint32_t slots,
+                                                         const uint32_t* __restrict__ flags, uint32_t* __restrict__ ev, uint32_t miss,
+                                                         uint32_t* __restrict__ mark) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j <= n_rows; j += (long)gridDim.x * blockDim.x) {
+    uint32_t m = 0;
+    if (j < n_rows) {
+      const uint32_t s = map_find(keys, slots, row_keys[j]);
+      m = 1u;
+      if (s != kExportNoSlot && (flags[s] & (kRayTraversed | kRayOccupied)) == kRayTraversed) {
+        uint32_t e = ev[j];
+        m = madicp_host::map_evidence_miss(&e, miss) ? 1u : 0u;
+        ev[j] = e;
+      }
+    }
+    mark[j] = m;  // (entry n_rows: the scan needs a terminator)
+  }
+}
+// the mark of madicp_map_download_min_evidence: mark[j] = the row's word is at least min_e; mark[M] = 0, the scan's terminator
+__global__ __launch_bounds__(256) void map_ev_mark(const uint32_t* __restrict__ ev, long n_rows, uint32_t min_e, uint32_t* __restrict__ mark) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j <= n_rows; j += (long)gridDim.x * blockDim.x)
+    mark[j] = (j < n_rows && ev[j] >= min_e) ? 1u : 0u;
 }
 
 }  // namespace fe

@@ -30,6 +30,13 @@ struct DevMap {
   uint32_t* attr = nullptr;                // (cap) the rows' attribute words: maps of madicp_map_create_attr only
   bool with_attr = false;
   uint32_t slots = 0;
+  // evidence (madicp_map_create_ev): the rows' words, and beside every table slot the row of its key and the number of the last
+  // fold that hit it (fe::map_hit); fold_no counts the folds since the stamps were last wiped
+  bool with_ev = false;
+  uint32_t ev_hit = 1, ev_miss = 1, ev_cap = 1, fold_no = 0;
+  uint32_t* ev = nullptr;        // (cap)
+  uint32_t* slot_row = nullptr;  // (slots)
+  uint32_t* stamp = nullptr;     // (slots) all ones = not hit since the wipe
   // the removal log (madicp_map_track_removed): a block of its own — the map's is swapped by every prune and growth —
   //   keys (log_cap x 8) | xyz (log_cap x 12) | attr (log_cap x 4, attribute maps only)
   // of which the first log_n entries are live; allocated at the first removal that can log
@@ -869,17 +876,25 @@ struct VoxelTable {
   uint32_t* owner;           // (slots) fe::kMapNever / kMapSettled / contended
   uint32_t slots;
 };
+// what a fold into an evidence map needs beside the table (DevMap has the columns)
+struct FoldEvidence {
+  uint32_t *ev, *slot_row, *stamp;
+  uint32_t fold_no, hit, cap;
+};
 
 // One fold of a resident cloud (n >= 1 points) through X into table T, on the copy stream: fe::voxel_claim, fe::voxel_mark, the
 // tile scan, fe::voxel_rows — the lowest-index point of every voxel T has not settled yet, as float rows from `first_row` of `rows`
 // on, in input order.  row_keys: where the rows' keys go, or null; settle: whether the rows' slots settle (a table that lives on).
 // row_attr: where the rows' attribute words go (the owning point's, 0 where the cloud carries no column), or null.
+// E: an evidence map's columns, or null — the fold's rows get `hit`, and fe::map_hit, behind the claim, reinforces the older rows
+// the cloud falls into (no launch without it).
 // The caller keeps T at most half full.  The per-fold scratch lives in idle parts of the builder's scratch, which the caller owns
 // (busy_with_lookahead, ensure_scratch for n) and which does not grow:
 //   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->r.kept  the scan's total
 // The rows are enqueued BEHIND the scan, before the host knows the count, and they are ready when it arrives: ONE synchronisation.
 int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::ExportPose& X, double voxel, VoxelTable T, bool settle,
-               float* rows, int64_t first_row, unsigned long long* row_keys, uint32_t* row_attr, int64_t* out_added) {
+               float* rows, int64_t first_row, unsigned long long* row_keys, uint32_t* row_attr, int64_t* out_added,
+               const FoldEvidence* E = nullptr) {
   const int64_t n = c->n;
   uint32_t* slot_of = fs->idx[0];
   uint32_t* mark = fs->P.leaf_start;
@@ -887,11 +902,14 @@ int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::E
   hipLaunchKernelGGL(fe::voxel_claim, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, T.keys, T.owner,
                      T.slots, slot_of);
   hipLaunchKernelGGL(fe::voxel_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)T.owner, (long)n, mark);
+  if (E)  // (in front of voxel_rows: what this fold claimed is still contended, only older rows' slots are settled)
+    hipLaunchKernelGGL(fe::map_hit, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)T.owner, (long)n,
+                       (const uint32_t*)E->slot_row, E->stamp, E->fold_no, E->ev, E->hit, E->cap);
   RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
   HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
   hipLaunchKernelGGL(fe::voxel_rows, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, (const uint32_t*)mark,
                      (const uint32_t*)fs->S, (const uint32_t*)(settle ? slot_of : nullptr), settle ? T.owner : nullptr, (long)first_row,
-                     rows, row_keys, (const uint32_t*)c->attr, row_attr);
+                     rows, row_keys, (const uint32_t*)c->attr, row_attr, E ? E->ev : nullptr, E ? E->hit : 0u, E ? E->slot_row : nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count
   *out_added = fs->h_rec_res->r.kept;
@@ -980,7 +998,7 @@ int cloud_export_on(madicp_ctx* ctx, int cloud_id, const double R[9], const doub
   if (voxel == 0.0) {
     hipLaunchKernelGGL(fe::voxel_rows, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel,
                        (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0L, d_rows,
-                       (unsigned long long*)nullptr, (const uint32_t*)c->attr, d_row_attr);
+                       (unsigned long long*)nullptr, (const uint32_t*)c->attr, d_row_attr, (uint32_t*)nullptr, 0u, (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
   } else {
     VoxelTable T;
@@ -1021,15 +1039,30 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
 // Growth invariant: before a fold of n points into M rows, M + n <= cap — so the table is never more than half full and every
 // probe ends; where it would not hold, a block for max(M + n, min(2 cap, max_rows)) rows is allocated, rows and keys move by device
 // copy, map_rehash refills the table, the old block is freed.  A map of madicp_map_create_attr has a fifth column
-// behind these — attr (cap x 4), the rows' attribute words: 48 bytes per row of capacity — that moves with the rows.  The host knows M exactly: every fold ends with ONE synchronisation,
+// behind these — attr (cap x 4), the rows' attribute words: 48 bytes per row of capacity — that moves with the rows.  A map of
+// madicp_map_create_ev has, behind whatever of these it holds, ev (cap x 4) | slot_row (2 cap x 4) | stamp (2 cap x 4): the rows'
+// evidence words, which move with the rows, and two more words per table slot, wiped (stamp) and refilled (slot_row) with the table
+// — 20 more bytes per row of capacity.  The host knows M exactly: every fold ends with ONE synchronisation,
 // for the count (none more at a growth but the one in front of freeing the old block).  A fold uses the builder's scratch: it is
 // refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
 namespace {
 
+// the ONE memset that empties the table; on an evidence map a second one for the slots' fold stamps, and the folds count from 0 again
+hipError_t map_stamp_wipe(madicp_ctx* ctx, DevMap* m) {
+  m->fold_no = 0;
+  return hipMemsetAsync(m->stamp, 0xff, sizeof(uint32_t) * (size_t)m->slots, ctx->copy);
+}
+hipError_t map_table_wipe(madicp_ctx* ctx, DevMap* m) {
+  hipError_t e = hipMemsetAsync(m->block, 0xff, 24 * (size_t)m->cap, ctx->copy);
+  if (e == hipSuccess && m->with_ev) e = map_stamp_wipe(ctx, m);
+  return e;
+}
+
 int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
   const size_t c = (size_t)cap;
   char* block = nullptr;
-  HIP_TRY(hipMalloc(&block, (m->with_attr ? 48 : 44) * c));
+  const size_t row_bytes = m->with_attr ? 48 : 44;
+  HIP_TRY(hipMalloc(&block, (row_bytes + (m->with_ev ? 20 : 0)) * c));
   m->block = block;
   m->cap = cap;
   m->slots = static_cast<uint32_t>(2 * c);
@@ -1038,7 +1071,10 @@ int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
   m->row_keys = reinterpret_cast<unsigned long long*>(block + 24 * c);
   m->xyz = reinterpret_cast<float*>(block + 32 * c);
   m->attr = m->with_attr ? reinterpret_cast<uint32_t*>(block + 44 * c) : nullptr;
-  hipError_t e = wipe ? hipMemsetAsync(block, 0xff, 24 * c, ctx->copy) : hipSuccess;  // (a prune wipes the table itself, later)
+  m->ev = m->with_ev ? reinterpret_cast<uint32_t*>(block + row_bytes * c) : nullptr;
+  m->slot_row = m->with_ev ? reinterpret_cast<uint32_t*>(block + (row_bytes + 4) * c) : nullptr;
+  m->stamp = m->with_ev ? reinterpret_cast<uint32_t*>(block + (row_bytes + 12) * c) : nullptr;
+  hipError_t e = wipe ? map_table_wipe(ctx, m) : hipSuccess;  // (a prune wipes the table itself, later)
   if (e != hipSuccess) {
     hipFree(block);
     *m = DevMap{};
@@ -1057,10 +1093,11 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
     e = hipMemcpyAsync(g.row_keys, m->row_keys, sizeof(unsigned long long) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) e = hipMemcpyAsync(g.xyz, m->xyz, sizeof(float) * 3 * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess && m->with_attr) e = hipMemcpyAsync(g.attr, m->attr, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess && m->with_ev) e = hipMemcpyAsync(g.ev, m->ev, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) {
       const int blocks = grid_256(ctx, m->rows);
       hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)m->rows, g.keys,
-                         g.owner, g.slots);
+                         g.owner, g.slots, g.slot_row);
       e = hipGetLastError();
     }
   }
@@ -1130,7 +1167,8 @@ int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uin
   hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, ctx->copy, tile_sums, tiles, total);
   hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
   hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
-                     (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark);
+                     (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark,
+                     (const uint32_t*)m->ev, g.ev);
   if (const int64_t below = std::min(watermark, M); m->track && below > 0)
     hipLaunchKernelGGL(fe::map_log_removed, dim3(grid_256(ctx, below)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)below, (long)m->log_n,
                        (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, m->log_keys(), m->log_xyz(),
@@ -1141,10 +1179,10 @@ int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uin
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy);  // the counts (the old block is read until here)
   const int64_t kept = res[0];
   if (e == hipSuccess && kept < M) {
-    e = hipMemsetAsync(g.block, 0xff, 24 * (size_t)g.cap, ctx->copy);
+    e = map_table_wipe(ctx, &g);
     if (e == hipSuccess && kept > 0) {
       hipLaunchKernelGGL(fe::map_rehash, dim3(grid_256(ctx, kept)), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)kept,
-                         g.keys, g.owner, g.slots);
+                         g.keys, g.owner, g.slots, g.slot_row);
       e = hipGetLastError();
     }
   }
@@ -1194,12 +1232,17 @@ int map_clear_rays_on(madicp_ctx* ctx, DevMap* m, const DevCloud* c, const fe::R
   }
   hipLaunchKernelGGL(fe::ray_flags, dim3(grid_256(ctx, 64 * c->n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)c->n, F, m->voxel,
                      (const unsigned long long*)m->keys, m->slots, flags);
-  hipLaunchKernelGGL(fe::map_clear_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys, (long)M,
-                     (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, mark);
+  if (m->with_ev)  // (the misses, in place on the live column: they hold whether or not a row leaves)
+    hipLaunchKernelGGL(fe::map_clear_mark_ev, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys,
+                       (long)M, (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, m->ev, m->ev_miss, mark);
+  else
+    hipLaunchKernelGGL(fe::map_clear_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys, (long)M,
+                       (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, mark);
   return map_remove_marked(ctx, m, g, mark, flags, mark + (M + 1), watermark, "voxel map clearing: ", out_kept, out_watermark);
 }
 
 constexpr const char* kMapLogFull = "the map's removal log holds max_rows entries or more (madicp_map_take_removed empties it)";
+constexpr const char* kMapNoEvidence = "the map was made without the evidence column (madicp_map_create_ev makes one with it)";
 
 DevMap* find_map(madicp_ctx* ctx, int id) {
   if (!ctx->front) return nullptr;
@@ -1207,14 +1250,23 @@ DevMap* find_map(madicp_ctx* ctx, int id) {
   return it == ctx->front->maps.end() ? nullptr : &it->second;
 }
 
-int map_create_on(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr, int* out_map_id) {
+int map_create_on(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr, int* out_map_id,
+                  const uint32_t* evidence = nullptr /* {hit, miss, cap} */) {
   if (!ctx || !out_map_id) return fail(MADICP_ERR_INVALID, "null argument");
   if (const char* why = madicp_host::map_create_refusal(voxel, initial_rows, max_rows)) return fail(MADICP_ERR_INVALID, why);
+  if (evidence)
+    if (const char* why = madicp_host::map_evidence_refusal(evidence[0], evidence[1], evidence[2])) return fail(MADICP_ERR_INVALID, why);
   HIP_TRY(hipSetDevice(ctx->device));
   DevMap m;
   m.voxel = voxel;
   m.max_rows = max_rows;
   m.with_attr = with_attr;
+  if (evidence) {
+    m.with_ev = true;
+    m.ev_hit = evidence[0];
+    m.ev_miss = evidence[1];
+    m.ev_cap = evidence[2];
+  }
   RC_TRY(map_block_alloc(ctx, std::min(initial_rows, max_rows), &m));
   const int id = ctx->next_id++;
   front_of(ctx).maps[id] = m;
@@ -1228,6 +1280,11 @@ int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64
 }
 int madicp_map_create_attr(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id) {
   return map_create_on(ctx, voxel, initial_rows, max_rows, true, out_map_id);
+}
+int madicp_map_create_ev(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, uint32_t hit, uint32_t miss,
+                         uint32_t cap, int* out_map_id) {
+  const uint32_t evidence[3] = {hit, miss, cap};
+  return map_create_on(ctx, voxel, initial_rows, max_rows, with_attr != 0, out_map_id, evidence);
 }
 
 int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
@@ -1251,8 +1308,13 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
   RC_TRY(ensure_scratch(ctx, n, &fs));
   if (m->rows + n > m->cap) RC_TRY(map_grow(ctx, m, m->rows + n));
   int64_t added = 0;
+  FoldEvidence E{};
+  if (m->with_ev) {
+    if (m->fold_no == fe::kMapNever) HIP_TRY(map_stamp_wipe(ctx, m));  // (2^32 - 1 folds without a removal or a growth)
+    E = FoldEvidence{m->ev, m->slot_row, m->stamp, m->fold_no++, m->ev_hit, m->ev_cap};
+  }
   RC_TRY(voxel_fold(ctx, fs, c, export_pose(R, t), m->voxel, VoxelTable{m->keys, m->owner, m->slots}, true, m->xyz, m->rows, m->row_keys,
-                    m->attr, &added));
+                    m->attr, &added, m->with_ev ? &E : nullptr));
   m->rows += added;
   *out_added = added;
   *out_rows = m->rows;
@@ -1336,6 +1398,83 @@ int madicp_map_download_rows(madicp_ctx* ctx, int map_id, int64_t first_row, flo
   if (e == hipSuccess) e = w;
   if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map download: ") + hipGetErrorString(e));
   return MADICP_OK;
+}
+
+int madicp_map_download_evidence(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_ev || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!m->with_ev) return fail(MADICP_ERR_INVALID, kMapNoEvidence);
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_ev holds fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out_ev, m->ev + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
+}
+
+// The rows whose word is at least min_e, compacted on the device into a transient block of the call's own (the builder's scratch
+// is sized by the largest CLOUD and may be a look-ahead's):
+//   keys (M x 8) | xyz (M x 12) | attr (M x 4) | ev (M x 4) | mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)
+// fe::map_ev_mark, the tile scan, and map_compact as the one gather (watermark 0: it leaves the count over the first mark).  Two
+// waits: the count — which decides whether the caller's buffers are large enough — then the rows.
+int madicp_map_download_min_evidence(madicp_ctx* ctx, int map_id, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                                     uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!m->with_ev) return fail(MADICP_ERR_INVALID, kMapNoEvidence);
+  if (out_attr && !m->with_attr)
+    return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
+  const int64_t M = m->rows;
+  *out_n = 0;
+  if (M == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t Ms = (size_t)M;
+  const int tiles = static_cast<int>((M + 1 + tb::kScanTile - 1) / tb::kScanTile);
+  char* block = nullptr;
+  HIP_TRY(hipMalloc(&block, 28 * Ms + 8 * (Ms + 1) + 4 * ((size_t)tiles + 1)));
+  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(block);
+  float* d_xyz = reinterpret_cast<float*>(block + 8 * Ms);
+  uint32_t* d_attr = reinterpret_cast<uint32_t*>(block + 20 * Ms);
+  uint32_t* d_ev = d_attr + Ms;
+  uint32_t* mark = d_ev + Ms;
+  uint32_t* S = mark + (Ms + 1);
+  uint32_t* tile_sums = S + (Ms + 1);
+  int32_t* total = reinterpret_cast<int32_t*>(tile_sums + tiles);
+  hipLaunchKernelGGL(fe::map_ev_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)m->ev, (long)M, min_e, mark);
+  hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, tile_sums);
+  hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, ctx->copy, tile_sums, tiles, total);
+  hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
+  hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, 0L,
+                     (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, d_keys, d_xyz, d_attr, mark,
+                     (const uint32_t*)m->ev, d_ev);
+  uint32_t res[2] = {0, 0};
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(res, mark, sizeof(res), hipMemcpyDeviceToHost, ctx->copy);
+  hipError_t w = hipStreamSynchronize(ctx->copy);  // the count
+  if (e == hipSuccess) e = w;
+  const int64_t rows = res[0];
+  int rc = MADICP_OK;
+  if (e == hipSuccess) {
+    *out_n = rows;
+    if (capacity_rows < rows) {
+      rc = fail(MADICP_ERR_CAPACITY, "the buffers hold fewer rows than qualify (*out_n)");
+    } else if (rows > 0) {
+      e = hipMemcpyAsync(out_xyz, d_xyz, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+      if (e == hipSuccess && out_keys) e = hipMemcpyAsync(out_keys, d_keys, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+      if (e == hipSuccess && out_attr) e = hipMemcpyAsync(out_attr, d_attr, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+      if (e == hipSuccess && out_ev) e = hipMemcpyAsync(out_ev, d_ev, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
+      w = hipStreamSynchronize(ctx->copy);  // the rows
+      if (e == hipSuccess) e = w;
+    }
+  }
+  hipFree(block);
+  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map evidence download: ") + hipGetErrorString(e));
+  return rc;
 }
 
 int madicp_map_track_removed(madicp_ctx* ctx, int map_id, int on) {
@@ -1446,7 +1585,7 @@ int madicp_map_clear(madicp_ctx* ctx, int map_id) {
   DevMap* m = find_map(ctx, map_id);
   if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
   HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMemsetAsync(m->block, 0xff, 24 * (size_t)m->cap, ctx->copy));
+  HIP_TRY(map_table_wipe(ctx, m));
   m->rows = 0;
   m->log_n = 0;  // (the log's memory is kept)
   return MADICP_OK;

@@ -237,12 +237,18 @@ void Pipeline::dropMap() {
   map_log_full_ = false;
 }
 
-void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute) {
+void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, const uint32_t* evidence) {
   if (!std::isfinite(voxel_size) || voxel_size < 0.0)
     throw std::invalid_argument("Pipeline::setMapAccumulation: voxel_size must be finite and >= 0 (0 = off)");
   if (voxel_size > 0.0 && (max_points < 1 || max_points > static_cast<size_t>(kMapMaxRows)))
     throw std::invalid_argument("Pipeline::setMapAccumulation: max_points must be 1 .. 2^30");
-  if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_ && with_attribute == map_with_attr_)))
+  if (voxel_size > 0.0 && evidence)
+    if (const char* why = map_evidence_refusal(evidence[0], evidence[1], evidence[2]))
+      throw std::invalid_argument(std::string("Pipeline::setMapAccumulation: ") + why);
+  const bool with_ev = voxel_size > 0.0 && evidence;
+  const bool same_ev = with_ev == map_with_ev_ && (!with_ev || std::equal(evidence, evidence + 3, map_ev_));
+  if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_ &&
+                                                        with_attribute == map_with_attr_ && same_ev)))
     return;
   dropMap();
   const bool was_on = map_voxel_ > 0.0;
@@ -251,6 +257,8 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
   map_max_points_ = max_points;
   map_with_attr_ = voxel_size > 0.0 && with_attribute;
   map_attr_type_ = kAttrNone;
+  map_with_ev_ = with_ev;
+  if (with_ev) std::copy(evidence, evidence + 3, map_ev_);
   if (voxel_size > 0.0) {
     if (!was_on) dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
   } else {
@@ -278,7 +286,10 @@ void Pipeline::foldFrame() {
       madicp_ctx* ctx = fresh ? Device::ctx() : Device::current(map_generation_);
       if (!ctx) throw std::logic_error("Pipeline: the device context the map lived in is gone");
       if (fresh) {
-        if (map_with_attr_)
+        if (map_with_ev_)
+          check(madicp_map_create_ev(ctx, map_voxel_, first_rows, max_rows, map_with_attr_ ? 1 : 0, map_ev_[0], map_ev_[1], map_ev_[2], &map_id_),
+                "madicp_map_create_ev");
+        else if (map_with_attr_)
           check(madicp_map_create_attr(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create_attr");
         else
           check(madicp_map_create(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create");
@@ -317,7 +328,7 @@ void Pipeline::foldFrame() {
       }
     } else {
       if (fresh) {
-        map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_);
+        map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_, map_with_ev_, map_ev_[0], map_ev_[1], map_ev_[2]);
         map_host_->track_removed(map_track_removed_);
       }
       ContainerType down;  // (a resident scan into a host map: the front-end was switched — its column crosses with it)
@@ -617,6 +628,54 @@ size_t Pipeline::mapAttribute(uint32_t* out, size_t capacity, size_t first_row) 
     check(madicp_map_download_attr(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
           "madicp_map_download_attr");
   }
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::mapEvidence(uint32_t* out, size_t capacity, size_t first_row) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapEvidence: setMapAccumulation(voxel_size > 0) first");
+  if (!map_with_ev_) throw std::logic_error("Pipeline::mapEvidence: the map was made without evidence (setMapAccumulation's evidence)");
+  if (!out) throw std::invalid_argument("Pipeline::mapEvidence: null buffer");
+  const size_t size = mapSize();
+  if (first_row > size) throw std::invalid_argument("Pipeline::mapEvidence: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (capacity < size - first_row)
+    throw std::invalid_argument("Pipeline::mapEvidence: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
+                                std::to_string(size - first_row));
+  if (size == first_row) return 0;
+  int64_t rows = 0;
+  if (map_host_) {
+    if (map_host_->download_evidence(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
+      throw std::runtime_error("Pipeline::mapEvidence: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapEvidence: the device context the map lived in is gone");
+    check(madicp_map_download_evidence(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
+          "madicp_map_download_evidence");
+  }
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::mapConfirmed(uint32_t min_evidence, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, size_t capacity) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapConfirmed: setMapAccumulation(voxel_size > 0) first");
+  if (!map_with_ev_) throw std::logic_error("Pipeline::mapConfirmed: the map was made without evidence (setMapAccumulation's evidence)");
+  if (out_attr && !map_with_attr_)
+    throw std::logic_error("Pipeline::mapConfirmed: the map was made without the attribute (setMapAccumulation's with_attribute)");
+  if (!out_xyz) throw std::invalid_argument("Pipeline::mapConfirmed: null buffer");
+  int64_t rows = 0;
+  int rc = MADICP_OK;
+  if (map_host_) {
+    rc = map_host_->download_min_evidence(min_evidence, out_xyz, out_keys, out_attr, out_ev, static_cast<int64_t>(capacity), &rows);
+    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline::mapConfirmed: the host voxel map refused its arguments");
+  } else if (map_id_ >= 0) {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapConfirmed: the device context the map lived in is gone");
+    rc = madicp_map_download_min_evidence(ctx, map_id_, min_evidence, out_xyz, out_keys, out_attr, out_ev, static_cast<int64_t>(capacity), &rows);
+    if (rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_download_min_evidence");
+  }
+  if (rc == MADICP_ERR_CAPACITY)
+    throw std::invalid_argument("Pipeline::mapConfirmed: the buffers hold " + std::to_string(capacity) + " rows, " + std::to_string(rows) +
+                                " qualify");
   return static_cast<size_t>(rows);
 }
 

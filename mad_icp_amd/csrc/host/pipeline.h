@@ -165,8 +165,21 @@ class Pipeline {
   // with_attribute: the map is made with the attribute column (madicp_map_create_attr / VoxelMap's) — a row keeps its owning
   // point's word; frames that arrive without an attribute (compute, computeRecords ...) contribute the word 0.  mapAttribute
   // runs beside mapCloud: the words of rows [first_row, mapSize()), the same refusals; std::logic_error without the column.
+  // evidence: null — the default: nothing changes, not a launch, not an allocation, the same pose and map bits — or {hit, miss,
+  // cap}: the map is made with the EVIDENCE column (madicp_map_create_ev / VoxelMap's; include/madicp_hip.h has the rule): every
+  // fold reinforces the voxels it hits, once per fold, up to cap; a clearing (setMapClearing, mapClearRays) takes miss from the
+  // voxels it sees through, and a row leaves only when its evidence is used up.  The frame order stays fold, clearing, range
+  // prune: a fold's own hits are occupied in its clearing, so one scan never both reinforces and weakens a voxel.  Another
+  // triple starts a new, empty map; std::invalid_argument for hit < 1, miss < 1, cap < hit, cap > 2^31 - 1.
+  // mapEvidence: the words of rows [first_row, mapSize()), mapCloud's refusals; mapConfirmed: the rows with word >= min_evidence
+  // in row order — xyz, and keys / attr / ev where not null — compacted where the map lives (madicp_map_download_min_evidence),
+  // returns their number (at most mapSize(): a buffer that holds that many always suffices); std::invalid_argument for a null xyz
+  // or a capacity below that number (nothing written).  Both: std::logic_error while accumulation is off or without the column.
   void setMapAccumulation(double voxel_size, bool keyframes_only = false, size_t max_points = kMapMaxPointsDefault,
-                          bool with_attribute = false);
+                          bool with_attribute = false, const uint32_t* evidence = nullptr);
+  bool mapWithEvidence() const { return map_voxel_ > 0.0 && map_with_ev_; }
+  size_t mapEvidence(uint32_t* out, size_t capacity, size_t first_row = 0);
+  size_t mapConfirmed(uint32_t min_evidence, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, size_t capacity);
   bool mapWithAttribute() const { return map_voxel_ > 0.0 && map_with_attr_; }
   int mapAttributeType() const { return map_attr_type_; }  // the field type of the last attribute frame folded (kAttrNone: none yet)
   size_t mapAttribute(uint32_t* out, size_t capacity, size_t first_row = 0);
@@ -398,7 +411,8 @@ class Pipeline {
   // map accumulation (setMapAccumulation): the map lives where the first folded cloud did — a device map of the context generation
   // that issued its id, or the host twin; a cloud from the other side (the front-end was switched) crosses over for its fold
   double map_voxel_ = 0.0;
-  bool map_keyframes_only_ = false, map_overflowed_ = false, map_with_attr_ = false;
+  bool map_keyframes_only_ = false, map_overflowed_ = false, map_with_attr_ = false, map_with_ev_ = false;
+  uint32_t map_ev_[3] = {1, 1, 1};  // hit, miss, cap (setMapAccumulation's evidence)
   int map_attr_type_ = 0;
   size_t map_max_points_ = kMapMaxPointsDefault;
   int map_id_ = -1;

@@ -32,6 +32,28 @@ int madicp_host_map_create_attr(double voxel, int64_t initial_rows, int64_t max_
   return MADICP_OK;
 }
 
+int madicp_host_map_create_ev(double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, uint32_t hit, uint32_t miss, uint32_t cap,
+                              madicp_host_map** out_map) {
+  if (!out_map || madicp_host::map_create_refusal(voxel, initial_rows, max_rows) || madicp_host::map_evidence_refusal(hit, miss, cap))
+    return MADICP_ERR_INVALID;
+  madicp_host_map* m =
+      new (std::nothrow) madicp_host_map{madicp_host::VoxelMap(voxel, initial_rows, max_rows, with_attr != 0, true, hit, miss, cap)};
+  if (!m) return MADICP_ERR_CAPACITY;
+  *out_map = m;
+  return MADICP_OK;
+}
+
+int madicp_host_map_download_evidence(const madicp_host_map* map, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_evidence(first_row, out_ev, capacity_rows, out_n);
+}
+
+int madicp_host_map_download_min_evidence(const madicp_host_map* map, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
+                                          uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_min_evidence(min_e, out_xyz, out_keys, out_attr, out_ev, capacity_rows, out_n);
+}
+
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
                            int64_t* out_rows) {
   if (!map) return MADICP_ERR_INVALID;

@@ -8,6 +8,9 @@
 // floating-point contraction.
 // A map made `with_attr` holds one more column: the 32-bit attribute word of every row — its OWNING point's, 0 where the folded
 // cloud carries none (madicp_map_create_attr).
+// A map made `with_ev` holds the evidence column (export_point.h has the rule: map_evidence_hit / map_evidence_miss): a fold
+// reinforces the rows it hits, once per fold, a clearing weakens the rows it sees through, and a row leaves only when its evidence
+// is used up (madicp_map_create_ev).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -23,14 +26,17 @@ constexpr int kMapOk = 0, kMapInvalid = -1, kMapCapacity = -4;  // MADICP_OK, MA
 
 class VoxelMap {
  public:
-  VoxelMap(double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr = false)
-      : voxel_(voxel), max_rows_(max_rows), with_attr_(with_attr) {
+  VoxelMap(double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr = false, bool with_ev = false, uint32_t hit = 1,
+           uint32_t miss = 1, uint32_t cap = 1)
+      : voxel_(voxel), max_rows_(max_rows), with_attr_(with_attr), with_ev_(with_ev), hit_(hit), miss_(miss), cap_(cap) {
     const size_t first = static_cast<size_t>(std::min(initial_rows, max_rows));
     rows_.reserve(3 * first);
     keys_.reserve(first);
     row_keys_.reserve(first);
     if (with_attr_) attr_.reserve(first);
+    if (with_ev_) ev_.reserve(first);
   }
+  bool with_ev() const { return with_ev_; }
   double voxel() const { return voxel_; }
   bool with_attr() const { return with_attr_; }
   int64_t size() const { return static_cast<int64_t>(rows_.size() / 3); }
@@ -42,15 +48,24 @@ class VoxelMap {
     if (export_refusal(R, t, voxel_)) return kMapInvalid;
     if (size() + n > max_rows_) return kMapCapacity;  // (conservative: decided before a point is looked at, as on the device)
     const int64_t before = size();
+    std::unordered_set<uint64_t> met;  // evidence maps: the candidate keys that met a row (this fold's own rows among them)
     for (int64_t i = 0; i < n; ++i) {
       double q[3];
       export_position(xyz + 3 * i, R, t, q);
       const uint64_t key = export_key(q, voxel_);
-      if (key == kExportNoKey || !keys_.insert(key).second) continue;
+      if (key == kExportNoKey) continue;
+      if (!keys_.insert(key).second) {
+        if (with_ev_) met.insert(key);
+        continue;
+      }
       for (int k = 0; k < 3; ++k) rows_.push_back(export_value(q[k]));
       row_keys_.push_back(key);
       if (with_attr_) attr_.push_back(attr ? attr[i] : 0u);
+      if (with_ev_) ev_.push_back(hit_);
     }
+    if (with_ev_ && !met.empty())  // the rows that were there before the fold: once per fold
+      for (int64_t j = 0; j < before; ++j)
+        if (met.count(row_keys_[j])) ev_[j] = map_evidence_hit(ev_[j], hit_, cap_);
     *out_added = size() - before;
     *out_rows = size();
     return kMapOk;
@@ -94,6 +109,38 @@ class VoxelMap {
     std::memcpy(out_xyz, rows_.data() + 3 * first_row, sizeof(float) * 3 * static_cast<size_t>(m));
     if (out_keys) std::memcpy(out_keys, row_keys_.data() + first_row, sizeof(uint64_t) * static_cast<size_t>(m));
     if (out_attr) std::memcpy(out_attr, attr_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
+    return kMapOk;
+  }
+
+  // include/madicp_host.h: madicp_host_map_download_evidence — the evidence words of rows [first_row, size()); invalid on a map
+  // without the column
+  int download_evidence(int64_t first_row, uint32_t* out, int64_t capacity_rows, int64_t* out_n) const {
+    if (!with_ev_ || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
+    const int64_t m = size() - first_row;
+    *out_n = m;
+    if (capacity_rows < m) return kMapCapacity;
+    if (m > 0) std::memcpy(out, ev_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
+    return kMapOk;
+  }
+  // include/madicp_host.h: madicp_host_map_download_min_evidence — the rows whose word is >= min_e, in row order, with the columns
+  // asked for; a short buffer is not written
+  int download_min_evidence(uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, int64_t capacity_rows,
+                            int64_t* out_n) const {
+    if (!with_ev_ || !out_xyz || !out_n || (out_attr && !with_attr_)) return kMapInvalid;
+    const int64_t m = size();
+    int64_t d = 0;
+    for (int64_t j = 0; j < m; ++j) d += ev_[j] >= min_e ? 1 : 0;
+    *out_n = d;
+    if (capacity_rows < d) return kMapCapacity;
+    d = 0;
+    for (int64_t j = 0; j < m; ++j) {
+      if (ev_[j] < min_e) continue;
+      for (int k = 0; k < 3; ++k) out_xyz[3 * d + k] = rows_[3 * j + k];
+      if (out_keys) out_keys[d] = row_keys_[j];
+      if (out_attr) out_attr[d] = attr_[j];
+      if (out_ev) out_ev[d] = ev_[j];
+      ++d;
+    }
     return kMapOk;
   }
 
@@ -141,7 +188,7 @@ class VoxelMap {
   // include/madicp_host.h: madicp_host_map_clear_rays — the rays of a scan (export_point.h: ray_length / ray_sample_count / ray_sample)
   // from `origin` to every point of the cloud, both taken into the map frame by (R, t): the candidate keys of the samples are
   // traversed, those of the end points occupied; a row leaves iff its STORED key is traversed and not occupied.  Two sets, then
-  // prune's stable pass.
+  // prune's stable pass.  On an evidence map such a row is MISSED: it loses `miss` and leaves only when that uses its word up.
   int clearRays(const double* xyz, int64_t n, const double* R, const double* t, const double* origin, double margin, int64_t watermark,
                 int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) {
     if (!out_removed || !out_rows || !out_watermark || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
@@ -169,8 +216,12 @@ class VoxelMap {
         }
       }
     }
-    close_up([&](int64_t j) { return !traversed.count(row_keys_[j]) || occupied.count(row_keys_[j]); }, watermark, out_removed, out_rows,
-             out_watermark);
+    close_up(
+        [&](int64_t j) {
+          if (!traversed.count(row_keys_[j]) || occupied.count(row_keys_[j])) return true;
+          return with_ev_ && map_evidence_miss(&ev_[j], miss_);
+        },
+        watermark, out_removed, out_rows, out_watermark);
     return kMapOk;
   }
 
@@ -179,6 +230,7 @@ class VoxelMap {
     keys_.clear();
     row_keys_.clear();
     attr_.clear();
+    ev_.clear();
     log_keys_.clear();
     log_rows_.clear();
     log_attr_.clear();
@@ -188,7 +240,7 @@ class VoxelMap {
   // a removal on a tracking map whose log holds max_rows entries or more is refused: decided without looking at a row
   bool log_full() const { return track_ && removed_count() >= max_rows_; }
 
-  // the one way rows leave: row j stays iff kept(j); the kept rows close up in order, keys and attribute words with them, the keys
+  // the one way rows leave: row j stays iff kept(j) — asked once per row, in row order; the kept rows close up in order, keys, attribute and evidence words with them, the keys
   // of the others leave the set.  *out_watermark: the kept rows among [0, watermark).  On a tracking map the rows that leave from
   // below the watermark go to the removal log, in row order.
   template <class Kept>
@@ -210,6 +262,7 @@ class VoxelMap {
         for (int k = 0; k < 3; ++k) rows_[3 * d + k] = rows_[3 * j + k];
         row_keys_[d] = row_keys_[j];
         if (with_attr_) attr_[d] = attr_[j];
+        if (with_ev_) ev_[d] = ev_[j];
       }
       ++d;
     }
@@ -217,6 +270,7 @@ class VoxelMap {
     rows_.resize(3 * static_cast<size_t>(d));
     row_keys_.resize(static_cast<size_t>(d));
     if (with_attr_) attr_.resize(static_cast<size_t>(d));
+    if (with_ev_) ev_.resize(static_cast<size_t>(d));
     *out_removed = m - d;
     *out_rows = d;
     *out_watermark = mark;
@@ -225,8 +279,11 @@ class VoxelMap {
   double voxel_;
   int64_t max_rows_;
   bool with_attr_;
+  bool with_ev_;
+  uint32_t hit_, miss_, cap_;  // the evidence rule's parameters (export_point.h)
   std::vector<float> rows_;
   std::vector<uint32_t> attr_;
+  std::vector<uint32_t> ev_;  // evidence maps: one word per row, 1 .. cap_
   std::vector<uint64_t> row_keys_;  // the key of every row (prune erases by it: a float row cannot reproduce its key)
   std::unordered_set<uint64_t> keys_;
   bool track_ = false;  // the removal log: entries of (key, float row, word), oldest first

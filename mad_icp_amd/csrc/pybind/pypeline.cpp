@@ -104,8 +104,70 @@ PYBIND11_MODULE(pypeline, m) {
     // with_attribute: the map keeps every row's attribute too; mapCloud(first_row, with_attribute=True) returns (rows, attr), attr
     // viewed as the dtype of the last attribute frame folded (uint32 words before there is one; frames without an attribute
     // contribute zeros).
-    .def("setMapAccumulation", &Pipeline::setMapAccumulation, py::arg("voxel_size"), py::arg("keyframes_only") = false,
-         py::arg("max_points") = Pipeline::kMapMaxPointsDefault, py::arg("with_attribute") = false)
+    // evidence=(hit, miss, cap): the map keeps a hit/miss count per voxel (include/madicp_hip.h has the rule) — folds reinforce,
+    // clearings weaken, a row leaves only when its evidence is used up; None (the default) changes nothing.  mapEvidence(first_row=0)
+    // returns the words of rows [first_row, mapSize()) as (M,) uint32; mapConfirmed(min_evidence, with_keys=False,
+    // with_attribute=False) the rows with evidence >= min_evidence, in row order, compacted where the map lives: (n, 3) float32, or
+    // a tuple (rows[, keys][, attr]).  ValueError for hit < 1, miss < 1, cap < hit, cap > 2^31 - 1; RuntimeError (std::logic_error)
+    // from both without the column.
+    .def("setMapAccumulation",
+         [](Pipeline& self, double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, py::object evidence) {
+           if (evidence.is_none()) {
+             self.setMapAccumulation(voxel_size, keyframes_only, max_points, with_attribute);
+             return;
+           }
+           const py::sequence ev = evidence.cast<py::sequence>();
+           if (ev.size() != 3) throw py::value_error("evidence must be None or (hit, miss, cap)");
+           uint32_t e[3];
+           for (int i = 0; i < 3; ++i) {
+             const long long v = ev[i].cast<long long>();
+             if (v < 0 || v > 0xffffffffll) throw py::value_error("evidence: hit, miss and cap are 32-bit unsigned values");
+             e[i] = static_cast<uint32_t>(v);
+           }
+           self.setMapAccumulation(voxel_size, keyframes_only, max_points, with_attribute, e);
+         },
+         py::arg("voxel_size"), py::arg("keyframes_only") = false, py::arg("max_points") = Pipeline::kMapMaxPointsDefault,
+         py::arg("with_attribute") = false, py::arg("evidence") = py::none())
+    .def("mapWithEvidence", &Pipeline::mapWithEvidence)
+    .def("mapEvidence",
+         [](Pipeline& self, size_t first_row) {
+           const size_t size = self.mapSize();
+           if (first_row > size) throw py::value_error("first_row is beyond the map's rows");
+           const size_t m = size - first_row;
+           py::array_t<uint32_t> w(static_cast<py::ssize_t>(m));
+           uint32_t no_word[1];
+           if (self.mapEvidence(m ? w.mutable_data() : no_word, m, first_row) != m)
+             throw std::runtime_error("Pipeline::mapEvidence: the map changed during the call");
+           return w;
+         },
+         py::arg("first_row") = 0)
+    .def("mapConfirmed",
+         [](Pipeline& self, uint32_t min_evidence, bool with_keys, bool with_attribute) -> py::object {
+           if (with_attribute && !self.mapWithAttribute())
+             throw std::logic_error("Pipeline::mapConfirmed: the map was made without the attribute (setMapAccumulation's with_attribute)");
+           const size_t cap = std::max<size_t>(self.mapSize(), 1);  // (no more rows can qualify than the map holds)
+           std::vector<float> xyz(3 * cap);
+           std::vector<uint64_t> keys(with_keys ? cap : 0);
+           std::vector<uint32_t> words(with_attribute ? cap : 0);
+           const size_t n = self.mapConfirmed(min_evidence, xyz.data(), with_keys ? keys.data() : nullptr,
+                                              with_attribute ? words.data() : nullptr, nullptr, cap);
+           py::array_t<float> out({static_cast<py::ssize_t>(n), static_cast<py::ssize_t>(3)});
+           std::copy(xyz.begin(), xyz.begin() + 3 * n, out.mutable_data());
+           if (!with_keys && !with_attribute) return std::move(out);
+           py::array_t<uint64_t> k(static_cast<py::ssize_t>(with_keys ? n : 0));
+           if (with_keys) std::copy(keys.begin(), keys.begin() + n, k.mutable_data());
+           py::array_t<uint32_t> w(static_cast<py::ssize_t>(with_attribute ? n : 0));
+           if (with_attribute) std::copy(words.begin(), words.begin() + n, w.mutable_data());
+           py::object wv = w;
+           if (const int type = self.mapAttributeType(); with_attribute && type != madicp_host::kAttrNone) {
+             const py::module_ rec = py::module_::import("mad_icp_amd.records");
+             wv = rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]);
+           }
+           if (!with_attribute) return py::make_tuple(out, k);
+           if (!with_keys) return py::make_tuple(out, wv);
+           return py::make_tuple(out, k, wv);
+         },
+         py::arg("min_evidence"), py::arg("with_keys") = false, py::arg("with_attribute") = false)
     .def("mapWithAttribute", &Pipeline::mapWithAttribute)
     .def("mapVoxelSize", &Pipeline::mapVoxelSize)
     .def("mapOverflowed", &Pipeline::mapOverflowed)
