@@ -552,6 +552,33 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                                   MADICP_ERR_INVALID on a map without the column or for an out_attr on a map without that
  *                                   one.  TWO host synchronisations: the count, then the rows (none on an empty map, one where
  *                                   no row qualifies or the buffer is short).
+ * MOMENTS.  A map of madicp_map_create_mom keeps, per row, the count, the sums and the sums of products of every point that fell into
+ * its voxel — ten unsigned 64-bit words n | S1[3] | S2[6] (xx, xy, xz, yy, yz, zz) over 16-bit offsets inside the voxel — and serves
+ * a centroid and a PCA normal per row from them (the rule, the offsets, the surfel formula and why nothing can wrap:
+ * csrc/common/voxel_moments.h, shared with the host twin).  One more creation parameter, max_count, 1 .. 2^31: a row takes ALL
+ * candidate points of a fold that fall into its voxel iff its n before that fold is < max_count, the creating point included, else
+ * none — it freezes at the end of the fold that brings it to or past max_count, whatever the order of arrival within the fold.
+ *   fold      one more kernel behind the rows' scatter and in front of the fold's one wait (fe::map_moments: one lane per point; the
+ *             lanes of a wavefront that fall into one voxel side by side add up in registers and issue ten 64-bit integer atomics
+ *             together; the add on n returns, and the one that reaches max_count stamps the row's freeze word with the fold's
+ *             ordinal): no host synchronisation is added, no float atomic is used, and the words are a function of the sequence
+ *             of (cloud, pose) alone.  Moments never decide which rows exist: rows, keys, attribute, evidence and log
+ *             are those of the same map without them.  The ordinal is a 32-bit count of the map's folds since creation or
+ *             madicp_map_clear; the fold that would need ordinal 2^32 - 1 is refused with MADICP_ERR_CAPACITY
+ *   prune, clearing, growth: the ten words and the freeze word travel with their row; madicp_map_clear forgets them with the rows.
+ *             The removal log's entries carry NO moments: a consumer that wants a removed row's statistics reads them before.
+ *   madicp_map_create_mom         madicp_map_create's arguments, with_attr != 0 for the attribute column, evidence = {hit, miss, cap}
+ *                                 or null, and max_count; MADICP_ERR_INVALID for what map_evidence_refusal or map_moments_refusal
+ *                                 refuse.  The block gains mom (cap x 80) and the freeze words (cap x 4), and the slot_row words of an
+ *                                 evidence map where it has none: 84 more bytes per row of capacity, 92 on a map without evidence.
+ *   madicp_map_download_moments   the ten words of rows [first_row, rows) as (rows, 10) uint64: madicp_map_download_f32's refusals,
+ *                                 MADICP_ERR_INVALID on a map without moments.  One host synchronisation.
+ *   madicp_map_download_surfels   per row of [first_row, rows): centroid (3 floats), and where not null the normal (3 floats, zero for
+ *                                 n < 3, sign not part of the contract), the eigenvalues of the covariance in m^2, ascending
+ *                                 (3 floats), and n as uint32 — computed on the device (fe::map_surfels, one lane per
+ *                                 row, fp64) into a transient block: one kernel, one copy chain, ONE host synchronisation.  The same
+ *                                 refusals.  Centroid and count are bit-equal to the host twin's; eigenvalues and normals go
+ *                                 through atan2 / cos / sin and agree to the last bits only.
  * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes,
  * clearings and takes. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
@@ -577,6 +604,11 @@ int madicp_map_create_ev(madicp_ctx* ctx, double voxel, int64_t initial_rows, in
 int madicp_map_download_evidence(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_download_min_evidence(madicp_ctx* ctx, int map_id, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
                                      uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_create_mom(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, const uint32_t evidence[3],
+                          uint32_t max_count, int* out_map_id);
+int madicp_map_download_moments(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_download_surfels(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
+                                uint32_t* out_count, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

@@ -152,7 +152,11 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  well.  MADICP_ERR_INVALID for hit < 1, miss < 1, cap < hit, cap > 2^31 - 1, and for both downloads on a map
  *                  made without the column.  _download_min_evidence: the rows with word >= min_e in row order, out_keys /
  *                  out_attr / out_ev null where not wanted; *out_n is always their number, MADICP_ERR_CAPACITY, nothing
- *                  written, when capacity_rows is smaller. */
+ *                  written, when capacity_rows is smaller.
+ *   _create_mom / _download_moments / _download_surfels
+ *                  the twins of madicp_map_create_mom and its neighbours (madicp_hip.h and csrc/common/voxel_moments.h have the
+ *                  rule): ten 64-bit moment words per row, max_count, the same refusals and codes.  Words, centroid and count are
+ *                  bit-equal to the device's; eigenvalues and normals agree to the last bits (libm against the device library). */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -180,6 +184,11 @@ int madicp_host_map_create_ev(double voxel, int64_t initial_rows, int64_t max_ro
 int madicp_host_map_download_evidence(const madicp_host_map* map, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_download_min_evidence(const madicp_host_map* map, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
                                           uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_create_mom(double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, const uint32_t evidence[3],
+                               uint32_t max_count, madicp_host_map** out_map);
+int madicp_host_map_download_moments(const madicp_host_map* map, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_download_surfels(const madicp_host_map* map, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
+                                     uint32_t* out_count, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

@@ -187,6 +187,10 @@ def hip_lib():
         L.madicp_map_download_evidence.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u32p, C.c_int64, _i64p]
         L.madicp_map_download_min_evidence.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_float), _u64p, _u32p, _u32p, C.c_int64,
                                                        _i64p]
+        L.madicp_map_create_mom.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, _u32p, C.c_uint32, _ip]
+        L.madicp_map_download_moments.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u64p, C.c_int64, _i64p]
+        L.madicp_map_download_surfels.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                  C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
@@ -261,6 +265,10 @@ def host_lib():
                                                 C.POINTER(C.c_void_p)]
         L.madicp_host_map_download_evidence.argtypes = [C.c_void_p, C.c_int64, _u32p, C.c_int64, _i64p]
         L.madicp_host_map_download_min_evidence.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), _u64p, _u32p, _u32p, C.c_int64, _i64p]
+        L.madicp_host_map_create_mom.argtypes = [C.c_double, C.c_int64, C.c_int64, C.c_int, _u32p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.madicp_host_map_download_moments.argtypes = [C.c_void_p, C.c_int64, _u64p, C.c_int64, _i64p]
+        L.madicp_host_map_download_surfels.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                       _u32p, C.c_int64, _i64p]
         L.madicp_host_map_destroy.restype = None
         L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
@@ -771,6 +779,49 @@ def host_map_download_min_evidence(h, min_e, with_keys=False, with_attr=False, w
             ((e[:g].copy(),) if with_ev else ()))
 
 
+def _evidence_arg(evidence):
+    """(hit, miss, cap) or None as the const uint32_t[3] argument of the _create_mom entry points."""
+    if evidence is None:
+        return None
+    hit, miss, cap = evidence
+    return (C.c_uint32 * 3)(int(hit), int(miss), int(cap))
+
+
+def _surfel_buffers(m):
+    f = lambda: np.empty((max(m, 1), 3), np.float32)
+    return f(), f(), f(), np.empty(max(m, 1), np.uint32)
+
+
+def host_map_create_mom(voxel, initial_rows, max_rows, max_count, with_attr=False, evidence=None):
+    """madicp_host_map_create_mom: a host map with per-voxel moments (the twin of Context.map_create_mom)."""
+    h = C.c_void_p()
+    _host_map_check(host_lib().madicp_host_map_create_mom(float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0,
+                                                          _evidence_arg(evidence), int(max_count), C.byref(h)), "madicp_host_map_create_mom")
+    return h
+
+
+def host_map_download_moments(h, first_row=0):
+    """The moment words of rows [first_row, size) as (M - first_row, 10) uint64: n, S1[3], S2[6]; MadIcpError without moments."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    out, got = np.empty((max(m, 1), 10), np.uint64), C.c_int64(0)
+    _host_map_check(host_lib().madicp_host_map_download_moments(h, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)),
+                    "madicp_host_map_download_moments")
+    return out[:got.value].copy()
+
+
+def host_map_download_surfels(h, first_row=0):
+    """madicp_host_map_download_surfels: (centroid (M, 3) f32, normal (M, 3) f32, eigenvalues (M, 3) f32, count (M,) u32)."""
+    m = max(host_map_size(h) - int(first_row), 0)
+    c, nrm, eig, cnt = _surfel_buffers(m)
+    got = C.c_int64(0)
+    fp = C.POINTER(C.c_float)
+    _host_map_check(host_lib().madicp_host_map_download_surfels(h, int(first_row), c.ctypes.data_as(fp), nrm.ctypes.data_as(fp),
+                                                                eig.ctypes.data_as(fp), cnt.ctypes.data_as(_u32p), m, C.byref(got)),
+                    "madicp_host_map_download_surfels")
+    g = got.value
+    return c[:g].copy(), nrm[:g].copy(), eig[:g].copy(), cnt[:g].copy()
+
+
 def host_map_clear(h):
     _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
 
@@ -1109,6 +1160,34 @@ class Context:
         g = got.value
         return ((xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ()) +
                 ((e[:g].copy(),) if with_ev else ()))
+
+    def map_create_mom(self, voxel, initial_rows, max_rows, max_count, with_attr=False, evidence=None):
+        """madicp_map_create_mom: a map with per-voxel moments — ten 64-bit words per row (n, S1[3], S2[6]) over 16-bit offsets of
+        the points that fell into the voxel; a row takes whole folds while its n is below `max_count`.  with_attr / evidence=(hit,
+        miss, cap): those columns as well.  Returns the map id."""
+        mid = C.c_int(0)
+        _check(hip_lib().madicp_map_create_mom(self._h, float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0,
+                                               _evidence_arg(evidence), int(max_count), C.byref(mid)))
+        return mid.value
+
+    def map_download_moments(self, mid, first_row=0):
+        """The moment words of rows [first_row, size) as (M - first_row, 10) uint64; MadIcpError on a map made without them."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        out, got = np.empty((max(m, 1), 10), np.uint64), C.c_int64(0)
+        _check(hip_lib().madicp_map_download_moments(self._h, mid, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)))
+        return out[:got.value].copy()
+
+    def map_download_surfels(self, mid, first_row=0):
+        """madicp_map_download_surfels: (centroid (M, 3) f32, normal (M, 3) f32, eigenvalues (M, 3) f32, count (M,) u32), computed
+        on the device from the moments and the stored keys."""
+        m = max(self.map_size(mid) - int(first_row), 0)
+        c, nrm, eig, cnt = _surfel_buffers(m)
+        got = C.c_int64(0)
+        fp = C.POINTER(C.c_float)
+        _check(hip_lib().madicp_map_download_surfels(self._h, mid, int(first_row), c.ctypes.data_as(fp), nrm.ctypes.data_as(fp),
+                                                     eig.ctypes.data_as(fp), cnt.ctypes.data_as(_u32p), m, C.byref(got)))
+        g = got.value
+        return c[:g].copy(), nrm[:g].copy(), eig[:g].copy(), cnt[:g].copy()
 
     def map_clear(self, mid):
         _check(hip_lib().madicp_map_clear(self._h, mid))

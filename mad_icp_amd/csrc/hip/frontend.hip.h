@@ -21,6 +21,7 @@
 #include "tree_build.hip.h"
 #include "../common/ingest_point.h"
 #include "../common/export_point.h"
+#include "../common/voxel_moments.h"
 
 #pragma clang fp contract(off)
 
@@ -517,13 +518,16 @@ __global__ __launch_bounds__(256) void voxel_mark(const uint32_t* __restrict__ s
 // Null arguments (kernel arguments: the branches are wave-uniform) switch parts off.  mark / pos: every point, at row first_row + i.
 // row_keys: no key is stored, and none is recomputed (three fp64 divisions per row).  owner / slot_of: nothing settles.
 // row_attr: no attribute column beside the rows; else every row written gets its owning point's word, or 0 where the cloud carries
-// none (attr == nullptr).  row_ev: no evidence column; else every row written gets `hit` and slot_row learns the row of its slot.
+// none (attr == nullptr).  row_ev: no evidence column; else every row written gets `hit`.  slot_row (evidence and moments maps):
+// learns the row of every slot that settles.  row_mom / row_closed (moments maps): every row written starts from ten zero words
+// and "never closed" — fe::map_moments, behind this kernel, counts its points, the creating one included.
 __global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
                                                   const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
                                                   const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner, long first_row,
                                                   float* __restrict__ rows, unsigned long long* __restrict__ row_keys,
                                                   const uint32_t* __restrict__ attr, uint32_t* __restrict__ row_attr,
-                                                  uint32_t* __restrict__ row_ev, uint32_t hit, uint32_t* __restrict__ slot_row) {
+                                                  uint32_t* __restrict__ row_ev, uint32_t hit, uint32_t* __restrict__ slot_row,
+                                                  unsigned long long* __restrict__ row_mom, uint32_t* __restrict__ row_closed) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     if (mark && !mark[i]) continue;
     const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
@@ -535,16 +539,18 @@ __global__ __launch_bounds__(256) void voxel_rows(const double* __restrict__ xyz
     rows[3 * d + 2] = madicp_host::export_value(q[2]);
     if (row_keys) row_keys[d] = madicp_host::export_key(q, voxel);
     if (row_attr) row_attr[d] = attr ? attr[i] : 0u;
-    if (row_ev) {  // (an evidence map: the new row's word, and where its slot's row is — what map_hit reads in later folds)
-      row_ev[d] = hit;
-      slot_row[slot_of[i]] = (uint32_t)d;
+    if (row_ev) row_ev[d] = hit;                      // (an evidence map: the new row's word)
+    if (slot_row) slot_row[slot_of[i]] = (uint32_t)d;  // (where its slot's row is — what map_hit and map_moments read)
+    if (row_mom) {
+      for (int k = 0; k < madicp_host::kMomentWords; ++k) row_mom[madicp_host::kMomentWords * d + k] = 0ull;
+      row_closed[d] = madicp_host::kMomentsNeverClosed;
     }
     if (owner) owner[slot_of[i]] = kMapSettled;  // (one marked point per slot: nobody else writes it in this kernel)
   }
 }
 __global__ __launch_bounds__(256) void map_rehash(const unsigned long long* __restrict__ row_keys, long n_rows,
                                                   unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
-                                                  uint32_t* __restrict__ slot_row /* evidence maps, else null */) {
+                                                  uint32_t* __restrict__ slot_row /* evidence and moments maps, else null */) {
   for (long r = blockIdx.x * (long)blockDim.x + threadIdx.x; r < n_rows; r += (long)gridDim.x * blockDim.x) {
     const uint32_t s = map_find_or_claim(keys, slots, row_keys[r]);
     owner[s] = kMapSettled;
@@ -578,6 +584,108 @@ __global__ __launch_bounds__(256) void map_hit(const uint32_t* __restrict__ slot
   }
 }
 
+// ---- moments: count, sums and sums of products of the points of every voxel (madicp_map_create_mom) ------------------------------
+// The rule is csrc/common/voxel_moments.h's, shared with the host twin: a 16-bit offset per axis inside the voxel, ten unsigned
+// 64-bit words per row (n, S1[3], S2[6]), and max_count, past which a row takes no further fold.
+//   map_moments  behind voxel_rows, one lane per point: by then every slot of the fold is settled and slot_row knows the row of every
+//                slot, this fold's new rows included (their words zeroed by voxel_rows).  A candidate lane recomputes q and w and
+//                finds r = slot_row[slot_of[i]]; a lane skips a row iff closed_at[r] holds an ordinal other than "never" and other
+//                than this fold's.  Neighbouring returns share voxels, so the lanes of a wavefront that hold a RUN of equal rows
+//                (adjacent lanes, the same r) add their ten terms up in registers first — a segmented inclusive scan over the run
+//                by shuffles, six steps — and the run's last lane issues the ten 64-bit integer atomics for all of them.  The add
+//                on n is the one that RETURNS: the single run that sees old < max_count <= old + cnt (the intervals [old, old + cnt)
+//                of a row's runs tile its count) stores the fold's ordinal into closed_at[r].
+// Determinism: within a fold closed_at[r] only goes from "never" to this fold's ordinal, and a lane proceeds on either, so what a
+// racing load returns decides nothing; a row closed by an earlier fold is skipped by every lane.  "All candidate points of the fold,
+// or none, by n before the fold" is therefore decided without a second launch; and the sums are integer sums, associative and
+// commutative — how the points are grouped into runs, which depends on the launch geometry, changes no bit: the words are a
+// function of the sequence of (cloud, pose) alone.  No float atomics.  Contention: all points in ONE voxel is one run per wavefront,
+// ten atomics per 64 points on ten words — correct, not tuned for.
+// -DMADICP_MOMENTS_PLAIN (a measurement aid, tools/map_moments_time.py --variant): the form without the scan, ten atomics per
+// point — the same bits, measured 0.044 ms slower per fold of 120 k points (profiles/map_moments_time.md).
+__device__ inline unsigned long long shfl_up_u64(unsigned long long v, int d) {
+  const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__global__ __launch_bounds__(256) void map_moments(const double* __restrict__ xyz, long n, ExportPose X, double voxel,
+                                                   const uint32_t* __restrict__ slot_of, const uint32_t* __restrict__ slot_row,
+                                                   unsigned long long* __restrict__ mom, uint32_t* __restrict__ closed_at, uint32_t ordinal,
+                                                   uint32_t max_count) {
+  constexpr uint32_t kNoRow = 0xffffffffu;  // no candidate, or a row that takes nothing in this fold (rows are < 2^30)
+  const int lane = threadIdx.x & 63;
+  // (blockDim and the stride are multiples of 64: i - lane is the wavefront's, so all its lanes leave the loop together)
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i - lane < n; i += (long)gridDim.x * blockDim.x) {
+    uint32_t r = kNoRow;
+    uint32_t a[4] = {0, 0, 0, 0};  // n, S1: at most 64 x 65535 within a wavefront
+    unsigned long long b[6] = {0, 0, 0, 0, 0, 0};
+    if (i < n) {
+      const uint32_t s = slot_of[i];
+      if (s != kExportNoSlot) {
+        const uint32_t row = slot_row[s];
+        if (madicp_host::moment_row_takes(__hip_atomic_load(&closed_at[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ordinal)) {
+          r = row;
+          const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+          double q[3];
+          madicp_host::export_position(p, X.R, X.t, q);
+          uint32_t w[3];
+          madicp_host::moment_offset(q, voxel, w);
+          uint64_t c[9];
+          madicp_host::moment_terms(w, c);
+          a[0] = 1;
+          for (int k = 0; k < 3; ++k) a[1 + k] = w[k];
+          for (int k = 0; k < 6; ++k) b[k] = c[3 + k];
+        }
+      }
+    }
+#ifndef MADICP_MOMENTS_PLAIN
+    const uint32_t left = __shfl_up(r, 1);
+    const unsigned long long heads = __ballot(lane == 0 || left != r);  // the lanes that start a run
+    const int head = 63 - __clzll(heads & ((2ull << lane) - 1ull));    // (lane 63: 2 << 63 wraps to 0, minus 1 is all ones)
+    for (int d = 1; d < 64; d <<= 1) {
+      uint32_t ua[4];
+      unsigned long long ub[6];
+      for (int k = 0; k < 4; ++k) ua[k] = __shfl_up(a[k], d);
+      for (int k = 0; k < 6; ++k) ub[k] = shfl_up_u64(b[k], d);
+      if (lane - d >= head) {
+        for (int k = 0; k < 4; ++k) a[k] += ua[k];
+        for (int k = 0; k < 6; ++k) b[k] += ub[k];
+      }
+    }
+    const bool last = lane == 63 || ((heads >> (lane + 1)) & 1ull);
+#else
+    const bool last = true;
+#endif
+    if (last && r != kNoRow) {
+      unsigned long long* M = mom + (size_t)madicp_host::kMomentWords * r;
+      const unsigned long long old = atomicAdd(&M[0], (unsigned long long)a[0]);
+      if (madicp_host::moment_closes(old, a[0], max_count))
+        __hip_atomic_store(&closed_at[r], ordinal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int k = 0; k < 3; ++k) atomicAdd(&M[1 + k], (unsigned long long)a[1 + k]);
+      for (int k = 0; k < 6; ++k) atomicAdd(&M[4 + k], b[k]);
+    }
+  }
+}
+//   map_surfels  one lane per row of the window [first_row, M): the row's ten words and stored key through madicp_host::map_surfel
+//                into a transient block of the call's own — centroid, normal, eigenvalues (three floats each) and the count
+__global__ __launch_bounds__(256) void map_surfels(const unsigned long long* __restrict__ mom, const unsigned long long* __restrict__ row_keys,
+                                                   long first_row, long n_rows, double voxel, float* __restrict__ centroid,
+                                                   float* __restrict__ normal, float* __restrict__ eig, uint32_t* __restrict__ count) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_rows - first_row; j += (long)gridDim.x * blockDim.x) {
+    const long r = first_row + j;
+    uint64_t M[madicp_host::kMomentWords];
+    for (int k = 0; k < madicp_host::kMomentWords; ++k) M[k] = mom[madicp_host::kMomentWords * r + k];
+    float c[3], nrm[3], e[3];
+    uint32_t cnt;
+    madicp_host::map_surfel(M, row_keys[r], voxel, c, nrm, e, &cnt);
+    for (int k = 0; k < 3; ++k) {
+      centroid[3 * j + k] = c[k];
+      normal[3 * j + k] = nrm[k];
+      eig[3 * j + k] = e[k];
+    }
+    count[j] = cnt;
+  }
+}
+
 // ---- pruning the map: rows beyond a radius of a centre leave, the kept ones close up in order (madicp_map_prune) -------------------
 // The rule is madicp_host::map_row_kept (csrc/common/export_point.h, shared with the host twin): fp64, from the STORED float row.
 //   map_prune_mark  one lane per row: mark[j] = the row stays; mark[M] = 0, the scan's terminator (as in voxel_mark)
@@ -585,7 +693,8 @@ __global__ __launch_bounds__(256) void map_hit(const uint32_t* __restrict__ slot
 //   map_compact     one lane per row: a kept row's stored key, three floats and, where the column exists, its word to row S[j] of the
 //                   DESTINATION block — coalesced reads, monotone writes; whether row j stays is read off the scan, S[j + 1] != S[j],
 //                   so the marks are dead by now and the lane of row 0 leaves {S[M], S[watermark]} in `res` (the caller lays it over
-//                   them): both answers of a prune in one small copy.  ev / out_ev: the evidence column, a null-able pair like attr
+//                   them): both answers of a prune in one small copy.  ev / out_ev: the evidence column, a null-able pair like attr;
+//                   mom / out_mom with closed_at / out_closed_at: the moments (ten words a row) and their freeze word, likewise
 // The table is then emptied by the one memset and refilled by map_rehash over the kept keys, which leaves every owner kMapNever or
 // kMapSettled — what the folds rely on.  Determinism: a comparison per row and an exclusive scan; nothing depends on the geometry.
 struct PruneSphere {  // by value, wave-uniform: scalar loads
@@ -605,7 +714,9 @@ __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ 
                                                    const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
                                                    const uint32_t* __restrict__ attr, unsigned long long* __restrict__ out_keys,
                                                    float* __restrict__ out_rows, uint32_t* __restrict__ out_attr, uint32_t* __restrict__ res,
-                                                   const uint32_t* __restrict__ ev, uint32_t* __restrict__ out_ev) {
+                                                   const uint32_t* __restrict__ ev, uint32_t* __restrict__ out_ev,
+                                                   const unsigned long long* __restrict__ mom, unsigned long long* __restrict__ out_mom,
+                                                   const uint32_t* __restrict__ closed_at, uint32_t* __restrict__ out_closed_at) {
   for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_rows; j += (long)gridDim.x * blockDim.x) {
     if (j == 0) {
       res[0] = pos[n_rows];
@@ -619,6 +730,10 @@ __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ 
     out_rows[3 * d + 2] = rows[3 * j + 2];
     if (attr) out_attr[d] = attr[j];
     if (ev) out_ev[d] = ev[j];
+    if (mom) {
+      for (int k = 0; k < madicp_host::kMomentWords; ++k) out_mom[madicp_host::kMomentWords * d + k] = mom[madicp_host::kMomentWords * j + k];
+      out_closed_at[d] = closed_at[j];
+    }
   }
 }
 // The removal log of a tracking map (madicp_map_track_removed): map_compact's complement over the rows below the watermark, beside it

@@ -37,6 +37,13 @@ struct DevMap {
   uint32_t* ev = nullptr;        // (cap)
   uint32_t* slot_row = nullptr;  // (slots)
   uint32_t* stamp = nullptr;     // (slots) all ones = not hit since the wipe
+  // moments (madicp_map_create_mom; csrc/common/voxel_moments.h has the rule): ten 64-bit words per row and the row's freeze word —
+  // the ordinal of the fold that brought it to max_count, all ones while it still takes points.  slot_row exists on these maps too.
+  // ordinal counts the folds since creation or madicp_map_clear; no table wipe resets it
+  bool with_mom = false;
+  uint32_t mom_max_count = 0, ordinal = 0;
+  unsigned long long* mom = nullptr;  // (cap, 10)
+  uint32_t* closed_at = nullptr;      // (cap)
   // the removal log (madicp_map_track_removed): a block of its own — the map's is swapped by every prune and growth —
   //   keys (log_cap x 8) | xyz (log_cap x 12) | attr (log_cap x 4, attribute maps only)
   // of which the first log_n entries are live; allocated at the first removal that can log
@@ -881,6 +888,12 @@ struct FoldEvidence {
   uint32_t *ev, *slot_row, *stamp;
   uint32_t fold_no, hit, cap;
 };
+// what a fold into a moments map needs (slot_row: the same array as FoldEvidence's where the map has both)
+struct FoldMoments {
+  unsigned long long* mom;
+  uint32_t *closed_at, *slot_row;
+  uint32_t ordinal, max_count;
+};
 
 // One fold of a resident cloud (n >= 1 points) through X into table T, on the copy stream: fe::voxel_claim, fe::voxel_mark, the
 // tile scan, fe::voxel_rows — the lowest-index point of every voxel T has not settled yet, as float rows from `first_row` of `rows`
@@ -888,13 +901,15 @@ struct FoldEvidence {
 // row_attr: where the rows' attribute words go (the owning point's, 0 where the cloud carries no column), or null.
 // E: an evidence map's columns, or null — the fold's rows get `hit`, and fe::map_hit, behind the claim, reinforces the older rows
 // the cloud falls into (no launch without it).
+// Mo: a moments map's columns, or null — fe::map_moments, behind voxel_rows (every slot settled, slot_row complete, the new rows'
+// words zeroed) and in front of the one wait, adds every candidate point to its row (no launch without it).
 // The caller keeps T at most half full.  The per-fold scratch lives in idle parts of the builder's scratch, which the caller owns
 // (busy_with_lookahead, ensure_scratch for n) and which does not grow:
 //   idx[0]  slot_of[]   leaf_start  the marks   S / tile_sums  the scan   rec_res->r.kept  the scan's total
 // The rows are enqueued BEHIND the scan, before the host knows the count, and they are ready when it arrives: ONE synchronisation.
 int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::ExportPose& X, double voxel, VoxelTable T, bool settle,
                float* rows, int64_t first_row, unsigned long long* row_keys, uint32_t* row_attr, int64_t* out_added,
-               const FoldEvidence* E = nullptr) {
+               const FoldEvidence* E = nullptr, const FoldMoments* Mo = nullptr) {
   const int64_t n = c->n;
   uint32_t* slot_of = fs->idx[0];
   uint32_t* mark = fs->P.leaf_start;
@@ -909,7 +924,11 @@ int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::E
   HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
   hipLaunchKernelGGL(fe::voxel_rows, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, (const uint32_t*)mark,
                      (const uint32_t*)fs->S, (const uint32_t*)(settle ? slot_of : nullptr), settle ? T.owner : nullptr, (long)first_row,
-                     rows, row_keys, (const uint32_t*)c->attr, row_attr, E ? E->ev : nullptr, E ? E->hit : 0u, E ? E->slot_row : nullptr);
+                     rows, row_keys, (const uint32_t*)c->attr, row_attr, E ? E->ev : nullptr, E ? E->hit : 0u,
+                     E ? E->slot_row : (Mo ? Mo->slot_row : nullptr), Mo ? Mo->mom : nullptr, Mo ? Mo->closed_at : nullptr);
+  if (Mo)
+    hipLaunchKernelGGL(fe::map_moments, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel,
+                       (const uint32_t*)slot_of, (const uint32_t*)Mo->slot_row, Mo->mom, Mo->closed_at, Mo->ordinal, Mo->max_count);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->copy));  // the count
   *out_added = fs->h_rec_res->r.kept;
@@ -998,7 +1017,8 @@ int cloud_export_on(madicp_ctx* ctx, int cloud_id, const double R[9], const doub
   if (voxel == 0.0) {
     hipLaunchKernelGGL(fe::voxel_rows, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel,
                        (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0L, d_rows,
-                       (unsigned long long*)nullptr, (const uint32_t*)c->attr, d_row_attr, (uint32_t*)nullptr, 0u, (uint32_t*)nullptr);
+                       (unsigned long long*)nullptr, (const uint32_t*)c->attr, d_row_attr, (uint32_t*)nullptr, 0u, (uint32_t*)nullptr,
+                       (unsigned long long*)nullptr, (uint32_t*)nullptr);
     HIP_TRY(hipGetLastError());
   } else {
     VoxelTable T;
@@ -1042,7 +1062,10 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
 // behind these — attr (cap x 4), the rows' attribute words: 48 bytes per row of capacity — that moves with the rows.  A map of
 // madicp_map_create_ev has, behind whatever of these it holds, ev (cap x 4) | slot_row (2 cap x 4) | stamp (2 cap x 4): the rows'
 // evidence words, which move with the rows, and two more words per table slot, wiped (stamp) and refilled (slot_row) with the table
-// — 20 more bytes per row of capacity.  The host knows M exactly: every fold ends with ONE synchronisation,
+// — 20 more bytes per row of capacity.  A map of madicp_map_create_mom has slot_row as well (8 bytes per row of capacity where the
+// map has no evidence) and, behind all of these, closed_at (cap x 4) | mom (cap x 80, its start rounded up to 8 bytes): the rows'
+// freeze words and their ten 64-bit moment words — 84 more bytes per row of capacity, 92 without evidence; both move with the
+// rows.  The host knows M exactly: every fold ends with ONE synchronisation,
 // for the count (none more at a growth but the one in front of freeing the old block).  A fold uses the builder's scratch: it is
 // refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
 namespace {
@@ -1062,7 +1085,10 @@ int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
   const size_t c = (size_t)cap;
   char* block = nullptr;
   const size_t row_bytes = m->with_attr ? 48 : 44;
-  HIP_TRY(hipMalloc(&block, (row_bytes + (m->with_ev ? 20 : 0)) * c));
+  const bool with_slot_row = m->with_ev || m->with_mom;
+  const size_t closed_off = (row_bytes + (m->with_ev ? 12 : 0) + (with_slot_row ? 8 : 0)) * c;
+  const size_t mom_off = (closed_off + 4 * c + 7) & ~size_t(7);
+  HIP_TRY(hipMalloc(&block, m->with_mom ? mom_off + 80 * c : closed_off));
   m->block = block;
   m->cap = cap;
   m->slots = static_cast<uint32_t>(2 * c);
@@ -1072,8 +1098,10 @@ int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
   m->xyz = reinterpret_cast<float*>(block + 32 * c);
   m->attr = m->with_attr ? reinterpret_cast<uint32_t*>(block + 44 * c) : nullptr;
   m->ev = m->with_ev ? reinterpret_cast<uint32_t*>(block + row_bytes * c) : nullptr;
-  m->slot_row = m->with_ev ? reinterpret_cast<uint32_t*>(block + (row_bytes + 4) * c) : nullptr;
+  m->slot_row = with_slot_row ? reinterpret_cast<uint32_t*>(block + (row_bytes + (m->with_ev ? 4 : 0)) * c) : nullptr;
   m->stamp = m->with_ev ? reinterpret_cast<uint32_t*>(block + (row_bytes + 12) * c) : nullptr;
+  m->closed_at = m->with_mom ? reinterpret_cast<uint32_t*>(block + closed_off) : nullptr;
+  m->mom = m->with_mom ? reinterpret_cast<unsigned long long*>(block + mom_off) : nullptr;
   hipError_t e = wipe ? map_table_wipe(ctx, m) : hipSuccess;  // (a prune wipes the table itself, later)
   if (e != hipSuccess) {
     hipFree(block);
@@ -1094,6 +1122,8 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
     if (e == hipSuccess) e = hipMemcpyAsync(g.xyz, m->xyz, sizeof(float) * 3 * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess && m->with_attr) e = hipMemcpyAsync(g.attr, m->attr, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess && m->with_ev) e = hipMemcpyAsync(g.ev, m->ev, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess && m->with_mom) e = hipMemcpyAsync(g.mom, m->mom, 80 * M, hipMemcpyDeviceToDevice, ctx->copy);
+    if (e == hipSuccess && m->with_mom) e = hipMemcpyAsync(g.closed_at, m->closed_at, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
     if (e == hipSuccess) {
       const int blocks = grid_256(ctx, m->rows);
       hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)m->rows, g.keys,
@@ -1168,7 +1198,7 @@ int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uin
   hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
   hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
                      (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark,
-                     (const uint32_t*)m->ev, g.ev);
+                     (const uint32_t*)m->ev, g.ev, (const unsigned long long*)m->mom, g.mom, (const uint32_t*)m->closed_at, g.closed_at);
   if (const int64_t below = std::min(watermark, M); m->track && below > 0)
     hipLaunchKernelGGL(fe::map_log_removed, dim3(grid_256(ctx, below)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)below, (long)m->log_n,
                        (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, m->log_keys(), m->log_xyz(),
@@ -1242,6 +1272,7 @@ int map_clear_rays_on(madicp_ctx* ctx, DevMap* m, const DevCloud* c, const fe::R
 }
 
 constexpr const char* kMapLogFull = "the map's removal log holds max_rows entries or more (madicp_map_take_removed empties it)";
+constexpr const char* kMapNoMoments = "the map was made without the moments (madicp_map_create_mom makes one with them)";
 constexpr const char* kMapNoEvidence = "the map was made without the evidence column (madicp_map_create_ev makes one with it)";
 
 DevMap* find_map(madicp_ctx* ctx, int id) {
@@ -1251,14 +1282,20 @@ DevMap* find_map(madicp_ctx* ctx, int id) {
 }
 
 int map_create_on(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr, int* out_map_id,
-                  const uint32_t* evidence = nullptr /* {hit, miss, cap} */) {
+                  const uint32_t* evidence = nullptr /* {hit, miss, cap} */, const uint32_t* max_count = nullptr /* moments */) {
   if (!ctx || !out_map_id) return fail(MADICP_ERR_INVALID, "null argument");
   if (const char* why = madicp_host::map_create_refusal(voxel, initial_rows, max_rows)) return fail(MADICP_ERR_INVALID, why);
   if (evidence)
     if (const char* why = madicp_host::map_evidence_refusal(evidence[0], evidence[1], evidence[2])) return fail(MADICP_ERR_INVALID, why);
+  if (max_count)
+    if (const char* why = madicp_host::map_moments_refusal(*max_count)) return fail(MADICP_ERR_INVALID, why);
   HIP_TRY(hipSetDevice(ctx->device));
   DevMap m;
   m.voxel = voxel;
+  if (max_count) {
+    m.with_mom = true;
+    m.mom_max_count = *max_count;
+  }
   m.max_rows = max_rows;
   m.with_attr = with_attr;
   if (evidence) {
@@ -1286,6 +1323,10 @@ int madicp_map_create_ev(madicp_ctx* ctx, double voxel, int64_t initial_rows, in
   const uint32_t evidence[3] = {hit, miss, cap};
   return map_create_on(ctx, voxel, initial_rows, max_rows, with_attr != 0, out_map_id, evidence);
 }
+int madicp_map_create_mom(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, const uint32_t evidence[3],
+                          uint32_t max_count, int* out_map_id) {
+  return map_create_on(ctx, voxel, initial_rows, max_rows, with_attr != 0, out_map_id, evidence, &max_count);
+}
 
 int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
                             int64_t* out_rows) {
@@ -1303,18 +1344,22 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
     *out_rows = m->rows;
     return MADICP_OK;
   }
+  if (m->with_mom && m->ordinal > madicp_host::kMomentsLastOrdinal)
+    return fail(MADICP_ERR_CAPACITY, "the moments map has folded 2^32 - 1 clouds since it was made or cleared (madicp_map_clear starts again)");
   HIP_TRY(hipSetDevice(ctx->device));
   FrontScratch* fs = nullptr;
   RC_TRY(ensure_scratch(ctx, n, &fs));
   if (m->rows + n > m->cap) RC_TRY(map_grow(ctx, m, m->rows + n));
   int64_t added = 0;
+  const FoldMoments Mo{m->mom, m->closed_at, m->slot_row, m->ordinal, m->mom_max_count};
   FoldEvidence E{};
   if (m->with_ev) {
     if (m->fold_no == fe::kMapNever) HIP_TRY(map_stamp_wipe(ctx, m));  // (2^32 - 1 folds without a removal or a growth)
     E = FoldEvidence{m->ev, m->slot_row, m->stamp, m->fold_no++, m->ev_hit, m->ev_cap};
   }
   RC_TRY(voxel_fold(ctx, fs, c, export_pose(R, t), m->voxel, VoxelTable{m->keys, m->owner, m->slots}, true, m->xyz, m->rows, m->row_keys,
-                    m->attr, &added, m->with_ev ? &E : nullptr));
+                    m->attr, &added, m->with_ev ? &E : nullptr, m->with_mom ? &Mo : nullptr));
+  if (m->with_mom) ++m->ordinal;
   m->rows += added;
   *out_added = added;
   *out_rows = m->rows;
@@ -1416,6 +1461,58 @@ int madicp_map_download_evidence(madicp_ctx* ctx, int map_id, int64_t first_row,
   return MADICP_OK;
 }
 
+int madicp_map_download_moments(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!m->with_mom) return fail(MADICP_ERR_INVALID, kMapNoMoments);
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out holds fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(out, m->mom + madicp_host::kMomentWords * first_row, 80 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
+  HIP_TRY(hipStreamSynchronize(ctx->copy));
+  return MADICP_OK;
+}
+
+// The surfels of rows [first_row, M): fe::map_surfels, one lane per row, into a transient block of the call's own
+//   centroid (rows x 12) | normal (rows x 12) | eig (rows x 12) | count (rows x 4)
+// then the copies of what the caller asked for in ONE chain behind the kernel, ONE wait.
+int madicp_map_download_surfels(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
+                                uint32_t* out_count, int64_t capacity_rows, int64_t* out_n) {
+  if (!ctx || !out_centroid || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!m->with_mom) return fail(MADICP_ERR_INVALID, kMapNoMoments);
+  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  const int64_t rows = m->rows - first_row;
+  *out_n = rows;
+  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "the buffers hold fewer rows than the window has (*out_n)");
+  if (rows == 0) return MADICP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t R = (size_t)rows;
+  char* block = nullptr;
+  HIP_TRY(hipMalloc(&block, 40 * R));
+  float* d_centroid = reinterpret_cast<float*>(block);
+  float* d_normal = d_centroid + 3 * R;
+  float* d_eig = d_normal + 3 * R;
+  uint32_t* d_count = reinterpret_cast<uint32_t*>(d_eig + 3 * R);
+  hipLaunchKernelGGL(fe::map_surfels, dim3(grid_256(ctx, rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->mom,
+                     (const unsigned long long*)m->row_keys, (long)first_row, (long)m->rows, m->voxel, d_centroid, d_normal, d_eig, d_count);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(out_centroid, d_centroid, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, d_normal, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess && out_eig) e = hipMemcpyAsync(out_eig, d_eig, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess && out_count) e = hipMemcpyAsync(out_count, d_count, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, ctx->copy);
+  const hipError_t w = hipStreamSynchronize(ctx->copy);
+  if (e == hipSuccess) e = w;
+  hipFree(block);
+  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map surfel download: ") + hipGetErrorString(e));
+  return MADICP_OK;
+}
+
 // The rows whose word is at least min_e, compacted on the device into a transient block of the call's own (the builder's scratch
 // is sized by the largest CLOUD and may be a look-ahead's):
 //   keys (M x 8) | xyz (M x 12) | attr (M x 4) | ev (M x 4) | mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)
@@ -1451,7 +1548,8 @@ int madicp_map_download_min_evidence(madicp_ctx* ctx, int map_id, uint32_t min_e
   hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
   hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, 0L,
                      (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, d_keys, d_xyz, d_attr, mark,
-                     (const uint32_t*)m->ev, d_ev);
+                     (const uint32_t*)m->ev, d_ev, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr,
+                     (uint32_t*)nullptr);
   uint32_t res[2] = {0, 0};
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(res, mark, sizeof(res), hipMemcpyDeviceToHost, ctx->copy);
@@ -1587,6 +1685,7 @@ int madicp_map_clear(madicp_ctx* ctx, int map_id) {
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(map_table_wipe(ctx, m));
   m->rows = 0;
+  m->ordinal = 0;  // (the moments and freeze words go with their rows: voxel_rows starts every new row afresh)
   m->log_n = 0;  // (the log's memory is kept)
   return MADICP_OK;
 }

@@ -237,7 +237,8 @@ void Pipeline::dropMap() {
   map_log_full_ = false;
 }
 
-void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, const uint32_t* evidence) {
+void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, const uint32_t* evidence,
+                                  uint32_t moments_max_count) {
   if (!std::isfinite(voxel_size) || voxel_size < 0.0)
     throw std::invalid_argument("Pipeline::setMapAccumulation: voxel_size must be finite and >= 0 (0 = off)");
   if (voxel_size > 0.0 && (max_points < 1 || max_points > static_cast<size_t>(kMapMaxRows)))
@@ -245,10 +246,13 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
   if (voxel_size > 0.0 && evidence)
     if (const char* why = map_evidence_refusal(evidence[0], evidence[1], evidence[2]))
       throw std::invalid_argument(std::string("Pipeline::setMapAccumulation: ") + why);
+  if (voxel_size > 0.0 && moments_max_count > 0)
+    if (const char* why = map_moments_refusal(moments_max_count)) throw std::invalid_argument(std::string("Pipeline::setMapAccumulation: ") + why);
+  const uint32_t mom = voxel_size > 0.0 ? moments_max_count : 0u;
   const bool with_ev = voxel_size > 0.0 && evidence;
   const bool same_ev = with_ev == map_with_ev_ && (!with_ev || std::equal(evidence, evidence + 3, map_ev_));
   if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_ &&
-                                                        with_attribute == map_with_attr_ && same_ev)))
+                                                        with_attribute == map_with_attr_ && same_ev && mom == map_mom_)))
     return;
   dropMap();
   const bool was_on = map_voxel_ > 0.0;
@@ -259,6 +263,7 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
   map_attr_type_ = kAttrNone;
   map_with_ev_ = with_ev;
   if (with_ev) std::copy(evidence, evidence + 3, map_ev_);
+  map_mom_ = mom;
   if (voxel_size > 0.0) {
     if (!was_on) dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
   } else {
@@ -286,7 +291,11 @@ void Pipeline::foldFrame() {
       madicp_ctx* ctx = fresh ? Device::ctx() : Device::current(map_generation_);
       if (!ctx) throw std::logic_error("Pipeline: the device context the map lived in is gone");
       if (fresh) {
-        if (map_with_ev_)
+        if (map_mom_ > 0)
+          check(madicp_map_create_mom(ctx, map_voxel_, first_rows, max_rows, map_with_attr_ ? 1 : 0, map_with_ev_ ? map_ev_ : nullptr, map_mom_,
+                                      &map_id_),
+                "madicp_map_create_mom");
+        else if (map_with_ev_)
           check(madicp_map_create_ev(ctx, map_voxel_, first_rows, max_rows, map_with_attr_ ? 1 : 0, map_ev_[0], map_ev_[1], map_ev_[2], &map_id_),
                 "madicp_map_create_ev");
         else if (map_with_attr_)
@@ -328,7 +337,8 @@ void Pipeline::foldFrame() {
       }
     } else {
       if (fresh) {
-        map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_, map_with_ev_, map_ev_[0], map_ev_[1], map_ev_[2]);
+        map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_, map_with_ev_, map_ev_[0], map_ev_[1], map_ev_[2],
+                                               map_mom_);
         map_host_->track_removed(map_track_removed_);
       }
       ContainerType down;  // (a resident scan into a host map: the front-end was switched — its column crosses with it)
@@ -651,6 +661,56 @@ size_t Pipeline::mapEvidence(uint32_t* out, size_t capacity, size_t first_row) {
     if (!ctx) throw std::logic_error("Pipeline::mapEvidence: the device context the map lived in is gone");
     check(madicp_map_download_evidence(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
           "madicp_map_download_evidence");
+  }
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::mapMoments(uint64_t* out, size_t capacity, size_t first_row) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapMoments: setMapAccumulation(voxel_size > 0) first");
+  if (map_mom_ == 0) throw std::logic_error("Pipeline::mapMoments: the map was made without moments (setMapAccumulation's moments_max_count)");
+  if (!out) throw std::invalid_argument("Pipeline::mapMoments: null buffer");
+  const size_t size = mapSize();
+  if (first_row > size) throw std::invalid_argument("Pipeline::mapMoments: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (capacity < size - first_row)
+    throw std::invalid_argument("Pipeline::mapMoments: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
+                                std::to_string(size - first_row));
+  if (size == first_row) return 0;
+  int64_t rows = 0;
+  if (map_host_) {
+    if (map_host_->download_moments(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
+      throw std::runtime_error("Pipeline::mapMoments: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapMoments: the device context the map lived in is gone");
+    check(madicp_map_download_moments(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
+          "madicp_map_download_moments");
+  }
+  return static_cast<size_t>(rows);
+}
+
+size_t Pipeline::mapSurfels(float* centroid, float* normal, float* eig, uint32_t* count, size_t capacity, size_t first_row) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapSurfels: setMapAccumulation(voxel_size > 0) first");
+  if (map_mom_ == 0) throw std::logic_error("Pipeline::mapSurfels: the map was made without moments (setMapAccumulation's moments_max_count)");
+  if (!centroid) throw std::invalid_argument("Pipeline::mapSurfels: null buffer");
+  const size_t size = mapSize();
+  if (first_row > size) throw std::invalid_argument("Pipeline::mapSurfels: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (capacity < size - first_row)
+    throw std::invalid_argument("Pipeline::mapSurfels: the buffers hold " + std::to_string(capacity) + " rows, the window needs " +
+                                std::to_string(size - first_row));
+  if (size == first_row) return 0;
+  int64_t rows = 0;
+  if (map_host_) {
+    if (map_host_->download_surfels(static_cast<int64_t>(first_row), centroid, normal, eig, count, static_cast<int64_t>(capacity), &rows) !=
+        MADICP_OK)
+      throw std::runtime_error("Pipeline::mapSurfels: the host voxel map refused its arguments");
+  } else {
+    DeviceLock lock(Device::mutex());
+    madicp_ctx* ctx = Device::current(map_generation_);
+    if (!ctx) throw std::logic_error("Pipeline::mapSurfels: the device context the map lived in is gone");
+    check(madicp_map_download_surfels(ctx, map_id_, static_cast<int64_t>(first_row), centroid, normal, eig, count,
+                                      static_cast<int64_t>(capacity), &rows),
+          "madicp_map_download_surfels");
   }
   return static_cast<size_t>(rows);
 }

@@ -176,7 +176,20 @@ class Pipeline {
   // returns their number (at most mapSize(): a buffer that holds that many always suffices); std::invalid_argument for a null xyz
   // or a capacity below that number (nothing written).  Both: std::logic_error while accumulation is off or without the column.
   void setMapAccumulation(double voxel_size, bool keyframes_only = false, size_t max_points = kMapMaxPointsDefault,
-                          bool with_attribute = false, const uint32_t* evidence = nullptr);
+                          bool with_attribute = false, const uint32_t* evidence = nullptr, uint32_t moments_max_count = 0);
+  // moments_max_count: 0 — the default: nothing changes, not a launch, not an allocation, the same pose and map bits — or 1 .. 2^31:
+  // the map is made with per-voxel MOMENTS (madicp_map_create_mom / VoxelMap's; csrc/common/voxel_moments.h has the rule): every
+  // fold adds its points to the count, sums and sums of products of the voxels they fall into, a row taking whole folds while its
+  // count is below moments_max_count; the words follow their rows through clearings and prunes.  It combines freely with
+  // with_attribute and evidence; another value starts a new, empty map; std::invalid_argument above 2^31.
+  // mapMoments: the ten 64-bit words (n, S1[3], S2[6]) of rows [first_row, mapSize()) as (rows, 10), mapCloud's refusals.
+  // mapSurfels: per row of the window the centroid (3 floats) and, where not null, the normal (3 floats, zero below three points,
+  // sign free), the covariance's eigenvalues in m^2 ascending (3 floats) and the count — computed where the map lives
+  // (madicp_map_download_surfels); the same refusals.  Both: std::logic_error while accumulation is off or without the moments.
+  // The removal log and MapMirror carry no moments — a row's change after it was delivered: a consumer re-reads mapSurfels.
+  bool mapWithMoments() const { return map_voxel_ > 0.0 && map_mom_ > 0; }
+  size_t mapMoments(uint64_t* out, size_t capacity, size_t first_row = 0);
+  size_t mapSurfels(float* centroid, float* normal, float* eig, uint32_t* count, size_t capacity, size_t first_row = 0);
   bool mapWithEvidence() const { return map_voxel_ > 0.0 && map_with_ev_; }
   size_t mapEvidence(uint32_t* out, size_t capacity, size_t first_row = 0);
   size_t mapConfirmed(uint32_t min_evidence, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, size_t capacity);
@@ -413,6 +426,7 @@ class Pipeline {
   double map_voxel_ = 0.0;
   bool map_keyframes_only_ = false, map_overflowed_ = false, map_with_attr_ = false, map_with_ev_ = false;
   uint32_t map_ev_[3] = {1, 1, 1};  // hit, miss, cap (setMapAccumulation's evidence)
+  uint32_t map_mom_ = 0;            // moments_max_count (0: no moments)
   int map_attr_type_ = 0;
   size_t map_max_points_ = kMapMaxPointsDefault;
   int map_id_ = -1;

@@ -43,6 +43,30 @@ int madicp_host_map_create_ev(double voxel, int64_t initial_rows, int64_t max_ro
   return MADICP_OK;
 }
 
+int madicp_host_map_create_mom(double voxel, int64_t initial_rows, int64_t max_rows, int with_attr, const uint32_t evidence[3],
+                               uint32_t max_count, madicp_host_map** out_map) {
+  if (!out_map || madicp_host::map_create_refusal(voxel, initial_rows, max_rows) || madicp_host::map_moments_refusal(max_count) ||
+      (evidence && madicp_host::map_evidence_refusal(evidence[0], evidence[1], evidence[2])))
+    return MADICP_ERR_INVALID;
+  madicp_host_map* m = new (std::nothrow)
+      madicp_host_map{madicp_host::VoxelMap(voxel, initial_rows, max_rows, with_attr != 0, evidence != nullptr, evidence ? evidence[0] : 1u,
+                                            evidence ? evidence[1] : 1u, evidence ? evidence[2] : 1u, max_count)};
+  if (!m) return MADICP_ERR_CAPACITY;
+  *out_map = m;
+  return MADICP_OK;
+}
+
+int madicp_host_map_download_moments(const madicp_host_map* map, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_moments(first_row, out, capacity_rows, out_n);
+}
+
+int madicp_host_map_download_surfels(const madicp_host_map* map, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
+                                     uint32_t* out_count, int64_t capacity_rows, int64_t* out_n) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.download_surfels(first_row, out_centroid, out_normal, out_eig, out_count, capacity_rows, out_n);
+}
+
 int madicp_host_map_download_evidence(const madicp_host_map* map, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n) {
   if (!map) return MADICP_ERR_INVALID;
   return map->map.download_evidence(first_row, out_ev, capacity_rows, out_n);

@@ -11,14 +11,19 @@
 // A map made `with_ev` holds the evidence column (export_point.h has the rule: map_evidence_hit / map_evidence_miss): a fold
 // reinforces the rows it hits, once per fold, a clearing weakens the rows it sees through, and a row leaves only when its evidence
 // is used up (madicp_map_create_ev).
+// A map made with `moments_max_count` > 0 holds the moments (../common/voxel_moments.h has the rule): ten 64-bit words per row over
+// the points that fell into its voxel, the freeze word beside them, and a key -> row index where the others need only the set
+// (madicp_map_create_mom).  The freeze is the device's mechanism, run sequentially: closed_at and the fold ordinal.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 #include "../common/export_point.h"
+#include "../common/voxel_moments.h"
 
 namespace madicp_host {
 
@@ -27,16 +32,23 @@ constexpr int kMapOk = 0, kMapInvalid = -1, kMapCapacity = -4;  // MADICP_OK, MA
 class VoxelMap {
  public:
   VoxelMap(double voxel, int64_t initial_rows, int64_t max_rows, bool with_attr = false, bool with_ev = false, uint32_t hit = 1,
-           uint32_t miss = 1, uint32_t cap = 1)
-      : voxel_(voxel), max_rows_(max_rows), with_attr_(with_attr), with_ev_(with_ev), hit_(hit), miss_(miss), cap_(cap) {
+           uint32_t miss = 1, uint32_t cap = 1, uint32_t moments_max_count = 0)
+      : voxel_(voxel), max_rows_(max_rows), with_attr_(with_attr), with_ev_(with_ev), hit_(hit), miss_(miss), cap_(cap),
+        with_mom_(moments_max_count > 0), max_count_(moments_max_count) {
     const size_t first = static_cast<size_t>(std::min(initial_rows, max_rows));
     rows_.reserve(3 * first);
     keys_.reserve(first);
     row_keys_.reserve(first);
     if (with_attr_) attr_.reserve(first);
     if (with_ev_) ev_.reserve(first);
+    if (with_mom_) {
+      mom_.reserve(kMomentWords * first);
+      closed_at_.reserve(first);
+      row_of_.reserve(first);
+    }
   }
   bool with_ev() const { return with_ev_; }
+  bool with_moments() const { return with_mom_; }
   double voxel() const { return voxel_; }
   bool with_attr() const { return with_attr_; }
   int64_t size() const { return static_cast<int64_t>(rows_.size() / 3); }
@@ -47,6 +59,7 @@ class VoxelMap {
     if (!out_added || !out_rows || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
     if (export_refusal(R, t, voxel_)) return kMapInvalid;
     if (size() + n > max_rows_) return kMapCapacity;  // (conservative: decided before a point is looked at, as on the device)
+    if (with_mom_ && n > 0 && ordinal_ > kMomentsLastOrdinal) return kMapCapacity;  // (2^32 - 1 folds since creation or clear)
     const int64_t before = size();
     std::unordered_set<uint64_t> met;  // evidence maps: the candidate keys that met a row (this fold's own rows among them)
     for (int64_t i = 0; i < n; ++i) {
@@ -56,13 +69,21 @@ class VoxelMap {
       if (key == kExportNoKey) continue;
       if (!keys_.insert(key).second) {
         if (with_ev_) met.insert(key);
+        if (with_mom_) take_point(row_of_.find(key)->second, q);
         continue;
       }
       for (int k = 0; k < 3; ++k) rows_.push_back(export_value(q[k]));
       row_keys_.push_back(key);
       if (with_attr_) attr_.push_back(attr ? attr[i] : 0u);
       if (with_ev_) ev_.push_back(hit_);
+      if (with_mom_) {  // (the creating point is the row's first)
+        mom_.insert(mom_.end(), kMomentWords, uint64_t(0));
+        closed_at_.push_back(kMomentsNeverClosed);
+        row_of_[key] = size() - 1;
+        take_point(size() - 1, q);
+      }
     }
+    if (with_mom_ && n > 0) ++ordinal_;
     if (with_ev_ && !met.empty())  // the rows that were there before the fold: once per fold
       for (int64_t j = 0; j < before; ++j)
         if (met.count(row_keys_[j])) ev_[j] = map_evidence_hit(ev_[j], hit_, cap_);
@@ -140,6 +161,38 @@ class VoxelMap {
       if (out_attr) out_attr[d] = attr_[j];
       if (out_ev) out_ev[d] = ev_[j];
       ++d;
+    }
+    return kMapOk;
+  }
+
+  // include/madicp_host.h: madicp_host_map_download_moments — the ten words of rows [first_row, size()) as (rows, 10); invalid on a
+  // map without moments
+  int download_moments(int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) const {
+    if (!with_mom_ || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
+    const int64_t m = size() - first_row;
+    *out_n = m;
+    if (capacity_rows < m) return kMapCapacity;
+    if (m > 0) std::memcpy(out, mom_.data() + kMomentWords * first_row, sizeof(uint64_t) * kMomentWords * static_cast<size_t>(m));
+    return kMapOk;
+  }
+  // include/madicp_host.h: madicp_host_map_download_surfels — map_surfel of rows [first_row, size()): centroid, and normal /
+  // eigenvalues / count where asked for
+  int download_surfels(int64_t first_row, float* out_centroid, float* out_normal, float* out_eig, uint32_t* out_count, int64_t capacity_rows,
+                       int64_t* out_n) const {
+    if (!with_mom_ || !out_centroid || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
+    const int64_t m = size() - first_row;
+    *out_n = m;
+    if (capacity_rows < m) return kMapCapacity;
+    for (int64_t j = 0; j < m; ++j) {
+      const int64_t r = first_row + j;
+      float nrm[3], eig[3];
+      uint32_t count;
+      map_surfel(mom_.data() + kMomentWords * r, row_keys_[r], voxel_, out_centroid + 3 * j, nrm, eig, &count);
+      for (int k = 0; k < 3; ++k) {
+        if (out_normal) out_normal[3 * j + k] = nrm[k];
+        if (out_eig) out_eig[3 * j + k] = eig[k];
+      }
+      if (out_count) out_count[j] = count;
     }
     return kMapOk;
   }
@@ -231,6 +284,10 @@ class VoxelMap {
     row_keys_.clear();
     attr_.clear();
     ev_.clear();
+    mom_.clear();
+    closed_at_.clear();
+    row_of_.clear();
+    ordinal_ = 0;
     log_keys_.clear();
     log_rows_.clear();
     log_attr_.clear();
@@ -263,6 +320,10 @@ class VoxelMap {
         row_keys_[d] = row_keys_[j];
         if (with_attr_) attr_[d] = attr_[j];
         if (with_ev_) ev_[d] = ev_[j];
+        if (with_mom_) {
+          std::copy(mom_.begin() + kMomentWords * j, mom_.begin() + kMomentWords * (j + 1), mom_.begin() + kMomentWords * d);
+          closed_at_[d] = closed_at_[j];
+        }
       }
       ++d;
     }
@@ -271,9 +332,30 @@ class VoxelMap {
     row_keys_.resize(static_cast<size_t>(d));
     if (with_attr_) attr_.resize(static_cast<size_t>(d));
     if (with_ev_) ev_.resize(static_cast<size_t>(d));
+    if (with_mom_) {
+      mom_.resize(kMomentWords * static_cast<size_t>(d));
+      closed_at_.resize(static_cast<size_t>(d));
+      if (d < m) {  // (rows moved: the index follows them)
+        row_of_.clear();
+        for (int64_t j = 0; j < d; ++j) row_of_[row_keys_[j]] = j;
+      }
+    }
     *out_removed = m - d;
     *out_rows = d;
     *out_watermark = mark;
+  }
+
+  // one candidate point into row r (voxel_moments.h: moment_row_takes / moment_closes — the device's map_moments, one point at a time)
+  void take_point(int64_t r, const double* q) {
+    if (!moment_row_takes(closed_at_[r], ordinal_)) return;
+    uint32_t w[3];
+    moment_offset(q, voxel_, w);
+    uint64_t c[9];
+    moment_terms(w, c);
+    uint64_t* M = mom_.data() + kMomentWords * r;
+    if (moment_closes(M[0], 1, max_count_)) closed_at_[r] = ordinal_;
+    M[0] += 1;
+    for (int k = 0; k < 9; ++k) M[1 + k] += c[k];
   }
 
   double voxel_;
@@ -284,6 +366,11 @@ class VoxelMap {
   std::vector<float> rows_;
   std::vector<uint32_t> attr_;
   std::vector<uint32_t> ev_;  // evidence maps: one word per row, 1 .. cap_
+  bool with_mom_;
+  uint32_t max_count_, ordinal_ = 0;              // moments maps: the freeze bound, the folds since creation or clear
+  std::vector<uint64_t> mom_;                     // (rows, 10)
+  std::vector<uint32_t> closed_at_;               // the ordinal of the fold that froze the row, all ones = none yet
+  std::unordered_map<uint64_t, int64_t> row_of_;  // key -> row
   std::vector<uint64_t> row_keys_;  // the key of every row (prune erases by it: a float row cannot reproduce its key)
   std::unordered_set<uint64_t> keys_;
   bool track_ = false;  // the removal log: entries of (key, float row, word), oldest first

@@ -111,9 +111,16 @@ PYBIND11_MODULE(pypeline, m) {
     // a tuple (rows[, keys][, attr]).  ValueError for hit < 1, miss < 1, cap < hit, cap > 2^31 - 1; RuntimeError (std::logic_error)
     // from both without the column.
     .def("setMapAccumulation",
-         [](Pipeline& self, double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, py::object evidence) {
+         [](Pipeline& self, double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, py::object evidence,
+            py::object moments) {
+           uint32_t max_count = 0;
+           if (!moments.is_none()) {
+             const long long v = moments.cast<long long>();
+             if (v < 1 || v > 0x80000000ll) throw py::value_error("moments must be None or max_count, 1 .. 2^31");
+             max_count = static_cast<uint32_t>(v);
+           }
            if (evidence.is_none()) {
-             self.setMapAccumulation(voxel_size, keyframes_only, max_points, with_attribute);
+             self.setMapAccumulation(voxel_size, keyframes_only, max_points, with_attribute, nullptr, max_count);
              return;
            }
            const py::sequence ev = evidence.cast<py::sequence>();
@@ -124,10 +131,48 @@ PYBIND11_MODULE(pypeline, m) {
              if (v < 0 || v > 0xffffffffll) throw py::value_error("evidence: hit, miss and cap are 32-bit unsigned values");
              e[i] = static_cast<uint32_t>(v);
            }
-           self.setMapAccumulation(voxel_size, keyframes_only, max_points, with_attribute, e);
+           self.setMapAccumulation(voxel_size, keyframes_only, max_points, with_attribute, e, max_count);
          },
          py::arg("voxel_size"), py::arg("keyframes_only") = false, py::arg("max_points") = Pipeline::kMapMaxPointsDefault,
-         py::arg("with_attribute") = false, py::arg("evidence") = py::none())
+         py::arg("with_attribute") = false, py::arg("evidence") = py::none(), py::arg("moments") = py::none())
+    // moments=max_count (1 .. 2^31): the map keeps count, sums and sums of products of the points of every voxel (include/madicp_hip.h
+    // has the rule); None (the default) changes nothing.  mapMoments(first_row=0) returns the ten words of rows [first_row, mapSize())
+    // as (M, 10) uint64; mapSurfels(first_row=0) returns (centroid (M, 3) float32, normal (M, 3) float32, eigenvalues (M, 3) float32,
+    // count (M,) uint32), computed where the map lives.  ValueError outside 1 .. 2^31; RuntimeError (std::logic_error) from both
+    // without the moments.
+    .def("mapWithMoments", &Pipeline::mapWithMoments)
+    .def("mapMoments",
+         [](Pipeline& self, size_t first_row) {
+           if (!self.mapWithMoments())
+             throw std::logic_error("Pipeline::mapMoments: the map was made without moments (setMapAccumulation's moments)");
+           const size_t size = self.mapSize();
+           if (first_row > size) throw py::value_error("first_row is beyond the map's rows");
+           const size_t m = size - first_row;
+           py::array_t<uint64_t> w({static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(10)});
+           uint64_t no_row[10];
+           if (self.mapMoments(m ? w.mutable_data() : no_row, m, first_row) != m)
+             throw std::runtime_error("Pipeline::mapMoments: the map changed during the call");
+           return w;
+         },
+         py::arg("first_row") = 0)
+    .def("mapSurfels",
+         [](Pipeline& self, size_t first_row) {
+           if (!self.mapWithMoments())
+             throw std::logic_error("Pipeline::mapSurfels: the map was made without moments (setMapAccumulation's moments)");
+           const size_t size = self.mapSize();
+           if (first_row > size) throw py::value_error("first_row is beyond the map's rows");
+           const size_t m = size - first_row;
+           const py::ssize_t rows = static_cast<py::ssize_t>(m), three = 3;
+           py::array_t<float> c({rows, three}), nrm({rows, three}), eig({rows, three});
+           py::array_t<uint32_t> cnt(rows);
+           float no_row[3];
+           uint32_t no_count[1];
+           if (self.mapSurfels(m ? c.mutable_data() : no_row, m ? nrm.mutable_data() : no_row, m ? eig.mutable_data() : no_row,
+                               m ? cnt.mutable_data() : no_count, m, first_row) != m)
+             throw std::runtime_error("Pipeline::mapSurfels: the map changed during the call");
+           return py::make_tuple(c, nrm, eig, cnt);
+         },
+         py::arg("first_row") = 0)
     .def("mapWithEvidence", &Pipeline::mapWithEvidence)
     .def("mapEvidence",
          [](Pipeline& self, size_t first_row) {
