@@ -710,13 +710,23 @@ __global__ __launch_bounds__(256) void map_prune_mark(const float* __restrict__ 
     mark[j] = m;  // (entry n_rows: the scan needs a terminator)
   }
 }
-__global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ pos, long n_rows, long watermark,
-                                                   const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
-                                                   const uint32_t* __restrict__ attr, unsigned long long* __restrict__ out_keys,
-                                                   float* __restrict__ out_rows, uint32_t* __restrict__ out_attr, uint32_t* __restrict__ res,
-                                                   const uint32_t* __restrict__ ev, uint32_t* __restrict__ out_ev,
-                                                   const unsigned long long* __restrict__ mom, unsigned long long* __restrict__ out_mom,
-                                                   const uint32_t* __restrict__ closed_at, uint32_t* __restrict__ out_closed_at) {
+// the row columns of a block as a kernel takes them, by value — one for where rows come from, one for where they go (null: no such column)
+struct MapRows {
+  unsigned long long* keys;
+  float* xyz;
+  uint32_t *attr, *ev;
+  unsigned long long* mom;
+  uint32_t* closed_at;
+};
+// (the bodies take the columns as __restrict__ parameters, the kernels below hand them the structs' members: a struct member cannot
+// promise that the columns do not overlap, and without the promise every one of a row's moment words waits for the one before it)
+__device__ __forceinline__ void map_compact_rows(const uint32_t* __restrict__ pos, long n_rows, long watermark,
+                                                 const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
+                                                 const uint32_t* __restrict__ attr, unsigned long long* __restrict__ out_keys,
+                                                 float* __restrict__ out_rows, uint32_t* __restrict__ out_attr, uint32_t* __restrict__ res,
+                                                 const uint32_t* __restrict__ ev, uint32_t* __restrict__ out_ev,
+                                                 const unsigned long long* __restrict__ mom, unsigned long long* __restrict__ out_mom,
+                                                 const uint32_t* __restrict__ closed_at, uint32_t* __restrict__ out_closed_at) {
   for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_rows; j += (long)gridDim.x * blockDim.x) {
     if (j == 0) {
       res[0] = pos[n_rows];
@@ -736,16 +746,20 @@ __global__ __launch_bounds__(256) void map_compact(const uint32_t* __restrict__ 
     }
   }
 }
+__global__ __launch_bounds__(256) void map_compact(const uint32_t* pos, long n_rows, long watermark, MapRows in, MapRows out, uint32_t* res) {
+  map_compact_rows(pos, n_rows, watermark, in.keys, in.xyz, in.attr, out.keys, out.xyz, out.attr, res, in.ev, out.ev, in.mom, out.mom,
+                   in.closed_at, out.closed_at);
+}
 // The removal log of a tracking map (madicp_map_track_removed): map_compact's complement over the rows below the watermark, beside it
 // behind the same scan.  One lane per row j < n_below = min(watermark, M): row j leaves iff pos[j + 1] == pos[j], and its place in
 // the log is base + (j - pos[j]) — the rows removed before j, behind the `base` entries the log already holds: no second scan, no
 // atomics, coalesced reads, monotone writes.  Reads the scan and the OLD block only, never the marks (in the clearing path the scan
 // lies over the dead ray flags, and map_compact's lane 0 writes its two answers over the first marks).  At most n_below entries are
 // written: the caller has ensured base + n_below.
-__global__ __launch_bounds__(256) void map_log_removed(const uint32_t* __restrict__ pos, long n_below, long base,
-                                                       const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
-                                                       const uint32_t* __restrict__ attr, unsigned long long* __restrict__ log_keys,
-                                                       float* __restrict__ log_rows, uint32_t* __restrict__ log_attr) {
+__device__ __forceinline__ void map_log_removed_rows(const uint32_t* __restrict__ pos, long n_below, long base,
+                                                     const unsigned long long* __restrict__ row_keys, const float* __restrict__ rows,
+                                                     const uint32_t* __restrict__ attr, unsigned long long* __restrict__ log_keys,
+                                                     float* __restrict__ log_rows, uint32_t* __restrict__ log_attr) {
   for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_below; j += (long)gridDim.x * blockDim.x) {
     const long d = pos[j];
     if ((long)pos[j + 1] != d) continue;
@@ -756,6 +770,9 @@ __global__ __launch_bounds__(256) void map_log_removed(const uint32_t* __restric
     log_rows[3 * e + 2] = rows[3 * j + 2];
     if (attr) log_attr[e] = attr[j];
   }
+}
+__global__ __launch_bounds__(256) void map_log_removed(const uint32_t* pos, long n_below, long base, MapRows in, MapRows log) {
+  map_log_removed_rows(pos, n_below, base, in.keys, in.xyz, in.attr, log.keys, log.xyz, log.attr);
 }
 
 // ---- clearing the map by a scan's rays: rows whose voxel a ray passes through and no point of the scan lies in leave ----------------

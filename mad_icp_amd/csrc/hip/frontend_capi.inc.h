@@ -18,41 +18,50 @@ struct DevCloud {
   hipEvent_t ready = nullptr;  // recorded on the copy stream behind whatever produced xyz
 };
 
-// a voxel map (madicp_map_*): one device block for `cap` rows and 2 cap table slots — laid out where the entry points are
-struct DevMap {
+// the columns of one device block (../common/map_layout.h has the list and the layout): null where the block has none
+struct MapCols {
+  char* col[kMapColumns] = {};
+  void point(char* block, const MapLayout& L) {
+    for (int c = 0; c < kMapColumns; ++c) col[c] = L.has(c) ? block + L.off[c] : nullptr;
+  }
+  template <class T>
+  T* at(MapColumn c) const { return reinterpret_cast<T*>(col[c]); }
+  unsigned long long* keys() const { return at<unsigned long long>(kColKeys); }  // (slots) the table's keys, empty = all ones
+  uint32_t* owner() const { return at<uint32_t>(kColOwner); }                    // (slots) fe::kMapNever / kMapSettled / contended
+  unsigned long long* row_keys() const { return at<unsigned long long>(kColRowKeys); }
+  float* xyz() const { return at<float>(kColXyz); }
+  uint32_t* attr() const { return at<uint32_t>(kColAttr); }
+  uint32_t* ev() const { return at<uint32_t>(kColEv); }
+  uint32_t* slot_row() const { return at<uint32_t>(kColSlotRow); }
+  uint32_t* stamp() const { return at<uint32_t>(kColStamp); }  // (slots) all ones = not hit since the wipe
+  uint32_t* closed_at() const { return at<uint32_t>(kColClosedAt); }
+  unsigned long long* mom() const { return at<unsigned long long>(kColMom); }
+  // what fe::map_compact / fe::map_log_removed read rows from and write them to
+  fe::MapRows moving() const { return {row_keys(), xyz(), attr(), ev(), mom(), closed_at()}; }
+};
+
+// a voxel map (madicp_map_*): one device block for `cap` rows and 2 cap table slots
+struct DevMap : MapCols {
   double voxel = 0.0;
   int64_t max_rows = 0, cap = 0, rows = 0;  // rows: what the map holds — exact, the host reads every fold's count
   char* block = nullptr;
-  unsigned long long* keys = nullptr;      // (slots) the table's keys, empty = all ones
-  uint32_t* owner = nullptr;               // (slots) fe::kMapNever / kMapSettled / contended
-  unsigned long long* row_keys = nullptr;  // (cap) the key of every row
-  float* xyz = nullptr;                    // (cap, 3)
-  uint32_t* attr = nullptr;                // (cap) the rows' attribute words: maps of madicp_map_create_attr only
-  bool with_attr = false;
+  bool with_attr = false;  // madicp_map_create_attr
   uint32_t slots = 0;
   // evidence (madicp_map_create_ev): the rows' words, and beside every table slot the row of its key and the number of the last
   // fold that hit it (fe::map_hit); fold_no counts the folds since the stamps were last wiped
   bool with_ev = false;
   uint32_t ev_hit = 1, ev_miss = 1, ev_cap = 1, fold_no = 0;
-  uint32_t* ev = nullptr;        // (cap)
-  uint32_t* slot_row = nullptr;  // (slots)
-  uint32_t* stamp = nullptr;     // (slots) all ones = not hit since the wipe
   // moments (madicp_map_create_mom; csrc/common/voxel_moments.h has the rule): ten 64-bit words per row and the row's freeze word —
   // the ordinal of the fold that brought it to max_count, all ones while it still takes points.  slot_row exists on these maps too.
   // ordinal counts the folds since creation or madicp_map_clear; no table wipe resets it
   bool with_mom = false;
   uint32_t mom_max_count = 0, ordinal = 0;
-  unsigned long long* mom = nullptr;  // (cap, 10)
-  uint32_t* closed_at = nullptr;      // (cap)
-  // the removal log (madicp_map_track_removed): a block of its own — the map's is swapped by every prune and growth —
-  //   keys (log_cap x 8) | xyz (log_cap x 12) | attr (log_cap x 4, attribute maps only)
-  // of which the first log_n entries are live; allocated at the first removal that can log
+  // the removal log (madicp_map_track_removed): a block of its own — the map's is swapped by every prune and growth — with the
+  // logged columns (map_log_layout), of which the first log_n entries are live; allocated at the first removal that can log
   bool track = false;
   char* log_block = nullptr;
   int64_t log_cap = 0, log_n = 0;
-  unsigned long long* log_keys() const { return reinterpret_cast<unsigned long long*>(log_block); }
-  float* log_xyz() const { return reinterpret_cast<float*>(log_block + 8 * (size_t)log_cap); }
-  uint32_t* log_attr() const { return with_attr ? reinterpret_cast<uint32_t*>(log_block + 20 * (size_t)log_cap) : nullptr; }
+  MapCols log;
 };
 
 // grow-only scratch of the tree builder / deskew / ingest
@@ -272,13 +281,13 @@ int drop_cloud(madicp_ctx* ctx, DevCloud& c, int rc) {
     if (e_ != hipSuccess) return drop_cloud(ctx, c, fail(MADICP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_))); \
   } while (0)
 
-int scan_marks(hipStream_t s, FrontScratch& fs, const uint32_t* marks, int64_t n, int32_t* d_total) {
-  const int tiles = static_cast<int>((n + 1 + tb::kScanTile - 1) / tb::kScanTile);
-  hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, s, marks, (int)n, fs.tile_sums);
-  hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, s, fs.tile_sums, tiles, d_total);
-  hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, s, marks, (int)n, (const uint32_t*)fs.tile_sums, fs.S);
-  HIP_TRY(hipGetLastError());
-  return MADICP_OK;
+// the tile scan of marks[0 .. n] (entry n: the terminator) into S, its total into *d_total: three launches, nothing waited for
+hipError_t scan_marks(hipStream_t s, const uint32_t* marks, int64_t n, uint32_t* S, uint32_t* tile_sums, int32_t* d_total) {
+  const int tiles = map_scan_tiles((size_t)n, tb::kScanTile);
+  hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, s, marks, (int)n, tile_sums);
+  hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, s, tile_sums, tiles, d_total);
+  hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, s, marks, (int)n, (const uint32_t*)tile_sums, S);
+  return hipGetLastError();
 }
 
 // dst[i] = (float)src[i] for a block of values; false as soon as a block holds a value that is not exactly a float (NaN included:
@@ -490,7 +499,7 @@ int ingest_sources_on(madicp_ctx* ctx, const madicp_host::RecordSource* src, int
   uint32_t* keep = fs->P.leaf_start;
   const int blocks = static_cast<int>(std::min<int64_t>(T.n_tiles, std::min<int64_t>((int64_t)ctx->n_cus * 8, fe::kRecMaxBlocks)));
   hipLaunchKernelGGL(fe::sources_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, T, keep, fs->rec_part);
-  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_total, &fs->P.st->n_leaves));
+  HIP_TRY(scan_marks(ctx->copy, keep, n_total, fs->S, fs->tile_sums, &fs->P.st->n_leaves));
   hipLaunchKernelGGL(fe::records_range, dim3(1), dim3(256), 0, ctx->copy, (const double*)fs->rec_part, blocks, T.has_time,
                      (T.has_time && t_range) ? 1 : 0, t_range ? t_range[0] : 0.0, t_range ? t_range[1] : 0.0,
                      (const int32_t*)&fs->P.st->n_leaves, &fs->rec_res->r);
@@ -598,7 +607,7 @@ int madicp_cloud_ingest_f32(madicp_ctx* ctx, const float* records, int64_t n_rec
   const int blocks = grid_256(ctx, n_records);
   hipLaunchKernelGGL(fe::ingest_mark, dim3(blocks), dim3(256), 0, ctx->copy, d_rec, (long)n_records, stride_floats,
                      min_range, max_range, keep);
-  RC_TRY(scan_marks(ctx->copy, *fs, keep, n_records, &fs->P.st->n_leaves));
+  HIP_TRY(scan_marks(ctx->copy, keep, n_records, fs->S, fs->tile_sums, &fs->P.st->n_leaves));
   HIP_TRY(hipMemcpyAsync(&fs->h_state->n_leaves, &fs->P.st->n_leaves, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
   HIP_TRY(hipStreamSynchronize(ctx->copy));  // the size of the result decides the allocation
   const int64_t kept = fs->h_state->n_leaves;
@@ -920,7 +929,7 @@ int voxel_fold(madicp_ctx* ctx, FrontScratch* fs, const DevCloud* c, const fe::E
   if (E)  // (in front of voxel_rows: what this fold claimed is still contended, only older rows' slots are settled)
     hipLaunchKernelGGL(fe::map_hit, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)T.owner, (long)n,
                        (const uint32_t*)E->slot_row, E->stamp, E->fold_no, E->ev, E->hit, E->cap);
-  RC_TRY(scan_marks(ctx->copy, *fs, mark, n, &fs->rec_res->r.kept));
+  HIP_TRY(scan_marks(ctx->copy, mark, n, fs->S, fs->tile_sums, &fs->rec_res->r.kept));
   HIP_TRY(hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy));
   hipLaunchKernelGGL(fe::voxel_rows, dim3(blocks), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n, X, voxel, (const uint32_t*)mark,
                      (const uint32_t*)fs->S, (const uint32_t*)(settle ? slot_of : nullptr), settle ? T.owner : nullptr, (long)first_row,
@@ -1053,19 +1062,11 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
 
 // ---- the voxel map: registered scans accumulated on the device (include/madicp_hip.h: madicp_map_*) ---------------------------------
 // Every insert is one voxel_fold into a table that persists; fe::map_rehash refills it at a growth (frontend.hip.h has the rule and
-// the determinism argument).  A map owns ONE device block laid out for `cap` rows and 2 cap table slots — 44 bytes per row of capacity:
-//   keys (2 cap x 8) | owner (2 cap x 4)    the table: emptied by ONE memset to all ones (empty key, "never owned")
-//   row_keys (cap x 8) | xyz (cap x 12)     what the rows hold, in row order
+// the determinism argument).  A map owns ONE device block laid out for `cap` rows and 2 cap table slots: ../common/map_layout.h has
+// the columns, their order and the bytes per row of capacity.
 // Growth invariant: before a fold of n points into M rows, M + n <= cap — so the table is never more than half full and every
-// probe ends; where it would not hold, a block for max(M + n, min(2 cap, max_rows)) rows is allocated, rows and keys move by device
-// copy, map_rehash refills the table, the old block is freed.  A map of madicp_map_create_attr has a fifth column
-// behind these — attr (cap x 4), the rows' attribute words: 48 bytes per row of capacity — that moves with the rows.  A map of
-// madicp_map_create_ev has, behind whatever of these it holds, ev (cap x 4) | slot_row (2 cap x 4) | stamp (2 cap x 4): the rows'
-// evidence words, which move with the rows, and two more words per table slot, wiped (stamp) and refilled (slot_row) with the table
-// — 20 more bytes per row of capacity.  A map of madicp_map_create_mom has slot_row as well (8 bytes per row of capacity where the
-// map has no evidence) and, behind all of these, closed_at (cap x 4) | mom (cap x 80, its start rounded up to 8 bytes): the rows'
-// freeze words and their ten 64-bit moment words — 84 more bytes per row of capacity, 92 without evidence; both move with the
-// rows.  The host knows M exactly: every fold ends with ONE synchronisation,
+// probe ends; where it would not hold, a block for max(M + n, min(2 cap, max_rows)) rows is allocated, the row columns move by device
+// copy, map_rehash refills the table, the old block is freed.  The host knows M exactly: every fold ends with ONE synchronisation,
 // for the count (none more at a growth but the one in front of freeing the old block).  A fold uses the builder's scratch: it is
 // refused with MADICP_ERR_CAPACITY while a look-ahead build is in flight.  Everything runs on the copy stream.
 namespace {
@@ -1073,35 +1074,22 @@ namespace {
 // the ONE memset that empties the table; on an evidence map a second one for the slots' fold stamps, and the folds count from 0 again
 hipError_t map_stamp_wipe(madicp_ctx* ctx, DevMap* m) {
   m->fold_no = 0;
-  return hipMemsetAsync(m->stamp, 0xff, sizeof(uint32_t) * (size_t)m->slots, ctx->copy);
+  return hipMemsetAsync(m->stamp(), 0xff, sizeof(uint32_t) * (size_t)m->slots, ctx->copy);
 }
 hipError_t map_table_wipe(madicp_ctx* ctx, DevMap* m) {
-  hipError_t e = hipMemsetAsync(m->block, 0xff, 24 * (size_t)m->cap, ctx->copy);
+  hipError_t e = hipMemsetAsync(m->block, 0xff, kMapTableBytesPerRow * (size_t)m->cap, ctx->copy);
   if (e == hipSuccess && m->with_ev) e = map_stamp_wipe(ctx, m);
   return e;
 }
 
 int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
-  const size_t c = (size_t)cap;
+  const MapLayout L = map_layout((size_t)cap, m->with_attr, m->with_ev, m->with_mom);
   char* block = nullptr;
-  const size_t row_bytes = m->with_attr ? 48 : 44;
-  const bool with_slot_row = m->with_ev || m->with_mom;
-  const size_t closed_off = (row_bytes + (m->with_ev ? 12 : 0) + (with_slot_row ? 8 : 0)) * c;
-  const size_t mom_off = (closed_off + 4 * c + 7) & ~size_t(7);
-  HIP_TRY(hipMalloc(&block, m->with_mom ? mom_off + 80 * c : closed_off));
+  HIP_TRY(hipMalloc(&block, L.bytes));
   m->block = block;
   m->cap = cap;
-  m->slots = static_cast<uint32_t>(2 * c);
-  m->keys = reinterpret_cast<unsigned long long*>(block);
-  m->owner = reinterpret_cast<uint32_t*>(block + 16 * c);
-  m->row_keys = reinterpret_cast<unsigned long long*>(block + 24 * c);
-  m->xyz = reinterpret_cast<float*>(block + 32 * c);
-  m->attr = m->with_attr ? reinterpret_cast<uint32_t*>(block + 44 * c) : nullptr;
-  m->ev = m->with_ev ? reinterpret_cast<uint32_t*>(block + row_bytes * c) : nullptr;
-  m->slot_row = with_slot_row ? reinterpret_cast<uint32_t*>(block + (row_bytes + (m->with_ev ? 4 : 0)) * c) : nullptr;
-  m->stamp = m->with_ev ? reinterpret_cast<uint32_t*>(block + (row_bytes + 12) * c) : nullptr;
-  m->closed_at = m->with_mom ? reinterpret_cast<uint32_t*>(block + closed_off) : nullptr;
-  m->mom = m->with_mom ? reinterpret_cast<unsigned long long*>(block + mom_off) : nullptr;
+  m->slots = static_cast<uint32_t>(2 * cap);
+  m->point(block, L);
   hipError_t e = wipe ? map_table_wipe(ctx, m) : hipSuccess;  // (a prune wipes the table itself, later)
   if (e != hipSuccess) {
     hipFree(block);
@@ -1111,23 +1099,59 @@ int map_block_alloc(madicp_ctx* ctx, int64_t cap, DevMap* m, bool wipe = true) {
   return MADICP_OK;
 }
 
+// the first n entries of the row columns that src and dst both have, device to device on the copy stream
+hipError_t map_move_rows(madicp_ctx* ctx, const MapCols& dst, const MapCols& src, size_t n) {
+  hipError_t e = hipSuccess;
+  for (int c = 0; c < kMapColumns && e == hipSuccess; ++c)
+    if (kMapColumnTable[c].row && src.col[c] && dst.col[c])
+      e = hipMemcpyAsync(dst.col[c], src.col[c], kMapColumnTable[c].bytes() * n, hipMemcpyDeviceToDevice, ctx->copy);
+  return e;
+}
+
+// Device-to-host copies on the copy stream behind whatever is enqueued (e: its error so far), each only where the caller gave a
+// buffer, then the ONE wait — which an earlier error does not spare: nothing may be in flight into the caller's buffers
+struct CopyOut {
+  void* dst;  // null: not asked for
+  const void* src;
+  size_t bytes;
+};
+int copies_then_wait(madicp_ctx* ctx, hipError_t e, const CopyOut* list, int count, const char* what) {
+  for (int i = 0; i < count && e == hipSuccess; ++i)
+    if (list[i].dst) e = hipMemcpyAsync(list[i].dst, list[i].src, list[i].bytes, hipMemcpyDeviceToHost, ctx->copy);
+  const hipError_t w = hipStreamSynchronize(ctx->copy);
+  if (e == hipSuccess) e = w;
+  return e == hipSuccess ? MADICP_OK : fail(MADICP_ERR_DEVICE, std::string(what) + hipGetErrorString(e));
+}
+// ... of `n` rows from row `first` on of every column `out` has a buffer for
+int map_rows_out(madicp_ctx* ctx, const MapCols& src, const MapCols& out, int64_t first, int64_t n, const char* what) {
+  CopyOut list[kMapColumns];
+  int count = 0;
+  for (int c = 0; c < kMapColumns; ++c)
+    if (out.col[c]) list[count++] = {out.col[c], src.col[c] + kMapColumnTable[c].bytes() * (size_t)first, kMapColumnTable[c].bytes() * (size_t)n};
+  return copies_then_wait(ctx, hipSuccess, list, count, what);
+}
+// the caller's buffers of a download, by column (null: not asked for)
+MapCols map_out(void* xyz, void* keys, void* attr, void* ev = nullptr, void* mom = nullptr) {
+  MapCols o;
+  o.col[kColXyz] = static_cast<char*>(xyz);
+  o.col[kColRowKeys] = static_cast<char*>(keys);
+  o.col[kColAttr] = static_cast<char*>(attr);
+  o.col[kColEv] = static_cast<char*>(ev);
+  o.col[kColMom] = static_cast<char*>(mom);
+  return o;
+}
+
 // a block that holds `need` rows (<= max_rows): the rows move, the table is refilled from their keys
 int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
   DevMap g = *m;
   RC_TRY(map_block_alloc(ctx, std::max(need, std::min(2 * m->cap, m->max_rows)), &g));
   hipError_t e = hipSuccess;
   if (m->rows > 0) {
-    const size_t M = (size_t)m->rows;
-    e = hipMemcpyAsync(g.row_keys, m->row_keys, sizeof(unsigned long long) * M, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess) e = hipMemcpyAsync(g.xyz, m->xyz, sizeof(float) * 3 * M, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess && m->with_attr) e = hipMemcpyAsync(g.attr, m->attr, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess && m->with_ev) e = hipMemcpyAsync(g.ev, m->ev, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess && m->with_mom) e = hipMemcpyAsync(g.mom, m->mom, 80 * M, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess && m->with_mom) e = hipMemcpyAsync(g.closed_at, m->closed_at, sizeof(uint32_t) * M, hipMemcpyDeviceToDevice, ctx->copy);
+    e = map_move_rows(ctx, g, *m, (size_t)m->rows);
     if (e == hipSuccess) {
       const int blocks = grid_256(ctx, m->rows);
-      hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)m->rows, g.keys,
-                         g.owner, g.slots, g.slot_row);
+      hipLaunchKernelGGL(fe::map_rehash, dim3(blocks), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys(), (long)m->rows,
+                         g.keys(), g.owner(), g.slots, g.slot_row());
       e = hipGetLastError();
     }
   }
@@ -1147,25 +1171,22 @@ int map_grow(madicp_ctx* ctx, DevMap* m, int64_t need) {
 int map_log_reserve(madicp_ctx* ctx, DevMap* m, int64_t need, char** old_block) {
   *old_block = nullptr;
   if (need <= m->log_cap) return MADICP_OK;
-  DevMap g = *m;
-  g.log_cap = std::max(need, std::min(2 * m->log_cap, 2 * m->max_rows));
-  g.log_block = nullptr;
-  HIP_TRY(hipMalloc(&g.log_block, (m->with_attr ? 24 : 20) * (size_t)g.log_cap));
-  hipError_t e = hipSuccess;
-  if (m->log_n > 0) {
-    const size_t n = (size_t)m->log_n;
-    e = hipMemcpyAsync(g.log_keys(), m->log_keys(), sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess) e = hipMemcpyAsync(g.log_xyz(), m->log_xyz(), sizeof(float) * 3 * n, hipMemcpyDeviceToDevice, ctx->copy);
-    if (e == hipSuccess && m->with_attr) e = hipMemcpyAsync(g.log_attr(), m->log_attr(), sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, ctx->copy);
-  }
+  const int64_t log_cap = std::max(need, std::min(2 * m->log_cap, 2 * m->max_rows));
+  const MapLayout L = map_log_layout((size_t)log_cap, m->with_attr);
+  char* block = nullptr;
+  HIP_TRY(hipMalloc(&block, L.bytes));
+  MapCols g;
+  g.point(block, L);
+  const hipError_t e = m->log_n > 0 ? map_move_rows(ctx, g, m->log, (size_t)m->log_n) : hipSuccess;
   if (e != hipSuccess) {
     hipStreamSynchronize(ctx->copy);
-    hipFree(g.log_block);
+    hipFree(block);
     return fail(MADICP_ERR_DEVICE, std::string("voxel map removal log: ") + hipGetErrorString(e));
   }
   *old_block = m->log_block;
-  m->log_block = g.log_block;
-  m->log_cap = g.log_cap;
+  m->log_block = block;
+  m->log_cap = log_cap;
+  m->log = g;
   return MADICP_OK;
 }
 
@@ -1181,38 +1202,35 @@ void map_log_settle(madicp_ctx* ctx, DevMap* m, char* old_block, int rc, int64_t
 
 // The tail every removal shares (madicp_map_prune, madicp_map_clear_rays).  The caller has allocated the FRESH block g of the same
 // capacity — the shape of a growth, and its transient cost: one more block — and enqueued the kernel that leaves mark[0 .. M] in g's
-// table region (24 cap bytes, not yet a table); here: the tile scan of the marks into S, map_compact into g, which leaves {rows kept,
-// kept below the watermark} over the first two marks, which nobody reads after the scan: ONE small copy, ONE synchronisation.
+// table region (not yet a table; W: where the removal's scratch lies in it, map_layout.h); here: the tile scan of the marks into S,
+// map_compact into g, which leaves {rows kept, kept below the watermark} over the first two marks, which nobody reads after the
+// scan: ONE small copy, ONE synchronisation.
 // Behind it nothing reads the old block any more: it is freed, the table wiped and refilled from the kept keys on the stream, in
 // front of whatever fold comes next.  Nothing removed: the fresh block is dropped, the map is not touched at all.
 // A tracking map (the caller has ensured its log, map_log_reserve) has map_log_removed beside map_compact: behind the scan, in front
 // of the one wait and of the wipe.  It reads S and the old block only — in the clearing path S lies over the dead ray flags, and
 // map_compact leaves its answers over the first marks — and writes the log; the caller moves log_n (map_log_settle).
-int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uint32_t* S, uint32_t* tile_sums, int64_t watermark,
-                      const char* what, int64_t* out_kept, int64_t* out_watermark) {
+int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, const MapScratch& W, int64_t watermark, const char* what, int64_t* out_kept,
+                      int64_t* out_watermark) {
   const int64_t M = m->rows;
-  const int tiles = static_cast<int>((M + 1 + tb::kScanTile - 1) / tb::kScanTile);
-  int32_t* total = reinterpret_cast<int32_t*>(tile_sums + tiles);
-  hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, tile_sums);
-  hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, ctx->copy, tile_sums, tiles, total);
-  hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
+  uint32_t* mark = reinterpret_cast<uint32_t*>(g.block + W.mark);
+  uint32_t* S = reinterpret_cast<uint32_t*>(g.block + W.S);
+  hipError_t e = scan_marks(ctx->copy, mark, M, S, reinterpret_cast<uint32_t*>(g.block + W.tile_sums), reinterpret_cast<int32_t*>(g.block + W.total));
   hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, (long)watermark,
-                     (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, g.row_keys, g.xyz, g.attr, mark,
-                     (const uint32_t*)m->ev, g.ev, (const unsigned long long*)m->mom, g.mom, (const uint32_t*)m->closed_at, g.closed_at);
+                     m->moving(), g.moving(), mark);
   if (const int64_t below = std::min(watermark, M); m->track && below > 0)
     hipLaunchKernelGGL(fe::map_log_removed, dim3(grid_256(ctx, below)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)below, (long)m->log_n,
-                       (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, m->log_keys(), m->log_xyz(),
-                       m->log_attr());
+                       m->moving(), m->log.moving());
   uint32_t res[2] = {0, 0};
-  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(res, mark, sizeof(res), hipMemcpyDeviceToHost, ctx->copy);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy);  // the counts (the old block is read until here)
   const int64_t kept = res[0];
   if (e == hipSuccess && kept < M) {
     e = map_table_wipe(ctx, &g);
     if (e == hipSuccess && kept > 0) {
-      hipLaunchKernelGGL(fe::map_rehash, dim3(grid_256(ctx, kept)), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys, (long)kept,
-                         g.keys, g.owner, g.slots, g.slot_row);
+      hipLaunchKernelGGL(fe::map_rehash, dim3(grid_256(ctx, kept)), dim3(256), 0, ctx->copy, (const unsigned long long*)g.row_keys(), (long)kept,
+                         g.keys(), g.owner(), g.slots, g.slot_row());
       e = hipGetLastError();
     }
   }
@@ -1230,47 +1248,46 @@ int map_remove_marked(madicp_ctx* ctx, DevMap* m, DevMap& g, uint32_t* mark, uin
   return MADICP_OK;
 }
 
-// The rows of *m that stay within sphere Q.  The fresh block's table region holds the prune's scratch until the memset that makes
-// it a table:   mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)   — 8 (M + 1) + 4 tiles + 4 bytes, within 24 cap
-// for every 1 <= M <= cap; the builder's scratch (sized by the largest CLOUD) is not touched.
+// The rows of *m that stay within sphere Q.  The fresh block's table region holds the prune's scratch (map_prune_scratch) until the
+// memset that makes it a table; the builder's scratch (sized by the largest CLOUD) is not touched.
 int map_prune_on(madicp_ctx* ctx, DevMap* m, const fe::PruneSphere& Q, int64_t watermark, int64_t* out_kept, int64_t* out_watermark) {
   const int64_t M = m->rows;
   DevMap g = *m;
   RC_TRY(map_block_alloc(ctx, m->cap, &g, false));
-  uint32_t* mark = reinterpret_cast<uint32_t*>(g.block);
-  uint32_t* S = mark + (M + 1);
-  hipLaunchKernelGGL(fe::map_prune_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const float*)m->xyz, (long)M, Q, mark);
-  return map_remove_marked(ctx, m, g, mark, S, S + (M + 1), watermark, "voxel map prune: ", out_kept, out_watermark);
+  const MapScratch W = map_prune_scratch((size_t)m->cap, (size_t)M, tb::kScanTile);
+  hipLaunchKernelGGL(fe::map_prune_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const float*)m->xyz(), (long)M, Q,
+                     reinterpret_cast<uint32_t*>(g.block + W.mark));
+  return map_remove_marked(ctx, m, g, W, watermark, "voxel map prune: ", out_kept, out_watermark);
 }
 
-// The rows of *m that the rays of cloud c do not clear.  The fresh block's table region, until the memset that makes it a table:
-//   flags (2 cap words: one per slot of the LIVE table, zeroed by the one memset) | mark (M + 1) | tile_sums (tiles) | total (1)
-// and S (M + 1 <= 2 cap words) is laid over the flags, which are dead once map_clear_mark has run: 8 cap + 4 (M + 1) + 4 tiles + 4
-// bytes, within 24 cap for every 1 <= M <= cap (cap = 1: 8 + 8 + 4 + 4 = 24).  The live table is only read; the builder's scratch
-// is not touched.
+// The rows of *m that the rays of cloud c do not clear.  The fresh block's table region holds the clearing's scratch
+// (map_clear_scratch: the flags, one per slot of the LIVE table, zeroed by the one memset, and S over them once they are dead) until
+// the memset that makes it a table.  The live table is only read; the builder's scratch is not touched.
 int map_clear_rays_on(madicp_ctx* ctx, DevMap* m, const DevCloud* c, const fe::RayFrame& F, int64_t watermark, int64_t* out_kept,
                       int64_t* out_watermark) {
   const int64_t M = m->rows;
   DevMap g = *m;
   RC_TRY(map_block_alloc(ctx, m->cap, &g, false));
-  uint32_t* flags = reinterpret_cast<uint32_t*>(g.block);
-  uint32_t* mark = flags + 2 * (size_t)m->cap;
-  const hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * 2 * (size_t)m->cap, ctx->copy);
+  const MapScratch W = map_clear_scratch((size_t)m->cap, (size_t)M, tb::kScanTile);
+  uint32_t* flags = reinterpret_cast<uint32_t*>(g.block + W.flags);
+  uint32_t* mark = reinterpret_cast<uint32_t*>(g.block + W.mark);
+  const hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t) * (size_t)m->slots, ctx->copy);
   if (e != hipSuccess) {
     hipFree(g.block);
     return fail(MADICP_ERR_DEVICE, std::string("voxel map clearing: ") + hipGetErrorString(e));
   }
   hipLaunchKernelGGL(fe::ray_flags, dim3(grid_256(ctx, 64 * c->n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)c->n, F, m->voxel,
-                     (const unsigned long long*)m->keys, m->slots, flags);
+                     (const unsigned long long*)m->keys(), m->slots, flags);
   if (m->with_ev)  // (the misses, in place on the live column: they hold whether or not a row leaves)
-    hipLaunchKernelGGL(fe::map_clear_mark_ev, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys,
-                       (long)M, (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, m->ev, m->ev_miss, mark);
+    hipLaunchKernelGGL(fe::map_clear_mark_ev, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys(),
+                       (long)M, (const unsigned long long*)m->keys(), m->slots, (const uint32_t*)flags, m->ev(), m->ev_miss, mark);
   else
-    hipLaunchKernelGGL(fe::map_clear_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys, (long)M,
-                       (const unsigned long long*)m->keys, m->slots, (const uint32_t*)flags, mark);
-  return map_remove_marked(ctx, m, g, mark, flags, mark + (M + 1), watermark, "voxel map clearing: ", out_kept, out_watermark);
+    hipLaunchKernelGGL(fe::map_clear_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys(), (long)M,
+                       (const unsigned long long*)m->keys(), m->slots, (const uint32_t*)flags, mark);
+  return map_remove_marked(ctx, m, g, W, watermark, "voxel map clearing: ", out_kept, out_watermark);
 }
 
+constexpr const char* kMapNoAttr = "the map was made without the attribute column (madicp_map_create_attr makes one with it)";
 constexpr const char* kMapLogFull = "the map's removal log holds max_rows entries or more (madicp_map_take_removed empties it)";
 constexpr const char* kMapNoMoments = "the map was made without the moments (madicp_map_create_mom makes one with them)";
 constexpr const char* kMapNoEvidence = "the map was made without the evidence column (madicp_map_create_ev makes one with it)";
@@ -1308,6 +1325,57 @@ int map_create_on(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t m
   const int id = ctx->next_id++;
   front_of(ctx).maps[id] = m;
   *out_map_id = id;
+  return MADICP_OK;
+}
+
+// What every window download starts with, in this order of refusals: a null argument (out: the one buffer the call cannot do
+// without), an unknown map, a column the map lacks (need; kColXyz: none), first_row outside [0, rows]; then *out_n is the window's
+// rows, and a buffer too small for them is refused with `short_buffer`, which names the caller's buffers.  *rows: what is left to
+// copy — 0: the call is over.
+int map_window(madicp_ctx* ctx, int map_id, MapColumn need, int64_t first_row, const void* out, int64_t capacity_rows, const char* short_buffer,
+               int64_t* out_n, DevMap** m, int64_t* rows) {
+  *rows = 0;
+  if (!ctx || !out || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
+  *m = find_map(ctx, map_id);
+  if (!*m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  if (!(*m)->col[need]) return fail(MADICP_ERR_INVALID, need == kColAttr ? kMapNoAttr : need == kColEv ? kMapNoEvidence : kMapNoMoments);
+  if (first_row < 0 || first_row > (*m)->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
+  *out_n = (*m)->rows - first_row;
+  if (capacity_rows < *out_n) return fail(MADICP_ERR_CAPACITY, short_buffer);
+  if (*out_n > 0) HIP_TRY(hipSetDevice(ctx->device));
+  *rows = *out_n;
+  return MADICP_OK;
+}
+// ... and a download of the map's own columns is: the window's rows of every column `out` asks for
+int map_download(madicp_ctx* ctx, int map_id, MapColumn need, int64_t first_row, const void* must, const MapCols& out, int64_t capacity_rows,
+                 const char* short_buffer, int64_t* out_n) {
+  DevMap* m = nullptr;
+  int64_t rows = 0;
+  RC_TRY(map_window(ctx, map_id, need, first_row, must, capacity_rows, short_buffer, out_n, &m, &rows));
+  return rows == 0 ? MADICP_OK : map_rows_out(ctx, *m, out, first_row, rows, "voxel map download: ");
+}
+
+// What madicp_map_prune and madicp_map_clear_rays share around `remove`, the one that makes its marks (map_prune_on /
+// map_clear_rays_on behind the caller's arguments): the refusals, the log's memory in front of it, the log's length behind it, the
+// three answers.  run: false where nothing can leave — nothing is launched
+template <class Remove>
+int map_removal(madicp_ctx* ctx, DevMap* m, bool run, int64_t watermark, Remove remove, int64_t* out_removed, int64_t* out_rows,
+                int64_t* out_watermark) {
+  if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
+  if (m->track && m->log_n >= m->max_rows) return fail(MADICP_ERR_CAPACITY, kMapLogFull);
+  const int64_t before = m->rows;
+  int64_t kept = before, mark = watermark;
+  if (run) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    char* old_log = nullptr;
+    if (m->track && watermark > 0) RC_TRY(map_log_reserve(ctx, m, m->log_n + watermark, &old_log));
+    const int rc = remove(&kept, &mark);
+    map_log_settle(ctx, m, old_log, rc, watermark - mark);
+    RC_TRY(rc);
+  }
+  *out_removed = before - kept;
+  *out_rows = kept;
+  *out_watermark = mark;
   return MADICP_OK;
 }
 }  // namespace
@@ -1351,14 +1419,14 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
   RC_TRY(ensure_scratch(ctx, n, &fs));
   if (m->rows + n > m->cap) RC_TRY(map_grow(ctx, m, m->rows + n));
   int64_t added = 0;
-  const FoldMoments Mo{m->mom, m->closed_at, m->slot_row, m->ordinal, m->mom_max_count};
+  const FoldMoments Mo{m->mom(), m->closed_at(), m->slot_row(), m->ordinal, m->mom_max_count};
   FoldEvidence E{};
   if (m->with_ev) {
     if (m->fold_no == fe::kMapNever) HIP_TRY(map_stamp_wipe(ctx, m));  // (2^32 - 1 folds without a removal or a growth)
-    E = FoldEvidence{m->ev, m->slot_row, m->stamp, m->fold_no++, m->ev_hit, m->ev_cap};
+    E = FoldEvidence{m->ev(), m->slot_row(), m->stamp(), m->fold_no++, m->ev_hit, m->ev_cap};
   }
-  RC_TRY(voxel_fold(ctx, fs, c, export_pose(R, t), m->voxel, VoxelTable{m->keys, m->owner, m->slots}, true, m->xyz, m->rows, m->row_keys,
-                    m->attr, &added, m->with_ev ? &E : nullptr, m->with_mom ? &Mo : nullptr));
+  RC_TRY(voxel_fold(ctx, fs, c, export_pose(R, t), m->voxel, VoxelTable{m->keys(), m->owner(), m->slots}, true, m->xyz(), m->rows,
+                    m->row_keys(), m->attr(), &added, m->with_ev ? &E : nullptr, m->with_mom ? &Mo : nullptr));
   if (m->with_mom) ++m->ordinal;
   m->rows += added;
   *out_added = added;
@@ -1374,107 +1442,31 @@ int madicp_map_size(madicp_ctx* ctx, int map_id, int64_t* out_rows) {
   return MADICP_OK;
 }
 
+// the window downloads: map_window's prologue, the copies in front of ONE wait (map_rows_out)
 int madicp_map_download_f32(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_xyz holds fewer rows than the window has (*out_n)");
-  if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMemcpyAsync(out_xyz, m->xyz + 3 * first_row, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));
-  return MADICP_OK;
+  return map_download(ctx, map_id, kColXyz, first_row, out_xyz, map_out(out_xyz, nullptr, nullptr), capacity_rows,
+                      "out_xyz holds fewer rows than the window has (*out_n)", out_n);
 }
-
 int madicp_map_download_attr(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out_attr || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (!m->with_attr) return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_attr holds fewer rows than the window has (*out_n)");
-  if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMemcpyAsync(out_attr, m->attr + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));
-  return MADICP_OK;
+  return map_download(ctx, map_id, kColAttr, first_row, out_attr, map_out(nullptr, nullptr, out_attr), capacity_rows,
+                      "out_attr holds fewer rows than the window has (*out_n)", out_n);
 }
-
 int madicp_map_download_keys(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out_keys, int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out_keys || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_keys holds fewer rows than the window has (*out_n)");
-  if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMemcpyAsync(out_keys, m->row_keys + first_row, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));
-  return MADICP_OK;
+  return map_download(ctx, map_id, kColXyz, first_row, out_keys, map_out(nullptr, out_keys, nullptr), capacity_rows,
+                      "out_keys holds fewer rows than the window has (*out_n)", out_n);
 }
-
-// the columns of a window of rows with their copies in front of ONE wait (each of the single-column downloads above has its own)
 int madicp_map_download_rows(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
                              int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out_xyz || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (out_attr && !m->with_attr)
-    return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "the buffers hold fewer rows than the window has (*out_n)");
-  if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipError_t e = hipMemcpyAsync(out_xyz, m->xyz + 3 * first_row, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess && out_keys)
-    e = hipMemcpyAsync(out_keys, m->row_keys + first_row, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess && out_attr)
-    e = hipMemcpyAsync(out_attr, m->attr + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-  const hipError_t w = hipStreamSynchronize(ctx->copy);
-  if (e == hipSuccess) e = w;
-  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map download: ") + hipGetErrorString(e));
-  return MADICP_OK;
+  return map_download(ctx, map_id, out_attr ? kColAttr : kColXyz, first_row, out_xyz, map_out(out_xyz, out_keys, out_attr), capacity_rows,
+                      "the buffers hold fewer rows than the window has (*out_n)", out_n);
 }
-
 int madicp_map_download_evidence(madicp_ctx* ctx, int map_id, int64_t first_row, uint32_t* out_ev, int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out_ev || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (!m->with_ev) return fail(MADICP_ERR_INVALID, kMapNoEvidence);
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out_ev holds fewer rows than the window has (*out_n)");
-  if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMemcpyAsync(out_ev, m->ev + first_row, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));
-  return MADICP_OK;
+  return map_download(ctx, map_id, kColEv, first_row, out_ev, map_out(nullptr, nullptr, nullptr, out_ev), capacity_rows,
+                      "out_ev holds fewer rows than the window has (*out_n)", out_n);
 }
-
 int madicp_map_download_moments(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (!m->with_mom) return fail(MADICP_ERR_INVALID, kMapNoMoments);
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "out holds fewer rows than the window has (*out_n)");
-  if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipMemcpyAsync(out, m->mom + madicp_host::kMomentWords * first_row, 80 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy));
-  HIP_TRY(hipStreamSynchronize(ctx->copy));
-  return MADICP_OK;
+  return map_download(ctx, map_id, kColMom, first_row, out, map_out(nullptr, nullptr, nullptr, nullptr, out), capacity_rows,
+                      "out holds fewer rows than the window has (*out_n)", out_n);
 }
 
 // The surfels of rows [first_row, M): fe::map_surfels, one lane per row, into a transient block of the call's own
@@ -1482,16 +1474,11 @@ int madicp_map_download_moments(madicp_ctx* ctx, int map_id, int64_t first_row, 
 // then the copies of what the caller asked for in ONE chain behind the kernel, ONE wait.
 int madicp_map_download_surfels(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
                                 uint32_t* out_count, int64_t capacity_rows, int64_t* out_n) {
-  if (!ctx || !out_centroid || !out_n) return fail(MADICP_ERR_INVALID, "null argument");
-  DevMap* m = find_map(ctx, map_id);
-  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
-  if (!m->with_mom) return fail(MADICP_ERR_INVALID, kMapNoMoments);
-  if (first_row < 0 || first_row > m->rows) return fail(MADICP_ERR_INVALID, "first_row outside [0, rows]");
-  const int64_t rows = m->rows - first_row;
-  *out_n = rows;
-  if (capacity_rows < rows) return fail(MADICP_ERR_CAPACITY, "the buffers hold fewer rows than the window has (*out_n)");
+  DevMap* m = nullptr;
+  int64_t rows = 0;
+  RC_TRY(map_window(ctx, map_id, kColMom, first_row, out_centroid, capacity_rows, "the buffers hold fewer rows than the window has (*out_n)",
+                    out_n, &m, &rows));
   if (rows == 0) return MADICP_OK;
-  HIP_TRY(hipSetDevice(ctx->device));
   const size_t R = (size_t)rows;
   char* block = nullptr;
   HIP_TRY(hipMalloc(&block, 40 * R));
@@ -1499,23 +1486,16 @@ int madicp_map_download_surfels(madicp_ctx* ctx, int map_id, int64_t first_row, 
   float* d_normal = d_centroid + 3 * R;
   float* d_eig = d_normal + 3 * R;
   uint32_t* d_count = reinterpret_cast<uint32_t*>(d_eig + 3 * R);
-  hipLaunchKernelGGL(fe::map_surfels, dim3(grid_256(ctx, rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->mom,
-                     (const unsigned long long*)m->row_keys, (long)first_row, (long)m->rows, m->voxel, d_centroid, d_normal, d_eig, d_count);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out_centroid, d_centroid, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess && out_normal) e = hipMemcpyAsync(out_normal, d_normal, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess && out_eig) e = hipMemcpyAsync(out_eig, d_eig, sizeof(float) * 3 * R, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess && out_count) e = hipMemcpyAsync(out_count, d_count, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, ctx->copy);
-  const hipError_t w = hipStreamSynchronize(ctx->copy);
-  if (e == hipSuccess) e = w;
+  hipLaunchKernelGGL(fe::map_surfels, dim3(grid_256(ctx, rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->mom(),
+                     (const unsigned long long*)m->row_keys(), (long)first_row, (long)m->rows, m->voxel, d_centroid, d_normal, d_eig, d_count);
+  const CopyOut outs[] = {{out_centroid, d_centroid, 12 * R}, {out_normal, d_normal, 12 * R}, {out_eig, d_eig, 12 * R}, {out_count, d_count, 4 * R}};
+  const int rc = copies_then_wait(ctx, hipGetLastError(), outs, 4, "voxel map surfel download: ");
   hipFree(block);
-  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map surfel download: ") + hipGetErrorString(e));
-  return MADICP_OK;
+  return rc;
 }
 
 // The rows whose word is at least min_e, compacted on the device into a transient block of the call's own (the builder's scratch
-// is sized by the largest CLOUD and may be a look-ahead's):
-//   keys (M x 8) | xyz (M x 12) | attr (M x 4) | ev (M x 4) | mark (M + 1) | S (M + 1) | tile_sums (tiles) | the scan's total (1)
+// is sized by the largest CLOUD and may be a look-ahead's): M entries of keys | xyz | attr | ev, and behind them a prune's scratch.
 // fe::map_ev_mark, the tile scan, and map_compact as the one gather (watermark 0: it leaves the count over the first mark).  Two
 // waits: the count — which decides whether the caller's buffers are large enough — then the rows.
 int madicp_map_download_min_evidence(madicp_ctx* ctx, int map_id, uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr,
@@ -1524,54 +1504,38 @@ int madicp_map_download_min_evidence(madicp_ctx* ctx, int map_id, uint32_t min_e
   DevMap* m = find_map(ctx, map_id);
   if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
   if (!m->with_ev) return fail(MADICP_ERR_INVALID, kMapNoEvidence);
-  if (out_attr && !m->with_attr)
-    return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
+  if (out_attr && !m->with_attr) return fail(MADICP_ERR_INVALID, kMapNoAttr);
   const int64_t M = m->rows;
   *out_n = 0;
   if (M == 0) return MADICP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  const size_t Ms = (size_t)M;
-  const int tiles = static_cast<int>((M + 1 + tb::kScanTile - 1) / tb::kScanTile);
+  const MapLayout L = map_layout_of((size_t)M, 0, map_bit(kColRowKeys) | map_bit(kColXyz) | map_bit(kColAttr) | map_bit(kColEv));
+  const MapScratch W = map_prune_scratch((size_t)M, (size_t)M, tb::kScanTile);
   char* block = nullptr;
-  HIP_TRY(hipMalloc(&block, 28 * Ms + 8 * (Ms + 1) + 4 * ((size_t)tiles + 1)));
-  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(block);
-  float* d_xyz = reinterpret_cast<float*>(block + 8 * Ms);
-  uint32_t* d_attr = reinterpret_cast<uint32_t*>(block + 20 * Ms);
-  uint32_t* d_ev = d_attr + Ms;
-  uint32_t* mark = d_ev + Ms;
-  uint32_t* S = mark + (Ms + 1);
-  uint32_t* tile_sums = S + (Ms + 1);
-  int32_t* total = reinterpret_cast<int32_t*>(tile_sums + tiles);
-  hipLaunchKernelGGL(fe::map_ev_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)m->ev, (long)M, min_e, mark);
-  hipLaunchKernelGGL(tb::tb_scan_tiles, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, tile_sums);
-  hipLaunchKernelGGL(tb::tb_scan_top, dim3(1), dim3(256), 0, ctx->copy, tile_sums, tiles, total);
-  hipLaunchKernelGGL(tb::tb_scan_apply, dim3(tiles), dim3(256), 0, ctx->copy, (const uint32_t*)mark, (int)M, (const uint32_t*)tile_sums, S);
-  hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, 0L,
-                     (const unsigned long long*)m->row_keys, (const float*)m->xyz, (const uint32_t*)m->attr, d_keys, d_xyz, d_attr, mark,
-                     (const uint32_t*)m->ev, d_ev, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr,
-                     (uint32_t*)nullptr);
+  HIP_TRY(hipMalloc(&block, L.bytes + W.bytes));
+  MapCols found;  // (no moments: the gather leaves them where they are)
+  found.point(block, L);
+  uint32_t* mark = reinterpret_cast<uint32_t*>(block + L.bytes + W.mark);
+  uint32_t* S = reinterpret_cast<uint32_t*>(block + L.bytes + W.S);
+  fe::MapRows in = m->moving();
+  in.mom = nullptr;
+  hipLaunchKernelGGL(fe::map_ev_mark, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)m->ev(), (long)M, min_e, mark);
+  hipError_t e = scan_marks(ctx->copy, mark, M, S, reinterpret_cast<uint32_t*>(block + L.bytes + W.tile_sums),
+                            reinterpret_cast<int32_t*>(block + L.bytes + W.total));
+  hipLaunchKernelGGL(fe::map_compact, dim3(grid_256(ctx, M + 1)), dim3(256), 0, ctx->copy, (const uint32_t*)S, (long)M, 0L, in, found.moving(),
+                     mark);
   uint32_t res[2] = {0, 0};
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(res, mark, sizeof(res), hipMemcpyDeviceToHost, ctx->copy);
-  hipError_t w = hipStreamSynchronize(ctx->copy);  // the count
-  if (e == hipSuccess) e = w;
-  const int64_t rows = res[0];
-  int rc = MADICP_OK;
-  if (e == hipSuccess) {
-    *out_n = rows;
-    if (capacity_rows < rows) {
+  if (e == hipSuccess) e = hipGetLastError();
+  const CopyOut count{res, mark, sizeof(res)};
+  int rc = copies_then_wait(ctx, e, &count, 1, "voxel map evidence download: ");  // the count
+  if (rc == MADICP_OK) {
+    *out_n = res[0];
+    if (capacity_rows < *out_n)
       rc = fail(MADICP_ERR_CAPACITY, "the buffers hold fewer rows than qualify (*out_n)");
-    } else if (rows > 0) {
-      e = hipMemcpyAsync(out_xyz, d_xyz, sizeof(float) * 3 * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-      if (e == hipSuccess && out_keys) e = hipMemcpyAsync(out_keys, d_keys, sizeof(uint64_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-      if (e == hipSuccess && out_attr) e = hipMemcpyAsync(out_attr, d_attr, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-      if (e == hipSuccess && out_ev) e = hipMemcpyAsync(out_ev, d_ev, sizeof(uint32_t) * (size_t)rows, hipMemcpyDeviceToHost, ctx->copy);
-      w = hipStreamSynchronize(ctx->copy);  // the rows
-      if (e == hipSuccess) e = w;
-    }
+    else if (*out_n > 0)  // the rows
+      rc = map_rows_out(ctx, found, map_out(out_xyz, out_keys, out_attr, out_ev), 0, *out_n, "voxel map evidence download: ");
   }
   hipFree(block);
-  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map evidence download: ") + hipGetErrorString(e));
   return rc;
 }
 
@@ -1584,6 +1548,7 @@ int madicp_map_track_removed(madicp_ctx* ctx, int map_id, int on) {
     HIP_TRY(hipSetDevice(ctx->device));
     hipFree(m->log_block);
     m->log_block = nullptr;
+    m->log = MapCols{};
     m->log_cap = 0;
   }
   if (!m->track) m->log_n = 0;
@@ -1604,19 +1569,13 @@ int madicp_map_take_removed(madicp_ctx* ctx, int map_id, uint64_t* out_keys, flo
   DevMap* m = find_map(ctx, map_id);
   if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
   if (!m->track) return fail(MADICP_ERR_INVALID, "the map does not track removals (madicp_map_track_removed)");
-  if (out_attr && !m->with_attr)
-    return fail(MADICP_ERR_INVALID, "the map was made without the attribute column (madicp_map_create_attr makes one with it)");
+  if (out_attr && !m->with_attr) return fail(MADICP_ERR_INVALID, kMapNoAttr);
   const int64_t n = m->log_n;
   *out_n = n;
   if (capacity < n) return fail(MADICP_ERR_CAPACITY, "the buffers hold fewer entries than the removal log has (*out_n)");
   if (n == 0) return MADICP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
-  hipError_t e = hipMemcpyAsync(out_keys, m->log_keys(), sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_xyz, m->log_xyz(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, ctx->copy);
-  if (e == hipSuccess && out_attr) e = hipMemcpyAsync(out_attr, m->log_attr(), sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->copy);
-  const hipError_t w = hipStreamSynchronize(ctx->copy);
-  if (e == hipSuccess) e = w;
-  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map removal log: ") + hipGetErrorString(e));
+  RC_TRY(map_rows_out(ctx, m->log, map_out(out_xyz, out_keys, out_attr), 0, n, "voxel map removal log: "));
   m->log_n = 0;  // (the memory is kept)
   return MADICP_OK;
 }
@@ -1627,25 +1586,12 @@ int madicp_map_prune(madicp_ctx* ctx, int map_id, const double center[3], double
   DevMap* m = find_map(ctx, map_id);
   if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
   if (const char* why = madicp_host::map_prune_refusal(center, radius)) return fail(MADICP_ERR_INVALID, why);
-  if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
-  if (m->track && m->log_n >= m->max_rows) return fail(MADICP_ERR_CAPACITY, kMapLogFull);
-  const int64_t before = m->rows;
-  int64_t kept = 0, mark = 0;
-  if (before > 0) {
-    HIP_TRY(hipSetDevice(ctx->device));
-    fe::PruneSphere Q;
-    std::memcpy(Q.c, center, sizeof(Q.c));
-    Q.r2 = radius * radius;
-    char* old_log = nullptr;
-    if (m->track && watermark > 0) RC_TRY(map_log_reserve(ctx, m, m->log_n + watermark, &old_log));
-    const int rc = map_prune_on(ctx, m, Q, watermark, &kept, &mark);
-    map_log_settle(ctx, m, old_log, rc, watermark - mark);
-    RC_TRY(rc);
-  }
-  *out_removed = before - kept;
-  *out_rows = kept;
-  *out_watermark = mark;
-  return MADICP_OK;
+  fe::PruneSphere Q;
+  std::memcpy(Q.c, center, sizeof(Q.c));
+  Q.r2 = radius * radius;
+  return map_removal(
+      ctx, m, m->rows > 0, watermark, [&](int64_t* kept, int64_t* mark) { return map_prune_on(ctx, m, Q, watermark, kept, mark); }, out_removed,
+      out_rows, out_watermark);
 }
 
 int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], const double origin[3],
@@ -1656,26 +1602,13 @@ int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const doubl
   DevCloud* c = find_cloud(ctx, cloud_id);
   if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
   if (const char* why = madicp_host::map_clear_refusal(R, t, origin, margin)) return fail(MADICP_ERR_INVALID, why);
-  if (watermark < 0 || watermark > m->rows) return fail(MADICP_ERR_INVALID, "watermark outside [0, rows]");
-  if (m->track && m->log_n >= m->max_rows) return fail(MADICP_ERR_CAPACITY, kMapLogFull);
-  const int64_t before = m->rows;
-  int64_t kept = before, mark = watermark;
-  if (before > 0 && c->n > 0) {  // (an empty map or an empty cloud: nothing can leave, nothing is launched)
-    HIP_TRY(hipSetDevice(ctx->device));
-    fe::RayFrame F;
-    F.X = export_pose(R, t);
-    std::memcpy(F.o, origin, sizeof(F.o));
-    F.margin = margin;
-    char* old_log = nullptr;
-    if (m->track && watermark > 0) RC_TRY(map_log_reserve(ctx, m, m->log_n + watermark, &old_log));
-    const int rc = map_clear_rays_on(ctx, m, c, F, watermark, &kept, &mark);
-    map_log_settle(ctx, m, old_log, rc, watermark - mark);
-    RC_TRY(rc);
-  }
-  *out_removed = before - kept;
-  *out_rows = kept;
-  *out_watermark = mark;
-  return MADICP_OK;
+  fe::RayFrame F;
+  F.X = export_pose(R, t);
+  std::memcpy(F.o, origin, sizeof(F.o));
+  F.margin = margin;
+  return map_removal(  // (an empty map or an empty cloud: nothing can leave, nothing is launched)
+      ctx, m, m->rows > 0 && c->n > 0, watermark, [&](int64_t* kept, int64_t* mark) { return map_clear_rays_on(ctx, m, c, F, watermark, kept, mark); },
+      out_removed, out_rows, out_watermark);
 }
 
 int madicp_map_clear(madicp_ctx* ctx, int map_id) {
@@ -1779,7 +1712,7 @@ int tb_summary_wait(madicp_ctx* ctx, FrontScratch& fs, int next_step) {
     return MADICP_OK;
   }
   // huge clouds: three-kernel scan, summary, the State copied back
-  RC_TRY(scan_marks(f.s, fs, f.P.leaf_start, f.n, &f.P.st->n_leaves));
+  HIP_TRY(scan_marks(f.s, f.P.leaf_start, f.n, fs.S, fs.tile_sums, &f.P.st->n_leaves));
   hipLaunchKernelGGL(tb::tb_summary, dim3(64), dim3(256), 0, f.s, f.P, kTopLevels);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(fs.h_state, f.P.st, sizeof(tb::State), hipMemcpyDeviceToHost, f.s));

@@ -10,6 +10,7 @@
 #include "madicp_hip_measure.h"
 #include "kernels.hip.h"
 #include "frontend.hip.h"  // + tree_build.hip.h: device front-end
+#include "../common/map_layout.h"  // the voxel map's columns and block layout (frontend_capi.inc.h)
 #include "../common/seq_wait.h"
 
 #include <hip/hip_ext.h>

@@ -508,27 +508,74 @@ size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr, uin
   return got;
 }
 
-size_t Pipeline::mapKeys(uint64_t* out, size_t capacity, size_t first_row) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapKeys: setMapAccumulation(voxel_size > 0) first");
-  if (!out) throw std::invalid_argument("Pipeline::mapKeys: null buffer");
+// ---- the window downloads (pipeline.h: mapCloud .. mapSurfels) ------------------------------------------------------------------
+template <class Host, class Dev>
+size_t Pipeline::mapWindow(const char* name, const char* missing, const void* out, const char* holds, size_t capacity, size_t first_row,
+                           const char* entry, Host host, Dev dev) {
+  const std::string who = std::string("Pipeline::") + name + ": ";
+  if (map_voxel_ == 0.0) throw std::logic_error(who + "setMapAccumulation(voxel_size > 0) first");
+  if (missing) throw std::logic_error(who + missing);
+  if (!out) throw std::invalid_argument(who + "null buffer");
   const size_t size = mapSize();
-  if (first_row > size) throw std::invalid_argument("Pipeline::mapKeys: first_row is beyond the map's " + std::to_string(size) + " rows");
+  if (first_row > size) throw std::invalid_argument(who + "first_row is beyond the map's " + std::to_string(size) + " rows");
   if (capacity < size - first_row)
-    throw std::invalid_argument("Pipeline::mapKeys: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
-                                std::to_string(size - first_row));
+    throw std::invalid_argument(who + holds + " " + std::to_string(capacity) + " rows, the window needs " + std::to_string(size - first_row));
   if (size == first_row) return 0;
+  const int64_t first = static_cast<int64_t>(first_row), cap = static_cast<int64_t>(capacity);
   int64_t rows = 0;
   if (map_host_) {
-    if (map_host_->download_keys(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
-      throw std::runtime_error("Pipeline::mapKeys: the host voxel map refused its arguments");
+    if (host(*map_host_, first, cap, &rows) != MADICP_OK) throw std::runtime_error(who + "the host voxel map refused its arguments");
   } else {
     DeviceLock lock(Device::mutex());
     madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapKeys: the device context the map lived in is gone");
-    check(madicp_map_download_keys(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
-          "madicp_map_download_keys");
+    if (!ctx) throw std::logic_error(who + "the device context the map lived in is gone");
+    check(dev(ctx, first, cap, &rows), entry);
   }
   return static_cast<size_t>(rows);
+}
+namespace {
+constexpr const char* kNoMapAttr = "the map was made without the attribute (setMapAccumulation's with_attribute)";
+constexpr const char* kNoMapEvidence = "the map was made without evidence (setMapAccumulation's evidence)";
+constexpr const char* kNoMapMoments = "the map was made without moments (setMapAccumulation's moments_max_count)";
+}  // namespace
+
+size_t Pipeline::mapKeys(uint64_t* out, size_t capacity, size_t first_row) {
+  return mapWindow(
+      "mapKeys", nullptr, out, "the buffer holds", capacity, first_row, "madicp_map_download_keys",
+      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_keys(first, out, cap, n); },
+      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_keys(ctx, map_id_, first, out, cap, n); });
+}
+size_t Pipeline::mapCloud(float* out, size_t capacity, size_t first_row) {
+  return mapWindow(
+      "mapCloud", nullptr, out, "the buffer holds", capacity, first_row, "madicp_map_download_f32",
+      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download(first, out, cap, n); },
+      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_f32(ctx, map_id_, first, out, cap, n); });
+}
+size_t Pipeline::mapAttribute(uint32_t* out, size_t capacity, size_t first_row) {
+  return mapWindow(
+      "mapAttribute", map_with_attr_ ? nullptr : kNoMapAttr, out, "the buffer holds", capacity, first_row, "madicp_map_download_attr",
+      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_attr(first, out, cap, n); },
+      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_attr(ctx, map_id_, first, out, cap, n); });
+}
+size_t Pipeline::mapEvidence(uint32_t* out, size_t capacity, size_t first_row) {
+  return mapWindow(
+      "mapEvidence", map_with_ev_ ? nullptr : kNoMapEvidence, out, "the buffer holds", capacity, first_row, "madicp_map_download_evidence",
+      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_evidence(first, out, cap, n); },
+      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_evidence(ctx, map_id_, first, out, cap, n); });
+}
+size_t Pipeline::mapMoments(uint64_t* out, size_t capacity, size_t first_row) {
+  return mapWindow(
+      "mapMoments", map_mom_ ? nullptr : kNoMapMoments, out, "the buffer holds", capacity, first_row, "madicp_map_download_moments",
+      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_moments(first, out, cap, n); },
+      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_moments(ctx, map_id_, first, out, cap, n); });
+}
+size_t Pipeline::mapSurfels(float* centroid, float* normal, float* eig, uint32_t* count, size_t capacity, size_t first_row) {
+  return mapWindow(
+      "mapSurfels", map_mom_ ? nullptr : kNoMapMoments, centroid, "the buffers hold", capacity, first_row, "madicp_map_download_surfels",
+      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_surfels(first, centroid, normal, eig, count, cap, n); },
+      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) {
+        return madicp_map_download_surfels(ctx, map_id_, first, centroid, normal, eig, count, cap, n);
+      });
 }
 
 // ---- the removal log (pipeline.h: setMapTrackRemoved) -------------------------------------------------------------------------
@@ -591,127 +638,6 @@ size_t Pipeline::mapSize() {
   if (!ctx) throw std::logic_error("Pipeline::mapSize: the device context the map lived in is gone");
   int64_t rows = 0;
   check(madicp_map_size(ctx, map_id_, &rows), "madicp_map_size");
-  return static_cast<size_t>(rows);
-}
-
-size_t Pipeline::mapCloud(float* out, size_t capacity, size_t first_row) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapCloud: setMapAccumulation(voxel_size > 0) first");
-  if (!out) throw std::invalid_argument("Pipeline::mapCloud: null buffer");
-  const size_t size = mapSize();
-  if (first_row > size) throw std::invalid_argument("Pipeline::mapCloud: first_row is beyond the map's " + std::to_string(size) + " rows");
-  if (capacity < size - first_row)
-    throw std::invalid_argument("Pipeline::mapCloud: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
-                                std::to_string(size - first_row));
-  if (size == first_row) return 0;
-  int64_t rows = 0;
-  if (map_host_) {
-    if (map_host_->download(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
-      throw std::runtime_error("Pipeline::mapCloud: the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapCloud: the device context the map lived in is gone");
-    check(madicp_map_download_f32(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
-          "madicp_map_download_f32");
-  }
-  return static_cast<size_t>(rows);
-}
-
-size_t Pipeline::mapAttribute(uint32_t* out, size_t capacity, size_t first_row) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapAttribute: setMapAccumulation(voxel_size > 0) first");
-  if (!map_with_attr_) throw std::logic_error("Pipeline::mapAttribute: the map was made without the attribute (setMapAccumulation's with_attribute)");
-  if (!out) throw std::invalid_argument("Pipeline::mapAttribute: null buffer");
-  const size_t size = mapSize();
-  if (first_row > size) throw std::invalid_argument("Pipeline::mapAttribute: first_row is beyond the map's " + std::to_string(size) + " rows");
-  if (capacity < size - first_row)
-    throw std::invalid_argument("Pipeline::mapAttribute: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
-                                std::to_string(size - first_row));
-  if (size == first_row) return 0;
-  int64_t rows = 0;
-  if (map_host_) {
-    if (map_host_->download_attr(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
-      throw std::runtime_error("Pipeline::mapAttribute: the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapAttribute: the device context the map lived in is gone");
-    check(madicp_map_download_attr(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
-          "madicp_map_download_attr");
-  }
-  return static_cast<size_t>(rows);
-}
-
-size_t Pipeline::mapEvidence(uint32_t* out, size_t capacity, size_t first_row) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapEvidence: setMapAccumulation(voxel_size > 0) first");
-  if (!map_with_ev_) throw std::logic_error("Pipeline::mapEvidence: the map was made without evidence (setMapAccumulation's evidence)");
-  if (!out) throw std::invalid_argument("Pipeline::mapEvidence: null buffer");
-  const size_t size = mapSize();
-  if (first_row > size) throw std::invalid_argument("Pipeline::mapEvidence: first_row is beyond the map's " + std::to_string(size) + " rows");
-  if (capacity < size - first_row)
-    throw std::invalid_argument("Pipeline::mapEvidence: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
-                                std::to_string(size - first_row));
-  if (size == first_row) return 0;
-  int64_t rows = 0;
-  if (map_host_) {
-    if (map_host_->download_evidence(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
-      throw std::runtime_error("Pipeline::mapEvidence: the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapEvidence: the device context the map lived in is gone");
-    check(madicp_map_download_evidence(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
-          "madicp_map_download_evidence");
-  }
-  return static_cast<size_t>(rows);
-}
-
-size_t Pipeline::mapMoments(uint64_t* out, size_t capacity, size_t first_row) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapMoments: setMapAccumulation(voxel_size > 0) first");
-  if (map_mom_ == 0) throw std::logic_error("Pipeline::mapMoments: the map was made without moments (setMapAccumulation's moments_max_count)");
-  if (!out) throw std::invalid_argument("Pipeline::mapMoments: null buffer");
-  const size_t size = mapSize();
-  if (first_row > size) throw std::invalid_argument("Pipeline::mapMoments: first_row is beyond the map's " + std::to_string(size) + " rows");
-  if (capacity < size - first_row)
-    throw std::invalid_argument("Pipeline::mapMoments: the buffer holds " + std::to_string(capacity) + " rows, the window needs " +
-                                std::to_string(size - first_row));
-  if (size == first_row) return 0;
-  int64_t rows = 0;
-  if (map_host_) {
-    if (map_host_->download_moments(static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
-      throw std::runtime_error("Pipeline::mapMoments: the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapMoments: the device context the map lived in is gone");
-    check(madicp_map_download_moments(ctx, map_id_, static_cast<int64_t>(first_row), out, static_cast<int64_t>(capacity), &rows),
-          "madicp_map_download_moments");
-  }
-  return static_cast<size_t>(rows);
-}
-
-size_t Pipeline::mapSurfels(float* centroid, float* normal, float* eig, uint32_t* count, size_t capacity, size_t first_row) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapSurfels: setMapAccumulation(voxel_size > 0) first");
-  if (map_mom_ == 0) throw std::logic_error("Pipeline::mapSurfels: the map was made without moments (setMapAccumulation's moments_max_count)");
-  if (!centroid) throw std::invalid_argument("Pipeline::mapSurfels: null buffer");
-  const size_t size = mapSize();
-  if (first_row > size) throw std::invalid_argument("Pipeline::mapSurfels: first_row is beyond the map's " + std::to_string(size) + " rows");
-  if (capacity < size - first_row)
-    throw std::invalid_argument("Pipeline::mapSurfels: the buffers hold " + std::to_string(capacity) + " rows, the window needs " +
-                                std::to_string(size - first_row));
-  if (size == first_row) return 0;
-  int64_t rows = 0;
-  if (map_host_) {
-    if (map_host_->download_surfels(static_cast<int64_t>(first_row), centroid, normal, eig, count, static_cast<int64_t>(capacity), &rows) !=
-        MADICP_OK)
-      throw std::runtime_error("Pipeline::mapSurfels: the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapSurfels: the device context the map lived in is gone");
-    check(madicp_map_download_surfels(ctx, map_id_, static_cast<int64_t>(first_row), centroid, normal, eig, count,
-                                      static_cast<int64_t>(capacity), &rows),
-          "madicp_map_download_surfels");
-  }
   return static_cast<size_t>(rows);
 }
 

@@ -433,6 +433,11 @@ class Pipeline {
   unsigned map_generation_ = 0;
   std::unique_ptr<VoxelMap> map_host_;
   void dropMap();
+  // (pipeline.cpp only) what mapCloud .. mapSurfels share: the refusals, in `name`'s name (missing: why the map lacks the column asked
+  // for, or null), then the rows of the window from the host twin (host) or the device map (dev, the C entry point `entry`)
+  template <class Host, class Dev>
+  size_t mapWindow(const char* name, const char* missing, const void* out, const char* holds, size_t capacity, size_t first_row,
+                   const char* entry, Host host, Dev dev);
   // setMapRange: the centre of the last prune and the position of the frame before this one (foldFrame's policy), the consumer's
   // cursor (mapNewRows) and the rows removed so far
   double map_range_ = 0.0;

@@ -92,57 +92,31 @@ class VoxelMap {
     return kMapOk;
   }
 
-  // include/madicp_host.h: madicp_host_map_download_f32 — rows [first_row, size())
+  // include/madicp_host.h: madicp_host_map_download_f32 / _attr / _keys / _evidence / _moments — rows [first_row, size()) of one
+  // column; invalid on a map without it
   int download(int64_t first_row, float* out, int64_t capacity_rows, int64_t* out_n) const {
-    if (!out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    if (m > 0) std::memcpy(out, rows_.data() + 3 * first_row, sizeof(float) * 3 * static_cast<size_t>(m));
-    return kMapOk;
+    return download_column(true, rows_, 3, first_row, out, capacity_rows, out_n);
   }
-  // include/madicp_host.h: madicp_host_map_download_attr — the words of rows [first_row, size()); invalid on a map without the column
   int download_attr(int64_t first_row, uint32_t* out, int64_t capacity_rows, int64_t* out_n) const {
-    if (!with_attr_ || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    if (m > 0) std::memcpy(out, attr_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
-    return kMapOk;
+    return download_column(with_attr_, attr_, 1, first_row, out, capacity_rows, out_n);
   }
-
-  // include/madicp_host.h: madicp_host_map_download_keys — the stored keys of rows [first_row, size())
   int download_keys(int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) const {
-    if (!out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    if (m > 0) std::memcpy(out, row_keys_.data() + first_row, sizeof(uint64_t) * static_cast<size_t>(m));
-    return kMapOk;
+    return download_column(true, row_keys_, 1, first_row, out, capacity_rows, out_n);
+  }
+  int download_evidence(int64_t first_row, uint32_t* out, int64_t capacity_rows, int64_t* out_n) const {
+    return download_column(with_ev_, ev_, 1, first_row, out, capacity_rows, out_n);
+  }
+  int download_moments(int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) const {  // as (rows, 10)
+    return download_column(with_mom_, mom_, kMomentWords, first_row, out, capacity_rows, out_n);
   }
   // include/madicp_host.h: madicp_host_map_download_rows — the columns of rows [first_row, size()): keys and words where asked for
   int download_rows(int64_t first_row, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) const {
-    if (!out_xyz || !out_n || first_row < 0 || first_row > size() || (out_attr && !with_attr_)) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    if (m == 0) return kMapOk;
-    std::memcpy(out_xyz, rows_.data() + 3 * first_row, sizeof(float) * 3 * static_cast<size_t>(m));
-    if (out_keys) std::memcpy(out_keys, row_keys_.data() + first_row, sizeof(uint64_t) * static_cast<size_t>(m));
-    if (out_attr) std::memcpy(out_attr, attr_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
-    return kMapOk;
+    const int rc = download_column(!out_attr || with_attr_, rows_, 3, first_row, out_xyz, capacity_rows, out_n);
+    if (rc == kMapOk && out_keys) copy_window(row_keys_, 1, first_row, *out_n, out_keys);
+    if (rc == kMapOk && out_attr) copy_window(attr_, 1, first_row, *out_n, out_attr);
+    return rc;
   }
 
-  // include/madicp_host.h: madicp_host_map_download_evidence — the evidence words of rows [first_row, size()); invalid on a map
-  // without the column
-  int download_evidence(int64_t first_row, uint32_t* out, int64_t capacity_rows, int64_t* out_n) const {
-    if (!with_ev_ || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    if (m > 0) std::memcpy(out, ev_.data() + first_row, sizeof(uint32_t) * static_cast<size_t>(m));
-    return kMapOk;
-  }
   // include/madicp_host.h: madicp_host_map_download_min_evidence — the rows whose word is >= min_e, in row order, with the columns
   // asked for; a short buffer is not written
   int download_min_evidence(uint32_t min_e, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, int64_t capacity_rows,
@@ -165,25 +139,12 @@ class VoxelMap {
     return kMapOk;
   }
 
-  // include/madicp_host.h: madicp_host_map_download_moments — the ten words of rows [first_row, size()) as (rows, 10); invalid on a
-  // map without moments
-  int download_moments(int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n) const {
-    if (!with_mom_ || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    if (m > 0) std::memcpy(out, mom_.data() + kMomentWords * first_row, sizeof(uint64_t) * kMomentWords * static_cast<size_t>(m));
-    return kMapOk;
-  }
   // include/madicp_host.h: madicp_host_map_download_surfels — map_surfel of rows [first_row, size()): centroid, and normal /
   // eigenvalues / count where asked for
   int download_surfels(int64_t first_row, float* out_centroid, float* out_normal, float* out_eig, uint32_t* out_count, int64_t capacity_rows,
                        int64_t* out_n) const {
-    if (!with_mom_ || !out_centroid || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
-    const int64_t m = size() - first_row;
-    *out_n = m;
-    if (capacity_rows < m) return kMapCapacity;
-    for (int64_t j = 0; j < m; ++j) {
+    const int rc = window(with_mom_, out_centroid, first_row, capacity_rows, out_n);
+    for (int64_t j = 0; rc == kMapOk && j < *out_n; ++j) {
       const int64_t r = first_row + j;
       float nrm[3], eig[3];
       uint32_t count;
@@ -194,7 +155,7 @@ class VoxelMap {
       }
       if (out_count) out_count[j] = count;
     }
-    return kMapOk;
+    return rc;
   }
 
   // include/madicp_host.h: madicp_host_map_track_removed / _removed_count / _take_removed — the removal log (madicp_hip.h has the
@@ -294,6 +255,24 @@ class VoxelMap {
   }
 
  private:
+  // what every window download starts with: the column is there (present), the buffers, first_row within [0, size()]; then *out_n
+  // = the window's rows, and a buffer too small for them
+  int window(bool present, const void* out, int64_t first_row, int64_t capacity_rows, int64_t* out_n) const {
+    if (!present || !out || !out_n || first_row < 0 || first_row > size()) return kMapInvalid;
+    *out_n = size() - first_row;
+    return capacity_rows < *out_n ? kMapCapacity : kMapOk;
+  }
+  template <class T>
+  static void copy_window(const std::vector<T>& col, int per_row, int64_t first_row, int64_t m, T* out) {
+    if (m > 0) std::memcpy(out, col.data() + per_row * first_row, sizeof(T) * per_row * static_cast<size_t>(m));
+  }
+  template <class T>
+  int download_column(bool present, const std::vector<T>& col, int per_row, int64_t first_row, T* out, int64_t capacity_rows, int64_t* out_n) const {
+    const int rc = window(present, out, first_row, capacity_rows, out_n);
+    if (rc == kMapOk) copy_window(col, per_row, first_row, *out_n, out);
+    return rc;
+  }
+
   // a removal on a tracking map whose log holds max_rows entries or more is refused: decided without looking at a row
   bool log_full() const { return track_ && removed_count() >= max_rows_; }
 
