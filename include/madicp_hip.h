@@ -579,8 +579,35 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                                 row, fp64) into a transient block: one kernel, one copy chain, ONE host synchronisation.  The same
  *                                 refusals.  Centroid and count are bit-equal to the host twin's; eigenvalues and normals go
  *                                 through atan2 / cos / sin and agree to the last bits only.
+ * QUERY.  Everything above writes the map or downloads it; madicp_map_query_cloud ASKS it, where it lives, what it holds at the
+ * points of a resident cloud: per point the nearest row of its voxel neighbourhood.  The rule (one source with the host twin:
+ * csrc/common/export_point.h — export_cells, query_cell_key, query_d2, query_before), fp64 and integers only, no library function,
+ * so every output is bit-equal between device, host twin and a numpy restatement:
+ *   point i goes through (R, t) by the export's position rule to q.  No candidate (a cell outside [-2^20, 2^20), NaN, infinite):
+ *   row -1, d2 +inf, key all ones, words 0.  Else its NEIGHBOURHOOD is the cells cell + o, o in {-reach .. reach}^3, reach 0 or 1;
+ *   a cell with an axis outside the key range is skipped, nothing wraps.  For every row j whose STORED key is the key of a cell of
+ *   the neighbourhood: dx = q[0] - (double)row[0] ..., d2 = dx dx + (dy dy + dz dz) — madicp_map_prune's association, from the
+ *   stored float row.  The answer is the row with the smallest (d2, j), lexicographically: a tie goes to the lower row index; no
+ *   such row: as for no candidate.  A minimum does not depend on the order of its arguments: the result is a function of (map,
+ *   cloud, pose, reach) alone, whatever the launch geometry.
+ *   out_row (int32), out_d2 (float64), out_keys (uint64: the matched row's stored key), out_attr, out_ev (its words): n entries
+ *   each, any of them null where not wanted — all five null is the SCORING form: only the counts come back.
+ *   out_counts[3] (always): the points that are candidates, those with row >= 0, and those of them with d2 <= max_dist max_dist
+ *   (the product in fp64; max_dist = +inf gives within == matched) — integer sums (per-wavefront ballots, integer atomics).
+ *   madicp_map_query_cloud   MADICP_ERR_INVALID, nothing written and nothing launched, for a null ctx, R, t or out_counts, an
+ *                            unknown id, a non-finite R or t, a reach other than 0 and 1, a max_dist that is NaN or negative, an
+ *                            out_attr on a map without the attribute column, an out_ev on a map without the evidence column;
+ *                            MADICP_ERR_CAPACITY, the same, when a per-point buffer is given and capacity_points < n.  An empty
+ *                            cloud answers 0, 0, 0 without a launch.  The map is only read: every column, the table, the removal
+ *                            log and every later answer are what they would be without the call.  Kernel: one lane per point, at reach 1
+ *                            the 27 cells one after the other (fe::map_query_lanes; a form with 32 lanes per point was built and
+ *                            measured slower, profiles/map_query_time.md); a
+ *                            map without the slot-to-row column (plain and attribute maps: their 44 / 48 bytes per row do not
+ *                            change) gets a transient one in the call's scratch first (fe::map_slot_rows, one lane per row).  The
+ *                            scratch is the call's own, pooled: the builder's is not touched (legal while a look-ahead build is in
+ *                            flight).  One host synchronisation, whatever n and M.
  * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes,
- * clearings and takes. */
+ * clearings, takes and queries. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
 int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int64_t* out_added,
                             int64_t* out_rows);
@@ -609,6 +636,9 @@ int madicp_map_create_mom(madicp_ctx* ctx, double voxel, int64_t initial_rows, i
 int madicp_map_download_moments(madicp_ctx* ctx, int map_id, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n);
 int madicp_map_download_surfels(madicp_ctx* ctx, int map_id, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
                                 uint32_t* out_count, int64_t capacity_rows, int64_t* out_n);
+int madicp_map_query_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int reach, double max_dist,
+                           int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
+                           int64_t capacity_points, uint64_t out_counts[3]);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

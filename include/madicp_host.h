@@ -156,7 +156,12 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *   _create_mom / _download_moments / _download_surfels
  *                  the twins of madicp_map_create_mom and its neighbours (madicp_hip.h and csrc/common/voxel_moments.h have the
  *                  rule): ten 64-bit moment words per row, max_count, the same refusals and codes.  Words, centroid and count are
- *                  bit-equal to the device's; eigenvalues and normals agree to the last bits (libm against the device library). */
+ *                  bit-equal to the device's; eigenvalues and normals agree to the last bits (libm against the device library).
+ *   _query         the twin of madicp_map_query_cloud (madicp_hip.h has the rule): for each of the n points of xyz taken through
+ *                  (R, t), the row with the smallest (d2, row) among the rows whose stored key is a cell of the point's
+ *                  neighbourhood (reach 0: its own cell, 1: the 27 around it); out_row / out_d2 / out_keys / out_attr / out_ev
+ *                  null where not wanted, out_counts = {candidates, matched, within max_dist}.  The map is only read.  The same
+ *                  refusals and codes, nothing written; xyz may be null when n == 0.  Every output bit-equal to the device's. */
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -189,6 +194,9 @@ int madicp_host_map_create_mom(double voxel, int64_t initial_rows, int64_t max_r
 int madicp_host_map_download_moments(const madicp_host_map* map, int64_t first_row, uint64_t* out, int64_t capacity_rows, int64_t* out_n);
 int madicp_host_map_download_surfels(const madicp_host_map* map, int64_t first_row, float* out_centroid, float* out_normal, float* out_eig,
                                      uint32_t* out_count, int64_t capacity_rows, int64_t* out_n);
+int madicp_host_map_query(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int reach,
+                          double max_dist, int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
+                          int64_t capacity_points, uint64_t out_counts[3]);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

@@ -178,6 +178,8 @@ def hip_lib():
         L.madicp_map_prune.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_map_clear_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
+        L.madicp_map_query_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p,
+                                             C.c_int64, _u64p]
         L.madicp_map_track_removed.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.madicp_map_removed_count.argtypes = [C.c_void_p, C.c_int, _i64p]
         L.madicp_map_take_removed.argtypes = [C.c_void_p, C.c_int, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
@@ -269,6 +271,8 @@ def host_lib():
         L.madicp_host_map_download_moments.argtypes = [C.c_void_p, C.c_int64, _u64p, C.c_int64, _i64p]
         L.madicp_host_map_download_surfels.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                        _u32p, C.c_int64, _i64p]
+        L.madicp_host_map_query.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p,
+                                            C.c_int64, _u64p]
         L.madicp_host_map_destroy.restype = None
         L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
@@ -695,6 +699,33 @@ def host_map_clear_rays(h, xyz, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, waterm
                                                           o.ctypes.data_as(_dp), float(margin), int(watermark), C.byref(removed),
                                                           C.byref(rows), C.byref(mark)), "madicp_host_map_clear_rays")
     return removed.value, rows.value, mark.value
+
+
+def _query_buffers(n, per_point, with_keys, with_attr, with_ev):
+    """the per-point buffers of a map query, in the C call's order (None: not asked for), and their ctypes arguments"""
+    m = max(n, 1)
+    bufs = [np.empty(m, np.int32) if per_point else None, np.empty(m, np.float64) if per_point else None,
+            np.empty(m, np.uint64) if with_keys else None, np.empty(m, np.uint32) if with_attr else None,
+            np.empty(m, np.uint32) if with_ev else None]
+    args = [b.ctypes.data_as(ct) if b is not None else None for b, ct in zip(bufs, (_i32p, _dp, _u64p, _u32p, _u32p))]
+    return bufs, args
+
+
+def _query_answer(counts, bufs, n, per_point):
+    c = tuple(int(v) for v in counts)
+    return (c,) + tuple(b[:n].copy() for b in bufs if b is not None) if per_point else c
+
+
+def host_map_query(h, xyz, R, t, reach=1, max_dist=float("inf"), per_point=True, with_keys=False, with_attr=False, with_ev=False):
+    """madicp_host_map_query: the host twin of Context.map_query over xyz (n, 3) float64, the same answer bit for bit."""
+    a = _f64(xyz).reshape(-1, 3)
+    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+    n = a.shape[0]
+    bufs, args = _query_buffers(n, per_point, with_keys, with_attr, with_ev)
+    counts = np.zeros(3, np.uint64)
+    _host_map_check(host_lib().madicp_host_map_query(h, a.ctypes.data_as(_dp), n, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), int(reach),
+                                                     float(max_dist), *args, n, counts.ctypes.data_as(_u64p)), "madicp_host_map_query")
+    return _query_answer(counts, bufs, n, per_point)
 
 
 def host_map_track_removed(h, on=True):
@@ -1188,6 +1219,20 @@ class Context:
                                                      eig.ctypes.data_as(fp), cnt.ctypes.data_as(_u32p), m, C.byref(got)))
         g = got.value
         return c[:g].copy(), nrm[:g].copy(), eig[:g].copy(), cnt[:g].copy()
+
+    def map_query(self, mid, cid, R, t, reach=1, max_dist=float("inf"), per_point=True, with_keys=False, with_attr=False, with_ev=False):
+        """madicp_map_query_cloud: for every point of resident cloud cid taken through (R (3, 3), t (3,)) the nearest map row of its
+        voxel neighbourhood (reach 0: its own voxel, 1: the 27 around it), found where the map lives; the map is only read.
+        Returns ((candidates, matched, within max_dist), row (n,) int32, d2 (n,) float64[, keys uint64][, words uint32][, evidence
+        uint32]) — row -1, d2 +inf, key all ones, words 0 where there is none — or, with per_point=False (the scoring form: no
+        per-point copy), the three counts alone.  One host synchronisation."""
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        n = self.cloud_size(cid)
+        bufs, args = _query_buffers(n, per_point, with_keys, with_attr, with_ev)
+        counts = np.zeros(3, np.uint64)
+        _check(hip_lib().madicp_map_query_cloud(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), int(reach),
+                                                float(max_dist), *args, n, counts.ctypes.data_as(_u64p)))
+        return _query_answer(counts, bufs, n, per_point)
 
     def map_clear(self, mid):
         _check(hip_lib().madicp_map_clear(self._h, mid))

@@ -42,6 +42,22 @@ MADICP_HD inline uint64_t export_key(const double* q, double voxel) {
   return key;
 }
 
+// the same decision with the three cells kept (the map query's neighbourhood starts from them): false when the point is no
+// candidate; export_key(q, voxel) == export_key_of_cells(cell) for every candidate (tests/cpp/map_query_check.cpp)
+MADICP_HD inline bool export_cells(const double* q, double voxel, int32_t* cell) {
+  for (int i = 0; i < 3; ++i) {
+    const double f = floor(q[i] / voxel);
+    if (!(f >= kExportCellMin && f < kExportCellEnd)) return false;
+    cell[i] = static_cast<int32_t>(f);
+  }
+  return true;
+}
+MADICP_HD inline uint64_t export_key_of_cells(const int32_t* cell) {  // every cell in [-2^20, 2^20)
+  uint64_t key = 0;
+  for (int i = 0; i < 3; ++i) key |= static_cast<uint64_t>(static_cast<int64_t>(cell[i]) + 1048576) << (21 * i);
+  return key;
+}
+
 // what both entry points refuse before they look at a point (null = nothing to refuse)
 inline const char* export_refusal(const double* R, const double* t, double voxel) {
   if (!R || !t) return "null argument";
@@ -159,6 +175,53 @@ MADICP_HD inline bool map_evidence_miss(uint32_t* e, uint32_t miss) {
   if (*e <= miss) return false;
   *e -= miss;
   return true;
+}
+
+// ---- querying the map (madicp_map_query_cloud / madicp_host_map_query): the nearest row per point, the map only read ---------------
+// Point i goes through (R, t) as everywhere (export_position) and, if it is a candidate, has its three cells (export_cells).  Its
+// NEIGHBOURHOOD is the cells cell + o, o in {-reach .. reach}^3, reach 0 or 1; a cell with an axis outside [-2^20, 2^20) is skipped
+// (nothing wraps).  For every row j whose STORED key is the key of a cell of the neighbourhood the squared distance comes from the
+// stored float row — map_row_kept's association, fp64, no contraction (query_d2) — and the answer is the row with the smallest
+// (d2, j), lexicographically: a tie goes to the lower row.  A minimum does not depend on the order of its arguments, so the answer
+// is a function of (map, cloud, pose, reach) alone.  No candidate, or no such row: row -1, d2 +inf, key kExportNoKey, words 0.  A
+// row whose d2 is NaN (a stored NaN float) is never the answer.  Everything is fp64 or integer and calls no library function.
+constexpr int kQueryCells = 27;  // the neighbourhood at reach 1; cell c has the offset (c % 3 - 1, c / 3 % 3 - 1, c / 9 - 1)
+constexpr int kQueryOwnCell = 13;  // ... whose middle one is the point's own: all there is at reach 0
+constexpr double kQueryNoDistance = __builtin_huge_val();  // +inf: the d2 of "no row"
+
+// what both entry points refuse (null = nothing to refuse): export_refusal's conditions on R and t, reach 0 or 1, max_dist >= 0
+inline const char* map_query_refusal(const double* R, const double* t, int reach, double max_dist) {
+  if (!R || !t) return "null argument";
+  if (const char* why = export_refusal(R, t, 1.0)) return why;
+  if (reach != 0 && reach != 1) return "reach: 0 or 1";
+  if (!(max_dist >= 0.0)) return "max_dist: >= 0 and not NaN (+inf is legal)";
+  return nullptr;
+}
+
+// the key of cell c (0 .. kQueryCells - 1) of the neighbourhood of `cell`; false where an axis leaves the key range
+MADICP_HD inline bool query_cell_key(const int32_t* cell, int c, uint64_t* key) {
+  const int32_t o[3] = {c % 3 - 1, c / 3 % 3 - 1, c / 9 - 1};
+  int32_t nb[3];
+  for (int i = 0; i < 3; ++i) {
+    nb[i] = cell[i] + o[i];
+    if (nb[i] < -1048576 || nb[i] >= 1048576) return false;
+  }
+  *key = export_key_of_cells(nb);
+  return true;
+}
+
+// the squared distance of a position to a stored float row
+MADICP_HD inline double query_d2(const double* q, const float* row) {
+  const double dx = q[0] - static_cast<double>(row[0]);
+  const double dy = q[1] - static_cast<double>(row[1]);
+  const double dz = q[2] - static_cast<double>(row[2]);
+  return sum3s(dx * dx, dy * dy, dz * dz);
+}
+
+// whether (d2, row) comes before (best_d2, best_row); "no row yet" is (+inf, -1), which every real row beats — -1 is the LARGEST
+// row in the unsigned comparison — and a NaN d2 beats nothing
+MADICP_HD inline bool query_before(double d2, int32_t row, double best_d2, int32_t best_row) {
+  return d2 < best_d2 || (d2 == best_d2 && static_cast<uint32_t>(row) < static_cast<uint32_t>(best_row));
 }
 
 }  // namespace madicp_host

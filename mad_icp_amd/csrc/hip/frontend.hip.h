@@ -884,5 +884,153 @@ __global__ __launch_bounds__(256) void map_ev_mark(const uint32_t* __restrict__ 
     mark[j] = (j < n_rows && ev[j] >= min_e) ? 1u : 0u;
 }
 
+// ---- querying the map: the nearest row per point of a cloud (madicp_map_query_cloud) ------------------------------------------------
+// The rule is csrc/common/export_point.h's, shared with the host twin: export_cells, query_cell_key, query_d2, query_before.  The map
+// is only read — the table through map_find, the slot's row, the stored float row — and the answers go to scratch of the call's own.
+//   map_slot_rows    maps WITHOUT the slot_row column (plain and attribute maps): one lane per row stores j at the slot map_find
+//                    returns for row_keys[j], into a transient array of the call's own; slots that hold no key are never read
+//   map_query_lanes  one lane per point: reach 0 is one probe, reach 1 the 27 cells one after the other, unrolled — 27 dependent
+//                    gather chains per point (key, slot's row, 12-byte row), all latency, of which the unrolled form keeps several
+//                    in flight per lane.  The product's kernel for both reaches.
+//   map_query_coop   -DMADICP_QUERY_COOP (a measurement aid, tools/map_query_time.py --variant): reach 1 with 32 lanes per point,
+//                    two points per wavefront-step: a wavefront takes 64 consecutive points, lane l computes q and the cells of
+//                    point base + l once; in step s half h (lanes 32 h .. 32 h + 31) gets the point of lane 32 h + s by shuffles,
+//                    lane c < 27 of the half probes cell c, a 5-step butterfly minimum over (d2, row) runs within the half and
+//                    lane 32 h + s — the point's owner — keeps it.  After at most 32 steps every lane holds its own point's
+//                    answer: the per-point stores are coalesced.  A half with no point left (the cloud's last wavefront) takes
+//                    part in every shuffle with the neutral (+inf, -1); loop bounds are wave-uniform.  The same bits, measured
+//                    0.028 ms SLOWER per scoring query of 120 k points (profiles/map_query_time.md): the same number of
+//                    wavefronts walks 32 steps of one probe each instead of 27 probes whose loads overlap — not kept as default.
+// Determinism: a minimum over (d2, row) with a strict total order does not depend on how its arguments are grouped, so the
+// geometry changes no bit.  Counts: per-wavefront ballots and popcounts, lane 0 adds three 64-bit integers — no float atomics.
+struct QueryMap {  // by value: what the query reads of a map
+  const unsigned long long* keys;
+  uint32_t slots;
+  const uint32_t* slot_row;  // the map's own column, or the call's transient array
+  const float* xyz;
+  long n_rows;
+  const unsigned long long* row_keys;
+  const uint32_t* attr;  // null: none asked for
+  const uint32_t* ev;
+};
+struct QueryOut {  // by value: the call's scratch; null where a column was not asked for
+  int32_t* row;
+  double* d2;
+  unsigned long long* keys;
+  uint32_t* attr;
+  uint32_t* ev;
+  unsigned long long* counts;  // candidates, matched, within
+};
+__global__ __launch_bounds__(256) void map_slot_rows(const unsigned long long* __restrict__ row_keys, long n_rows,
+                                                     const unsigned long long* __restrict__ keys, uint32_t slots,
+                                                     uint32_t* __restrict__ slot_row) {
+  for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < n_rows; j += (long)gridDim.x * blockDim.x) {
+    const uint32_t s = map_find(keys, slots, row_keys[j]);
+    if (s != kExportNoSlot) slot_row[s] = (uint32_t)j;
+  }
+}
+// cell c of the neighbourhood of `cell`: (d2, row) becomes its row's where that comes before
+__device__ inline void query_probe(const QueryMap& M, const double* q, const int32_t* cell, int c, double* d2, int32_t* row) {
+  uint64_t key;
+  if (!madicp_host::query_cell_key(cell, c, &key)) return;
+  const uint32_t s = map_find(M.keys, M.slots, key);
+  if (s == kExportNoSlot) return;
+  const uint32_t j = M.slot_row[s];
+  if ((long)j >= M.n_rows) return;  // (never: every slot that holds a key knows its row)
+  const float r[3] = {M.xyz[3 * (size_t)j], M.xyz[3 * (size_t)j + 1], M.xyz[3 * (size_t)j + 2]};
+  const double d = madicp_host::query_d2(q, r);
+  if (madicp_host::query_before(d, (int32_t)j, *d2, *row)) {
+    *d2 = d;
+    *row = (int32_t)j;
+  }
+}
+// what every lane of a wavefront ends a pass with: its point's columns (i < n) and the wavefront's three counts
+__device__ inline void query_finish(long i, long n, bool candidate, double d2, int32_t row, double md2, const QueryMap& M, const QueryOut& O) {
+  if (i < n) {
+    if (O.row) O.row[i] = row;
+    if (O.d2) O.d2[i] = d2;
+    if (O.keys) O.keys[i] = row >= 0 ? M.row_keys[row] : (unsigned long long)madicp_host::kExportNoKey;
+    if (O.attr) O.attr[i] = row >= 0 ? M.attr[row] : 0u;
+    if (O.ev) O.ev[i] = row >= 0 ? M.ev[row] : 0u;
+  }
+  const bool matched = i < n && row >= 0;
+  const unsigned long long a = __popcll(__ballot(i < n && candidate));
+  const unsigned long long b = __popcll(__ballot(matched));
+  const unsigned long long w = __popcll(__ballot(matched && d2 <= md2));
+  if ((threadIdx.x & 63) == 0) {
+    if (a) atomicAdd(&O.counts[0], a);
+    if (b) atomicAdd(&O.counts[1], b);
+    if (w) atomicAdd(&O.counts[2], w);
+  }
+}
+__global__ __launch_bounds__(256) void map_query_lanes(const double* __restrict__ xyz, long n, ExportPose X, double voxel, int reach,
+                                                       double md2, QueryMap M, QueryOut O) {
+  const int lane = threadIdx.x & 63;
+  // (blockDim and the stride are multiples of 64: i - lane is the wavefront's, so all its lanes leave the loop together)
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i - lane < n; i += (long)gridDim.x * blockDim.x) {
+    bool candidate = false;
+    double d2 = madicp_host::kQueryNoDistance;
+    int32_t row = -1;
+    if (i < n) {
+      const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+      double q[3];
+      int32_t cell[3];
+      madicp_host::export_position(p, X.R, X.t, q);
+      candidate = madicp_host::export_cells(q, voxel, cell);
+      if (candidate && reach == 0) query_probe(M, q, cell, madicp_host::kQueryOwnCell, &d2, &row);
+      if (candidate && reach != 0) {
+#pragma unroll
+        for (int c = 0; c < madicp_host::kQueryCells; ++c) query_probe(M, q, cell, c, &d2, &row);
+      }
+    }
+    query_finish(i, n, candidate, d2, row, md2, M, O);
+  }
+}
+__global__ __launch_bounds__(256) void map_query_coop(const double* __restrict__ xyz, long n, ExportPose X, double voxel, double md2,
+                                                      QueryMap M, QueryOut O) {
+  const int lane = threadIdx.x & 63, c = lane & 31, first = lane & 32;  // first: lane 0 of this lane's half
+  const long waves = ((long)gridDim.x * blockDim.x) >> 6;
+  for (long base = ((((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 6); base < n; base += waves << 6) {  // (wave-uniform)
+    const long i = base + lane;
+    int candidate = 0;
+    double q[3] = {0.0, 0.0, 0.0};
+    int32_t cell[3] = {0, 0, 0};
+    if (i < n) {
+      const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+      madicp_host::export_position(p, X.R, X.t, q);
+      candidate = madicp_host::export_cells(q, voxel, cell) ? 1 : 0;
+    }
+    double best_d2 = madicp_host::kQueryNoDistance;
+    int32_t best = -1;
+    const int steps = n - base < 32 ? (int)(n - base) : 32;  // (wave-uniform; the second half never holds more points than the first)
+    for (int s = 0; s < steps; ++s) {
+      const int owner = first + s;  // the lane whose point this half takes now: no candidate when it has none
+      const int live = __shfl(candidate, owner);
+      double pq[3];
+      int32_t pcell[3];
+      for (int k = 0; k < 3; ++k) {
+        pq[k] = __shfl(q[k], owner);
+        pcell[k] = __shfl(cell[k], owner);
+      }
+      double d2 = madicp_host::kQueryNoDistance;
+      int32_t row = -1;
+      if (live && c < madicp_host::kQueryCells) query_probe(M, pq, pcell, c, &d2, &row);
+      for (int d = 1; d < 32; d <<= 1) {  // (lane ^ d stays within the half)
+        const double od2 = __shfl_xor(d2, d);
+        const int32_t orow = __shfl_xor(row, d);
+        if (madicp_host::query_before(od2, orow, d2, row)) {
+          d2 = od2;
+          row = orow;
+        }
+      }
+      if (c == s) {
+        best_d2 = d2;
+        best = row;
+      }
+    }
+    query_finish(i, n, candidate != 0, best_d2, best, md2, M, O);
+  }
+}
+
 }  // namespace fe
 }  // namespace madicp

@@ -1611,6 +1611,79 @@ int madicp_map_clear_rays(madicp_ctx* ctx, int map_id, int cloud_id, const doubl
       out_removed, out_rows, out_watermark);
 }
 
+// The nearest row per point (fe::map_query_lanes; csrc/common/export_point.h has the rule).  The map's block is
+// only read.  The call's scratch is ONE pooled block of its own — the builder's is not touched —
+//   counts (3 x 8) | d2 (n x 8) | keys (n x 8) | row (n x 4) | attr (n x 4) | ev (n x 4) | slot_row (slots x 4)
+// of which only what the caller asked for is there, and the last only on a map without the column (fe::map_slot_rows fills it).
+// One memset for the counts, the kernels, the copies of what was asked for, ONE wait.
+int madicp_map_query_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int reach, double max_dist,
+                           int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
+                           int64_t capacity_points, uint64_t out_counts[3]) {
+  if (!ctx || !R || !t || !out_counts) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (const char* why = madicp_host::map_query_refusal(R, t, reach, max_dist)) return fail(MADICP_ERR_INVALID, why);
+  if (out_attr && !m->with_attr) return fail(MADICP_ERR_INVALID, kMapNoAttr);
+  if (out_ev && !m->with_ev) return fail(MADICP_ERR_INVALID, kMapNoEvidence);
+  const int64_t n = c->n;
+  if ((out_row || out_d2 || out_keys || out_attr || out_ev) && capacity_points < n)
+    return fail(MADICP_ERR_CAPACITY, "the per-point buffers hold fewer entries than the cloud has points");
+  if (n == 0) {
+    out_counts[0] = out_counts[1] = out_counts[2] = 0;
+    return MADICP_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t N = (size_t)n;
+  const bool own_slot_row = !m->slot_row();
+  size_t off = align_up(3 * sizeof(uint64_t));
+  auto place = [&](bool wanted, size_t bytes) {
+    const size_t at = off;
+    if (wanted) off = align_up(off + bytes);
+    return at;
+  };
+  const size_t at_d2 = place(out_d2, 8 * N), at_keys = place(out_keys, 8 * N), at_row = place(out_row, 4 * N);
+  const size_t at_attr = place(out_attr, 4 * N), at_ev = place(out_ev, 4 * N), at_slot_row = place(own_slot_row, 4 * (size_t)m->slots);
+  void* p = nullptr;
+  RC_TRY(pool_alloc(ctx, off, ctx->copy, &p));
+  char* block = static_cast<char*>(p);
+  auto at = [&](bool wanted, size_t where) { return wanted ? block + where : nullptr; };
+  fe::QueryOut O;
+  O.counts = reinterpret_cast<unsigned long long*>(block);
+  O.d2 = reinterpret_cast<double*>(at(out_d2, at_d2));
+  O.keys = reinterpret_cast<unsigned long long*>(at(out_keys, at_keys));
+  O.row = reinterpret_cast<int32_t*>(at(out_row, at_row));
+  O.attr = reinterpret_cast<uint32_t*>(at(out_attr, at_attr));
+  O.ev = reinterpret_cast<uint32_t*>(at(out_ev, at_ev));
+  uint32_t* slot_row = own_slot_row ? reinterpret_cast<uint32_t*>(block + at_slot_row) : m->slot_row();
+  const fe::QueryMap Q{m->keys(), m->slots, slot_row, m->xyz(), (long)m->rows, m->row_keys(), out_attr ? m->attr() : nullptr,
+                       out_ev ? m->ev() : nullptr};
+  hipError_t e = hipMemsetAsync(O.counts, 0, 3 * sizeof(uint64_t), ctx->copy);
+  if (e == hipSuccess) {
+    if (own_slot_row && m->rows > 0)
+      hipLaunchKernelGGL(fe::map_slot_rows, dim3(grid_256(ctx, m->rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys(),
+                         (long)m->rows, (const unsigned long long*)m->keys(), m->slots, slot_row);
+    const double md2 = max_dist * max_dist;
+#ifdef MADICP_QUERY_COOP  // (the measurement's other leg, tools/map_query_time.py --variant: measured slower, the same bits)
+    if (reach == 1)
+      hipLaunchKernelGGL(fe::map_query_coop, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n,
+                         export_pose(R, t), m->voxel, md2, Q, O);
+    else
+#endif
+      hipLaunchKernelGGL(fe::map_query_lanes, dim3(grid_256(ctx, n)), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n,
+                         export_pose(R, t), m->voxel, reach, md2, Q, O);
+    e = hipGetLastError();
+  }
+  uint64_t counts[3] = {0, 0, 0};
+  const CopyOut outs[] = {{counts, O.counts, sizeof(counts)}, {out_row, O.row, 4 * N},   {out_d2, O.d2, 8 * N},
+                          {out_keys, O.keys, 8 * N},          {out_attr, O.attr, 4 * N}, {out_ev, O.ev, 4 * N}};
+  const int rc = copies_then_wait(ctx, e, outs, 6, "voxel map query: ");
+  pool_free(ctx, block, nullptr);  // (behind the wait: nothing is in flight on it)
+  if (rc == MADICP_OK) std::memcpy(out_counts, counts, sizeof(counts));
+  return rc;
+}
+
 int madicp_map_clear(madicp_ctx* ctx, int map_id) {
   if (!ctx) return fail(MADICP_ERR_INVALID, "null argument");
   DevMap* m = find_map(ctx, map_id);

@@ -274,6 +274,7 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
 
 void Pipeline::foldFrame() {
   if (map_voxel_ == 0.0) return;
+  std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));  // (a frame that is not folded answers zeros)
   if (have_kept_ && !map_overflowed_ && (!map_keyframes_only_ || is_map_updated_)) {
     const int64_t max_rows = static_cast<int64_t>(map_max_points_);
     const int64_t first_rows = std::min<int64_t>(max_rows, int64_t(1) << 18);
@@ -317,6 +318,12 @@ void Pipeline::foldFrame() {
           }
         }
       }
+      int qrc = MADICP_OK;  // setMapOverlap: what the map knows of this frame, asked before the frame is folded
+      if (map_overlap_)
+        qrc = madicp_map_query_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, map_overlap_reach_, map_overlap_max_dist_, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr, 0, map_frame_overlap_);
+      if (qrc != MADICP_OK && kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
+      check(qrc, "madicp_map_query_cloud");
       rc = madicp_map_insert_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, &added, &rows);
       // setMapClearing: what the cloud just folded sees through leaves, before the range prune below
       int64_t removed = 0, mark = 0;
@@ -356,6 +363,10 @@ void Pipeline::foldFrame() {
       }
       const ContainerType& c = kept_cloud_id_ >= 0 ? down : kept_host_;
       const std::vector<uint32_t>& a = kept_cloud_id_ >= 0 ? down_attr : kept_attr_;
+      if (map_overlap_ &&
+          map_host_->query(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, map_overlap_reach_,
+                           map_overlap_max_dist_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, map_frame_overlap_) != MADICP_OK)
+        throw std::runtime_error("Pipeline: the host voxel map refused the overlap query's arguments");
       rc = map_host_->insert(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, &added,
                              &rows, (kept_has_attr_ && a.size() == c.size()) ? a.data() : nullptr);
       if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline: the host voxel map refused its arguments");
@@ -374,6 +385,7 @@ void Pipeline::foldFrame() {
       }
     }
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
+    if (rc != MADICP_OK) std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));  // (refused: not folded)
     if (rc == MADICP_OK && map_with_attr_ && kept_has_attr_) map_attr_type_ = kept_attr_type_;
     // (a) the vehicle has moved a quarter of the range since the last prune: squared distances, fp64 — the poses alone decide
     if (rc == MADICP_OK && map_range_ > 0.0) {
@@ -470,6 +482,42 @@ size_t Pipeline::mapClearRays(const double* xyz, size_t n, const double R[9], co
   map_cursor_ = static_cast<size_t>(mark);
   map_removed_ += static_cast<size_t>(removed);
   return static_cast<size_t>(removed);
+}
+
+void Pipeline::setMapOverlap(bool on, int reach, double max_dist) {
+  if (reach != 0 && reach != 1) throw std::invalid_argument("Pipeline::setMapOverlap: reach must be 0 or 1");
+  if (!(max_dist >= 0.0)) throw std::invalid_argument("Pipeline::setMapOverlap: max_dist must be >= 0 and not NaN");
+  map_overlap_ = on;
+  map_overlap_reach_ = reach;
+  map_overlap_max_dist_ = max_dist;
+  if (!on) std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));
+}
+
+void Pipeline::mapQuery(const double* xyz, size_t n, const double R[9], const double t[3], int reach, double max_dist, int32_t* row, double* d2,
+                        uint64_t* keys, uint32_t* attr, uint32_t* ev, uint64_t counts[3]) {
+  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapQuery: setMapAccumulation(voxel_size > 0) first");
+  if (attr && !map_with_attr_)
+    throw std::logic_error("Pipeline::mapQuery: the map was made without the attribute (setMapAccumulation's with_attribute)");
+  if (ev && !map_with_ev_) throw std::logic_error("Pipeline::mapQuery: the map was made without evidence (setMapAccumulation's evidence)");
+  if ((!xyz && n > 0) || !R || !t || !counts) throw std::invalid_argument("Pipeline::mapQuery: null argument");
+  if (n > static_cast<size_t>(kMapMaxRows)) throw std::invalid_argument("Pipeline::mapQuery: at most 2^30 points");
+  if (const char* why = map_query_refusal(R, t, reach, max_dist)) throw std::invalid_argument(std::string("Pipeline::mapQuery: ") + why);
+  const int64_t n64 = static_cast<int64_t>(n);
+  if (map_host_ || map_id_ < 0 || n == 0) {  // the host twin; before the first fold and for no point at all: an empty map of the same kind
+    const VoxelMap empty(map_voxel_, 1, 1, map_with_attr_, map_with_ev_);
+    if ((map_host_ ? *map_host_ : empty).query(xyz, n64, R, t, reach, max_dist, row, d2, keys, attr, ev, n64, counts) != MADICP_OK)
+      throw std::invalid_argument("Pipeline::mapQuery: the host voxel map refused its arguments");
+    return;
+  }
+  DeviceLock lock(Device::mutex());
+  madicp_ctx* ctx = Device::current(map_generation_);
+  if (!ctx) throw std::logic_error("Pipeline::mapQuery: the device context the map lived in is gone");
+  int cloud_id = -1;
+  check(madicp_cloud_upload(ctx, xyz, n64, &cloud_id), "madicp_cloud_upload");
+  const int rc = madicp_map_query_cloud(ctx, map_id_, cloud_id, R, t, reach, max_dist, row, d2, keys, attr, ev, n64, counts);
+  madicp_cloud_release(ctx, cloud_id);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapQuery: ") + madicp_last_error());
+  check(rc, "madicp_map_query_cloud");
 }
 
 size_t Pipeline::mapNewRowCount() {

@@ -265,6 +265,27 @@ class Pipeline {
   void setMapClearing(bool on, double margin = 0.0, const double origin[3] = nullptr);
   bool mapClearing() const { return map_clearing_; }
   size_t mapClearRays(const double* xyz, size_t n, const double R[9], const double t[3], const double origin[3], double margin = 0.0);
+  // additive: ASKING THE MAP.  mapQuery: for each of the n points xyz (n, 3) taken through (R, t), the nearest row of its voxel
+  // neighbourhood (reach 0: its own voxel, 1: the 27 around it; include/madicp_hip.h: madicp_map_query_cloud has the rule) — row
+  // (int32, -1: none), d2 (+inf: none), the row's stored key (all ones: none) and its attribute and evidence words (0: none), each
+  // buffer of n entries or null, and counts = {candidates, matched, within max_dist}, always.  With all five buffers null it is the
+  // scoring form (mapOverlap in the bindings): nothing per point is copied.  Device front-end: the points are uploaded as
+  // mapClearRays uploads them and asked where the map lives (one host synchronisation); host front-end: the bit-equal host twin.
+  // Before the first fold the map is empty: every candidate is unmatched.  The map is only read.  std::logic_error while
+  // accumulation is off and for attr / ev on a map without that column; std::invalid_argument for a null argument, a non-finite R
+  // or t, a reach other than 0 and 1, a max_dist that is NaN or negative.
+  // setMapOverlap(on, reach, max_dist) — default off: not a launch, not an allocation, the same pose and map bits — lets foldFrame()
+  // ask the map about the frame's cloud at the frame's pose BEFORE it folds it (behind a capacity prune of setMapRange, if one runs);
+  // mapFrameOverlap() answers that frame's three counts: how much of the scan the map already knew.  Zeros when the fold was
+  // skipped by keyframes_only, when it was refused (mapOverflowed()) and before the first frame.  With the option on, poses,
+  // keyframe decisions and every map column are bit for bit what they are with it off.  The counts come back through the query's
+  // own wait: one host synchronisation more per folded frame on the device front-end (profiles/map_query_time.md).  A sharded
+  // Pipeline holds the whole map on every rank: the answers are the same on every rank, nothing is exchanged.
+  void mapQuery(const double* xyz, size_t n, const double R[9], const double t[3], int reach, double max_dist, int32_t* row, double* d2,
+                uint64_t* keys, uint32_t* attr, uint32_t* ev, uint64_t counts[3]);
+  void setMapOverlap(bool on, int reach = 1, double max_dist = kQueryNoDistance);
+  bool mapOverlapOn() const { return map_overlap_; }
+  const uint64_t* mapFrameOverlap() const { return map_frame_overlap_; }
   // additive: one frame straight from sensor records — float32 (x, y, z, intensity ...) `stride_floats` apart, range
   // filter and optional KITTI correction as in apps/cpp_runners/bin_runner.cpp:126-166 — ingest, deskew, build and
   // registration all on the device (implies the device front-end for this frame)
@@ -447,6 +468,10 @@ class Pipeline {
   bool map_clearing_ = false;  // setMapClearing
   bool map_track_removed_ = false, map_log_full_ = false;  // setMapTrackRemoved; a removal was skipped because the log is full
   double map_clear_margin_ = 0.0, map_clear_origin_[3] = {0.0, 0.0, 0.0};
+  bool map_overlap_ = false;  // setMapOverlap: foldFrame asks the map about the frame before it folds it
+  int map_overlap_reach_ = 1;
+  double map_overlap_max_dist_ = kQueryNoDistance;
+  uint64_t map_frame_overlap_[3] = {0, 0, 0};
   size_t pruneMapAt(const double center[3], double radius);  // madicp_map_prune / VoxelMap::prune with the cursor as watermark
   void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;

@@ -148,6 +148,13 @@ int madicp_host_map_download_rows(const madicp_host_map* map, int64_t first_row,
   return map->map.download_rows(first_row, out_xyz, out_keys, out_attr, capacity_rows, out_n);
 }
 
+int madicp_host_map_query(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int reach,
+                          double max_dist, int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
+                          int64_t capacity_points, uint64_t out_counts[3]) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.query(xyz, n, R, t, reach, max_dist, out_row, out_d2, out_keys, out_attr, out_ev, capacity_points, out_counts);
+}
+
 int madicp_host_map_clear(madicp_host_map* map) {
   if (!map) return MADICP_ERR_INVALID;
   map->map.clear();

@@ -239,6 +239,59 @@ class VoxelMap {
     return kMapOk;
   }
 
+  // include/madicp_host.h: madicp_host_map_query — the nearest row per point (export_point.h has the rule: export_cells,
+  // query_cell_key, query_d2, query_before), the map only read.  Per-point buffers may be null; counts = {candidates, matched,
+  // within max_dist}.  A map without moments has no key -> row index: the call makes a transient one of its own.
+  int query(const double* xyz, int64_t n, const double* R, const double* t, int reach, double max_dist, int32_t* out_row, double* out_d2,
+            uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, int64_t capacity_points, uint64_t* out_counts) const {
+    if (!out_counts || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
+    if (map_query_refusal(R, t, reach, max_dist)) return kMapInvalid;
+    if ((out_attr && !with_attr_) || (out_ev && !with_ev_)) return kMapInvalid;
+    if ((out_row || out_d2 || out_keys || out_attr || out_ev) && capacity_points < n) return kMapCapacity;
+    std::unordered_map<uint64_t, int64_t> own_index;
+    if (!with_mom_ && n > 0) {
+      own_index.reserve(row_keys_.size());
+      for (int64_t j = 0; j < size(); ++j) own_index[row_keys_[j]] = j;
+    }
+    const std::unordered_map<uint64_t, int64_t>& index = with_mom_ ? row_of_ : own_index;
+    const double md2 = max_dist * max_dist;
+    uint64_t candidates = 0, matched = 0, within = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      double q[3];
+      export_position(xyz + 3 * i, R, t, q);
+      int32_t cell[3], best = -1;
+      double best_d2 = kQueryNoDistance;
+      if (export_cells(q, voxel_, cell)) {
+        ++candidates;
+        for (int c = reach ? 0 : kQueryOwnCell; c < (reach ? kQueryCells : kQueryOwnCell + 1); ++c) {
+          uint64_t key;
+          if (!query_cell_key(cell, c, &key)) continue;
+          const auto it = index.find(key);
+          if (it == index.end()) continue;
+          const int32_t j = static_cast<int32_t>(it->second);
+          const double d2 = query_d2(q, rows_.data() + 3 * it->second);
+          if (query_before(d2, j, best_d2, best)) {
+            best_d2 = d2;
+            best = j;
+          }
+        }
+      }
+      if (best >= 0) {
+        ++matched;
+        if (best_d2 <= md2) ++within;
+      }
+      if (out_row) out_row[i] = best;
+      if (out_d2) out_d2[i] = best_d2;
+      if (out_keys) out_keys[i] = best >= 0 ? row_keys_[best] : kExportNoKey;
+      if (out_attr) out_attr[i] = best >= 0 ? attr_[best] : 0u;
+      if (out_ev) out_ev[i] = best >= 0 ? ev_[best] : 0u;
+    }
+    out_counts[0] = candidates;
+    out_counts[1] = matched;
+    out_counts[2] = within;
+    return kMapOk;
+  }
+
   void clear() {  // (keeps the memory, forgets the rows)
     rows_.clear();
     keys_.clear();

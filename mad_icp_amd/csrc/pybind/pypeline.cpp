@@ -279,6 +279,70 @@ PYBIND11_MODULE(pypeline, m) {
            return self.mapClearRays(cloud.data(), static_cast<size_t>(cloud.shape(0)), R, t, origin.data(), margin);
          },
          py::arg("cloud"), py::arg("pose"), py::arg("origin") = std::vector<double>{0.0, 0.0, 0.0}, py::arg("margin") = 0.0)
+    // additive: asking the map (Pipeline::mapQuery).  mapQuery(cloud (n, 3), pose (4, 4), reach=1, max_dist=inf, with_keys=False,
+    // with_attribute=False, with_evidence=False) returns (counts, row (n,) int32, d2 (n,) float64[, keys uint64][, attr][, ev uint32]):
+    // per point the nearest map row of its voxel neighbourhood (-1, +inf, all ones, 0 where there is none), counts = (candidates,
+    // matched, within max_dist); attr viewed as the field's dtype as in mapCloud.  mapOverlap(cloud, pose, reach=1, max_dist=inf)
+    // returns the three counts alone: the scoring form, no per-point copy.  setMapOverlap(on, reach=1, max_dist=inf) makes every fold
+    // ask the map about the frame first; mapFrameOverlap() returns that frame's counts (zeros for a frame that was not folded).
+    // ValueError for a reach other than 0 and 1, a max_dist that is NaN or negative, a non-finite pose; RuntimeError (std::logic_error)
+    // while accumulation is off and for a column the map lacks.
+    .def("mapQuery",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> pose, int reach, double max_dist, bool with_keys,
+            bool with_attribute, bool with_evidence) -> py::object {
+           if (cloud.ndim() != 2 || cloud.shape(1) != 3) throw py::value_error("cloud must be (n, 3)");
+           if (pose.ndim() != 2 || pose.shape(0) != 4 || pose.shape(1) != 4) throw py::value_error("pose must be (4, 4)");
+           const double* T = pose.data();
+           const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+           const double t[3] = {T[3], T[7], T[11]};
+           const py::ssize_t n = cloud.shape(0);
+           py::array_t<int32_t> row(n);
+           py::array_t<double> d2(n);
+           py::array_t<uint64_t> k(with_keys ? n : 0);
+           py::array_t<uint32_t> w(with_attribute ? n : 0), e(with_evidence ? n : 0);
+           uint64_t counts[3] = {0, 0, 0};
+           self.mapQuery(cloud.data(), static_cast<size_t>(n), R, t, reach, max_dist, row.mutable_data(), d2.mutable_data(),
+                         with_keys ? k.mutable_data() : nullptr, with_attribute ? w.mutable_data() : nullptr,
+                         with_evidence ? e.mutable_data() : nullptr, counts);
+           py::list out;
+           out.append(py::make_tuple(counts[0], counts[1], counts[2]));
+           out.append(row);
+           out.append(d2);
+           if (with_keys) out.append(k);
+           if (with_attribute) {
+             py::object words = w;
+             if (const int type = self.mapAttributeType(); type != madicp_host::kAttrNone) {
+               const py::module_ rec = py::module_::import("mad_icp_amd.records");
+               words = rec.attr("attribute_view")(w, rec.attr("ATTR_DTYPE")[py::int_(type)]);
+             }
+             out.append(words);
+           }
+           if (with_evidence) out.append(e);
+           return py::tuple(out);
+         },
+         py::arg("cloud"), py::arg("pose"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance,
+         py::arg("with_keys") = false, py::arg("with_attribute") = false, py::arg("with_evidence") = false)
+    .def("mapOverlap",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> pose, int reach, double max_dist) {
+           if (cloud.ndim() != 2 || cloud.shape(1) != 3) throw py::value_error("cloud must be (n, 3)");
+           if (pose.ndim() != 2 || pose.shape(0) != 4 || pose.shape(1) != 4) throw py::value_error("pose must be (4, 4)");
+           const double* T = pose.data();
+           const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+           const double t[3] = {T[3], T[7], T[11]};
+           uint64_t counts[3] = {0, 0, 0};
+           self.mapQuery(cloud.data(), static_cast<size_t>(cloud.shape(0)), R, t, reach, max_dist, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         counts);
+           return py::make_tuple(counts[0], counts[1], counts[2]);
+         },
+         py::arg("cloud"), py::arg("pose"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance)
+    .def("setMapOverlap", &Pipeline::setMapOverlap, py::arg("on"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance)
+    .def("mapFrameOverlap",
+         [](const Pipeline& self) {
+           const uint64_t* c = self.mapFrameOverlap();
+           return py::make_tuple(c[0], c[1], c[2]);
+         })
     .def("mapNewRows",
          [](Pipeline& self, bool with_attribute, bool with_keys) -> py::object {
            const size_t m = self.mapNewRowCount();
