@@ -99,7 +99,7 @@ def hip_source_hash():
 
 
 HOST_SRCS = ("tree_builder.cpp", "host_capi.cpp", "mad_tree.cpp", "mad_icp.cpp", "vel_estimator.cpp", "pipeline.cpp", "deskew.cpp",
-             "ingest_records.cpp", "cloud_export.cpp", "voxel_map.cpp")
+             "ingest_records.cpp", "cloud_export.cpp", "voxel_map.cpp", "device_map_store.cpp")
 
 
 def build_host(force=False):

@@ -182,7 +182,7 @@ void Pipeline::keepHostScan(const ContainerType& c) {
   std::vector<uint32_t> attr = std::move(frame_attr_);
   frame_attr_type_ = kAttrNone;
   frame_attr_.clear();
-  if (!keep_scan_ && map_voxel_ == 0.0) return;
+  if (!keep_scan_ && map_spec_.voxel == 0.0) return;
   dropKeptScan();
   kept_host_ = c;
   kept_n_ = c.size();
@@ -224,17 +224,25 @@ void Pipeline::setKeepScan(bool on) {
 }
 
 // ---- map accumulation (pipeline.h: setMapAccumulation) -----------------------------------------------------------------------
+// The map itself is a MapStore (map_store.h): the device map or the host twin, decided once, in foldFrame, when the first frame is
+// folded.  Everything below asks the store and turns its return codes into this class's exceptions — written once for both sides.
 void Pipeline::dropMap() {
-  if (map_id_ >= 0) {
-    DeviceLock lock(Device::mutex());
-    if (madicp_ctx* ctx = Device::current(map_generation_)) madicp_map_release(ctx, map_id_);  // (as for a kept cloud's id)
-    map_id_ = -1;
-  }
-  map_host_.reset();
+  map_.reset();  // (a device map gives its id back while the context generation that issued it lives)
   map_overflowed_ = false;
   map_have_center_ = map_have_last_ = false;
   map_cursor_ = map_removed_ = 0;
   map_log_full_ = false;
+}
+
+void Pipeline::mapCheck(int rc, const std::string& who) const {
+  if (rc != MADICP_OK) throw std::runtime_error(who + map_->lastError());
+}
+
+ScanRef Pipeline::keptScan() const {
+  if (kept_cloud_id_ >= 0) return ScanRef::cloud(kept_cloud_id_, kept_generation_, static_cast<int64_t>(kept_n_), kept_has_attr_);
+  const bool attr = kept_has_attr_ && kept_attr_.size() == kept_host_.size();
+  return ScanRef::host(kept_host_.empty() ? nullptr : kept_host_[0].data(), attr ? kept_attr_.data() : nullptr,
+                       static_cast<int64_t>(kept_host_.size()));
 }
 
 void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t max_points, bool with_attribute, const uint32_t* evidence,
@@ -248,23 +256,23 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
       throw std::invalid_argument(std::string("Pipeline::setMapAccumulation: ") + why);
   if (voxel_size > 0.0 && moments_max_count > 0)
     if (const char* why = map_moments_refusal(moments_max_count)) throw std::invalid_argument(std::string("Pipeline::setMapAccumulation: ") + why);
-  const uint32_t mom = voxel_size > 0.0 ? moments_max_count : 0u;
-  const bool with_ev = voxel_size > 0.0 && evidence;
-  const bool same_ev = with_ev == map_with_ev_ && (!with_ev || std::equal(evidence, evidence + 3, map_ev_));
-  if (voxel_size == map_voxel_ && (voxel_size == 0.0 || (keyframes_only == map_keyframes_only_ && max_points == map_max_points_ &&
-                                                        with_attribute == map_with_attr_ && same_ev && mom == map_mom_)))
-    return;
-  dropMap();
-  const bool was_on = map_voxel_ > 0.0;
-  map_voxel_ = voxel_size;
-  map_keyframes_only_ = keyframes_only;
-  map_max_points_ = max_points;
-  map_with_attr_ = voxel_size > 0.0 && with_attribute;
-  map_attr_type_ = kAttrNone;
-  map_with_ev_ = with_ev;
-  if (with_ev) std::copy(evidence, evidence + 3, map_ev_);
-  map_mom_ = mom;
+  MapSpec spec;  // (off: the default spec, whatever else was asked for)
   if (voxel_size > 0.0) {
+    spec.voxel = voxel_size;
+    spec.max_rows = static_cast<int64_t>(max_points);
+    spec.first_rows = std::min<int64_t>(spec.max_rows, int64_t(1) << 18);
+    spec.with_attr = with_attribute;
+    spec.with_ev = evidence != nullptr;
+    if (evidence) std::copy(evidence, evidence + 3, spec.ev);
+    spec.mom = moments_max_count;
+  }
+  if (spec == map_spec_ && (spec.voxel == 0.0 || keyframes_only == map_keyframes_only_)) return;
+  dropMap();
+  const bool was_on = map_spec_.voxel > 0.0;
+  map_spec_ = spec;
+  map_keyframes_only_ = keyframes_only;
+  map_attr_type_ = kAttrNone;
+  if (spec.voxel > 0.0) {
     if (!was_on) dropDeviceLookAhead();  // (a tree built ahead comes without its scan: the next frame builds synchronously)
   } else {
     map_track_removed_ = false;  // (setMapTrackRemoved is an option of the accumulation: off with it)
@@ -273,120 +281,51 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
 }
 
 void Pipeline::foldFrame() {
-  if (map_voxel_ == 0.0) return;
+  if (map_spec_.voxel == 0.0) return;
   std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));  // (a frame that is not folded answers zeros)
   if (have_kept_ && !map_overflowed_ && (!map_keyframes_only_ || is_map_updated_)) {
-    const int64_t max_rows = static_cast<int64_t>(map_max_points_);
-    const int64_t first_rows = std::min<int64_t>(max_rows, int64_t(1) << 18);
-    const bool fresh = map_id_ < 0 && !map_host_;
     // (b) a fold the capacity rule would refuse: the rows out of range of the frame before this one give way first, once
-    if (map_range_ > 0.0 && !fresh && map_have_last_ && mapSize() + kept_n_ > map_max_points_) {
+    if (map_range_ > 0.0 && map_ && map_have_last_ && mapSize() + kept_n_ > static_cast<size_t>(map_spec_.max_rows)) {
       pruneMapAt(map_last_position_, map_range_);
       std::copy(map_last_position_, map_last_position_ + 3, map_prune_center_);
       map_have_center_ = true;
     }
+    // a fresh map goes where the frame's scan lives; a device map's frame holds the device lock from the creation to the clearing
+    const bool device = map_ ? map_->onDevice() : kept_cloud_id_ >= 0;
+    std::unique_lock<std::recursive_mutex> lock(Device::mutex(), std::defer_lock);
+    if (device) lock.lock();
+    if (!map_) {
+      if (device)
+        map_ = make_device_map_store(map_spec_);
+      else
+        map_ = std::make_unique<HostMapStore>(map_spec_, fetch_resident_scan);
+      if (map_track_removed_) mapCheck(map_->trackRemoved(true), "Pipeline: ");
+    }
+    if (device) MADtree::cancelDeviceBuild(0);  // the fold needs the builder's scratch: a look-ahead of another Pipeline gives way
     int64_t added = 0, rows = 0;
     int rc;
-    if (fresh ? kept_cloud_id_ >= 0 : map_id_ >= 0) {
-      DeviceLock lock(Device::mutex());
-      madicp_ctx* ctx = fresh ? Device::ctx() : Device::current(map_generation_);
-      if (!ctx) throw std::logic_error("Pipeline: the device context the map lived in is gone");
-      if (fresh) {
-        if (map_mom_ > 0)
-          check(madicp_map_create_mom(ctx, map_voxel_, first_rows, max_rows, map_with_attr_ ? 1 : 0, map_with_ev_ ? map_ev_ : nullptr, map_mom_,
-                                      &map_id_),
-                "madicp_map_create_mom");
-        else if (map_with_ev_)
-          check(madicp_map_create_ev(ctx, map_voxel_, first_rows, max_rows, map_with_attr_ ? 1 : 0, map_ev_[0], map_ev_[1], map_ev_[2], &map_id_),
-                "madicp_map_create_ev");
-        else if (map_with_attr_)
-          check(madicp_map_create_attr(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create_attr");
-        else
-          check(madicp_map_create(ctx, map_voxel_, first_rows, max_rows, &map_id_), "madicp_map_create");
-        map_generation_ = Device::generation();
-        if (map_track_removed_) check(madicp_map_track_removed(ctx, map_id_, 1), "madicp_map_track_removed");
-      }
-      MADtree::cancelDeviceBuild(0);  // the fold needs the builder's scratch: a look-ahead of another Pipeline gives way
-      int cloud_id = kept_cloud_id_;
-      if (cloud_id < 0) {  // (a host-side scan into a device map: the front-end was switched — its column crosses with it)
-        check(madicp_cloud_upload(ctx, kept_host_[0].data(), static_cast<int64_t>(kept_host_.size()), &cloud_id), "madicp_cloud_upload");
-        if (map_with_attr_ && kept_has_attr_) {
-          const int arc = madicp_cloud_set_attr(ctx, cloud_id, kept_attr_.data(), static_cast<int64_t>(kept_attr_.size()));
-          if (arc != MADICP_OK) {
-            madicp_cloud_release(ctx, cloud_id);
-            check(arc, "madicp_cloud_set_attr");
-          }
-        }
-      }
-      int qrc = MADICP_OK;  // setMapOverlap: what the map knows of this frame, asked before the frame is folded
-      if (map_overlap_)
-        qrc = madicp_map_query_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, map_overlap_reach_, map_overlap_max_dist_, nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, 0, map_frame_overlap_);
-      if (qrc != MADICP_OK && kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
-      check(qrc, "madicp_map_query_cloud");
-      rc = madicp_map_insert_cloud(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, &added, &rows);
+    {
+      // a scan from the other side (the front-end was switched) crosses once — its column with it — for the query, the fold and the clearing
+      ScanBorrow borrow(*map_, keptScan());
+      const ScanRef& scan = borrow.scan();
+      if (map_overlap_)  // setMapOverlap: what the map knows of this frame, asked before the frame is folded
+        mapCheck(map_->query(scan, frame_to_map_.R, frame_to_map_.t, map_overlap_reach_, map_overlap_max_dist_, nullptr, nullptr, nullptr, nullptr,
+                             nullptr, 0, map_frame_overlap_),
+                 "Pipeline: the overlap query: ");
+      rc = map_->insert(scan, frame_to_map_.R, frame_to_map_.t, &added, &rows);
+      if (rc != MADICP_ERR_CAPACITY) mapCheck(rc, "Pipeline: the fold: ");
       // setMapClearing: what the cloud just folded sees through leaves, before the range prune below
-      int64_t removed = 0, mark = 0;
-      int crc = MADICP_OK;
-      if (rc == MADICP_OK && map_clearing_)
-        crc = madicp_map_clear_rays(ctx, map_id_, cloud_id, frame_to_map_.R, frame_to_map_.t, map_clear_origin_, map_clear_margin_,
-                                    static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
-      if (kept_cloud_id_ < 0) madicp_cloud_release(ctx, cloud_id);
-      if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_insert_cloud");
-      if (crc == MADICP_ERR_CAPACITY && map_track_removed_) {  // (the removal log is full: this clearing is skipped, map and mirror agree)
-        map_log_full_ = true;
-      } else {
-        check(crc, "madicp_map_clear_rays");
-      }
-      if (rc == MADICP_OK && map_clearing_ && crc == MADICP_OK) {
-        map_cursor_ = static_cast<size_t>(mark);
-        map_removed_ += static_cast<size_t>(removed);
-      }
-    } else {
-      if (fresh) {
-        map_host_ = std::make_unique<VoxelMap>(map_voxel_, first_rows, max_rows, map_with_attr_, map_with_ev_, map_ev_[0], map_ev_[1], map_ev_[2],
-                                               map_mom_);
-        map_host_->track_removed(map_track_removed_);
-      }
-      ContainerType down;  // (a resident scan into a host map: the front-end was switched — its column crosses with it)
-      std::vector<uint32_t> down_attr;
-      if (kept_cloud_id_ >= 0) {
-        DeviceLock lock(Device::mutex());
-        madicp_ctx* ctx = Device::current(kept_generation_);
-        if (!ctx) throw std::logic_error("Pipeline: the device context the scan lived in is gone");
-        down.resize(kept_n_);
-        check(madicp_cloud_download(ctx, kept_cloud_id_, down[0].data(), static_cast<int64_t>(kept_n_)), "madicp_cloud_download");
-        if (map_with_attr_ && kept_has_attr_) {
-          down_attr.resize(kept_n_);
-          check(madicp_cloud_attr(ctx, kept_cloud_id_, down_attr.data(), static_cast<int64_t>(kept_n_)), "madicp_cloud_attr");
-        }
-      }
-      const ContainerType& c = kept_cloud_id_ >= 0 ? down : kept_host_;
-      const std::vector<uint32_t>& a = kept_cloud_id_ >= 0 ? down_attr : kept_attr_;
-      if (map_overlap_ &&
-          map_host_->query(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, map_overlap_reach_,
-                           map_overlap_max_dist_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, map_frame_overlap_) != MADICP_OK)
-        throw std::runtime_error("Pipeline: the host voxel map refused the overlap query's arguments");
-      rc = map_host_->insert(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t, &added,
-                             &rows, (kept_has_attr_ && a.size() == c.size()) ? a.data() : nullptr);
-      if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline: the host voxel map refused its arguments");
       if (rc == MADICP_OK && map_clearing_) {
         int64_t removed = 0, mark = 0;
-        const int crc = map_host_->clearRays(c.empty() ? nullptr : c[0].data(), static_cast<int64_t>(c.size()), frame_to_map_.R, frame_to_map_.t,
-                                             map_clear_origin_, map_clear_margin_, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
-        if (crc == MADICP_ERR_CAPACITY && map_track_removed_) {  // (the removal log is full: this clearing is skipped)
-          map_log_full_ = true;
-        } else if (crc != MADICP_OK) {
-          throw std::runtime_error("Pipeline: the host voxel map refused the clearing's arguments");
-        } else {
-          map_cursor_ = static_cast<size_t>(mark);
-          map_removed_ += static_cast<size_t>(removed);
-        }
+        const int crc = map_->clearRays(scan, frame_to_map_.R, frame_to_map_.t, map_clear_origin_, map_clear_margin_,
+                                        static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+        settleRemoval(crc, removed, mark);
       }
     }
+    if (device) lock.unlock();
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
     if (rc != MADICP_OK) std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));  // (refused: not folded)
-    if (rc == MADICP_OK && map_with_attr_ && kept_has_attr_) map_attr_type_ = kept_attr_type_;
+    if (rc == MADICP_OK && map_spec_.with_attr && kept_has_attr_) map_attr_type_ = kept_attr_type_;
     // (a) the vehicle has moved a quarter of the range since the last prune: squared distances, fp64 — the poses alone decide
     if (rc == MADICP_OK && map_range_ > 0.0) {
       const double* p = frame_to_map_.t;
@@ -409,36 +348,32 @@ void Pipeline::setMapRange(double radius) {
   map_range_ = radius;
 }
 
-size_t Pipeline::pruneMapAt(const double center[3], double radius) {
-  int64_t removed = 0, rows = 0, mark = 0;
-  int rc = MADICP_OK;
-  if (map_host_) {
-    rc = map_host_->prune(center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
-    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY)
-      throw std::invalid_argument("Pipeline::mapPrune: center must be finite, radius finite and > 0 with a finite square");
-  } else if (map_id_ >= 0) {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapPrune: the device context the map lived in is gone");
-    rc = madicp_map_prune(ctx, map_id_, center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
-    if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapPrune: ") + madicp_last_error());
-    if (!(rc == MADICP_ERR_CAPACITY && map_track_removed_)) check(rc, "madicp_map_prune");
-  } else {  // (no frame folded yet: nothing to remove, but the arguments are held to the same rule)
-    if (map_prune_refusal(center, radius))
-      throw std::invalid_argument("Pipeline::mapPrune: center must be finite, radius finite and > 0 with a finite square");
-    mark = static_cast<int64_t>(map_cursor_);
-  }
-  if (rc == MADICP_ERR_CAPACITY) {  // (the removal log is full: this prune is skipped, map and mirror agree)
+// What every removal ends with — foldFrame's clearing, pruneMapAt, mapClearRays: a removal refused because the log is full is
+// skipped (map and mirror agree, mapRemovedLogFull() says so); any other refusal is an error; else the cursor follows the rows
+// that closed up below it.  Returns the rows removed.
+size_t Pipeline::settleRemoval(int rc, int64_t removed, int64_t mark) {
+  if (rc == MADICP_ERR_CAPACITY && map_track_removed_) {
     map_log_full_ = true;
     return 0;
   }
+  mapCheck(rc, "Pipeline: a removal from the map: ");
   map_cursor_ = static_cast<size_t>(mark);
   map_removed_ += static_cast<size_t>(removed);
   return static_cast<size_t>(removed);
 }
 
+size_t Pipeline::pruneMapAt(const double center[3], double radius) {
+  // (held to the one rule here, so also while no frame has been folded yet: then there is nothing to remove)
+  if (const char* why = map_prune_refusal(center, radius)) throw std::invalid_argument(std::string("Pipeline::mapPrune: ") + why);
+  int64_t removed = 0, rows = 0, mark = static_cast<int64_t>(map_cursor_);
+  int rc = MADICP_OK;
+  if (map_) rc = map_->prune(center, radius, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapPrune: " + map_->lastError());
+  return settleRemoval(rc, removed, mark);
+}
+
 size_t Pipeline::mapPrune(const double center[3], double radius) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapPrune: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapPrune: setMapAccumulation(voxel_size > 0) first");
   if (!center) throw std::invalid_argument("Pipeline::mapPrune: null center");
   return pruneMapAt(center, radius);
 }
@@ -455,33 +390,16 @@ void Pipeline::setMapClearing(bool on, double margin, const double origin[3]) {
 }
 
 size_t Pipeline::mapClearRays(const double* xyz, size_t n, const double R[9], const double t[3], const double origin[3], double margin) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapClearRays: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapClearRays: setMapAccumulation(voxel_size > 0) first");
   if ((!xyz && n > 0) || !R || !t || !origin) throw std::invalid_argument("Pipeline::mapClearRays: null argument");
   if (const char* why = map_clear_refusal(R, t, origin, margin)) throw std::invalid_argument(std::string("Pipeline::mapClearRays: ") + why);
   int64_t removed = 0, rows = 0, mark = static_cast<int64_t>(map_cursor_);
-  int rc = MADICP_OK;
-  if (map_host_) {
-    rc = map_host_->clearRays(xyz, static_cast<int64_t>(n), R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
-    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY)
-      throw std::invalid_argument("Pipeline::mapClearRays: the host voxel map refused its arguments");
-  } else if (map_id_ >= 0 && n > 0) {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapClearRays: the device context the map lived in is gone");
-    int cloud_id = -1;
-    check(madicp_cloud_upload(ctx, xyz, static_cast<int64_t>(n), &cloud_id), "madicp_cloud_upload");
-    rc = madicp_map_clear_rays(ctx, map_id_, cloud_id, R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed, &rows, &mark);
-    madicp_cloud_release(ctx, cloud_id);
-    if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapClearRays: ") + madicp_last_error());
-    if (!(rc == MADICP_ERR_CAPACITY && map_track_removed_)) check(rc, "madicp_map_clear_rays");
-  }  // (no frame folded yet, or no ray: nothing to remove)
-  if (rc == MADICP_ERR_CAPACITY) {  // (the removal log is full: this clearing is skipped)
-    map_log_full_ = true;
-    return 0;
-  }
-  map_cursor_ = static_cast<size_t>(mark);
-  map_removed_ += static_cast<size_t>(removed);
-  return static_cast<size_t>(removed);
+  int rc = MADICP_OK;  // (no frame folded yet: nothing to remove)
+  if (map_)
+    rc = map_->clearRays(ScanRef::host(xyz, nullptr, static_cast<int64_t>(n)), R, t, origin, margin, static_cast<int64_t>(map_cursor_), &removed,
+                         &rows, &mark);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapClearRays: " + map_->lastError());
+  return settleRemoval(rc, removed, mark);
 }
 
 void Pipeline::setMapOverlap(bool on, int reach, double max_dist) {
@@ -495,40 +413,35 @@ void Pipeline::setMapOverlap(bool on, int reach, double max_dist) {
 
 void Pipeline::mapQuery(const double* xyz, size_t n, const double R[9], const double t[3], int reach, double max_dist, int32_t* row, double* d2,
                         uint64_t* keys, uint32_t* attr, uint32_t* ev, uint64_t counts[3]) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapQuery: setMapAccumulation(voxel_size > 0) first");
-  if (attr && !map_with_attr_)
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapQuery: setMapAccumulation(voxel_size > 0) first");
+  if (attr && !map_spec_.with_attr)
     throw std::logic_error("Pipeline::mapQuery: the map was made without the attribute (setMapAccumulation's with_attribute)");
-  if (ev && !map_with_ev_) throw std::logic_error("Pipeline::mapQuery: the map was made without evidence (setMapAccumulation's evidence)");
+  if (ev && !map_spec_.with_ev) throw std::logic_error("Pipeline::mapQuery: the map was made without evidence (setMapAccumulation's evidence)");
   if ((!xyz && n > 0) || !R || !t || !counts) throw std::invalid_argument("Pipeline::mapQuery: null argument");
   if (n > static_cast<size_t>(kMapMaxRows)) throw std::invalid_argument("Pipeline::mapQuery: at most 2^30 points");
   if (const char* why = map_query_refusal(R, t, reach, max_dist)) throw std::invalid_argument(std::string("Pipeline::mapQuery: ") + why);
-  const int64_t n64 = static_cast<int64_t>(n);
-  if (map_host_ || map_id_ < 0 || n == 0) {  // the host twin; before the first fold and for no point at all: an empty map of the same kind
-    const VoxelMap empty(map_voxel_, 1, 1, map_with_attr_, map_with_ev_);
-    if ((map_host_ ? *map_host_ : empty).query(xyz, n64, R, t, reach, max_dist, row, d2, keys, attr, ev, n64, counts) != MADICP_OK)
-      throw std::invalid_argument("Pipeline::mapQuery: the host voxel map refused its arguments");
-    return;
+  std::unique_ptr<MapStore> empty;  // before the first fold and for no point at all: an empty host map of the same kind answers
+  if (!map_ || n == 0) {
+    MapSpec kind = map_spec_;
+    kind.first_rows = kind.max_rows = 1;
+    empty = std::make_unique<HostMapStore>(kind);
   }
-  DeviceLock lock(Device::mutex());
-  madicp_ctx* ctx = Device::current(map_generation_);
-  if (!ctx) throw std::logic_error("Pipeline::mapQuery: the device context the map lived in is gone");
-  int cloud_id = -1;
-  check(madicp_cloud_upload(ctx, xyz, n64, &cloud_id), "madicp_cloud_upload");
-  const int rc = madicp_map_query_cloud(ctx, map_id_, cloud_id, R, t, reach, max_dist, row, d2, keys, attr, ev, n64, counts);
-  madicp_cloud_release(ctx, cloud_id);
-  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument(std::string("Pipeline::mapQuery: ") + madicp_last_error());
-  check(rc, "madicp_map_query_cloud");
+  MapStore& map = empty ? *empty : *map_;
+  const int64_t n64 = static_cast<int64_t>(n);
+  const int rc = map.query(ScanRef::host(xyz, nullptr, n64), R, t, reach, max_dist, row, d2, keys, attr, ev, n64, counts);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapQuery: " + map.lastError());
+  if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapQuery: " + map.lastError());
 }
 
 size_t Pipeline::mapNewRowCount() {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapNewRows: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapNewRows: setMapAccumulation(voxel_size > 0) first");
   return mapSize() - map_cursor_;
 }
 
 size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr, uint64_t* out_keys) {
   const size_t m = mapNewRowCount();
   if (!out) throw std::invalid_argument("Pipeline::mapNewRows: null buffer");
-  if (out_attr && !map_with_attr_)
+  if (out_attr && !map_spec_.with_attr)
     throw std::logic_error("Pipeline::mapNewRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
   if (capacity < m)
     throw std::invalid_argument("Pipeline::mapNewRows: the buffer holds " + std::to_string(capacity) + " rows, " + std::to_string(m) +
@@ -536,18 +449,12 @@ size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr, uin
   if (m == 0) return 0;
   size_t got = 0;
   if (out_keys || out_attr) {  // more than one column: through the one call — on the device, their copies in front of ONE wait
+    MapColumns cols;
+    cols.xyz = out;
+    cols.keys = out_keys;
+    cols.attr = out_attr;
     int64_t rows = 0;
-    if (map_host_) {
-      if (map_host_->download_rows(static_cast<int64_t>(map_cursor_), out, out_keys, out_attr, static_cast<int64_t>(capacity), &rows) != MADICP_OK)
-        throw std::runtime_error("Pipeline::mapNewRows: the host voxel map refused its arguments");
-    } else {
-      DeviceLock lock(Device::mutex());
-      madicp_ctx* ctx = Device::current(map_generation_);
-      if (!ctx) throw std::logic_error("Pipeline::mapNewRows: the device context the map lived in is gone");
-      check(madicp_map_download_rows(ctx, map_id_, static_cast<int64_t>(map_cursor_), out, out_keys, out_attr, static_cast<int64_t>(capacity),
-                                     &rows),
-            "madicp_map_download_rows");
-    }
+    mapCheck(map_->download(static_cast<int64_t>(map_cursor_), cols, static_cast<int64_t>(capacity), &rows), "Pipeline::mapNewRows: ");
     got = static_cast<size_t>(rows);
   } else {
     got = mapCloud(out, capacity, map_cursor_);
@@ -557,28 +464,24 @@ size_t Pipeline::mapNewRows(float* out, size_t capacity, uint32_t* out_attr, uin
 }
 
 // ---- the window downloads (pipeline.h: mapCloud .. mapSurfels) ------------------------------------------------------------------
-template <class Host, class Dev>
-size_t Pipeline::mapWindow(const char* name, const char* missing, const void* out, const char* holds, size_t capacity, size_t first_row,
-                           const char* entry, Host host, Dev dev) {
-  const std::string who = std::string("Pipeline::") + name + ": ";
-  if (map_voxel_ == 0.0) throw std::logic_error(who + "setMapAccumulation(voxel_size > 0) first");
+bool Pipeline::mapWindow(const std::string& who, const char* missing, const void* out, const char* holds, size_t capacity, size_t first_row) {
+  if (map_spec_.voxel == 0.0) throw std::logic_error(who + "setMapAccumulation(voxel_size > 0) first");
   if (missing) throw std::logic_error(who + missing);
   if (!out) throw std::invalid_argument(who + "null buffer");
   const size_t size = mapSize();
   if (first_row > size) throw std::invalid_argument(who + "first_row is beyond the map's " + std::to_string(size) + " rows");
   if (capacity < size - first_row)
     throw std::invalid_argument(who + holds + " " + std::to_string(capacity) + " rows, the window needs " + std::to_string(size - first_row));
-  if (size == first_row) return 0;
-  const int64_t first = static_cast<int64_t>(first_row), cap = static_cast<int64_t>(capacity);
+  return size > first_row;
+}
+template <class T>
+size_t Pipeline::mapColumn(const char* name, const char* missing, T* MapColumns::*column, T* out, size_t capacity, size_t first_row) {
+  const std::string who = std::string("Pipeline::") + name + ": ";
+  if (!mapWindow(who, missing, out, "the buffer holds", capacity, first_row)) return 0;
+  MapColumns cols;
+  cols.*column = out;
   int64_t rows = 0;
-  if (map_host_) {
-    if (host(*map_host_, first, cap, &rows) != MADICP_OK) throw std::runtime_error(who + "the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error(who + "the device context the map lived in is gone");
-    check(dev(ctx, first, cap, &rows), entry);
-  }
+  mapCheck(map_->download(static_cast<int64_t>(first_row), cols, static_cast<int64_t>(capacity), &rows), who);
   return static_cast<size_t>(rows);
 }
 namespace {
@@ -588,68 +491,41 @@ constexpr const char* kNoMapMoments = "the map was made without moments (setMapA
 }  // namespace
 
 size_t Pipeline::mapKeys(uint64_t* out, size_t capacity, size_t first_row) {
-  return mapWindow(
-      "mapKeys", nullptr, out, "the buffer holds", capacity, first_row, "madicp_map_download_keys",
-      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_keys(first, out, cap, n); },
-      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_keys(ctx, map_id_, first, out, cap, n); });
+  return mapColumn("mapKeys", nullptr, &MapColumns::keys, out, capacity, first_row);
 }
 size_t Pipeline::mapCloud(float* out, size_t capacity, size_t first_row) {
-  return mapWindow(
-      "mapCloud", nullptr, out, "the buffer holds", capacity, first_row, "madicp_map_download_f32",
-      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download(first, out, cap, n); },
-      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_f32(ctx, map_id_, first, out, cap, n); });
+  return mapColumn("mapCloud", nullptr, &MapColumns::xyz, out, capacity, first_row);
 }
 size_t Pipeline::mapAttribute(uint32_t* out, size_t capacity, size_t first_row) {
-  return mapWindow(
-      "mapAttribute", map_with_attr_ ? nullptr : kNoMapAttr, out, "the buffer holds", capacity, first_row, "madicp_map_download_attr",
-      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_attr(first, out, cap, n); },
-      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_attr(ctx, map_id_, first, out, cap, n); });
+  return mapColumn("mapAttribute", map_spec_.with_attr ? nullptr : kNoMapAttr, &MapColumns::attr, out, capacity, first_row);
 }
 size_t Pipeline::mapEvidence(uint32_t* out, size_t capacity, size_t first_row) {
-  return mapWindow(
-      "mapEvidence", map_with_ev_ ? nullptr : kNoMapEvidence, out, "the buffer holds", capacity, first_row, "madicp_map_download_evidence",
-      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_evidence(first, out, cap, n); },
-      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_evidence(ctx, map_id_, first, out, cap, n); });
+  return mapColumn("mapEvidence", map_spec_.with_ev ? nullptr : kNoMapEvidence, &MapColumns::ev, out, capacity, first_row);
 }
 size_t Pipeline::mapMoments(uint64_t* out, size_t capacity, size_t first_row) {
-  return mapWindow(
-      "mapMoments", map_mom_ ? nullptr : kNoMapMoments, out, "the buffer holds", capacity, first_row, "madicp_map_download_moments",
-      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_moments(first, out, cap, n); },
-      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) { return madicp_map_download_moments(ctx, map_id_, first, out, cap, n); });
+  return mapColumn("mapMoments", map_spec_.mom ? nullptr : kNoMapMoments, &MapColumns::moments, out, capacity, first_row);
 }
 size_t Pipeline::mapSurfels(float* centroid, float* normal, float* eig, uint32_t* count, size_t capacity, size_t first_row) {
-  return mapWindow(
-      "mapSurfels", map_mom_ ? nullptr : kNoMapMoments, centroid, "the buffers hold", capacity, first_row, "madicp_map_download_surfels",
-      [&](VoxelMap& h, int64_t first, int64_t cap, int64_t* n) { return h.download_surfels(first, centroid, normal, eig, count, cap, n); },
-      [&](madicp_ctx* ctx, int64_t first, int64_t cap, int64_t* n) {
-        return madicp_map_download_surfels(ctx, map_id_, first, centroid, normal, eig, count, cap, n);
-      });
+  const std::string who = "Pipeline::mapSurfels: ";
+  if (!mapWindow(who, map_spec_.mom ? nullptr : kNoMapMoments, centroid, "the buffers hold", capacity, first_row)) return 0;
+  int64_t rows = 0;
+  mapCheck(map_->downloadSurfels(static_cast<int64_t>(first_row), centroid, normal, eig, count, static_cast<int64_t>(capacity), &rows), who);
+  return static_cast<size_t>(rows);
 }
 
 // ---- the removal log (pipeline.h: setMapTrackRemoved) -------------------------------------------------------------------------
 void Pipeline::setMapTrackRemoved(bool on) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::setMapTrackRemoved: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::setMapTrackRemoved: setMapAccumulation(voxel_size > 0) first");
   if (on == map_track_removed_) return;
-  if (map_host_) map_host_->track_removed(on);
-  if (map_id_ >= 0) {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::setMapTrackRemoved: the device context the map lived in is gone");
-    check(madicp_map_track_removed(ctx, map_id_, on ? 1 : 0), "madicp_map_track_removed");
-  }
+  if (map_) mapCheck(map_->trackRemoved(on), "Pipeline::setMapTrackRemoved: ");
   map_track_removed_ = on;
   if (!on) map_log_full_ = false;
 }
 
 size_t Pipeline::mapRemovedRowCount() {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapRemovedRows: setMapAccumulation(voxel_size > 0) first");
-  if (map_host_) return static_cast<size_t>(map_host_->removed_count());
-  if (map_id_ < 0) return 0;  // (no frame folded yet)
-  DeviceLock lock(Device::mutex());
-  madicp_ctx* ctx = Device::current(map_generation_);
-  if (!ctx) throw std::logic_error("Pipeline::mapRemovedRows: the device context the map lived in is gone");
-  int64_t n = 0;
-  check(madicp_map_removed_count(ctx, map_id_, &n), "madicp_map_removed_count");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapRemovedRows: setMapAccumulation(voxel_size > 0) first");
+  int64_t n = 0;  // (no frame folded yet: none)
+  if (map_) mapCheck(map_->removedCount(&n), "Pipeline::mapRemovedRows: ");
   return static_cast<size_t>(n);
 }
 
@@ -657,7 +533,7 @@ size_t Pipeline::mapRemovedRows(uint64_t* keys, float* rows, uint32_t* attr, siz
   const size_t m = mapRemovedRowCount();
   if (!map_track_removed_) throw std::logic_error("Pipeline::mapRemovedRows: setMapTrackRemoved(true) first");
   if (!keys || !rows) throw std::invalid_argument("Pipeline::mapRemovedRows: null buffer");
-  if (attr && !map_with_attr_)
+  if (attr && !map_spec_.with_attr)
     throw std::logic_error("Pipeline::mapRemovedRows: the map was made without the attribute (setMapAccumulation's with_attribute)");
   if (capacity < m)
     throw std::invalid_argument("Pipeline::mapRemovedRows: the buffers hold " + std::to_string(capacity) + " rows, the log has " +
@@ -665,67 +541,40 @@ size_t Pipeline::mapRemovedRows(uint64_t* keys, float* rows, uint32_t* attr, siz
   map_log_full_ = false;
   if (m == 0) return 0;
   int64_t n = 0;
-  if (map_host_) {
-    if (map_host_->take_removed(keys, rows, attr, static_cast<int64_t>(capacity), &n) != MADICP_OK)
-      throw std::runtime_error("Pipeline::mapRemovedRows: the host voxel map refused its arguments");
-  } else {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapRemovedRows: the device context the map lived in is gone");
-    check(madicp_map_take_removed(ctx, map_id_, keys, rows, attr, static_cast<int64_t>(capacity), &n), "madicp_map_take_removed");
-  }
+  mapCheck(map_->takeRemoved(keys, rows, attr, static_cast<int64_t>(capacity), &n), "Pipeline::mapRemovedRows: ");
   return static_cast<size_t>(n);
 }
 
 size_t Pipeline::mapSize() {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapSize: setMapAccumulation(voxel_size > 0) first");
-  if (map_host_) return static_cast<size_t>(map_host_->size());
-  if (map_id_ < 0) return 0;  // (no frame folded yet)
-  DeviceLock lock(Device::mutex());
-  madicp_ctx* ctx = Device::current(map_generation_);
-  if (!ctx) throw std::logic_error("Pipeline::mapSize: the device context the map lived in is gone");
-  int64_t rows = 0;
-  check(madicp_map_size(ctx, map_id_, &rows), "madicp_map_size");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapSize: setMapAccumulation(voxel_size > 0) first");
+  int64_t rows = 0;  // (no frame folded yet: none)
+  if (map_) mapCheck(map_->size(&rows), "Pipeline::mapSize: ");
   return static_cast<size_t>(rows);
 }
 
 size_t Pipeline::mapConfirmed(uint32_t min_evidence, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, size_t capacity) {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::mapConfirmed: setMapAccumulation(voxel_size > 0) first");
-  if (!map_with_ev_) throw std::logic_error("Pipeline::mapConfirmed: the map was made without evidence (setMapAccumulation's evidence)");
-  if (out_attr && !map_with_attr_)
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapConfirmed: setMapAccumulation(voxel_size > 0) first");
+  if (!map_spec_.with_ev) throw std::logic_error("Pipeline::mapConfirmed: the map was made without evidence (setMapAccumulation's evidence)");
+  if (out_attr && !map_spec_.with_attr)
     throw std::logic_error("Pipeline::mapConfirmed: the map was made without the attribute (setMapAccumulation's with_attribute)");
   if (!out_xyz) throw std::invalid_argument("Pipeline::mapConfirmed: null buffer");
   int64_t rows = 0;
-  int rc = MADICP_OK;
-  if (map_host_) {
-    rc = map_host_->download_min_evidence(min_evidence, out_xyz, out_keys, out_attr, out_ev, static_cast<int64_t>(capacity), &rows);
-    if (rc != MADICP_OK && rc != MADICP_ERR_CAPACITY) throw std::runtime_error("Pipeline::mapConfirmed: the host voxel map refused its arguments");
-  } else if (map_id_ >= 0) {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::mapConfirmed: the device context the map lived in is gone");
-    rc = madicp_map_download_min_evidence(ctx, map_id_, min_evidence, out_xyz, out_keys, out_attr, out_ev, static_cast<int64_t>(capacity), &rows);
-    if (rc != MADICP_ERR_CAPACITY) check(rc, "madicp_map_download_min_evidence");
-  }
+  int rc = MADICP_OK;  // (no frame folded yet: none qualifies)
+  if (map_) rc = map_->downloadMinEvidence(min_evidence, out_xyz, out_keys, out_attr, out_ev, static_cast<int64_t>(capacity), &rows);
   if (rc == MADICP_ERR_CAPACITY)
     throw std::invalid_argument("Pipeline::mapConfirmed: the buffers hold " + std::to_string(capacity) + " rows, " + std::to_string(rows) +
                                 " qualify");
+  mapCheck(rc, "Pipeline::mapConfirmed: ");
   return static_cast<size_t>(rows);
 }
 
 void Pipeline::clearMap() {
-  if (map_voxel_ == 0.0) throw std::logic_error("Pipeline::clearMap: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::clearMap: setMapAccumulation(voxel_size > 0) first");
   map_overflowed_ = false;
   map_have_center_ = false;
   map_cursor_ = map_removed_ = 0;
   map_log_full_ = false;
-  if (map_host_) map_host_->clear();
-  if (map_id_ >= 0) {
-    DeviceLock lock(Device::mutex());
-    madicp_ctx* ctx = Device::current(map_generation_);
-    if (!ctx) throw std::logic_error("Pipeline::clearMap: the device context the map lived in is gone");
-    check(madicp_map_clear(ctx, map_id_), "madicp_map_clear");
-  }
+  if (map_) mapCheck(map_->clear(), "Pipeline::clearMap: ");
 }
 
 size_t Pipeline::registeredScan(float* out, size_t capacity, double voxel, bool map_frame) {
@@ -836,7 +685,7 @@ void Pipeline::prefetchView(const Vector3d* next_cloud, size_t n) {
     // the tree is built on the GPU — a host build would only compete for the CPU — and the look-ahead is the library's:
     // collect the construction in flight (the scan about to be consumed), start this one beside the coming registration
     if (deskew_) return;  // (the tree needs the previous pose)
-    if (keep_scan_ || map_voxel_ > 0.0) return;  // (a look-ahead build gives back the tree alone, not the scan: pipeline.h, setKeepScan)
+    if (keep_scan_ || map_spec_.voxel > 0.0) return;  // (a look-ahead build gives back the tree alone, not the scan: pipeline.h, setKeepScan)
     // begun by the next compute(), behind its registration's submission; assign() into a buffer that lives as long as the
     // Pipeline: after the first frames no allocation, no fresh pages
     dev_next_cloud_.assign(next_cloud, next_cloud + n);
@@ -909,7 +758,7 @@ std::unique_ptr<MADtree> Pipeline::buildOnDevice(int cloud_id, const double* sta
   }
   // retained instead (map accumulation alone: until the frame's fold): the buffer goes back to the pool when the next frame,
   // setKeepScan(false) or the end drops it
-  if (keep_scan_ || map_voxel_ > 0.0) {
+  if (keep_scan_ || map_spec_.voxel > 0.0) {
     int64_t n = 0;
     check(madicp_cloud_size(ctx, cloud_id, &n), "madicp_cloud_size");
     kept_cloud_id_ = cloud_id;

@@ -38,7 +38,7 @@
 
 #include "deskew.h"
 #include "ingest_records.h"
-#include "voxel_map.h"
+#include "map_store.h"
 #include "keyframe_ledger.h"
 #include "linalg.h"
 #include "mad_icp.h"
@@ -187,16 +187,16 @@ class Pipeline {
   // sign free), the covariance's eigenvalues in m^2 ascending (3 floats) and the count — computed where the map lives
   // (madicp_map_download_surfels); the same refusals.  Both: std::logic_error while accumulation is off or without the moments.
   // The removal log and MapMirror carry no moments — a row's change after it was delivered: a consumer re-reads mapSurfels.
-  bool mapWithMoments() const { return map_voxel_ > 0.0 && map_mom_ > 0; }
+  bool mapWithMoments() const { return map_spec_.mom > 0; }
   size_t mapMoments(uint64_t* out, size_t capacity, size_t first_row = 0);
   size_t mapSurfels(float* centroid, float* normal, float* eig, uint32_t* count, size_t capacity, size_t first_row = 0);
-  bool mapWithEvidence() const { return map_voxel_ > 0.0 && map_with_ev_; }
+  bool mapWithEvidence() const { return map_spec_.with_ev; }
   size_t mapEvidence(uint32_t* out, size_t capacity, size_t first_row = 0);
   size_t mapConfirmed(uint32_t min_evidence, float* out_xyz, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, size_t capacity);
-  bool mapWithAttribute() const { return map_voxel_ > 0.0 && map_with_attr_; }
+  bool mapWithAttribute() const { return map_spec_.with_attr; }
   int mapAttributeType() const { return map_attr_type_; }  // the field type of the last attribute frame folded (kAttrNone: none yet)
   size_t mapAttribute(uint32_t* out, size_t capacity, size_t first_row = 0);
-  double mapVoxelSize() const { return map_voxel_; }  // 0: off
+  double mapVoxelSize() const { return map_spec_.voxel; }  // 0: off
   bool mapOverflowed() const { return map_overflowed_; }
   size_t mapSize();  // rows the map holds; std::logic_error while the option is off (mapCloud and clearMap too)
   // rows [first_row, mapSize()) as float32 (x, y, z) into out[0, 3 * capacity): rows are never changed or removed by a fold, so
@@ -442,23 +442,24 @@ class Pipeline {
   void permuteFrameAttr(const DeskewOrder& order);  // host azimuth deskew: the column follows the points
   void dropKeptScan();                        // forget it; the device buffer goes back to the pool
   void keepHostScan(const ContainerType& c);  // host front-end: the copy, when the option (or map accumulation) is on
-  // map accumulation (setMapAccumulation): the map lives where the first folded cloud did — a device map of the context generation
-  // that issued its id, or the host twin; a cloud from the other side (the front-end was switched) crosses over for its fold
-  double map_voxel_ = 0.0;
-  bool map_keyframes_only_ = false, map_overflowed_ = false, map_with_attr_ = false, map_with_ev_ = false;
-  uint32_t map_ev_[3] = {1, 1, 1};  // hit, miss, cap (setMapAccumulation's evidence)
-  uint32_t map_mom_ = 0;            // moments_max_count (0: no moments)
+  // map accumulation (setMapAccumulation): map_spec_ is what the map is made from (voxel 0: off), map_ the map itself — one
+  // MapStore (map_store.h), null until the first frame is folded.  foldFrame decides where it lives, once: a fresh map goes where
+  // that frame's scan does — the device map, with its id and context generation inside the store, or the host twin.  From then on
+  // the retained scan reaches the store as a ScanRef (keptScan) and, when the front-end was switched and it lies on the other
+  // side, crosses once per frame through a ScanBorrow, its column with it.  No method below knows which side the map is on.
+  MapSpec map_spec_;
+  bool map_keyframes_only_ = false, map_overflowed_ = false;
   int map_attr_type_ = 0;
-  size_t map_max_points_ = kMapMaxPointsDefault;
-  int map_id_ = -1;
-  unsigned map_generation_ = 0;
-  std::unique_ptr<VoxelMap> map_host_;
+  std::unique_ptr<MapStore> map_;
   void dropMap();
-  // (pipeline.cpp only) what mapCloud .. mapSurfels share: the refusals, in `name`'s name (missing: why the map lacks the column asked
-  // for, or null), then the rows of the window from the host twin (host) or the device map (dev, the C entry point `entry`)
-  template <class Host, class Dev>
-  size_t mapWindow(const char* name, const char* missing, const void* out, const char* holds, size_t capacity, size_t first_row,
-                   const char* entry, Host host, Dev dev);
+  ScanRef keptScan() const;                                // the retained scan, where it lies
+  void mapCheck(int rc, const std::string& who) const;     // a refusal of the store: std::runtime_error, `who` + the store's reason
+  size_t settleRemoval(int rc, int64_t removed, int64_t mark);  // the log-full / cursor / mapRemoved() rule of every removal
+  // what mapCloud .. mapSurfels share: the refusals, in `who`'s name (missing: why the map lacks the column asked for, or null);
+  // false: the window is empty.  mapColumn (pipeline.cpp only): then the rows of the window, one column of MapColumns, from the store
+  bool mapWindow(const std::string& who, const char* missing, const void* out, const char* holds, size_t capacity, size_t first_row);
+  template <class T>
+  size_t mapColumn(const char* name, const char* missing, T* MapColumns::*column, T* out, size_t capacity, size_t first_row);
   // setMapRange: the centre of the last prune and the position of the frame before this one (foldFrame's policy), the consumer's
   // cursor (mapNewRows) and the rows removed so far
   double map_range_ = 0.0;
@@ -472,7 +473,7 @@ class Pipeline {
   int map_overlap_reach_ = 1;
   double map_overlap_max_dist_ = kQueryNoDistance;
   uint64_t map_frame_overlap_[3] = {0, 0, 0};
-  size_t pruneMapAt(const double center[3], double radius);  // madicp_map_prune / VoxelMap::prune with the cursor as watermark
+  size_t pruneMapAt(const double center[3], double radius);  // MapStore::prune with the cursor as watermark (mapPrune's refusals; 0 before the first fold)
   void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;
   int last_rounds_ = 0;

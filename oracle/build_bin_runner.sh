@@ -25,5 +25,6 @@ g++ -O3 -std=c++17 -fopenmp -ffp-contract=off -DNDEBUG -DMADICP_STANDIN_TYPES_ON
   -I"$HERE/bin_runner_shim" -I"$HERE/eigen_standin" -I"$APP" -I"$ROOT/include" -I"$HOST" \
   "$APP/bin_runner.cpp" \
   "$HOST/tree_builder.cpp" "$HOST/mad_tree.cpp" "$HOST/mad_icp.cpp" "$HOST/vel_estimator.cpp" "$HOST/pipeline.cpp" "$HOST/deskew.cpp" \
+  "$HOST/device_map_store.cpp" \
   -o "$OUT/bin_runner" -L"$ROOT/mad_icp_amd" -lmadicp_hip -Wl,-rpath,'$ORIGIN/../../mad_icp_amd' -pthread
 echo "build_bin_runner.sh: $OUT/bin_runner (reference caller from $APP, product host layer in its Eigen-typed mode, libmadicp_hip.so)"
