@@ -606,6 +606,36 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                            change) gets a transient one in the call's scratch first (fe::map_slot_rows, one lane per row).  The
  *                            scratch is the call's own, pooled: the builder's is not touched (legal while a look-ahead build is in
  *                            flight).  One host synchronisation, whatever n and M.
+ * REGISTER.  madicp_map_register_cloud gives the pose that FITS a resident cloud to a moments map: `iterations` rounds of
+ * point-to-plane Gauss-Newton against the map's surfels, all on the device.  The rule (one source with the host twin:
+ * csrc/common/map_align.h), fp64 and integers only, no contraction, no library function in the linearisation:
+ *   the surfel columns are those of madicp_map_download_surfels, bit for bit — the call runs fe::map_surfels itself, ONCE per call,
+ *   into its own scratch.  Point i at pose (R, t): q and the candidate decision as in the query; its row j is the QUERY's answer at
+ *   params->reach; matched iff j >= 0, within iff also d2 <= max_dist max_dist; an INLIER iff within, count[j] >= min_count,
+ *   (double)eig[j][1] > 0 and (double)eig[j][0] <= flat (double)eig[j][1].  For an inlier, with c, n the float32 centroid and normal
+ *   taken to double: e = n0 (q0 - c0) + (n1 (q1 - c1) + n2 (q2 - c2)); m = n^T R (each entry x0 + (x1 + x2)); J = [m, p x m] — the
+ *   reference's Jacobian for the right-multiplied update; s = |e| > rho ? rho / |e| : 1 (rho = +inf: no robust kernel); 28 terms
+ *   H(r, c) = (s J[r]) J[c] (r >= c, packed column by column), b[r] = (s J[r]) e, chi2 = (s e) e.  Every other point adds +0.0.
+ *   THE SUM is the adjacent-pair binary tree over the term vectors in point order, padded with +0.0 to a power of two — a function
+ *   of (map, cloud, pose, parameters) alone, whatever the launch geometry; numpy reproduces it with reshapes.  No float atomics.
+ *   Round k linearises at X_k and takes X_{k+1} from the product's one update step (solve_pose: dx = H^-1 (-b), X <- X * dX); an
+ *   all-zero H leaves the pose where it is.
+ *   out_trace ((iterations + 1) x 40 doubles): row k = X_k (R row-major, t) | H (21, packed) | b (6) | chi2 of the linearisation at
+ *   X_k; row `iterations` is the one at the RETURNED pose — its H is the information a consumer wants beside the pose.
+ *   out_counts ((iterations + 1) x 4): candidates, matched, within, inliers of the same linearisations.
+ *   iterations = 0 is the LINEARISE-ONLY form, the only one in which out_row (int32) / out_e (float64, +0.0 for a point that is no
+ *   inlier) may be given: n entries each.
+ *   madicp_map_register_cloud  MADICP_ERR_INVALID, nothing written and nothing launched, for a null ctx, R, t, params, out_R, out_t,
+ *                            out_trace or out_counts, an unknown id, a map without moments, a non-finite R or t, a reach other
+ *                            than 0 and 1, a max_dist that is NaN or negative, a rho that is NaN or <= 0, a min_count below 3, a
+ *                            flat outside (0, 1], iterations outside 0 .. 64, a per-point buffer with iterations > 0;
+ *                            MADICP_ERR_CAPACITY, the same, when a per-point buffer is given and capacity_points < n.  An empty
+ *                            map is legal: every point is unmatched, the sums are zero, the pose comes back as given.  The map
+ *                            is only read.  Kernels: fe::map_surfels; per round fe::map_align_terms (one lane per point, a
+ *                            workgroup per 256 consecutive points, the terms in registers: a wavefront butterfly and two levels
+ *                            in LDS), fe::map_align_join (256 partial rows per workgroup until one is left) and
+ *                            fe::map_align_step (one wavefront); one closing linearisation; the copies.  Everything on the copy
+ *                            stream, the scratch the call's own, pooled.  ONE host synchronisation, whatever n, M and iterations.
  * Several maps per context are independent.  Bit-equal to madicp_host_map_* (madicp_host.h) for every sequence of folds, prunes,
  * clearings, takes and queries. */
 int madicp_map_create(madicp_ctx* ctx, double voxel, int64_t initial_rows, int64_t max_rows, int* out_map_id);
@@ -639,6 +669,21 @@ int madicp_map_download_surfels(madicp_ctx* ctx, int map_id, int64_t first_row, 
 int madicp_map_query_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3], int reach, double max_dist,
                            int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
                            int64_t capacity_points, uint64_t out_counts[3]);
+#ifndef MADICP_MAP_ALIGN_PARAMS_DEFINED
+#define MADICP_MAP_ALIGN_PARAMS_DEFINED
+typedef struct {
+  int reach;          /* 0: the point's own voxel, 1: the 27 around it */
+  double max_dist;    /* >= 0, +inf legal */
+  double rho;         /* > 0, +inf: no robust kernel */
+  uint32_t min_count; /* >= 3 */
+  double flat;        /* in (0, 1]: eig0 <= flat eig1 */
+} madicp_map_align_params;
+#endif
+int madicp_map_register_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3],
+                              const madicp_map_align_params* params, int iterations, double out_R[9], double out_t[3],
+                              double* out_trace /* (iterations + 1) x 40: X[12] | H[21] | b[6] | chi2 */,
+                              uint64_t* out_counts /* (iterations + 1) x 4 */, int32_t* out_row, double* out_e,
+                              int64_t capacity_points);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

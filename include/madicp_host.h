@@ -161,7 +161,24 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  (R, t), the row with the smallest (d2, row) among the rows whose stored key is a cell of the point's
  *                  neighbourhood (reach 0: its own cell, 1: the 27 around it); out_row / out_d2 / out_keys / out_attr / out_ev
  *                  null where not wanted, out_counts = {candidates, matched, within max_dist}.  The map is only read.  The same
- *                  refusals and codes, nothing written; xyz may be null when n == 0.  Every output bit-equal to the device's. */
+ *                  refusals and codes, nothing written; xyz may be null when n == 0.  Every output bit-equal to the device's.
+ *   _register      the twin of madicp_map_register_cloud (madicp_hip.h and csrc/common/map_align.h have the rule): `iterations`
+ *                  rounds of point-to-plane Gauss-Newton of the n points of xyz against the map's surfels — its own map_surfel of
+ *                  every row, computed once per call — the same gates, terms and adjacent-pair tree sum; the step is the host's
+ *                  LDLT solve and exponential.  Trace, counts, out_row / out_e (iterations == 0 only) as on the device, the same
+ *                  refusals and codes, nothing written.  n == 0 is legal here (xyz may then be null): zero sums, the pose as
+ *                  given.  Fed the same surfel bits the sums are bit-equal to the device's; the surfels' normals and eigenvalues
+ *                  agree to the last bits only, and so do poses: within the pose contract, not to the bit. */
+#ifndef MADICP_MAP_ALIGN_PARAMS_DEFINED
+#define MADICP_MAP_ALIGN_PARAMS_DEFINED
+typedef struct {
+  int reach;          /* 0: the point's own voxel, 1: the 27 around it */
+  double max_dist;    /* >= 0, +inf legal */
+  double rho;         /* > 0, +inf: no robust kernel */
+  uint32_t min_count; /* >= 3 */
+  double flat;        /* in (0, 1]: eig0 <= flat eig1 */
+} madicp_map_align_params;
+#endif
 typedef struct madicp_host_map madicp_host_map;
 int madicp_host_map_create(double voxel, int64_t initial_rows, int64_t max_rows, madicp_host_map** out_map);
 int madicp_host_map_insert(madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int64_t* out_added,
@@ -197,6 +214,9 @@ int madicp_host_map_download_surfels(const madicp_host_map* map, int64_t first_r
 int madicp_host_map_query(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int reach,
                           double max_dist, int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
                           int64_t capacity_points, uint64_t out_counts[3]);
+int madicp_host_map_register(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
+                             const madicp_map_align_params* params, int iterations, double out_R[9], double out_t[3],
+                             double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

@@ -47,8 +47,13 @@ class AttrFieldC(C.Structure):
     _fields_ = [("offset", C.c_int32), ("type", C.c_int32)]
 
 
+class MapAlignParams(C.Structure):
+    """madicp_map_align_params (include/madicp_hip.h, include/madicp_host.h)"""
+    _fields_ = [("reach", C.c_int), ("max_dist", C.c_double), ("rho", C.c_double), ("min_count", C.c_uint32), ("flat", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int)
+_ip =C.POINTER(C.c_int)
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
@@ -180,6 +185,8 @@ def hip_lib():
         L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
         L.madicp_map_query_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p,
                                              C.c_int64, _u64p]
+        L.madicp_map_register_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp,
+                                                _u64p, _i32p, _dp, C.c_int64]
         L.madicp_map_track_removed.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.madicp_map_removed_count.argtypes = [C.c_void_p, C.c_int, _i64p]
         L.madicp_map_take_removed.argtypes = [C.c_void_p, C.c_int, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
@@ -273,6 +280,8 @@ def host_lib():
                                                        _u32p, C.c_int64, _i64p]
         L.madicp_host_map_query.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p,
                                             C.c_int64, _u64p]
+        L.madicp_host_map_register.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp, _u64p,
+                                               _i32p, _dp, C.c_int64]
         L.madicp_host_map_destroy.restype = None
         L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
@@ -726,6 +735,43 @@ def host_map_query(h, xyz, R, t, reach=1, max_dist=float("inf"), per_point=True,
     _host_map_check(host_lib().madicp_host_map_query(h, a.ctypes.data_as(_dp), n, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), int(reach),
                                                      float(max_dist), *args, n, counts.ctypes.data_as(_u64p)), "madicp_host_map_query")
     return _query_answer(counts, bufs, n, per_point)
+
+
+def _align_call(call, n, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point):
+    """the buffers of a map registration around `call(Rp, tp, params, iterations, out_R, out_t, trace, counts, row, e, capacity)`, and
+    its answer: dict(R (3, 3), t (3,), X (K + 1, 12), H (K + 1, 6, 6), b (K + 1, 6), chi2 (K + 1,), counts (K + 1, 4) uint64
+    [, row (n,) int32, e (n,) float64]) — row k the linearisation at X[k], the last one at the returned pose"""
+    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+    k1 = max(int(iterations), 0) + 1
+    params = MapAlignParams(int(reach), float(max_dist), float(rho), int(min_count), float(flat))
+    out_R, out_t = np.zeros(9), np.zeros(3)
+    trace, counts = np.zeros((k1, 40)), np.zeros((k1, 4), np.uint64)
+    row = np.empty(max(n, 1), np.int32) if per_point else None
+    e = np.empty(max(n, 1), np.float64) if per_point else None
+    call(Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), C.byref(params), int(iterations), out_R.ctypes.data_as(_dp),
+         out_t.ctypes.data_as(_dp), trace.ctypes.data_as(_dp), counts.ctypes.data_as(_u64p),
+         row.ctypes.data_as(_i32p) if per_point else None, e.ctypes.data_as(_dp) if per_point else None, n)
+    H = np.zeros((k1, 6, 6))
+    v = 12
+    for c in range(6):
+        for r in range(c, 6):
+            H[:, r, c] = H[:, c, r] = trace[:, v]
+            v += 1
+    ans = dict(R=out_R.reshape(3, 3), t=out_t, X=trace[:, :12].copy(), H=H, b=trace[:, 33:39].copy(), chi2=trace[:, 39].copy(), counts=counts)
+    if per_point:
+        ans["row"], ans["e"] = row[:n].copy(), e[:n].copy()
+    return ans
+
+
+def host_map_register(h, xyz, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0, per_point=False):
+    """madicp_host_map_register: the host twin of Context.map_register_cloud over xyz (n, 3) float64."""
+    a = _f64(xyz).reshape(-1, 3)
+    n = a.shape[0]
+
+    def call(*args):
+        _host_map_check(host_lib().madicp_host_map_register(h, a.ctypes.data_as(_dp) if n else None, n, *args), "madicp_host_map_register")
+
+    return _align_call(call, n, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
 
 
 def host_map_track_removed(h, on=True):
@@ -1233,6 +1279,19 @@ class Context:
         _check(hip_lib().madicp_map_query_cloud(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), int(reach),
                                                 float(max_dist), *args, n, counts.ctypes.data_as(_u64p)))
         return _query_answer(counts, bufs, n, per_point)
+
+    def map_register_cloud(self, mid, cid, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0,
+                           per_point=False):
+        """madicp_map_register_cloud: `iterations` rounds of point-to-plane Gauss-Newton of resident cloud cid against the surfels
+        of moments map mid, from the pose (R (3, 3), t (3,)), all on the device; the map is only read.  Returns dict(R, t, X, H, b,
+        chi2, counts) with one row per linearisation — row k at X[k], the last at the returned pose — and, with per_point (only
+        with iterations == 0), row (n,) int32 and e (n,) float64.  One host synchronisation."""
+        n = self.cloud_size(cid)
+
+        def call(*args):
+            _check(hip_lib().madicp_map_register_cloud(self._h, mid, cid, *args))
+
+        return _align_call(call, n, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
 
     def map_clear(self, mid):
         _check(hip_lib().madicp_map_clear(self._h, mid))

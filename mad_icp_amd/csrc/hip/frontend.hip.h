@@ -18,10 +18,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.hip.h"  // solve_pose: the one Gauss-Newton update step (map_align_step)
 #include "tree_build.hip.h"
 #include "../common/ingest_point.h"
 #include "../common/export_point.h"
 #include "../common/voxel_moments.h"
+#include "../common/map_align.h"
 
 #pragma clang fp contract(off)
 
@@ -1029,6 +1031,132 @@ __global__ __launch_bounds__(256) void map_query_coop(const double* __restrict__
       }
     }
     query_finish(i, n, candidate != 0, best_d2, best, md2, M, O);
+  }
+}
+
+// ---- registering a scan against the map's surfels (madicp_map_register_cloud; csrc/common/map_align.h has the rule) -----------------
+// K Gauss-Newton rounds of point-to-plane terms against the surfels fe::map_surfels wrote into the call's scratch, the pose and every
+// sum resident on the device:
+//   map_align_pose   the caller's pose into the device pose (a launch, not a copy: nothing of the host is read later)
+//   map_align_terms  one lane per point, block k covers points [256 k, 256 k + 256) — NOT a grid-stride loop: the block index fixes
+//                    the position in the tree.  The pose is read from device memory; the row is the query's (query_probe); the 28
+//                    terms stay in registers and align_block_sum adds them: a wavefront's xor-butterfly over 64 consecutive points
+//                    is six levels of the adjacent-pair tree (fp addition commutes: both lanes of a pair get the same bits), two
+//                    levels through LDS make the workgroup's row.  Counts: ballots, popcounts, integer atomics.  out_row / out_e:
+//                    the linearise-only form's per-point columns, null otherwise.
+//   map_align_join   the same eight levels over 256 consecutive partial rows per workgroup (a missing row is +0.0), launched until
+//                    one row is left: 120 000 points are 469 rows, then 2, then 1
+//   map_align_step   one wavefront: the total into LDS, solve_pose (kernels.hip.h — the product's one update step), X_{k+1} over
+//                    the device pose, and the round's trace row X_k | H | b | chi2; update = 0 is the closing linearisation
+// Determinism: the association of every addition is fixed by point index alone.  No float atomics.
+struct AlignSurfels {  // by value: the surfel columns in the call's scratch
+  const float* centroid;
+  const float* normal;
+  const float* eig;
+  const uint32_t* count;
+};
+struct AlignGates {  // by value, wave-uniform
+  double md2, rho, flat;
+  uint32_t min_count;
+  int reach;
+};
+__global__ __launch_bounds__(64) void map_align_pose(ExportPose X, double* __restrict__ pose) {
+  if (threadIdx.x < 9) pose[threadIdx.x] = X.R[threadIdx.x];
+  else if (threadIdx.x < 12) pose[threadIdx.x] = X.t[threadIdx.x - 9];
+}
+// eight levels of the tree over the 256 vectors a workgroup's lanes hold, in lane order, into one row (whole workgroup of 256)
+__device__ __forceinline__ void align_block_sum(double (&x)[madicp_host::kAlignTerms], double* __restrict__ out_row) {
+  __shared__ double s_part[4][madicp_host::kAlignTerms];
+#pragma unroll
+  for (int c = 0; c < madicp_host::kAlignTerms; ++c) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) x[c] = x[c] + __shfl_xor(x[c], d, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < madicp_host::kAlignTerms; ++c) s_part[threadIdx.x >> 6][c] = x[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < madicp_host::kAlignTerms)
+    out_row[threadIdx.x] = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
+}
+__global__ __launch_bounds__(256) void map_align_terms(const double* __restrict__ xyz, long n, const double* __restrict__ pose, double voxel,
+                                                       AlignGates G, QueryMap M, AlignSurfels S, double* __restrict__ partials,
+                                                       unsigned long long* __restrict__ counts, int32_t* __restrict__ out_row,
+                                                       double* __restrict__ out_e) {
+  const long i = (long)blockIdx.x * madicp_host::kAlignBlock + threadIdx.x;
+  double x[madicp_host::kAlignTerms];
+#pragma unroll
+  for (int c = 0; c < madicp_host::kAlignTerms; ++c) x[c] = 0.0;
+  bool candidate = false, within = false, inlier = false;
+  int32_t row = -1;
+  if (i < n) {
+    double R[9], t[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = pose[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = pose[9 + k];
+    const double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    double q[3], d2 = madicp_host::kQueryNoDistance, e = 0.0;
+    int32_t cell[3];
+    madicp_host::export_position(p, R, t, q);
+    candidate = madicp_host::export_cells(q, voxel, cell);
+    if (candidate && G.reach == 0) query_probe(M, q, cell, madicp_host::kQueryOwnCell, &d2, &row);
+    if (candidate && G.reach != 0) {
+#pragma unroll
+      for (int c = 0; c < madicp_host::kQueryCells; ++c) query_probe(M, q, cell, c, &d2, &row);
+    }
+    within = row >= 0 && d2 <= G.md2;
+    if (within) {
+      const size_t j = 3 * (size_t)row;
+      const float eg[3] = {S.eig[j], S.eig[j + 1], S.eig[j + 2]};
+      inlier = madicp_host::align_inlier(true, S.count[row], eg, G.min_count, G.flat);
+      if (inlier) {
+        const float c[3] = {S.centroid[j], S.centroid[j + 1], S.centroid[j + 2]};
+        const float nrm[3] = {S.normal[j], S.normal[j + 1], S.normal[j + 2]};
+        e = madicp_host::align_terms(p, R, q, c, nrm, G.rho, x);
+      }
+    }
+    if (out_row) out_row[i] = row;
+    if (out_e) out_e[i] = e;
+  }
+  const unsigned long long a = __popcll(__ballot(candidate));
+  const unsigned long long b = __popcll(__ballot(row >= 0));
+  const unsigned long long w = __popcll(__ballot(within));
+  const unsigned long long in = __popcll(__ballot(inlier));
+  if ((threadIdx.x & 63) == 0) {
+    if (a) atomicAdd(&counts[0], a);
+    if (b) atomicAdd(&counts[1], b);
+    if (w) atomicAdd(&counts[2], w);
+    if (in) atomicAdd(&counts[3], in);
+  }
+  align_block_sum(x, partials + (size_t)madicp_host::kAlignTerms * blockIdx.x);
+}
+__global__ __launch_bounds__(256) void map_align_join(const double* __restrict__ in, long rows, double* __restrict__ out) {
+  const long r = (long)blockIdx.x * madicp_host::kAlignBlock + threadIdx.x;
+  double x[madicp_host::kAlignTerms];
+#pragma unroll
+  for (int c = 0; c < madicp_host::kAlignTerms; ++c) x[c] = r < rows ? in[(size_t)madicp_host::kAlignTerms * r + c] : 0.0;
+  align_block_sum(x, out + (size_t)madicp_host::kAlignTerms * blockIdx.x);
+}
+__global__ __launch_bounds__(64) void map_align_step(const double* __restrict__ total_row, double* pose, int update,
+                                                     double* __restrict__ trace_row) {
+  __shared__ double s_total[madicp_host::kAlignTerms];
+  const int lane = threadIdx.x;
+  const double xk = lane < 12 ? pose[lane] : 0.0;  // (X_k, before the update goes over it)
+  if (lane < madicp_host::kAlignTerms) s_total[lane] = total_row[lane];
+  wave_lds_order();
+  if (lane < 12) trace_row[lane] = xk;
+  else if (lane < madicp_host::kAlignTraceRow) trace_row[lane] = s_total[lane - 12];
+  if (update) {  // (wave-uniform)
+    double X[12], Xn[12], H[36], b[6], moved[2];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) X[k] = pose[k];
+    solve_pose(s_total, X, true, Xn, H, b, moved, lane);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) pose[k] = Xn[k];
+    }
   }
 }
 

@@ -1684,6 +1684,104 @@ int madicp_map_query_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const doub
   return rc;
 }
 
+// `iterations` Gauss-Newton rounds of a resident cloud against the map's surfels (csrc/common/map_align.h has the rule).  The
+// map's block is only read.  The call's scratch is ONE pooled block of its own — the builder's is not touched —
+//   counts ((K + 1) x 4 x 8) | pose (12 x 8) | trace ((K + 1) x 40 x 8) | partial rows A (ceil(n / 256) x 28 x 8) | partial rows B
+//   (ceil(rows A / 256) x 28 x 8) | e (n x 8) | centroid, normal, eig (M x 12 each) | count (M x 4) | row (n x 4) | slot_row
+// of which the per-point columns are there only where asked for and the last only on a map without the column (none with moments
+// today).  One memset for the counts, fe::map_surfels once, K x (terms, joins, step), the closing linearisation, the copies, ONE wait.
+int madicp_map_register_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const double R[9], const double t[3],
+                              const madicp_map_align_params* params, int iterations, double out_R[9], double out_t[3], double* out_trace,
+                              uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points) {
+  if (!ctx || !R || !t || !params || !out_R || !out_t || !out_trace || !out_counts) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (!m->with_mom) return fail(MADICP_ERR_INVALID, kMapNoMoments);
+  if (const char* why = madicp_host::map_align_refusal(R, t, params->reach, params->max_dist, params->rho, params->min_count, params->flat))
+    return fail(MADICP_ERR_INVALID, why);
+  if (iterations < 0 || iterations > madicp_host::kAlignMaxIterations) return fail(MADICP_ERR_INVALID, "iterations: 0 .. 64");
+  if ((out_row || out_e) && iterations > 0)
+    return fail(MADICP_ERR_INVALID, "per-point buffers belong to the linearise-only form (iterations == 0)");
+  const int64_t n = c->n;
+  if ((out_row || out_e) && capacity_points < n)
+    return fail(MADICP_ERR_CAPACITY, "the per-point buffers hold fewer entries than the cloud has points");
+  if (n <= 0) return fail(MADICP_ERR_INVALID, "the cloud is empty");  // (never: a resident cloud holds at least one point)
+  HIP_TRY(hipSetDevice(ctx->device));
+  constexpr size_t kT = madicp_host::kAlignTerms, kRow = madicp_host::kAlignTraceRow, kC = madicp_host::kAlignCounts;
+  const size_t N = (size_t)n, M = (size_t)m->rows, K1 = (size_t)iterations + 1;
+  const int64_t rows_a = (n + madicp_host::kAlignBlock - 1) / madicp_host::kAlignBlock;
+  const int64_t rows_b = (rows_a + madicp_host::kAlignBlock - 1) / madicp_host::kAlignBlock;
+  const bool own_slot_row = !m->slot_row();
+  size_t off = 0;
+  auto place = [&](bool wanted, size_t bytes) {
+    const size_t at = off;
+    if (wanted) off = align_up(off + bytes);
+    return at;
+  };
+  const size_t at_counts = place(true, 8 * kC * K1), at_pose = place(true, 8 * 12), at_trace = place(true, 8 * kRow * K1);
+  const size_t at_a = place(true, 8 * kT * (size_t)rows_a), at_b = place(true, 8 * kT * (size_t)rows_b), at_e = place(out_e, 8 * N);
+  const size_t at_centroid = place(true, 12 * M), at_normal = place(true, 12 * M), at_eig = place(true, 12 * M), at_count = place(true, 4 * M);
+  const size_t at_row = place(out_row, 4 * N), at_slot_row = place(own_slot_row, 4 * (size_t)m->slots);
+  void* p = nullptr;
+  RC_TRY(pool_alloc(ctx, off, ctx->copy, &p));
+  char* block = static_cast<char*>(p);
+  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(block + at_counts);
+  double* d_pose = reinterpret_cast<double*>(block + at_pose);
+  double* d_trace = reinterpret_cast<double*>(block + at_trace);
+  double* d_rows[2] = {reinterpret_cast<double*>(block + at_a), reinterpret_cast<double*>(block + at_b)};
+  double* d_e = out_e ? reinterpret_cast<double*>(block + at_e) : nullptr;
+  int32_t* d_row = out_row ? reinterpret_cast<int32_t*>(block + at_row) : nullptr;
+  float* d_centroid = reinterpret_cast<float*>(block + at_centroid);
+  float* d_normal = reinterpret_cast<float*>(block + at_normal);
+  float* d_eig = reinterpret_cast<float*>(block + at_eig);
+  uint32_t* d_count = reinterpret_cast<uint32_t*>(block + at_count);
+  uint32_t* slot_row = own_slot_row ? reinterpret_cast<uint32_t*>(block + at_slot_row) : m->slot_row();
+  const fe::QueryMap Q{m->keys(), m->slots, slot_row, m->xyz(), (long)m->rows, m->row_keys(), nullptr, nullptr};
+  const fe::AlignSurfels S{d_centroid, d_normal, d_eig, d_count};
+  const fe::AlignGates G{params->max_dist * params->max_dist, params->rho, params->flat, params->min_count, params->reach};
+  hipError_t e = hipMemsetAsync(d_counts, 0, 8 * kC * K1, ctx->copy);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fe::map_align_pose, dim3(1), dim3(64), 0, ctx->copy, export_pose(R, t), d_pose);
+    if (m->rows > 0) {
+      if (own_slot_row)
+        hipLaunchKernelGGL(fe::map_slot_rows, dim3(grid_256(ctx, m->rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys(),
+                           (long)m->rows, (const unsigned long long*)m->keys(), m->slots, slot_row);
+      hipLaunchKernelGGL(fe::map_surfels, dim3(grid_256(ctx, m->rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->mom(),
+                         (const unsigned long long*)m->row_keys(), 0L, (long)m->rows, m->voxel, d_centroid, d_normal, d_eig, d_count);
+    }
+    for (int k = 0; k <= iterations; ++k) {  // (round `iterations` is the closing linearisation: no update)
+      hipLaunchKernelGGL(fe::map_align_terms, dim3((unsigned)rows_a), dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n,
+                         (const double*)d_pose, m->voxel, G, Q, S, d_rows[0], d_counts + kC * (size_t)k, d_row, d_e);
+      int from = 0;
+      for (int64_t rows = rows_a; rows > 1; from ^= 1) {  // 256 rows a workgroup: A -> B -> A ... until one row is left
+        const int64_t next = (rows + madicp_host::kAlignBlock - 1) / madicp_host::kAlignBlock;
+        hipLaunchKernelGGL(fe::map_align_join, dim3((unsigned)next), dim3(256), 0, ctx->copy, (const double*)d_rows[from], (long)rows,
+                           d_rows[from ^ 1]);
+        rows = next;
+      }
+      hipLaunchKernelGGL(fe::map_align_step, dim3(1), dim3(64), 0, ctx->copy, (const double*)d_rows[from], d_pose, k < iterations ? 1 : 0,
+                         d_trace + kRow * (size_t)k);
+    }
+    e = hipGetLastError();
+  }
+  double X[12];
+  std::vector<double> trace(kRow * K1);
+  std::vector<uint64_t> counts(kC * K1);
+  const CopyOut outs[] = {{X, d_pose, sizeof(X)},  {trace.data(), d_trace, 8 * kRow * K1}, {counts.data(), d_counts, 8 * kC * K1},
+                          {out_row, d_row, 4 * N}, {out_e, d_e, 8 * N}};
+  const int rc = copies_then_wait(ctx, e, outs, 5, "voxel map registration: ");
+  pool_free(ctx, block, nullptr);  // (behind the wait: nothing is in flight on it)
+  if (rc == MADICP_OK) {
+    std::memcpy(out_R, X, 9 * sizeof(double));
+    std::memcpy(out_t, X + 9, 3 * sizeof(double));
+    std::memcpy(out_trace, trace.data(), 8 * kRow * K1);
+    std::memcpy(out_counts, counts.data(), 8 * kC * K1);
+  }
+  return rc;
+}
+
 int madicp_map_clear(madicp_ctx* ctx, int map_id) {
   if (!ctx) return fail(MADICP_ERR_INVALID, "null argument");
   DevMap* m = find_map(ctx, map_id);

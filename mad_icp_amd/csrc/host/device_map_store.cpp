@@ -76,6 +76,15 @@ class DeviceMapStore final : public MapStore {
                                     capacity_points, out_counts);
     });
   }
+  int align(const ScanRef& scan, const double* R, const double* t, const AlignParams& p, int iterations, double* out_R, double* out_t,
+            double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points) override {
+    ScanBorrow b(*this, scan);
+    const madicp_map_align_params params{p.reach, p.max_dist, p.rho, p.min_count, p.flat};
+    return call("madicp_map_register_cloud", [&](madicp_ctx* ctx) {
+      return madicp_map_register_cloud(ctx, id_, b.scan().cloud_id, R, t, &params, iterations, out_R, out_t, out_trace, out_counts, out_row,
+                                       out_e, capacity_points);
+    });
+  }
   int trackRemoved(bool on) override {
     return call("madicp_map_track_removed", [&](madicp_ctx* ctx) { return madicp_map_track_removed(ctx, id_, on ? 1 : 0); });
   }

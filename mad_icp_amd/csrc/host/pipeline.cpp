@@ -283,6 +283,7 @@ void Pipeline::setMapAccumulation(double voxel_size, bool keyframes_only, size_t
 void Pipeline::foldFrame() {
   if (map_spec_.voxel == 0.0) return;
   std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));  // (a frame that is not folded answers zeros)
+  map_frame_alignment_.valid = false;                                    // (... and no alignment)
   if (have_kept_ && !map_overflowed_ && (!map_keyframes_only_ || is_map_updated_)) {
     // (b) a fold the capacity rule would refuse: the rows out of range of the frame before this one give way first, once
     if (map_range_ > 0.0 && map_ && map_have_last_ && mapSize() + kept_n_ > static_cast<size_t>(map_spec_.max_rows)) {
@@ -312,6 +313,22 @@ void Pipeline::foldFrame() {
         mapCheck(map_->query(scan, frame_to_map_.R, frame_to_map_.t, map_overlap_reach_, map_overlap_max_dist_, nullptr, nullptr, nullptr, nullptr,
                              nullptr, 0, map_frame_overlap_),
                  "Pipeline: the overlap query: ");
+      if (map_alignment_ && map_spec_.mom > 0) {  // setMapAlignment: the frame registered against the map as it stands, reported only
+        FrameAlignment& a = map_frame_alignment_;
+        std::vector<double> trace(static_cast<size_t>(kAlignTraceRow) * (map_align_iterations_ + 1));
+        std::vector<uint64_t> counts(static_cast<size_t>(kAlignCounts) * (map_align_iterations_ + 1));
+        mapCheck(map_->align(scan, frame_to_map_.R, frame_to_map_.t, map_align_params_, map_align_iterations_, a.R, a.t, trace.data(),
+                             counts.data(), nullptr, nullptr, 0),
+                 "Pipeline: the frame's alignment: ");
+        a.valid = true;
+        a.iterations = map_align_iterations_;
+        const double* last = trace.data() + static_cast<size_t>(kAlignTraceRow) * map_align_iterations_;
+        const uint64_t* last_counts = counts.data() + static_cast<size_t>(kAlignCounts) * map_align_iterations_;
+        std::memcpy(a.sums, last + 12, sizeof(a.sums));
+        std::memcpy(a.counts, last_counts, sizeof(a.counts));
+        a.first_chi2 = trace[kAlignTraceRow - 1];
+        std::copy(counts.begin(), counts.begin() + kAlignCounts, a.first_counts);
+      }
       rc = map_->insert(scan, frame_to_map_.R, frame_to_map_.t, &added, &rows);
       if (rc != MADICP_ERR_CAPACITY) mapCheck(rc, "Pipeline: the fold: ");
       // setMapClearing: what the cloud just folded sees through leaves, before the range prune below
@@ -325,6 +342,7 @@ void Pipeline::foldFrame() {
     if (device) lock.unlock();
     if (rc == MADICP_ERR_CAPACITY) map_overflowed_ = true;
     if (rc != MADICP_OK) std::fill(map_frame_overlap_, map_frame_overlap_ + 3, uint64_t(0));  // (refused: not folded)
+    if (rc != MADICP_OK) map_frame_alignment_.valid = false;
     if (rc == MADICP_OK && map_spec_.with_attr && kept_has_attr_) map_attr_type_ = kept_attr_type_;
     // (a) the vehicle has moved a quarter of the range since the last prune: squared distances, fp64 — the poses alone decide
     if (rc == MADICP_OK && map_range_ > 0.0) {
@@ -431,6 +449,43 @@ void Pipeline::mapQuery(const double* xyz, size_t n, const double R[9], const do
   const int rc = map.query(ScanRef::host(xyz, nullptr, n64), R, t, reach, max_dist, row, d2, keys, attr, ev, n64, counts);
   if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapQuery: " + map.lastError());
   if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapQuery: " + map.lastError());
+}
+
+void Pipeline::setMapAlignment(bool on, int iterations, const AlignParams& params) {
+  if (iterations < 0 || iterations > kAlignMaxIterations) throw std::invalid_argument("Pipeline::setMapAlignment: iterations must be 0 .. 64");
+  const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, z[3] = {0, 0, 0};
+  if (const char* why = map_align_refusal(I, z, params.reach, params.max_dist, params.rho, params.min_count, params.flat))
+    throw std::invalid_argument(std::string("Pipeline::setMapAlignment: ") + why);
+  if (on && map_spec_.voxel > 0.0 && map_spec_.mom == 0)
+    throw std::logic_error("Pipeline::setMapAlignment: the map was made without moments (setMapAccumulation's moments)");
+  map_alignment_ = on;
+  map_align_iterations_ = iterations;
+  map_align_params_ = params;
+  if (!on) map_frame_alignment_.valid = false;
+}
+
+void Pipeline::mapRegister(const double* xyz, size_t n, const double R[9], const double t[3], const AlignParams& params, int iterations,
+                           double out_R[9], double out_t[3], double* trace, uint64_t* counts, int32_t* row, double* e) {
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapRegister: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.mom == 0) throw std::logic_error("Pipeline::mapRegister: the map was made without moments (setMapAccumulation's moments)");
+  if ((!xyz && n > 0) || !R || !t || !out_R || !out_t || !trace || !counts) throw std::invalid_argument("Pipeline::mapRegister: null argument");
+  if (n > static_cast<size_t>(kMapMaxRows)) throw std::invalid_argument("Pipeline::mapRegister: at most 2^30 points");
+  if (const char* why = map_align_refusal(R, t, params.reach, params.max_dist, params.rho, params.min_count, params.flat))
+    throw std::invalid_argument(std::string("Pipeline::mapRegister: ") + why);
+  if (iterations < 0 || iterations > kAlignMaxIterations) throw std::invalid_argument("Pipeline::mapRegister: iterations must be 0 .. 64");
+  if ((row || e) && iterations > 0)
+    throw std::invalid_argument("Pipeline::mapRegister: per-point buffers belong to the linearise-only form (iterations == 0)");
+  std::unique_ptr<MapStore> empty;  // before the first fold and for no point at all: an empty host map of the same kind answers
+  if (!map_ || n == 0) {
+    MapSpec kind = map_spec_;
+    kind.first_rows = kind.max_rows = 1;
+    empty = std::make_unique<HostMapStore>(kind);
+  }
+  MapStore& map = empty ? *empty : *map_;
+  const int64_t n64 = static_cast<int64_t>(n);
+  const int rc = map.align(ScanRef::host(xyz, nullptr, n64), R, t, params, iterations, out_R, out_t, trace, counts, row, e, n64);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapRegister: " + map.lastError());
+  if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapRegister: " + map.lastError());
 }
 
 size_t Pipeline::mapNewRowCount() {

@@ -283,6 +283,37 @@ class Pipeline {
   // Pipeline holds the whole map on every rank: the answers are the same on every rank, nothing is exchanged.
   void mapQuery(const double* xyz, size_t n, const double R[9], const double t[3], int reach, double max_dist, int32_t* row, double* d2,
                 uint64_t* keys, uint32_t* attr, uint32_t* ev, uint64_t counts[3]);
+  // additive: REGISTERING A SCAN AGAINST THE MAP.  mapRegister: `iterations` (0 .. 64) rounds of point-to-plane Gauss-Newton of the n
+  // points xyz (n, 3) against the surfels of the moments map, from the pose (R, t) (include/madicp_hip.h: madicp_map_register_cloud
+  // and csrc/common/map_align.h have the rule) — out_R / out_t: the pose after the last round; trace ((iterations + 1) x 40: X | H
+  // packed | b | chi2) and counts ((iterations + 1) x 4: candidates, matched, within, inliers): row k the linearisation at X_k, the
+  // last one at the returned pose.  iterations == 0 is the linearise-only form, the only one that takes row (int32) / e (float64),
+  // n entries each or null.  Device front-end: the points are uploaded as mapQuery uploads them and every round runs where the map
+  // lives (one host synchronisation); host front-end: the host twin.  Before the first fold the map is empty: zero sums, the pose
+  // as given.  The map is only read and the pipeline's own pose is never touched.  std::logic_error while accumulation is off or
+  // without moments; std::invalid_argument for a null argument and for what madicp_map_register_cloud refuses.
+  void mapRegister(const double* xyz, size_t n, const double R[9], const double t[3], const AlignParams& params, int iterations,
+                   double out_R[9], double out_t[3], double* trace, uint64_t* counts, int32_t* row = nullptr, double* e = nullptr);
+  // setMapAlignment(on, iterations, params) — default off: not a launch, not an allocation, the same pose and map bits — lets
+  // foldFrame(), inside its one borrow of the frame's cloud and BEFORE the fold, register that cloud against the map as it stands,
+  // from the frame's own pose (a drift check of the odometry against its own map).  The result is only REPORTED: mapFrameAlignment()
+  // holds the pose after `iterations` rounds, the sums and counts of the closing linearisation, and chi2 and counts of the first;
+  // valid is false for a frame that was not folded, while the option is off and on a map without moments.  The pipeline's pose is
+  // never changed by it: with the option on, poses, keyframe decisions and every map column are bit for bit what they are with it
+  // off.  One host synchronisation more per folded frame on the device front-end.  std::invalid_argument for what
+  // madicp_map_register_cloud refuses of the parameters, std::logic_error when the accumulation is on without moments.
+  struct FrameAlignment {
+    bool valid = false;
+    int iterations = 0;
+    double R[9] = {}, t[3] = {};       // the pose after the rounds
+    double sums[kAlignTerms] = {};     // H (21, packed) | b (6) | chi2 of the linearisation at that pose
+    uint64_t counts[kAlignCounts] = {};
+    double first_chi2 = 0.0;           // ... and of the one at the frame's own pose
+    uint64_t first_counts[kAlignCounts] = {};
+  };
+  void setMapAlignment(bool on, int iterations = 5, const AlignParams& params = AlignParams());
+  bool mapAlignmentOn() const { return map_alignment_; }
+  const FrameAlignment& mapFrameAlignment() const { return map_frame_alignment_; }
   void setMapOverlap(bool on, int reach = 1, double max_dist = kQueryNoDistance);
   bool mapOverlapOn() const { return map_overlap_; }
   const uint64_t* mapFrameOverlap() const { return map_frame_overlap_; }
@@ -473,6 +504,10 @@ class Pipeline {
   int map_overlap_reach_ = 1;
   double map_overlap_max_dist_ = kQueryNoDistance;
   uint64_t map_frame_overlap_[3] = {0, 0, 0};
+  bool map_alignment_ = false;  // setMapAlignment: foldFrame registers the frame against the map before it folds it, and only reports
+  int map_align_iterations_ = 5;
+  AlignParams map_align_params_;
+  FrameAlignment map_frame_alignment_;
   size_t pruneMapAt(const double center[3], double radius);  // MapStore::prune with the cursor as watermark (mapPrune's refusals; 0 before the first fold)
   void foldFrame();  // the end of every compute*: folds the retained scan, then lets it go unless setKeepScan holds it
   double virtual_pre_ms_ = -1.0, virtual_round_ms_ = 0.0;

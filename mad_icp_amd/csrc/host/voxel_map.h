@@ -23,7 +23,9 @@
 #include <vector>
 
 #include "../common/export_point.h"
+#include "../common/map_align.h"
 #include "../common/voxel_moments.h"
+#include "linalg.h"  // ldlt6_solve, exp_so3: the host's update step (align)
 
 namespace madicp_host {
 
@@ -292,6 +294,59 @@ class VoxelMap {
     return kMapOk;
   }
 
+  // include/madicp_host.h: madicp_host_map_register — `iterations` rounds of point-to-plane Gauss-Newton against the surfels
+  // (../common/map_align.h has the rule: align_inlier, align_terms, align_tree), the map only read.  The surfels are map_surfel of
+  // every row, once per call; the row of a point is query()'s; the step is ldlt6_solve and exp_so3 of linalg.h.  out_trace:
+  // (iterations + 1) x 40, out_counts: (iterations + 1) x 4; out_row / out_e only with iterations == 0.
+  int align(const double* xyz, int64_t n, const double* R, const double* t, int reach, double max_dist, double rho, uint32_t min_count,
+            double flat, int iterations, double* out_R, double* out_t, double* out_trace, uint64_t* out_counts, int32_t* out_row,
+            double* out_e, int64_t capacity_points) const {
+    if (!out_R || !out_t || !out_trace || !out_counts || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
+    if (!with_mom_ || map_align_refusal(R, t, reach, max_dist, rho, min_count, flat)) return kMapInvalid;
+    if (iterations < 0 || iterations > kAlignMaxIterations || ((out_row || out_e) && iterations > 0)) return kMapInvalid;
+    if ((out_row || out_e) && capacity_points < n) return kMapCapacity;
+    const size_t m = static_cast<size_t>(size());
+    std::vector<float> centroid(3 * m), normal(3 * m), eig(3 * m);
+    std::vector<uint32_t> count(m);
+    for (size_t j = 0; j < m; ++j)
+      map_surfel(mom_.data() + kMomentWords * j, row_keys_[j], voxel_, &centroid[3 * j], &normal[3 * j], &eig[3 * j], &count[j]);
+    std::vector<int32_t> row(static_cast<size_t>(n));
+    std::vector<double> d2(static_cast<size_t>(n)), x(kAlignTerms * static_cast<size_t>(n > 0 ? n : 1));
+    const double md2 = max_dist * max_dist;
+    double X[12];
+    std::memcpy(X, R, 9 * sizeof(double));
+    std::memcpy(X + 9, t, 3 * sizeof(double));
+    std::vector<double> trace(static_cast<size_t>(kAlignTraceRow) * (iterations + 1));
+    std::vector<uint64_t> counts(static_cast<size_t>(kAlignCounts) * (iterations + 1));
+    for (int k = 0; k <= iterations; ++k) {  // (round `iterations` is the closing linearisation: no update)
+      uint64_t* cnt = counts.data() + kAlignCounts * k;
+      if (query(xyz, n, X, X + 9, reach, max_dist, row.data(), d2.data(), nullptr, nullptr, nullptr, n, cnt) != kMapOk) return kMapInvalid;
+      std::fill(x.begin(), x.end(), 0.0);
+      for (int64_t i = 0; i < n; ++i) {
+        const int32_t j = row[i];
+        double e = 0.0;
+        if (j >= 0 && align_inlier(d2[i] <= md2, count[j], &eig[3 * j], min_count, flat)) {
+          double q[3];
+          export_position(xyz + 3 * i, X, X + 9, q);
+          e = align_terms(xyz + 3 * i, X, q, &centroid[3 * j], &normal[3 * j], rho, &x[kAlignTerms * i]);
+          ++cnt[3];
+        }
+        if (out_row) out_row[i] = j;
+        if (out_e) out_e[i] = e;
+      }
+      align_tree(x.data(), n > 0 ? n : 1);
+      double* row_k = trace.data() + kAlignTraceRow * k;
+      std::memcpy(row_k, X, sizeof(X));
+      std::memcpy(row_k + 12, x.data(), kAlignTerms * sizeof(double));
+      if (k < iterations) align_step(x.data(), X);
+    }
+    std::memcpy(out_R, X, 9 * sizeof(double));
+    std::memcpy(out_t, X + 9, 3 * sizeof(double));
+    std::memcpy(out_trace, trace.data(), trace.size() * sizeof(double));
+    std::memcpy(out_counts, counts.data(), counts.size() * sizeof(uint64_t));
+    return kMapOk;
+  }
+
   void clear() {  // (keeps the memory, forgets the rows)
     rows_.clear();
     keys_.clear();
@@ -375,6 +430,22 @@ class VoxelMap {
     *out_removed = m - d;
     *out_rows = d;
     *out_watermark = mark;
+  }
+
+  // one Gauss-Newton update of the pose X (R row-major | t) from the 28 sums (map_align.h's packing): dx = H^-1 (-b) by the LDLT of
+  // linalg.h, X <- X * (exp_so3(dx[3 .. 5]), dx[0 .. 2]) — MADicp::updateState (mad_icp.cpp:105-117 of the reference)
+  static void align_step(const double* total, double* X) {
+    double H[36], nb[6], dx[6], dR[9], Rn[9], rt[3];
+    int v = 0;
+    for (int c = 0; c < 6; ++c)
+      for (int r = c; r < 6; ++r) H[6 * r + c] = H[6 * c + r] = total[v++];
+    for (int r = 0; r < 6; ++r) nb[r] = -total[21 + r];
+    ldlt6_solve(H, nb, dx);
+    exp_so3(dx + 3, dR);
+    matmul3(X, dR, Rn);
+    matvec3(X, dx, rt);
+    for (int i = 0; i < 3; ++i) X[9 + i] = rt[i] + X[9 + i];
+    std::memcpy(X, Rn, sizeof(Rn));
   }
 
   // one candidate point into row r (voxel_moments.h: moment_row_takes / moment_closes — the device's map_moments, one point at a time)

@@ -8,6 +8,66 @@
 #include <string>
 #include <vector>
 
+// Pipeline::mapRegister behind mapRegister / mapLinearize: -> (pose (4, 4), info) — info holds H (6, 6), b (6,), chi2 and counts
+// (candidates, matched, within, inliers) of the CLOSING linearisation (the one at the returned pose); with `trace` the per-round
+// arrays X (K + 1, 12), H_rounds (K + 1, 6, 6), b_rounds (K + 1, 6), chi2_rounds (K + 1,), counts_rounds (K + 1, 4); with `rows`
+// (iterations == 0 only) row (n,) int32 and e (n,) float64
+static py::tuple map_register_py(Pipeline& self, const py::array_t<double, py::array::c_style | py::array::forcecast>& cloud,
+                                 const py::array_t<double, py::array::c_style | py::array::forcecast>& pose, int iterations,
+                                 const madicp_host::AlignParams& params, bool trace, bool rows) {
+  if (cloud.ndim() != 2 || cloud.shape(1) != 3) throw py::value_error("cloud must be (n, 3)");
+  if (pose.ndim() != 2 || pose.shape(0) != 4 || pose.shape(1) != 4) throw py::value_error("pose must be (4, 4)");
+  if (iterations < 0 || iterations > madicp_host::kAlignMaxIterations) throw py::value_error("iterations must be 0 .. 64");
+  const double* T = pose.data();
+  const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+  const double t[3] = {T[3], T[7], T[11]};
+  const py::ssize_t n = cloud.shape(0), k1 = iterations + 1;
+  std::vector<double> tr(static_cast<size_t>(madicp_host::kAlignTraceRow * k1));
+  py::array_t<uint64_t> counts({k1, static_cast<py::ssize_t>(madicp_host::kAlignCounts)});
+  py::array_t<int32_t> row(rows ? n : 0);
+  py::array_t<double> e(rows ? n : 0);
+  double oR[9], ot[3];
+  self.mapRegister(cloud.data(), static_cast<size_t>(n), R, t, params, iterations, oR, ot, tr.data(), counts.mutable_data(),
+                   rows ? row.mutable_data() : nullptr, rows ? e.mutable_data() : nullptr);
+  py::array_t<double> out_pose({4, 4}), X({k1, static_cast<py::ssize_t>(12)}), H({k1, static_cast<py::ssize_t>(6), static_cast<py::ssize_t>(6)}),
+      b({k1, static_cast<py::ssize_t>(6)}), chi2(k1);
+  double* P = out_pose.mutable_data();
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) P[4 * r + c] = oR[3 * r + c];
+    P[4 * r + 3] = ot[r];
+  }
+  P[12] = P[13] = P[14] = 0.0;
+  P[15] = 1.0;
+  for (py::ssize_t k = 0; k < k1; ++k) {
+    const double* q = tr.data() + madicp_host::kAlignTraceRow * k;
+    std::copy(q, q + 12, X.mutable_data() + 12 * k);
+    double* Hk = H.mutable_data() + 36 * k;
+    int v = 12;
+    for (int c = 0; c < 6; ++c)
+      for (int r = c; r < 6; ++r) Hk[6 * r + c] = Hk[6 * c + r] = q[v++];
+    std::copy(q + 33, q + 39, b.mutable_data() + 6 * k);
+    chi2.mutable_data()[k] = q[39];
+  }
+  py::dict info;
+  const py::object last = py::int_(k1 - 1);
+  info["H"] = H.attr("__getitem__")(last).attr("copy")();
+  info["b"] = b.attr("__getitem__")(last).attr("copy")();
+  info["chi2"] = chi2.attr("__getitem__")(last);
+  info["counts"] = counts.attr("__getitem__")(last).attr("copy")();
+  if (trace) {
+    info["X"] = X;
+    info["H_rounds"] = H;
+    info["b_rounds"] = b;
+    info["chi2_rounds"] = chi2;
+    info["counts_rounds"] = counts;
+  }
+  if (rows) {
+    info["row"] = row;
+    info["e"] = e;
+  }
+  return py::make_tuple(out_pose, info);
+}
+
 PYBIND11_MODULE(pypeline, m) {
   m.doc() = "mad_icp_amd: MAD-ICP odometry pipeline with the registration on MI355X, drop-in for mad_icp.src.pybind.pypeline";
   // the reference registers the same container in pyvector and pypeline; module_local lets both be imported
@@ -342,6 +402,66 @@ PYBIND11_MODULE(pypeline, m) {
          [](const Pipeline& self) {
            const uint64_t* c = self.mapFrameOverlap();
            return py::make_tuple(c[0], c[1], c[2]);
+         })
+    // additive: registering a scan against the map's surfels (Pipeline::mapRegister).  mapRegister(cloud (n, 3), pose (4, 4),
+    // iterations, reach=1, max_dist=inf, rho=inf, min_count=3, flat=1.0, trace=False) returns (pose (4, 4), info): the pose after
+    // `iterations` Gauss-Newton rounds, and H (6, 6), b, chi2, counts of the linearisation AT that pose (plus the per-round arrays
+    // with trace).  The defaults are the neutral parameters, not tuned ones.  mapLinearize(cloud, pose, ..., with_rows=False) is the
+    // iterations = 0 form: the pose comes back as given, with_rows adds the per-point row and e.  ValueError for what
+    // madicp_map_register_cloud refuses; RuntimeError (std::logic_error) while accumulation is off or without moments.
+    .def("mapRegister",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> pose, int iterations, int reach, double max_dist, double rho,
+            uint32_t min_count, double flat, bool trace) {
+           return map_register_py(self, cloud, pose, iterations, madicp_host::AlignParams{reach, max_dist, rho, min_count, flat}, trace, false);
+         },
+         py::arg("cloud"), py::arg("pose"), py::arg("iterations"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance,
+         py::arg("rho") = madicp_host::kQueryNoDistance, py::arg("min_count") = 3, py::arg("flat") = 1.0, py::arg("trace") = false)
+    .def("mapLinearize",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> pose, int reach, double max_dist, double rho, uint32_t min_count,
+            double flat, bool with_rows) {
+           return map_register_py(self, cloud, pose, 0, madicp_host::AlignParams{reach, max_dist, rho, min_count, flat}, false, with_rows);
+         },
+         py::arg("cloud"), py::arg("pose"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance,
+         py::arg("rho") = madicp_host::kQueryNoDistance, py::arg("min_count") = 3, py::arg("flat") = 1.0, py::arg("with_rows") = false)
+    // setMapAlignment(on, iterations=5, reach=1, max_dist=inf, rho=inf, min_count=3, flat=1.0) makes every fold register the frame
+    // against the map first and only REPORT it; mapFrameAlignment() returns None for a frame without one, else (pose (4, 4), info) with
+    // H, b, chi2, counts at that pose and chi2_start, counts_start at the frame's own.
+    .def("setMapAlignment",
+         [](Pipeline& self, bool on, int iterations, int reach, double max_dist, double rho, uint32_t min_count, double flat) {
+           self.setMapAlignment(on, iterations, madicp_host::AlignParams{reach, max_dist, rho, min_count, flat});
+         },
+         py::arg("on"), py::arg("iterations") = 5, py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance,
+         py::arg("rho") = madicp_host::kQueryNoDistance, py::arg("min_count") = 3, py::arg("flat") = 1.0)
+    .def("mapFrameAlignment",
+         [](const Pipeline& self) -> py::object {
+           const Pipeline::FrameAlignment& a = self.mapFrameAlignment();
+           if (!a.valid) return py::none();
+           py::array_t<double> pose({4, 4}), H({6, 6}), b(6);
+           py::array_t<uint64_t> counts(madicp_host::kAlignCounts), first(madicp_host::kAlignCounts);
+           double* P = pose.mutable_data();
+           for (int r = 0; r < 3; ++r) {
+             for (int c = 0; c < 3; ++c) P[4 * r + c] = a.R[3 * r + c];
+             P[4 * r + 3] = a.t[r];
+           }
+           P[12] = P[13] = P[14] = 0.0;
+           P[15] = 1.0;
+           int v = 0;
+           for (int c = 0; c < 6; ++c)
+             for (int r = c; r < 6; ++r) H.mutable_data()[6 * r + c] = H.mutable_data()[6 * c + r] = a.sums[v++];
+           std::copy(a.sums + 21, a.sums + 27, b.mutable_data());
+           std::copy(a.counts, a.counts + madicp_host::kAlignCounts, counts.mutable_data());
+           std::copy(a.first_counts, a.first_counts + madicp_host::kAlignCounts, first.mutable_data());
+           py::dict info;
+           info["iterations"] = a.iterations;
+           info["H"] = H;
+           info["b"] = b;
+           info["chi2"] = a.sums[27];
+           info["counts"] = counts;
+           info["chi2_start"] = a.first_chi2;
+           info["counts_start"] = first;
+           return py::make_tuple(pose, info);
          })
     .def("mapNewRows",
          [](Pipeline& self, bool with_attribute, bool with_keys) -> py::object {
