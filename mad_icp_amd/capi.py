@@ -59,6 +59,53 @@ _u32p = C.POINTER(C.c_uint32)
 _i32p = C.POINTER(C.c_int32)
 _u64p = C.POINTER(C.c_uint64)
 _i64p = C.POINTER(C.c_int64)
+_fp = C.POINTER(C.c_float)
+
+# The voxel map's entry points, once for both libraries: (name after madicp_map_, name after madicp_host_map_, the C argument types
+# after the handle — (context, map id) on the device, the map on the host).  Three markers stand for what differs between the sides:
+_SCAN = "scan"            # the scan: a cloud id on the device, (xyz, n) on the host
+_SCAN_ATTR = "scan+attr"  # ... the host's (xyz, attribute words, n); a device cloud carries its words itself
+_NEW = "new"              # a create's last argument, the new map: int* id after the context, madicp_host_map** with no handle at all
+_SIZING = [C.c_double, C.c_int64, C.c_int64]
+_REMOVAL = [C.c_int64, _i64p, _i64p, _i64p]
+_WINDOW = [C.c_int64, _i64p]
+MAP_ENTRY_POINTS = [
+    ("create", "create", _SIZING + [_NEW]),
+    ("create_attr", "create_attr", _SIZING + [_NEW]),
+    ("create_ev", "create_ev", _SIZING + [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _NEW]),
+    ("create_mom", "create_mom", _SIZING + [C.c_int, _u32p, C.c_uint32, _NEW]),
+    ("insert_cloud", "insert", [_SCAN, _dp, _dp, _i64p, _i64p]),
+    ("insert_cloud", "insert_attr", [_SCAN_ATTR, _dp, _dp, _i64p, _i64p]),
+    ("size", "size", [_i64p]),
+    ("prune", "prune", [_dp, C.c_double] + _REMOVAL),
+    ("clear_rays", "clear_rays", [_SCAN, _dp, _dp, _dp, C.c_double] + _REMOVAL),
+    ("query_cloud", "query", [_SCAN, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p, C.c_int64, _u64p]),
+    ("register_cloud", "register", [_SCAN, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp, _u64p, _i32p, _dp, C.c_int64]),
+    ("track_removed", "track_removed", [C.c_int]),
+    ("removed_count", "removed_count", [_i64p]),
+    ("take_removed", "take_removed", [_u64p, _fp, _u32p] + _WINDOW),
+    ("download_f32", "download_f32", [C.c_int64, _fp] + _WINDOW),
+    ("download_keys", "download_keys", [C.c_int64, _u64p] + _WINDOW),
+    ("download_attr", "download_attr", [C.c_int64, _u32p] + _WINDOW),
+    ("download_evidence", "download_evidence", [C.c_int64, _u32p] + _WINDOW),
+    ("download_moments", "download_moments", [C.c_int64, _u64p] + _WINDOW),
+    ("download_rows", "download_rows", [C.c_int64, _fp, _u64p, _u32p] + _WINDOW),
+    ("download_min_evidence", "download_min_evidence", [C.c_uint32, _fp, _u64p, _u32p, _u32p] + _WINDOW),
+    ("download_surfels", "download_surfels", [C.c_int64, _fp, _fp, _fp, _u32p] + _WINDOW),
+    ("clear", "clear", []),
+    ("release", "destroy", []),
+]
+
+
+def map_argtypes(device):
+    """{entry point: argtypes} of one library's side of MAP_ENTRY_POINTS"""
+    scan = {_SCAN: [C.c_int] if device else [_dp, C.c_int64], _SCAN_ATTR: [C.c_int] if device else [_dp, _u32p, C.c_int64],
+            _NEW: [_ip] if device else [C.POINTER(C.c_void_p)]}
+    out = {}
+    for dev_name, host_name, args in MAP_ENTRY_POINTS:
+        handle = ([C.c_void_p] if device else []) + ([] if _NEW in args else [C.c_int if device else C.c_void_p])
+        out[("madicp_map_" + dev_name) if device else ("madicp_host_map_" + host_name)] = handle + [t for a in args for t in scan.get(a, [a])]
+    return out
 
 # madicp_host_allreduce_fn: int (*)(void* user, void* buf, int64_t count, int kind)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
@@ -115,7 +162,6 @@ def hip_lib():
         L.madicp_ctx_synchronize.argtypes = [C.c_void_p]
         L.madicp_ctx_get_option.argtypes = [C.c_void_p, C.c_char_p, _i64p]
         L.madicp_ctx_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-        L.madicp_ctx_get_option.argtypes = [C.c_void_p, C.c_char_p, _i64p]
         L.madicp_tree_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _ip]
         L.madicp_tree_upload_trusted.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, _ip]
         L.madicp_tree_release.argtypes = [C.c_void_p, C.c_int]
@@ -172,34 +218,9 @@ def hip_lib():
         L.madicp_cloud_set_attr.argtypes = [C.c_void_p, C.c_int, _u32p, C.c_int64]
         L.madicp_cloud_attr.argtypes = [C.c_void_p, C.c_int, _u32p, C.c_int64]
         L.madicp_cloud_export_f32_attr.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
-        L.madicp_map_create_attr.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, _ip]
-        L.madicp_map_download_attr.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u32p, C.c_int64, _i64p]
         L.madicp_cloud_export_f32.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
-        L.madicp_map_create.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, _ip]
-        L.madicp_map_insert_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _i64p, _i64p]
-        L.madicp_map_size.argtypes = [C.c_void_p, C.c_int, _i64p]
-        L.madicp_map_download_f32.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
-        L.madicp_map_clear.argtypes = [C.c_void_p, C.c_int]
-        L.madicp_map_prune.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
-        L.madicp_map_clear_rays.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
-        L.madicp_map_release.argtypes = [C.c_void_p, C.c_int]
-        L.madicp_map_query_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p,
-                                             C.c_int64, _u64p]
-        L.madicp_map_register_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp,
-                                                _u64p, _i32p, _dp, C.c_int64]
-        L.madicp_map_track_removed.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.madicp_map_removed_count.argtypes = [C.c_void_p, C.c_int, _i64p]
-        L.madicp_map_take_removed.argtypes = [C.c_void_p, C.c_int, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
-        L.madicp_map_download_keys.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u64p, C.c_int64, _i64p]
-        L.madicp_map_download_rows.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), _u64p, _u32p, C.c_int64, _i64p]
-        L.madicp_map_create_ev.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, _ip]
-        L.madicp_map_download_evidence.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u32p, C.c_int64, _i64p]
-        L.madicp_map_download_min_evidence.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_float), _u64p, _u32p, _u32p, C.c_int64,
-                                                       _i64p]
-        L.madicp_map_create_mom.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, _u32p, C.c_uint32, _ip]
-        L.madicp_map_download_moments.argtypes = [C.c_void_p, C.c_int, C.c_int64, _u64p, C.c_int64, _i64p]
-        L.madicp_map_download_surfels.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                                  C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
+        for name, argtypes in map_argtypes(device=True).items():
+            getattr(L, name).argtypes = argtypes
         L.madicp_cloud_deskew_own_stamps.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, _i32p]
         L.madicp_cloud_deskew_stamped.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int64, _dp, C.c_double, _i32p]
@@ -251,39 +272,13 @@ def host_lib():
                                                  _dp, _dp, _i64p, _dp]
         L.madicp_host_ingest_sources.argtypes = [C.POINTER(RecordSourceC), C.c_int, _dp, _dp, _dp, _i64p, _i64p, _dp]
         L.madicp_host_cloud_export_f32.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), C.c_int64, _i64p]
-        L.madicp_host_map_create.argtypes = [C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
-        L.madicp_host_map_insert.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, _i64p, _i64p]
-        L.madicp_host_map_size.argtypes = [C.c_void_p, _i64p]
-        L.madicp_host_map_download_f32.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.c_int64, _i64p]
-        L.madicp_host_map_clear.argtypes = [C.c_void_p]
-        L.madicp_host_map_prune.argtypes = [C.c_void_p, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
-        L.madicp_host_map_clear_rays.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, _dp, C.c_double, C.c_int64, _i64p, _i64p, _i64p]
         L.madicp_host_ingest_sources_attr.argtypes = [C.POINTER(RecordSourceC), C.c_int, C.POINTER(AttrFieldC), _dp, _dp, _dp, _u32p, _i64p,
                                                       _i64p, _dp]
         L.madicp_host_cloud_export_f32_attr.argtypes = [_dp, _u32p, C.c_int64, _dp, _dp, C.c_double, C.POINTER(C.c_float), _u32p, C.c_int64,
                                                         _i64p]
-        L.madicp_host_map_create_attr.argtypes = [C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
-        L.madicp_host_map_insert_attr.argtypes = [C.c_void_p, _dp, _u32p, C.c_int64, _dp, _dp, _i64p, _i64p]
-        L.madicp_host_map_download_attr.argtypes = [C.c_void_p, C.c_int64, _u32p, C.c_int64, _i64p]
-        L.madicp_host_map_track_removed.argtypes = [C.c_void_p, C.c_int]
-        L.madicp_host_map_removed_count.argtypes = [C.c_void_p, _i64p]
-        L.madicp_host_map_take_removed.argtypes = [C.c_void_p, _u64p, C.POINTER(C.c_float), _u32p, C.c_int64, _i64p]
-        L.madicp_host_map_download_keys.argtypes = [C.c_void_p, C.c_int64, _u64p, C.c_int64, _i64p]
-        L.madicp_host_map_download_rows.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), _u64p, _u32p, C.c_int64, _i64p]
-        L.madicp_host_map_create_ev.argtypes = [C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32,
-                                                C.POINTER(C.c_void_p)]
-        L.madicp_host_map_download_evidence.argtypes = [C.c_void_p, C.c_int64, _u32p, C.c_int64, _i64p]
-        L.madicp_host_map_download_min_evidence.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), _u64p, _u32p, _u32p, C.c_int64, _i64p]
-        L.madicp_host_map_create_mom.argtypes = [C.c_double, C.c_int64, C.c_int64, C.c_int, _u32p, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.madicp_host_map_download_moments.argtypes = [C.c_void_p, C.c_int64, _u64p, C.c_int64, _i64p]
-        L.madicp_host_map_download_surfels.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                                       _u32p, C.c_int64, _i64p]
-        L.madicp_host_map_query.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p,
-                                            C.c_int64, _u64p]
-        L.madicp_host_map_register.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp, _u64p,
-                                               _i32p, _dp, C.c_int64]
+        for name, argtypes in map_argtypes(device=False).items():
+            getattr(L, name).argtypes = argtypes
         L.madicp_host_map_destroy.restype = None
-        L.madicp_host_map_destroy.argtypes = [C.c_void_p]
         L.madicp_host_debug_tree_points.argtypes = [_dp, C.c_int64, C.c_double, C.c_double, C.c_int]
         L.madicp_host_debug_partition.restype = C.c_int64
         L.madicp_host_debug_partition.argtypes = [_dp, C.c_int64, _dp, _dp, C.c_int]
@@ -624,287 +619,228 @@ def _host_map_check(rc, what):
         raise MadIcpError("%s: error %d (%s)" % (what, rc, "capacity" if rc == -4 else "bad arguments"))
 
 
-def host_map_create(voxel, initial_rows, max_rows):
-    """madicp_host_map_create: the host twin of Context.map_create.  Returns the handle the other host_map_* calls take;
-    host_map_destroy frees it."""
-    h = C.c_void_p()
-    _host_map_check(host_lib().madicp_host_map_create(float(voxel), int(initial_rows), int(max_rows), C.byref(h)), "madicp_host_map_create")
-    return h
+_PTR = {np.float32: _fp, np.float64: _dp, np.int32: _i32p, np.uint32: _u32p, np.uint64: _u64p}
 
 
-def host_map_create_attr(voxel, initial_rows, max_rows):
-    """madicp_host_map_create_attr: a host map with the attribute column (the twin of Context.map_create_attr)."""
-    h = C.c_void_p()
-    _host_map_check(host_lib().madicp_host_map_create_attr(float(voxel), int(initial_rows), int(max_rows), C.byref(h)),
-                    "madicp_host_map_create_attr")
-    return h
+def _ptr(a):
+    """an array as the pointer argument of its element type (None: not asked for)"""
+    return None if a is None else a.ctypes.data_as(_PTR[a.dtype.type])
 
 
-def host_map_insert_attr(h, xyz, attr, R, t):
-    """host_map_insert with the cloud's attribute column (n words, or None: the cloud carries none)."""
-    a = _f64(xyz).reshape(-1, 3)
-    w = None if attr is None else _u32(attr)
-    if w is not None and w.shape[0] != a.shape[0]:
-        raise ValueError("one attribute word per point")
-    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
-    added, rows = C.c_int64(0), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_insert_attr(h, a.ctypes.data_as(_dp), w.ctypes.data_as(_u32p) if w is not None else None,
-                                                           a.shape[0], Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), C.byref(added),
-                                                           C.byref(rows)), "madicp_host_map_insert_attr")
-    return added.value, rows.value
+# the columns a map hands out: (shape of one row's entry, dtype)
+_XYZ, _KEYS, _WORDS, _MOMENTS = ((3,), np.float32), ((), np.uint64), ((), np.uint32), ((10,), np.uint64)
 
 
-def host_map_download_attr(h, first_row=0):
-    """The attribute words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_download_attr(h, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)),
-                    "madicp_host_map_download_attr")
-    return out[:got.value].copy()
+class _Map:
+    """One voxel map, every operation once; Context.map_* (the device's) and host_map_* (the twin's) are these and the
+    Context methods document them.  HostMap and DeviceMap say how a call reaches C (create, _call) and what a scan becomes as C
+    arguments (_scan): a resident cloud's id on the device, xyz (n, 3) float64 on the host."""
+    _NAMES = {}  # the operations whose entry point is named otherwise on this side
+
+    @staticmethod
+    def _creation(voxel, initial_rows, max_rows, with_attr=False, evidence=None, max_count=None):
+        """(the create entry point of a combination of columns, its arguments before the new map)"""
+        sizing = (float(voxel), int(initial_rows), int(max_rows))
+        if evidence is not None:
+            hit, miss, cap = (int(v) for v in evidence)
+        if max_count is not None:
+            ev = None if evidence is None else (C.c_uint32 * 3)(hit, miss, cap)
+            return "create_mom", sizing + (1 if with_attr else 0, ev, int(max_count))
+        if evidence is not None:
+            return "create_ev", sizing + (1 if with_attr else 0, hit, miss, cap)
+        return ("create_attr" if with_attr else "create"), sizing
+
+    def _fetch(self, op, m, columns, *lead):
+        """`op` into one buffer of m rows per column asked for (None: not asked for); the copies of what it wrote"""
+        bufs = [None if c is None else np.empty((max(m, 1),) + c[0], c[1]) for c in columns]
+        got = C.c_int64(0)
+        self._call(op, *lead, *[_ptr(b) for b in bufs], m, C.byref(got))
+        return tuple(b[:got.value].copy() for b in bufs if b is not None)
+
+    def _window(self, op, first_row, *columns):
+        return self._fetch(op, max(self.size() - int(first_row), 0), columns, int(first_row))
+
+    def _removal(self, op, *args):
+        removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._call(op, *args, C.byref(removed), C.byref(rows), C.byref(mark))
+        return removed.value, rows.value, mark.value
+
+    def size(self):
+        rows = C.c_int64(0)
+        self._call("size", C.byref(rows))
+        return rows.value
+
+    def insert(self, scan, R, t, *attr):
+        """*attr (the host's insert_attr): the scan's words or None, where it is not a cloud that carries them"""
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        added, rows = C.c_int64(0), C.c_int64(0)
+        self._call("insert_attr" if attr else "insert", *self._scan(scan, *attr)[0], _ptr(Rm), _ptr(tv), C.byref(added), C.byref(rows))
+        return added.value, rows.value
+
+    def prune(self, center, radius, watermark=0):
+        return self._removal("prune", _ptr(_f64(center, (3,))), float(radius), int(watermark))
+
+    def clear_rays(self, scan, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, watermark=0):
+        Rm, tv, o = _f64(R, (9,)), _f64(t, (3,)), _f64(origin, (3,))
+        return self._removal("clear_rays", *self._scan(scan)[0], _ptr(Rm), _ptr(tv), _ptr(o), float(margin), int(watermark))
+
+    def query(self, scan, R, t, reach=1, max_dist=float("inf"), per_point=True, with_keys=False, with_attr=False, with_ev=False):
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        where, n = self._scan(scan, sized=True)
+        asked = (per_point, per_point, with_keys, with_attr, with_ev)
+        bufs = [np.empty(max(n, 1), dt) if a else None for a, dt in zip(asked, (np.int32, np.float64, np.uint64, np.uint32, np.uint32))]
+        counts = np.zeros(3, np.uint64)
+        self._call("query", *where, _ptr(Rm), _ptr(tv), int(reach), float(max_dist), *[_ptr(b) for b in bufs], n, _ptr(counts))
+        c = tuple(int(v) for v in counts)
+        return (c,) + tuple(b[:n].copy() for b in bufs if b is not None) if per_point else c
+
+    def register(self, scan, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0, per_point=False):
+        where, n = self._scan(scan, sized=True)
+        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
+        k1 = max(int(iterations), 0) + 1
+        params = MapAlignParams(int(reach), float(max_dist), float(rho), int(min_count), float(flat))
+        out_R, out_t = np.zeros(9), np.zeros(3)
+        trace, counts = np.zeros((k1, 40)), np.zeros((k1, 4), np.uint64)  # a trace row: X[12] | H[21], the upper triangle | b[6] | chi2
+        row = np.empty(max(n, 1), np.int32) if per_point else None
+        e = np.empty(max(n, 1), np.float64) if per_point else None
+        self._call("register", *where, _ptr(Rm), _ptr(tv), C.byref(params), int(iterations), _ptr(out_R), _ptr(out_t), _ptr(trace),
+                   _ptr(counts), _ptr(row), _ptr(e), n)
+        H = np.zeros((k1, 6, 6))
+        v = 12
+        for c in range(6):
+            for r in range(c, 6):
+                H[:, r, c] = H[:, c, r] = trace[:, v]
+                v += 1
+        ans = dict(R=out_R.reshape(3, 3), t=out_t, X=trace[:, :12].copy(), H=H, b=trace[:, 33:39].copy(), chi2=trace[:, 39].copy(), counts=counts)
+        if per_point:
+            ans["row"], ans["e"] = row[:n].copy(), e[:n].copy()
+        return ans
+
+    def track_removed(self, on=True):
+        self._call("track_removed", 1 if on else 0)
+
+    def removed_count(self):
+        n = C.c_int64(0)
+        self._call("removed_count", C.byref(n))
+        return n.value
+
+    def take_removed(self, with_attr=False):
+        return self._fetch("take_removed", self.removed_count(), (_KEYS, _XYZ, _WORDS if with_attr else None))
+
+    def download_f32(self, first_row=0):
+        return self._window("download_f32", first_row, _XYZ)[0]
+
+    def download_keys(self, first_row=0):
+        return self._window("download_keys", first_row, _KEYS)[0]
+
+    def download_attr(self, first_row=0):
+        return self._window("download_attr", first_row, _WORDS)[0]
+
+    def download_evidence(self, first_row=0):
+        return self._window("download_evidence", first_row, _WORDS)[0]
+
+    def download_moments(self, first_row=0):
+        return self._window("download_moments", first_row, _MOMENTS)[0]
+
+    def download_rows(self, first_row=0, with_keys=True, with_attr=False):
+        return self._window("download_rows", first_row, _XYZ, _KEYS if with_keys else None, _WORDS if with_attr else None)
+
+    def download_min_evidence(self, min_e, with_keys=False, with_attr=False, with_ev=False):
+        columns = (_XYZ, _KEYS if with_keys else None, _WORDS if with_attr else None, _WORDS if with_ev else None)
+        return self._fetch("download_min_evidence", self.size(), columns, int(min_e))
+
+    def download_surfels(self, first_row=0):
+        return self._window("download_surfels", first_row, _XYZ, _XYZ, _XYZ, _WORDS)
+
+    def clear(self):
+        self._call("clear")
 
 
-def host_map_insert(h, xyz, R, t):
-    """Folds xyz (n, 3) float64 through (R (3, 3), t (3,)) into the map.  Returns (rows added, rows the map holds)."""
-    a = _f64(xyz).reshape(-1, 3)
-    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
-    added, rows = C.c_int64(0), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_insert(h, a.ctypes.data_as(_dp), a.shape[0], Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp),
-                                                      C.byref(added), C.byref(rows)), "madicp_host_map_insert")
-    return added.value, rows.value
+class HostMap(_Map):
+    """The host twin (madicp_host_map_*, include/madicp_host.h) behind a handle that HostMap.create made; close() frees it."""
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def create(cls, *spec, **more):
+        """voxel, initial_rows, max_rows, with_attr=False, evidence=None, max_count=None"""
+        op, args = cls._creation(*spec, **more)
+        h = C.c_void_p()
+        _host_map_check(getattr(host_lib(), "madicp_host_map_" + op)(*args, C.byref(h)), "madicp_host_map_" + op)
+        return cls(h)
+
+    def _call(self, op, *args):
+        name = "madicp_host_map_" + self._NAMES.get(op, op)
+        _host_map_check(getattr(host_lib(), name)(self._h, *args), name)
+
+    def _scan(self, xyz, *attr, sized=False):
+        a = _f64(xyz).reshape(-1, 3)
+        n = a.shape[0]
+        w = None if not attr or attr[0] is None else _u32(attr[0])
+        if w is not None and w.shape[0] != n:
+            raise ValueError("one attribute word per point")
+        return (_ptr(a) if n else None,) + ((_ptr(w),) if attr else ()) + (n,), n
+
+    def close(self):
+        host_lib().madicp_host_map_destroy(self._h)
 
 
-def host_map_size(h):
-    rows = C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_size(h, C.byref(rows)), "madicp_host_map_size")
-    return rows.value
+class DeviceMap(_Map):
+    """The map where it lives (madicp_map_*, include/madicp_hip.h): map `mid` of Context `ctx`; close() releases it."""
+    _NAMES = {"insert": "insert_cloud", "query": "query_cloud", "register": "register_cloud", "close": "release"}
+
+    def __init__(self, ctx, mid):
+        self._ctx, self.mid = ctx, mid
+
+    @classmethod
+    def create(cls, ctx, *spec, **more):
+        """voxel, initial_rows, max_rows, with_attr=False, evidence=None, max_count=None"""
+        op, args = cls._creation(*spec, **more)
+        mid = C.c_int(0)
+        _check(getattr(hip_lib(), "madicp_map_" + op)(ctx._h, *args, C.byref(mid)))
+        return cls(ctx, mid.value)
+
+    def _call(self, op, *args):
+        _check(getattr(hip_lib(), "madicp_map_" + self._NAMES.get(op, op))(self._ctx._h, self.mid, *args))
+
+    def _scan(self, cid, sized=False):
+        return (cid,), (self._ctx.cloud_size(cid) if sized else None)
+
+    def close(self):
+        self._call("close")
 
 
-def host_map_download_f32(h, first_row=0):
-    """Rows [first_row, size) of the map as (M - first_row, 3) float32."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    out, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_download_f32(h, int(first_row), out.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(got)),
-                    "madicp_host_map_download_f32")
-    return out[:got.value].copy()
-
-
-def host_map_prune(h, center, radius, watermark=0):
-    """madicp_host_map_prune: the host twin of Context.map_prune.  Returns (rows removed, rows the map holds, the kept rows among
-    rows [0, watermark))."""
-    c = _f64(center, (3,))
-    removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_prune(h, c.ctypes.data_as(_dp), float(radius), int(watermark), C.byref(removed),
-                                                     C.byref(rows), C.byref(mark)), "madicp_host_map_prune")
-    return removed.value, rows.value, mark.value
-
-
-def host_map_clear_rays(h, xyz, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, watermark=0):
-    """madicp_host_map_clear_rays: the host twin of Context.map_clear_rays over xyz (n, 3) float64.  Returns (rows removed, rows
-    the map holds, the kept rows among rows [0, watermark))."""
-    a = _f64(xyz).reshape(-1, 3)
-    Rm, tv, o = _f64(R, (9,)), _f64(t, (3,)), _f64(origin, (3,))
-    removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_clear_rays(h, a.ctypes.data_as(_dp), a.shape[0], Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp),
-                                                          o.ctypes.data_as(_dp), float(margin), int(watermark), C.byref(removed),
-                                                          C.byref(rows), C.byref(mark)), "madicp_host_map_clear_rays")
-    return removed.value, rows.value, mark.value
-
-
-def _query_buffers(n, per_point, with_keys, with_attr, with_ev):
-    """the per-point buffers of a map query, in the C call's order (None: not asked for), and their ctypes arguments"""
-    m = max(n, 1)
-    bufs = [np.empty(m, np.int32) if per_point else None, np.empty(m, np.float64) if per_point else None,
-            np.empty(m, np.uint64) if with_keys else None, np.empty(m, np.uint32) if with_attr else None,
-            np.empty(m, np.uint32) if with_ev else None]
-    args = [b.ctypes.data_as(ct) if b is not None else None for b, ct in zip(bufs, (_i32p, _dp, _u64p, _u32p, _u32p))]
-    return bufs, args
-
-
-def _query_answer(counts, bufs, n, per_point):
-    c = tuple(int(v) for v in counts)
-    return (c,) + tuple(b[:n].copy() for b in bufs if b is not None) if per_point else c
-
-
-def host_map_query(h, xyz, R, t, reach=1, max_dist=float("inf"), per_point=True, with_keys=False, with_attr=False, with_ev=False):
-    """madicp_host_map_query: the host twin of Context.map_query over xyz (n, 3) float64, the same answer bit for bit."""
-    a = _f64(xyz).reshape(-1, 3)
-    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
-    n = a.shape[0]
-    bufs, args = _query_buffers(n, per_point, with_keys, with_attr, with_ev)
-    counts = np.zeros(3, np.uint64)
-    _host_map_check(host_lib().madicp_host_map_query(h, a.ctypes.data_as(_dp), n, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), int(reach),
-                                                     float(max_dist), *args, n, counts.ctypes.data_as(_u64p)), "madicp_host_map_query")
-    return _query_answer(counts, bufs, n, per_point)
-
-
-def _align_call(call, n, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point):
-    """the buffers of a map registration around `call(Rp, tp, params, iterations, out_R, out_t, trace, counts, row, e, capacity)`, and
-    its answer: dict(R (3, 3), t (3,), X (K + 1, 12), H (K + 1, 6, 6), b (K + 1, 6), chi2 (K + 1,), counts (K + 1, 4) uint64
-    [, row (n,) int32, e (n,) float64]) — row k the linearisation at X[k], the last one at the returned pose"""
-    Rm, tv = _f64(R, (9,)), _f64(t, (3,))
-    k1 = max(int(iterations), 0) + 1
-    params = MapAlignParams(int(reach), float(max_dist), float(rho), int(min_count), float(flat))
-    out_R, out_t = np.zeros(9), np.zeros(3)
-    trace, counts = np.zeros((k1, 40)), np.zeros((k1, 4), np.uint64)
-    row = np.empty(max(n, 1), np.int32) if per_point else None
-    e = np.empty(max(n, 1), np.float64) if per_point else None
-    call(Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), C.byref(params), int(iterations), out_R.ctypes.data_as(_dp),
-         out_t.ctypes.data_as(_dp), trace.ctypes.data_as(_dp), counts.ctypes.data_as(_u64p),
-         row.ctypes.data_as(_i32p) if per_point else None, e.ctypes.data_as(_dp) if per_point else None, n)
-    H = np.zeros((k1, 6, 6))
-    v = 12
-    for c in range(6):
-        for r in range(c, 6):
-            H[:, r, c] = H[:, c, r] = trace[:, v]
-            v += 1
-    ans = dict(R=out_R.reshape(3, 3), t=out_t, X=trace[:, :12].copy(), H=H, b=trace[:, 33:39].copy(), chi2=trace[:, 39].copy(), counts=counts)
-    if per_point:
-        ans["row"], ans["e"] = row[:n].copy(), e[:n].copy()
-    return ans
-
-
-def host_map_register(h, xyz, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0, per_point=False):
-    """madicp_host_map_register: the host twin of Context.map_register_cloud over xyz (n, 3) float64."""
-    a = _f64(xyz).reshape(-1, 3)
-    n = a.shape[0]
-
-    def call(*args):
-        _host_map_check(host_lib().madicp_host_map_register(h, a.ctypes.data_as(_dp) if n else None, n, *args), "madicp_host_map_register")
-
-    return _align_call(call, n, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
-
-
-def host_map_track_removed(h, on=True):
-    """madicp_host_map_track_removed: the host twin of Context.map_track_removed."""
-    _host_map_check(host_lib().madicp_host_map_track_removed(h, 1 if on else 0), "madicp_host_map_track_removed")
-
-
-def host_map_removed_count(h):
-    n = C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_removed_count(h, C.byref(n)), "madicp_host_map_removed_count")
-    return n.value
-
-
-def host_map_take_removed(h, with_attr=False):
-    """madicp_host_map_take_removed: the host twin of Context.map_take_removed.  Returns (keys (n,) uint64, rows (n, 3) float32
-    [, words (n,) uint32]) and empties the log."""
-    n = host_map_removed_count(h)
-    keys, xyz, got = np.empty(max(n, 1), np.uint64), np.empty((max(n, 1), 3), np.float32), C.c_int64(0)
-    w = np.empty(max(n, 1), np.uint32) if with_attr else None
-    _host_map_check(host_lib().madicp_host_map_take_removed(h, keys.ctypes.data_as(_u64p), xyz.ctypes.data_as(C.POINTER(C.c_float)),
-                                                            w.ctypes.data_as(_u32p) if with_attr else None, n, C.byref(got)),
-                    "madicp_host_map_take_removed")
-    m = got.value
-    return (keys[:m].copy(), xyz[:m].copy()) + ((w[:m].copy(),) if with_attr else ())
-
-
-def host_map_download_keys(h, first_row=0):
-    """The stored voxel keys of rows [first_row, size) as (M - first_row,) uint64."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    out, got = np.empty(max(m, 1), np.uint64), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_download_keys(h, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)),
-                    "madicp_host_map_download_keys")
-    return out[:got.value].copy()
-
-
-def host_map_download_rows(h, first_row=0, with_keys=True, with_attr=False):
-    """madicp_host_map_download_rows: the columns of rows [first_row, size): (rows (M, 3) float32[, keys uint64][, words uint32])."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
-    k = np.empty(max(m, 1), np.uint64) if with_keys else None
-    w = np.empty(max(m, 1), np.uint32) if with_attr else None
-    _host_map_check(host_lib().madicp_host_map_download_rows(h, int(first_row), xyz.ctypes.data_as(C.POINTER(C.c_float)),
-                                                             k.ctypes.data_as(_u64p) if with_keys else None,
-                                                             w.ctypes.data_as(_u32p) if with_attr else None, m, C.byref(got)),
-                    "madicp_host_map_download_rows")
-    g = got.value
-    return (xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ())
-
-
+# the documented names of the host twin: h is what host_map_create* returned; Context.map_* has the words for each
+def host_map_create(voxel, initial_rows, max_rows): return HostMap.create(voxel, initial_rows, max_rows)._h
+def host_map_create_attr(voxel, initial_rows, max_rows): return HostMap.create(voxel, initial_rows, max_rows, True)._h
 def host_map_create_ev(voxel, initial_rows, max_rows, hit, miss, cap, with_attr=False):
-    """madicp_host_map_create_ev: a host map with the evidence column (the twin of Context.map_create_ev)."""
-    h = C.c_void_p()
-    _host_map_check(host_lib().madicp_host_map_create_ev(float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0, int(hit),
-                                                         int(miss), int(cap), C.byref(h)), "madicp_host_map_create_ev")
-    return h
-
-
-def host_map_download_evidence(h, first_row=0):
-    """The evidence words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_download_evidence(h, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)),
-                    "madicp_host_map_download_evidence")
-    return out[:got.value].copy()
-
-
-def host_map_download_min_evidence(h, min_e, with_keys=False, with_attr=False, with_ev=False):
-    """madicp_host_map_download_min_evidence: the rows whose evidence word is >= min_e, in row order:
-    (rows (n, 3) float32[, keys uint64][, words uint32][, evidence uint32])."""
-    m = host_map_size(h)
-    xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
-    k = np.empty(max(m, 1), np.uint64) if with_keys else None
-    w = np.empty(max(m, 1), np.uint32) if with_attr else None
-    e = np.empty(max(m, 1), np.uint32) if with_ev else None
-    _host_map_check(host_lib().madicp_host_map_download_min_evidence(h, int(min_e), xyz.ctypes.data_as(C.POINTER(C.c_float)),
-                                                                     k.ctypes.data_as(_u64p) if with_keys else None,
-                                                                     w.ctypes.data_as(_u32p) if with_attr else None,
-                                                                     e.ctypes.data_as(_u32p) if with_ev else None, m, C.byref(got)),
-                    "madicp_host_map_download_min_evidence")
-    g = got.value
-    return ((xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ()) +
-            ((e[:g].copy(),) if with_ev else ()))
-
-
-def _evidence_arg(evidence):
-    """(hit, miss, cap) or None as the const uint32_t[3] argument of the _create_mom entry points."""
-    if evidence is None:
-        return None
-    hit, miss, cap = evidence
-    return (C.c_uint32 * 3)(int(hit), int(miss), int(cap))
-
-
-def _surfel_buffers(m):
-    f = lambda: np.empty((max(m, 1), 3), np.float32)
-    return f(), f(), f(), np.empty(max(m, 1), np.uint32)
-
-
+    return HostMap.create(voxel, initial_rows, max_rows, with_attr, (hit, miss, cap))._h
 def host_map_create_mom(voxel, initial_rows, max_rows, max_count, with_attr=False, evidence=None):
-    """madicp_host_map_create_mom: a host map with per-voxel moments (the twin of Context.map_create_mom)."""
-    h = C.c_void_p()
-    _host_map_check(host_lib().madicp_host_map_create_mom(float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0,
-                                                          _evidence_arg(evidence), int(max_count), C.byref(h)), "madicp_host_map_create_mom")
-    return h
-
-
-def host_map_download_moments(h, first_row=0):
-    """The moment words of rows [first_row, size) as (M - first_row, 10) uint64: n, S1[3], S2[6]; MadIcpError without moments."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    out, got = np.empty((max(m, 1), 10), np.uint64), C.c_int64(0)
-    _host_map_check(host_lib().madicp_host_map_download_moments(h, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)),
-                    "madicp_host_map_download_moments")
-    return out[:got.value].copy()
-
-
-def host_map_download_surfels(h, first_row=0):
-    """madicp_host_map_download_surfels: (centroid (M, 3) f32, normal (M, 3) f32, eigenvalues (M, 3) f32, count (M,) u32)."""
-    m = max(host_map_size(h) - int(first_row), 0)
-    c, nrm, eig, cnt = _surfel_buffers(m)
-    got = C.c_int64(0)
-    fp = C.POINTER(C.c_float)
-    _host_map_check(host_lib().madicp_host_map_download_surfels(h, int(first_row), c.ctypes.data_as(fp), nrm.ctypes.data_as(fp),
-                                                                eig.ctypes.data_as(fp), cnt.ctypes.data_as(_u32p), m, C.byref(got)),
-                    "madicp_host_map_download_surfels")
-    g = got.value
-    return c[:g].copy(), nrm[:g].copy(), eig[:g].copy(), cnt[:g].copy()
-
-
-def host_map_clear(h):
-    _host_map_check(host_lib().madicp_host_map_clear(h), "madicp_host_map_clear")
-
-
-def host_map_destroy(h):
-    host_lib().madicp_host_map_destroy(h)
+    return HostMap.create(voxel, initial_rows, max_rows, with_attr, evidence, max_count)._h
+def host_map_insert(h, xyz, R, t): return HostMap(h).insert(xyz, R, t)
+def host_map_insert_attr(h, xyz, attr, R, t): return HostMap(h).insert(xyz, R, t, attr)
+def host_map_size(h): return HostMap(h).size()
+def host_map_prune(h, center, radius, watermark=0): return HostMap(h).prune(center, radius, watermark)
+def host_map_clear_rays(h, xyz, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, watermark=0):
+    return HostMap(h).clear_rays(xyz, R, t, origin, margin, watermark)
+def host_map_query(h, xyz, R, t, reach=1, max_dist=float("inf"), per_point=True, with_keys=False, with_attr=False, with_ev=False):
+    return HostMap(h).query(xyz, R, t, reach, max_dist, per_point, with_keys, with_attr, with_ev)
+def host_map_register(h, xyz, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0, per_point=False):
+    return HostMap(h).register(xyz, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
+def host_map_track_removed(h, on=True): HostMap(h).track_removed(on)
+def host_map_removed_count(h): return HostMap(h).removed_count()
+def host_map_take_removed(h, with_attr=False): return HostMap(h).take_removed(with_attr)
+def host_map_download_f32(h, first_row=0): return HostMap(h).download_f32(first_row)
+def host_map_download_keys(h, first_row=0): return HostMap(h).download_keys(first_row)
+def host_map_download_attr(h, first_row=0): return HostMap(h).download_attr(first_row)
+def host_map_download_evidence(h, first_row=0): return HostMap(h).download_evidence(first_row)
+def host_map_download_moments(h, first_row=0): return HostMap(h).download_moments(first_row)
+def host_map_download_rows(h, first_row=0, with_keys=True, with_attr=False): return HostMap(h).download_rows(first_row, with_keys, with_attr)
+def host_map_download_min_evidence(h, min_e, with_keys=False, with_attr=False, with_ev=False):
+    return HostMap(h).download_min_evidence(min_e, with_keys, with_attr, with_ev)
+def host_map_download_surfels(h, first_row=0): return HostMap(h).download_surfels(first_row)
+def host_map_clear(h): HostMap(h).clear()
+def host_map_destroy(h): HostMap(h).close()
 
 
 class Context:
@@ -1088,16 +1024,11 @@ class Context:
 
     def map_create_attr(self, voxel, initial_rows, max_rows):
         """map_create with the attribute column: every row keeps its owning point's word (0 for clouds that carry none)."""
-        mid = C.c_int(0)
-        _check(hip_lib().madicp_map_create_attr(self._h, float(voxel), int(initial_rows), int(max_rows), C.byref(mid)))
-        return mid.value
+        return DeviceMap.create(self, voxel, initial_rows, max_rows, True).mid
 
     def map_download_attr(self, mid, first_row=0):
         """The attribute words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
-        _check(hip_lib().madicp_map_download_attr(self._h, mid, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)))
-        return out[:got.value].copy()
+        return DeviceMap(self, mid).download_attr(first_row)
 
     def cloud_stamps(self, cid):
         """The stamps a cloud of cloud_ingest_records carries, (n,) float64 in the cloud's order; MadIcpError when it has none."""
@@ -1119,152 +1050,84 @@ class Context:
     def map_create(self, voxel, initial_rows, max_rows):
         """A device-resident, append-only voxel map (madicp_map_create): one float32 row per voxel, the first point ever to fall
         into it.  Returns the map id."""
-        mid = C.c_int(0)
-        _check(hip_lib().madicp_map_create(self._h, float(voxel), int(initial_rows), int(max_rows), C.byref(mid)))
-        return mid.value
+        return DeviceMap.create(self, voxel, initial_rows, max_rows).mid
 
     def map_insert_cloud(self, mid, cid, R, t):
         """Folds a resident cloud through (R (3, 3), t (3,)) into the map; the cloud is only read.  Returns (rows added, rows the
         map holds)."""
-        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
-        added, rows = C.c_int64(0), C.c_int64(0)
-        _check(hip_lib().madicp_map_insert_cloud(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), C.byref(added),
-                                                 C.byref(rows)))
-        return added.value, rows.value
+        return DeviceMap(self, mid).insert(cid, R, t)
 
     def map_size(self, mid):
-        rows = C.c_int64(0)
-        _check(hip_lib().madicp_map_size(self._h, mid, C.byref(rows)))
-        return rows.value
+        return DeviceMap(self, mid).size()
 
     def map_download_f32(self, mid, first_row=0):
         """Rows [first_row, size) of the map as (M - first_row, 3) float32: what was added since the caller last looked."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        out, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
-        _check(hip_lib().madicp_map_download_f32(self._h, mid, int(first_row), out.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(got)))
-        return out[:got.value].copy()
+        return DeviceMap(self, mid).download_f32(first_row)
 
     def map_prune(self, mid, center, radius, watermark=0):
         """Removes the rows whose stored float position is farther than radius from center (3,), with their voxels; the kept rows
         close up in order (madicp_map_prune).  Returns (rows removed, rows the map holds, the kept rows among rows [0, watermark)):
         a consumer that had fetched rows [0, watermark) has fetched exactly rows [0, that) of the pruned map."""
-        c = _f64(center, (3,))
-        removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        _check(hip_lib().madicp_map_prune(self._h, mid, c.ctypes.data_as(_dp), float(radius), int(watermark), C.byref(removed),
-                                          C.byref(rows), C.byref(mark)))
-        return removed.value, rows.value, mark.value
+        return DeviceMap(self, mid).prune(center, radius, watermark)
 
     def map_clear_rays(self, mid, cid, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, watermark=0):
         """Free-space clearing (madicp_map_clear_rays): the rays from origin (3,) to the points of resident cloud cid, taken into
         the map frame by (R (3, 3), t (3,)), are sampled one voxel edge apart, stopping margin short of the point; the rows whose
         voxel a sample falls in and no point of the cloud lies in leave, the kept rows close up in order.  The cloud is only read.
         Returns (rows removed, rows the map holds, the kept rows among rows [0, watermark))."""
-        Rm, tv, o = _f64(R, (9,)), _f64(t, (3,)), _f64(origin, (3,))
-        removed, rows, mark = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        _check(hip_lib().madicp_map_clear_rays(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), o.ctypes.data_as(_dp),
-                                               float(margin), int(watermark), C.byref(removed), C.byref(rows), C.byref(mark)))
-        return removed.value, rows.value, mark.value
+        return DeviceMap(self, mid).clear_rays(cid, R, t, origin, margin, watermark)
 
     def map_track_removed(self, mid, on=True):
         """madicp_map_track_removed: from now on the map logs the rows that map_prune and map_clear_rays remove from below their
         watermark (key, float row, word) until map_take_removed fetches them; on=False stops that and frees the log."""
-        _check(hip_lib().madicp_map_track_removed(self._h, mid, 1 if on else 0))
+        DeviceMap(self, mid).track_removed(on)
 
     def map_removed_count(self, mid):
-        n = C.c_int64(0)
-        _check(hip_lib().madicp_map_removed_count(self._h, mid, C.byref(n)))
-        return n.value
+        return DeviceMap(self, mid).removed_count()
 
     def map_take_removed(self, mid, with_attr=False):
         """madicp_map_take_removed: the removal log, oldest first, as (keys (n,) uint64, rows (n, 3) float32[, words (n,) uint32]);
         the log is empty afterwards.  One host synchronisation."""
-        n = self.map_removed_count(mid)
-        keys, xyz, got = np.empty(max(n, 1), np.uint64), np.empty((max(n, 1), 3), np.float32), C.c_int64(0)
-        w = np.empty(max(n, 1), np.uint32) if with_attr else None
-        _check(hip_lib().madicp_map_take_removed(self._h, mid, keys.ctypes.data_as(_u64p), xyz.ctypes.data_as(C.POINTER(C.c_float)),
-                                                 w.ctypes.data_as(_u32p) if with_attr else None, n, C.byref(got)))
-        m = got.value
-        return (keys[:m].copy(), xyz[:m].copy()) + ((w[:m].copy(),) if with_attr else ())
+        return DeviceMap(self, mid).take_removed(with_attr)
 
     def map_download_keys(self, mid, first_row=0):
         """The stored voxel keys of rows [first_row, size) as (M - first_row,) uint64: a row's identity across prunes."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        out, got = np.empty(max(m, 1), np.uint64), C.c_int64(0)
-        _check(hip_lib().madicp_map_download_keys(self._h, mid, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)))
-        return out[:got.value].copy()
+        return DeviceMap(self, mid).download_keys(first_row)
 
     def map_download_rows(self, mid, first_row=0, with_keys=True, with_attr=False):
         """madicp_map_download_rows: the columns of rows [first_row, size) behind ONE host synchronisation:
         (rows (M, 3) float32[, keys (M,) uint64][, words (M,) uint32])."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
-        k = np.empty(max(m, 1), np.uint64) if with_keys else None
-        w = np.empty(max(m, 1), np.uint32) if with_attr else None
-        _check(hip_lib().madicp_map_download_rows(self._h, mid, int(first_row), xyz.ctypes.data_as(C.POINTER(C.c_float)),
-                                                  k.ctypes.data_as(_u64p) if with_keys else None,
-                                                  w.ctypes.data_as(_u32p) if with_attr else None, m, C.byref(got)))
-        g = got.value
-        return (xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ())
+        return DeviceMap(self, mid).download_rows(first_row, with_keys, with_attr)
 
     def map_create_ev(self, voxel, initial_rows, max_rows, hit, miss, cap, with_attr=False):
         """madicp_map_create_ev: a map with the evidence column — a fold gives `hit` to the rows it creates and adds `hit`, once per
         fold and saturating at `cap`, to the older rows it falls into; map_clear_rays takes `miss` from a row it sees through and
         removes it only when that uses the word up.  with_attr: the attribute column as well.  Returns the map id."""
-        mid = C.c_int(0)
-        _check(hip_lib().madicp_map_create_ev(self._h, float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0, int(hit),
-                                              int(miss), int(cap), C.byref(mid)))
-        return mid.value
+        return DeviceMap.create(self, voxel, initial_rows, max_rows, with_attr, (hit, miss, cap)).mid
 
     def map_download_evidence(self, mid, first_row=0):
         """The evidence words of rows [first_row, size) as (M - first_row,) uint32; MadIcpError on a map made without the column."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        out, got = np.empty(max(m, 1), np.uint32), C.c_int64(0)
-        _check(hip_lib().madicp_map_download_evidence(self._h, mid, int(first_row), out.ctypes.data_as(_u32p), m, C.byref(got)))
-        return out[:got.value].copy()
+        return DeviceMap(self, mid).download_evidence(first_row)
 
     def map_download_min_evidence(self, mid, min_e, with_keys=False, with_attr=False, with_ev=False):
         """madicp_map_download_min_evidence: the rows whose evidence word is >= min_e, in row order, compacted on the device:
         (rows (n, 3) float32[, keys uint64][, words uint32][, evidence uint32])."""
-        m = self.map_size(mid)
-        xyz, got = np.empty((max(m, 1), 3), np.float32), C.c_int64(0)
-        k = np.empty(max(m, 1), np.uint64) if with_keys else None
-        w = np.empty(max(m, 1), np.uint32) if with_attr else None
-        e = np.empty(max(m, 1), np.uint32) if with_ev else None
-        _check(hip_lib().madicp_map_download_min_evidence(self._h, mid, int(min_e), xyz.ctypes.data_as(C.POINTER(C.c_float)),
-                                                          k.ctypes.data_as(_u64p) if with_keys else None,
-                                                          w.ctypes.data_as(_u32p) if with_attr else None,
-                                                          e.ctypes.data_as(_u32p) if with_ev else None, m, C.byref(got)))
-        g = got.value
-        return ((xyz[:g].copy(),) + ((k[:g].copy(),) if with_keys else ()) + ((w[:g].copy(),) if with_attr else ()) +
-                ((e[:g].copy(),) if with_ev else ()))
+        return DeviceMap(self, mid).download_min_evidence(min_e, with_keys, with_attr, with_ev)
 
     def map_create_mom(self, voxel, initial_rows, max_rows, max_count, with_attr=False, evidence=None):
         """madicp_map_create_mom: a map with per-voxel moments — ten 64-bit words per row (n, S1[3], S2[6]) over 16-bit offsets of
         the points that fell into the voxel; a row takes whole folds while its n is below `max_count`.  with_attr / evidence=(hit,
         miss, cap): those columns as well.  Returns the map id."""
-        mid = C.c_int(0)
-        _check(hip_lib().madicp_map_create_mom(self._h, float(voxel), int(initial_rows), int(max_rows), 1 if with_attr else 0,
-                                               _evidence_arg(evidence), int(max_count), C.byref(mid)))
-        return mid.value
+        return DeviceMap.create(self, voxel, initial_rows, max_rows, with_attr, evidence, max_count).mid
 
     def map_download_moments(self, mid, first_row=0):
         """The moment words of rows [first_row, size) as (M - first_row, 10) uint64; MadIcpError on a map made without them."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        out, got = np.empty((max(m, 1), 10), np.uint64), C.c_int64(0)
-        _check(hip_lib().madicp_map_download_moments(self._h, mid, int(first_row), out.ctypes.data_as(_u64p), m, C.byref(got)))
-        return out[:got.value].copy()
+        return DeviceMap(self, mid).download_moments(first_row)
 
     def map_download_surfels(self, mid, first_row=0):
         """madicp_map_download_surfels: (centroid (M, 3) f32, normal (M, 3) f32, eigenvalues (M, 3) f32, count (M,) u32), computed
         on the device from the moments and the stored keys."""
-        m = max(self.map_size(mid) - int(first_row), 0)
-        c, nrm, eig, cnt = _surfel_buffers(m)
-        got = C.c_int64(0)
-        fp = C.POINTER(C.c_float)
-        _check(hip_lib().madicp_map_download_surfels(self._h, mid, int(first_row), c.ctypes.data_as(fp), nrm.ctypes.data_as(fp),
-                                                     eig.ctypes.data_as(fp), cnt.ctypes.data_as(_u32p), m, C.byref(got)))
-        g = got.value
-        return c[:g].copy(), nrm[:g].copy(), eig[:g].copy(), cnt[:g].copy()
+        return DeviceMap(self, mid).download_surfels(first_row)
 
     def map_query(self, mid, cid, R, t, reach=1, max_dist=float("inf"), per_point=True, with_keys=False, with_attr=False, with_ev=False):
         """madicp_map_query_cloud: for every point of resident cloud cid taken through (R (3, 3), t (3,)) the nearest map row of its
@@ -1272,13 +1135,7 @@ class Context:
         Returns ((candidates, matched, within max_dist), row (n,) int32, d2 (n,) float64[, keys uint64][, words uint32][, evidence
         uint32]) — row -1, d2 +inf, key all ones, words 0 where there is none — or, with per_point=False (the scoring form: no
         per-point copy), the three counts alone.  One host synchronisation."""
-        Rm, tv = _f64(R, (9,)), _f64(t, (3,))
-        n = self.cloud_size(cid)
-        bufs, args = _query_buffers(n, per_point, with_keys, with_attr, with_ev)
-        counts = np.zeros(3, np.uint64)
-        _check(hip_lib().madicp_map_query_cloud(self._h, mid, cid, Rm.ctypes.data_as(_dp), tv.ctypes.data_as(_dp), int(reach),
-                                                float(max_dist), *args, n, counts.ctypes.data_as(_u64p)))
-        return _query_answer(counts, bufs, n, per_point)
+        return DeviceMap(self, mid).query(cid, R, t, reach, max_dist, per_point, with_keys, with_attr, with_ev)
 
     def map_register_cloud(self, mid, cid, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0,
                            per_point=False):
@@ -1286,18 +1143,13 @@ class Context:
         of moments map mid, from the pose (R (3, 3), t (3,)), all on the device; the map is only read.  Returns dict(R, t, X, H, b,
         chi2, counts) with one row per linearisation — row k at X[k], the last at the returned pose — and, with per_point (only
         with iterations == 0), row (n,) int32 and e (n,) float64.  One host synchronisation."""
-        n = self.cloud_size(cid)
-
-        def call(*args):
-            _check(hip_lib().madicp_map_register_cloud(self._h, mid, cid, *args))
-
-        return _align_call(call, n, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
+        return DeviceMap(self, mid).register(cid, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
 
     def map_clear(self, mid):
-        _check(hip_lib().madicp_map_clear(self._h, mid))
+        DeviceMap(self, mid).clear()
 
     def map_release(self, mid):
-        _check(hip_lib().madicp_map_release(self._h, mid))
+        DeviceMap(self, mid).close()
 
     def cloud_deskew_own_stamps(self, cid, velocity, sensor_hz, want_chunks=False):
         """cloud_deskew_stamped from the stamps the cloud carries itself.  Returns the chunks (n,) int32 when asked for."""

@@ -14,6 +14,7 @@ import pytest
 import gn_step_ref as G
 import map_align_ref as A
 from mad_icp_amd import capi
+from map_impls import DevImpl
 from test_host_map_align import CAPACITY, INVALID, MAX_COUNT, make_map, same_linearisation
 
 pytestmark = pytest.mark.gpu
@@ -21,48 +22,27 @@ pytestmark = pytest.mark.gpu
 EYE = (np.eye(3), np.zeros(3))
 
 
-class DevMap:
-    def __init__(self, ctx, folds=(), with_attr=False, evidence=None, initial_rows=64):
-        self.ctx = ctx
-        self.mid = ctx.map_create_mom(A.VOXEL, initial_rows, 1 << 22, MAX_COUNT, with_attr=with_attr, evidence=evidence)
-        self.kind = (with_attr, evidence is not None)
-        for pts in folds:
-            self.fold(pts)
+def dev_map(ctx, folds=(), with_attr=False, evidence=None, initial_rows=64):
+    """a device moments map with the folds in it; the caller closes it"""
+    m = DevImpl(ctx, A.VOXEL, initial_rows, 1 << 22, with_attr, evidence, MAX_COUNT)
+    for pts in folds:
+        m.insert(pts, *EYE)
+    return m
 
-    def fold(self, pts):
-        cid = self.ctx.cloud_upload(np.ascontiguousarray(pts))
-        try:
-            self.ctx.map_insert_cloud(self.mid, cid, *EYE)
-        finally:
-            self.ctx.cloud_release(cid)
 
-    def columns(self):
-        return self.ctx.map_download_f32(self.mid), self.ctx.map_download_keys(self.mid), self.ctx.map_download_surfels(self.mid)
+def columns(m):
+    return m.rows(), m.keys(), m.surfels()
 
-    def everything(self):
-        out = [self.ctx.map_download_f32(self.mid), self.ctx.map_download_keys(self.mid), self.ctx.map_download_moments(self.mid)]
-        out += list(self.ctx.map_download_surfels(self.mid))
-        if self.kind[0]:
-            out.append(self.ctx.map_download_attr(self.mid))
-        if self.kind[1]:
-            out.append(self.ctx.map_download_evidence(self.mid))
-        return [c.tobytes() for c in out]
 
-    def register(self, cloud, R, t, iterations, **kw):
-        cid = self.ctx.cloud_upload(np.ascontiguousarray(cloud))
-        try:
-            return self.ctx.map_register_cloud(self.mid, cid, R, t, iterations, **kw)
-        finally:
-            self.ctx.cloud_release(cid)
-
-    def close(self):
-        self.ctx.map_release(self.mid)
+def everything(m):
+    out = [m.rows(), m.keys(), m.moments(), *m.surfels()] + [c for c in (m.words(), m.evidence()) if c is not None]
+    return [c.tobytes() for c in out]
 
 
 @pytest.fixture(scope="module")
 def corner(ctx):
-    m = DevMap(ctx, A.map_folds())
-    yield m, m.columns()
+    m = dev_map(ctx, A.map_folds())
+    yield m, columns(m)
     m.close()
 
 
@@ -78,7 +58,7 @@ def test_linearise_only_is_the_restatement(corner, n):
     m, (rows, keys, surfels) = corner
     R, t = A.start_pose()
     cloud = A.scan(n)
-    before = m.everything()
+    before = everything(m)
     for params in (A.DEFAULT, A.GATED, dict(A.GATED, reach=0)):
         want = A.linearize(rows, keys, surfels, cloud, R, t, **params)
         got = m.register(cloud, R, t, 0, per_point=True, **params)
@@ -88,7 +68,7 @@ def test_linearise_only_is_the_restatement(corner, n):
         for key in ("R", "t", "X", "H", "b", "chi2", "counts", "row", "e"):
             assert got[key].tobytes() == again[key].tobytes(), key
         same_linearisation(m.register(cloud, R, t, 0, **params), want, per_point=False)   # (no per-point buffer: the same sums)
-    assert m.everything() == before
+    assert everything(m) == before
 
 
 @pytest.mark.parametrize("params", [A.DEFAULT, A.GATED], ids=["neutral", "gated"])
@@ -96,9 +76,9 @@ def test_five_traced_rounds(corner, twin, params):
     m, (rows, keys, surfels) = corner
     R0, t0 = A.start_pose()
     cloud = A.scan(4097)
-    before = m.everything()
+    before = everything(m)
     got = m.register(cloud, R0, t0, 5, **params)
-    assert m.everything() == before
+    assert everything(m) == before
     assert np.array_equal(got["X"][0], np.concatenate([R0.reshape(-1), t0]))
     c = 8.0 * G.rho_ref()
     for k in range(6):
@@ -139,9 +119,9 @@ def test_large_cloud_rounds(corner):
 def test_maps_with_other_columns_and_after_removals(ctx, kind):
     R, t = A.start_pose()
     cloud = A.scan(1025)
-    m = DevMap(ctx, A.map_folds(), with_attr=kind[0], evidence=kind[1], initial_rows=64)   # (64 rows: the folds grow the block)
+    m = dev_map(ctx, A.map_folds(), with_attr=kind[0], evidence=kind[1], initial_rows=64)   # (64 rows: the folds grow the block)
     try:
-        same_linearisation(m.register(cloud, R, t, 0, per_point=True, **A.GATED), A.linearize(*m.columns(), cloud, R, t, **A.GATED))
+        same_linearisation(m.register(cloud, R, t, 0, per_point=True, **A.GATED), A.linearize(*columns(m), cloud, R, t, **A.GATED))
         rows_before = ctx.map_size(m.mid)
         ctx.map_prune(m.mid, A.CORNER + 2.0, 4.0)
         origin = A.CORNER + 1.5
@@ -150,20 +130,20 @@ def test_maps_with_other_columns_and_after_removals(ctx, kind):
             ctx.map_clear_rays(m.mid, cid, *EYE, origin)
         finally:
             ctx.cloud_release(cid)
-        m.fold(A.corner_points(3000, 10))
+        m.insert(A.corner_points(3000, 10), *EYE)
         assert ctx.map_size(m.mid) != rows_before
-        before = m.everything()
-        same_linearisation(m.register(cloud, R, t, 0, per_point=True, **A.GATED), A.linearize(*m.columns(), cloud, R, t, **A.GATED))
+        before = everything(m)
+        same_linearisation(m.register(cloud, R, t, 0, per_point=True, **A.GATED), A.linearize(*columns(m), cloud, R, t, **A.GATED))
         got = m.register(cloud, R, t, 3, **A.GATED)
-        same_linearisation(got, A.linearize(*m.columns(), cloud, got["R"], got["t"], **A.GATED), 3, per_point=False)
-        assert m.everything() == before
+        same_linearisation(got, A.linearize(*columns(m), cloud, got["R"], got["t"], **A.GATED), 3, per_point=False)
+        assert everything(m) == before
     finally:
         m.close()
 
 
 def test_empty_map(ctx):
     R, t = A.start_pose()
-    m = DevMap(ctx)
+    m = dev_map(ctx)
     try:
         for its in (0, 3):
             got = m.register(A.scan(257), R, t, its)
@@ -195,7 +175,7 @@ def test_refusals(ctx, corner):
                                            ptr(ee, dp), cap)
 
     try:
-        before = m.everything()
+        before = everything(m)
         bad_R, bad_t = R.copy(), t.copy()
         bad_R[0, 1], bad_t[2] = np.nan, np.inf
         refused = [dict(h=None), dict(R_=None), dict(t_=None), dict(params="null"), dict(oR=None), dict(ot=None), dict(tr=None), dict(cn=None),
@@ -208,7 +188,7 @@ def test_refusals(ctx, corner):
         assert np.all(out_R == 7.0) and np.all(out_t == 7.0) and np.all(trace == 7.0) and np.all(counts == 7)   # nothing written
         assert np.all(row == 7) and np.all(e == 7.0)
         assert call(its=64) == 0 and np.all(counts[:, 0] == 65)          # (the last legal round count)
-        assert m.everything() == before
+        assert everything(m) == before
     finally:
         ctx.map_release(plain)
         ctx.cloud_release(cid)

@@ -5,6 +5,7 @@ keys.  Ray counts and map sizes around the wavefront, the workgroup and the 1 02
 the contended flag; nothing, nearly everything and everything removed; cap == rows; growth; watermarks; two maps; a map far larger
 than any cloud its context has seen; every refusal; the scene the feature is for."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -12,7 +13,8 @@ import pytest
 import cloud_export_ref as E
 import map_clear_ref as Cl
 from mad_icp_amd import capi
-from test_host_map_clear import HostTwin
+from map_impls import DevImpl, maps  # noqa: F401 (maps is a fixture)
+from test_host_map_clear import TWIN
 
 pytestmark = pytest.mark.gpu
 
@@ -20,53 +22,10 @@ INVALID = -1
 _dp = C.POINTER(C.c_double)
 
 
-class DevMap:
-    def __init__(self, ctx, voxel=Cl.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True):
-        self.ctx, self.with_attr = ctx, with_attr
-        self.mid = (ctx.map_create_attr if with_attr else ctx.map_create)(voxel, initial_rows, max_rows)
-
-    def insert(self, pts, R, t, words):
-        cid = self.ctx.cloud_upload(pts)
-        try:
-            if self.with_attr and words is not None:
-                self.ctx.cloud_set_attr(cid, words)
-            return self.ctx.map_insert_cloud(self.mid, cid, R, t)
-        finally:
-            self.ctx.cloud_release(cid)
-
-    def clear_rays(self, pts, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, wm=0):
-        cid = self.ctx.cloud_upload(pts)
-        try:
-            return self.ctx.map_clear_rays(self.mid, cid, R, t, origin, margin, wm)
-        finally:
-            self.ctx.cloud_release(cid)
-
-    def rows(self):
-        return self.ctx.map_download_f32(self.mid)
-
-    def words(self):
-        return self.ctx.map_download_attr(self.mid) if self.with_attr else None
-
-    def close(self):
-        self.ctx.map_release(self.mid)
-
-
 @pytest.fixture
-def made(ctx):
-    """DevMap / HostTwin factories whose maps are released at the end of the test"""
-    alive = []
-
-    def dev(*a, **k):
-        alive.append(DevMap(k.pop("on", ctx), *a, **k))
-        return alive[-1]
-
-    def twin(*a, **k):
-        alive.append(HostTwin(*a, **k))
-        return alive[-1]
-
-    yield dev, twin
-    for m in alive:
-        m.close()
+def made(ctx, maps):
+    """device map / host twin factories"""
+    return functools.partial(maps.dev, ctx, **TWIN), functools.partial(maps.host, **TWIN)
 
 
 @pytest.mark.parametrize("name", Cl.SIZE_NAMES)
@@ -167,7 +126,7 @@ def test_a_map_much_larger_than_any_cloud(natives, made):
     _, twin = made
     own = capi.Context(0)
     try:
-        m = DevMap(own, initial_rows=1)
+        m = DevImpl(own, initial_rows=1, **TWIN)
         try:
             want = Cl.replay("large", m, also=(twin(initial_rows=1),))
             assert want[79][0] == (256, 20480) and want[80][0][0] > 100 and want[81][0][0] > 0

@@ -8,7 +8,7 @@ exactly 4 097 rows in front of the prune.  A column dropped from one of the loop
 import numpy as np
 import pytest
 
-from mad_icp_amd import capi
+from map_impls import maps  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,89 +36,14 @@ def lattice_clouds():
     return [(xyz[a:b].copy(), words[a:b].copy()) for a, b in cuts]
 
 
-class DevMap:
-    def __init__(self, ctx, attr, ev, mom):
-        self.ctx, self.attr, self.ev, self.mom = ctx, attr, ev, mom
-        if mom:
-            self.mid = ctx.map_create_mom(VOXEL, 1, 1 << 20, MAX_COUNT, with_attr=attr, evidence=EVIDENCE if ev else None)
-        elif ev:
-            self.mid = ctx.map_create_ev(VOXEL, 1, 1 << 20, *EVIDENCE, with_attr=attr)
-        else:
-            self.mid = ctx.map_create_attr(VOXEL, 1, 1 << 20) if attr else ctx.map_create(VOXEL, 1, 1 << 20)
-        ctx.map_track_removed(self.mid, True)
-        self.clouds = {}
-
-    def cloud(self, k, xyz, words):
-        if k not in self.clouds:
-            self.clouds[k] = self.ctx.cloud_upload(xyz)
-            self.ctx.cloud_set_attr(self.clouds[k], words)
-        return self.clouds[k]
-
-    def fold(self, k, xyz, words):
-        return self.ctx.map_insert_cloud(self.mid, self.cloud(k, xyz, words), R, T)
-
-    def prune(self, radius, watermark):
-        return self.ctx.map_prune(self.mid, (0.0, 0.0, 0.0), radius, watermark)
-
-    def clear_rays(self, k, xyz, words, watermark):
-        return self.ctx.map_clear_rays(self.mid, self.cloud(k, xyz, words), R, T, watermark=watermark)
-
-    def size(self):
-        return self.ctx.map_size(self.mid)
-
-    def columns(self):
-        got = dict(zip(("xyz", "keys", "attr"), self.ctx.map_download_rows(self.mid, with_keys=True, with_attr=self.attr)))
-        if self.ev:
-            got["evidence"] = self.ctx.map_download_evidence(self.mid)
-        if self.mom:
-            got["moments"] = self.ctx.map_download_moments(self.mid)
-        return got
-
-    def take(self):
-        return dict(zip(("keys", "xyz", "attr"), self.ctx.map_take_removed(self.mid, with_attr=self.attr)))
-
-    def close(self):
-        for cid in self.clouds.values():
-            self.ctx.cloud_release(cid)
-        self.ctx.map_release(self.mid)
+def spec(attr, ev, mom):
+    """a map made for ONE row with these columns and the removal log, as the adapters of tests/map_impls.py take it"""
+    return dict(voxel=VOXEL, initial_rows=1, max_rows=1 << 20, with_attr=attr, evidence=EVIDENCE if ev else None,
+                max_count=MAX_COUNT if mom else None, tracking=True)
 
 
-class Twin:
-    def __init__(self, attr, ev, mom):
-        self.attr, self.ev, self.mom = attr, ev, mom
-        if mom:
-            self.h = capi.host_map_create_mom(VOXEL, 1, 1 << 20, MAX_COUNT, with_attr=attr, evidence=EVIDENCE if ev else None)
-        elif ev:
-            self.h = capi.host_map_create_ev(VOXEL, 1, 1 << 20, *EVIDENCE, with_attr=attr)
-        else:
-            self.h = capi.host_map_create_attr(VOXEL, 1, 1 << 20) if attr else capi.host_map_create(VOXEL, 1, 1 << 20)
-        capi.host_map_track_removed(self.h, True)
-
-    def fold(self, k, xyz, words):
-        return capi.host_map_insert_attr(self.h, xyz, words, R, T)
-
-    def prune(self, radius, watermark):
-        return capi.host_map_prune(self.h, (0.0, 0.0, 0.0), radius, watermark)
-
-    def clear_rays(self, k, xyz, words, watermark):
-        return capi.host_map_clear_rays(self.h, xyz, R, T, watermark=watermark)
-
-    def size(self):
-        return capi.host_map_size(self.h)
-
-    def columns(self):
-        got = dict(zip(("xyz", "keys", "attr"), capi.host_map_download_rows(self.h, with_keys=True, with_attr=self.attr)))
-        if self.ev:
-            got["evidence"] = capi.host_map_download_evidence(self.h)
-        if self.mom:
-            got["moments"] = capi.host_map_download_moments(self.h)
-        return got
-
-    def take(self):
-        return dict(zip(("keys", "xyz", "attr"), capi.host_map_take_removed(self.h, with_attr=self.attr)))
-
-    def close(self):
-        capi.host_map_destroy(self.h)
+def log(m):
+    return dict(zip(("keys", "xyz", "attr"), m.take()))
 
 
 def same(step, got, want):
@@ -140,33 +65,27 @@ def run_script(dev, twin, clouds, rows_before_prune=None):
         need = twin.size() + clouds[k][0].shape[0]
         if need > cap:
             cap, growths = max(need, 2 * cap), growths + 1
-        both("fold %d" % k, lambda m: m.fold(k, *clouds[k]))
+        both("fold %d" % k, lambda m: m.insert(clouds[k][0], R, T, clouds[k][1], key=k))
     assert growths >= 3
     rows = twin.size()
     if rows_before_prune is not None:
         assert rows == rows_before_prune
-    removed, kept, _ = both("prune", lambda m: m.prune(PRUNE_RADIUS, rows))
+    removed, kept, _ = both("prune", lambda m: m.prune((0.0, 0.0, 0.0), PRUNE_RADIUS, rows))
     assert 0.3 * rows < removed < 0.7 * rows, (removed, rows)
-    both("fold behind the prune", lambda m: m.fold(3, *clouds[3]))
-    removed, _, _ = both("clearing", lambda m: m.clear_rays(1, *clouds[1], watermark=twin.size()))
-    assert removed > 0 or dev.ev
-    got, want = dev.take(), twin.take()
+    both("fold behind the prune", lambda m: m.insert(clouds[3][0], R, T, clouds[3][1], key=3))
+    removed, _, _ = both("clearing", lambda m: m.clear_rays(clouds[1][0], R, T, wm=twin.size(), words=clouds[1][1], key=1))
+    assert removed > 0 or dev.params is not None
+    got, want = log(dev), log(twin)
     assert want["keys"].shape[0] > 0
     same("the log", got, want)
     same("behind the take", dev.columns(), twin.columns())
 
 
 @pytest.fixture
-def pair(ctx):
-    alive = []
-
-    def make(attr, ev, mom):
-        alive.extend([DevMap(ctx, attr, ev, mom), Twin(attr, ev, mom)])
-        return alive[-2], alive[-1]
-
-    yield make
-    for m in alive:
-        m.close()
+def pair(ctx, maps):
+    """a device map, whose scans always get their words and stay resident per key, and its host twin, whose folds always go through
+    madicp_host_map_insert_attr"""
+    return lambda attr, ev, mom: (maps.dev(ctx, set_attr=True, **spec(attr, ev, mom)), maps.host(insert_attr=True, **spec(attr, ev, mom)))
 
 
 @pytest.mark.parametrize("attr,ev,mom", COMBOS)

@@ -15,52 +15,19 @@ import map_clear_ref as Cl
 import map_evidence_ref as Ev
 import map_removed_ref as Rm
 from mad_icp_amd import capi
-from test_gpu_map_removed import Dev
-from test_host_map_evidence import EvTwin
-from test_host_map_removed import CAPACITY, INVALID
+from map_impls import maps  # noqa: F401 (maps and twins are fixtures)
+from test_host_map_evidence import twins  # noqa: F401
+from test_host_map_removed import CAPACITY, INVALID, TWIN
 
 pytestmark = pytest.mark.gpu
 
 _fp, _u64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 
 
-class EvDev(Dev):
-    """tests/test_gpu_map_removed.py's adapter over a map of madicp_map_create_ev"""
-
-    def __init__(self, ctx, params, voxel=Ev.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True, tracking=True):
-        self.ctx, self.with_attr = ctx, with_attr
-        self.mid = ctx.map_create_ev(voxel, initial_rows, max_rows, *params, with_attr=with_attr)
-        if tracking:
-            self.track(True)
-
-    def evidence(self):
-        return self.ctx.map_download_evidence(self.mid)
-
-    def confirmed(self, min_e):
-        return self.ctx.map_download_min_evidence(self.mid, min_e, with_keys=True, with_attr=self.with_attr, with_ev=True)
-
-
-class PlainDev(Dev):
-    def evidence(self):
-        return None
-
-
 @pytest.fixture
-def made(ctx):
-    """EvDev / EvTwin factories whose maps are released at the end of the test; params None: a plain device map"""
-    alive = []
-
-    def dev(params, **k):
-        alive.append(EvDev(ctx, params, **k) if params is not None else PlainDev(ctx, **k))
-        return alive[-1]
-
-    def twin(params, **k):
-        alive.append(EvTwin(params, **k))
-        return alive[-1]
-
-    yield dev, twin
-    for m in alive:
-        m.close()
+def made(ctx, maps, twins):
+    """device map / host twin factories; params None: a plain device map"""
+    return (lambda params, **k: maps.dev(ctx, **{**TWIN, "voxel": Ev.VOXEL, "evidence": params, **k})), twins
 
 
 @pytest.mark.parametrize("params", [(1, 1, 8), (3, 2, 7)])

@@ -17,58 +17,19 @@ import map_evidence_ref as Ev
 import map_moments_ref as Mo
 import map_removed_ref as Rm
 from mad_icp_amd import capi
-from test_gpu_map_removed import Dev
-from test_host_map_moments import MomTwin
-from test_host_map_removed import CAPACITY, INVALID
+from map_impls import maps  # noqa: F401 (maps and twins are fixtures)
+from test_host_map_moments import twins  # noqa: F401
+from test_host_map_removed import CAPACITY, INVALID, TWIN
 
 pytestmark = pytest.mark.gpu
 
 _fp, _u64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 
 
-class MomDev(Dev):
-    """tests/test_gpu_map_removed.py's adapter over a map of madicp_map_create_mom"""
-
-    def __init__(self, ctx, max_count, params=None, voxel=Mo.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True, tracking=True):
-        self.ctx, self.with_attr, self.params = ctx, with_attr, params
-        self.mid = ctx.map_create_mom(voxel, initial_rows, max_rows, max_count, with_attr=with_attr, evidence=params)
-        if tracking:
-            self.track(True)
-
-    def evidence(self):
-        return self.ctx.map_download_evidence(self.mid) if self.params is not None else None
-
-    def moments(self):
-        return self.ctx.map_download_moments(self.mid)
-
-    def surfels(self, first_row=0):
-        return self.ctx.map_download_surfels(self.mid, first_row)
-
-
-class PlainDev(Dev):
-    def evidence(self):
-        return None
-
-    def moments(self):
-        return None
-
-
 @pytest.fixture
-def made(ctx):
-    """MomDev / MomTwin factories whose maps are released at the end of the test; max_count None: a plain device map"""
-    alive = []
-
-    def dev(max_count, *a, **k):
-        alive.append(MomDev(ctx, max_count, *a, **k) if max_count is not None else PlainDev(ctx, **k))
-        return alive[-1]
-
-    def twin(*a, **k):
-        alive.append(MomTwin(*a, **k))
-        return alive[-1]
-
-    yield dev, twin
-    for m in alive:
-        m.close()
+def made(ctx, maps, twins):
+    """device map / host twin factories; max_count None: a plain device map"""
+    return (lambda max_count, params=None, **k: maps.dev(ctx, **{**TWIN, "voxel": Mo.VOXEL, "max_count": max_count, "evidence": params, **k})), twins
 
 
 @pytest.mark.parametrize("max_count", [3, 1000])

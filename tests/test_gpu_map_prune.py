@@ -3,6 +3,7 @@ memset and fe::map_rehash) against BOTH the numpy restatement of tests/map_prune
 EVERY step of the shared sequences: row counts around the wavefront, the workgroup and the 1 024-mark scan tile, the four kinds
 of radius, the boundary, growth, the attribute column, a map far larger than any cloud its context has seen, every refusal."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -10,7 +11,8 @@ import pytest
 import cloud_export_ref as E
 import map_prune_ref as P
 from mad_icp_amd import capi
-from test_host_map_prune import HostTwin
+from map_impls import DevImpl, maps  # noqa: F401 (maps is a fixture)
+from test_host_map_prune import TWIN
 
 pytestmark = pytest.mark.gpu
 
@@ -18,49 +20,10 @@ INVALID = -1
 _dp = C.POINTER(C.c_double)
 
 
-class DevMap:
-    def __init__(self, ctx, voxel=P.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True):
-        self.ctx, self.with_attr = ctx, with_attr
-        self.mid = (ctx.map_create_attr if with_attr else ctx.map_create)(voxel, initial_rows, max_rows)
-
-    def insert(self, pts, R, t, words):
-        cid = self.ctx.cloud_upload(pts)
-        try:
-            if self.with_attr and words is not None:
-                self.ctx.cloud_set_attr(cid, words)
-            return self.ctx.map_insert_cloud(self.mid, cid, R, t)
-        finally:
-            self.ctx.cloud_release(cid)
-
-    def prune(self, c, r, wm):
-        return self.ctx.map_prune(self.mid, c, r, wm)
-
-    def rows(self):
-        return self.ctx.map_download_f32(self.mid)
-
-    def words(self):
-        return self.ctx.map_download_attr(self.mid) if self.with_attr else None
-
-    def close(self):
-        self.ctx.map_release(self.mid)
-
-
 @pytest.fixture
-def made(ctx):
-    """DevMap / HostTwin factories whose maps are released at the end of the test"""
-    alive = []
-
-    def dev(*a, **k):
-        alive.append(DevMap(k.pop("on", ctx), *a, **k))
-        return alive[-1]
-
-    def twin(*a, **k):
-        alive.append(HostTwin(*a, **k))
-        return alive[-1]
-
-    yield dev, twin
-    for m in alive:
-        m.close()
+def made(ctx, maps):
+    """device map / host twin factories"""
+    return functools.partial(maps.dev, ctx, **TWIN), functools.partial(maps.host, **TWIN)
 
 
 @pytest.mark.parametrize("name", P.SIZE_NAMES)
@@ -173,7 +136,7 @@ def test_a_map_much_larger_than_any_cloud(natives, made):
     _, twin = made
     own = capi.Context(0)
     try:
-        m = DevMap(own, initial_rows=1)
+        m = DevImpl(own, initial_rows=1, **TWIN)
         try:
             want = P.replay("large", m, also=(twin(initial_rows=1),))
             assert want[79][0] == (256, 20480) and 2000 < want[80][0][1] < 18000 and want[82][0][0] > 0

@@ -11,97 +11,21 @@ import pytest
 import cloud_export_ref as E
 import map_query_ref as Q
 from mad_icp_amd import capi
-from test_host_map_query import CAPACITY, INVALID, KINDS, Twin
+from map_impls import maps  # noqa: F401 (maps and twin are fixtures)
+from test_host_map_query import CAPACITY, INVALID, KINDS, SPECS, twin  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-class Dev:
-    """a device map of one of the four kinds behind map_query_ref.build / hold's interface"""
-
-    def __init__(self, ctx, kind="plain", voxel=Q.VOXEL, initial_rows=64, max_rows=1 << 24):
-        self.ctx, self.kind = ctx, kind
-        if kind == "plain":
-            self.mid = ctx.map_create(voxel, initial_rows, max_rows)
-        elif kind == "attr":
-            self.mid = ctx.map_create_attr(voxel, initial_rows, max_rows)
-        elif kind == "ev":
-            self.mid = ctx.map_create_ev(voxel, initial_rows, max_rows, 2, 1, 6, with_attr=True)
-        else:
-            self.mid = ctx.map_create_mom(voxel, initial_rows, max_rows, 4, with_attr=False)
-
-    def close(self):
-        self.ctx.map_release(self.mid)
-
-    def cloud(self, pts, words=None):
-        cid = self.ctx.cloud_upload(np.ascontiguousarray(pts, np.float64).reshape(-1, 3))
-        if words is not None and self.kind in ("attr", "ev"):
-            self.ctx.cloud_set_attr(cid, words)
-        return cid
-
-    def insert(self, pts, R, t, words):
-        cid = self.cloud(pts, words)
-        try:
-            return self.ctx.map_insert_cloud(self.mid, cid, R, t)
-        finally:
-            self.ctx.cloud_release(cid)
-
-    def prune(self, center, radius):
-        return self.ctx.map_prune(self.mid, center, radius)
-
-    def clear_rays(self, pts, R, t, origin):
-        cid = self.cloud(pts)
-        try:
-            return self.ctx.map_clear_rays(self.mid, cid, R, t, origin)
-        finally:
-            self.ctx.cloud_release(cid)
-
-    def wipe(self):
-        self.ctx.map_clear(self.mid)
-
-    def rows(self):
-        return self.ctx.map_download_f32(self.mid)
-
-    def keys(self):
-        return self.ctx.map_download_keys(self.mid)
-
-    def words(self):
-        return self.ctx.map_download_attr(self.mid) if self.kind in ("attr", "ev") else None
-
-    def evidence(self):
-        return self.ctx.map_download_evidence(self.mid) if self.kind == "ev" else None
-
-    def everything(self):
-        """every column the map has, as bytes"""
-        out = [self.rows().tobytes(), self.keys().tobytes()]
-        out += [c.tobytes() for c in (self.words(), self.evidence()) if c is not None]
-        if self.kind == "mom":
-            out.append(self.ctx.map_download_moments(self.mid).tobytes())
-        return out
-
-    def query(self, cloud, R, t, reach, max_dist, per_point=True, with_keys=False, with_attr=False, with_ev=False):
-        cid = self.cloud(cloud)
-        try:
-            return self.ctx.map_query(self.mid, cid, R, t, reach, max_dist, per_point, with_keys, with_attr, with_ev)
-        finally:
-            self.ctx.cloud_release(cid)
+def everything(m):
+    """every column the map has, as bytes"""
+    return [c.tobytes() for c in (m.rows(), m.keys(), m.words(), m.evidence(), m.moments()) if c is not None]
 
 
 @pytest.fixture
-def made(ctx):
-    alive = []
-
-    def dev(*a, **k):
-        alive.append(Dev(ctx, *a, **k))
-        return alive[-1]
-
-    def twin(*a, **k):
-        alive.append(Twin(*a, **k))
-        return alive[-1]
-
-    yield dev, twin
-    for m in alive:
-        m.close()
+def made(ctx, maps, twin):
+    """a device map of one of the four kinds (a scan gets its words on the kinds with the attribute column) and its host twin"""
+    return (lambda kind="plain", **k: maps.dev(ctx, **{"voxel": Q.VOXEL, **SPECS[kind], **k})), twin
 
 
 # (a resident cloud always holds a point — madicp_cloud_upload and the ingests refuse an empty one — so n = 0 is the host twin's case:
@@ -165,16 +89,16 @@ def test_device_query_only_reads(made):
         a, b = dev(kind), dev(kind)
         Q.build(a, steps)
         Q.build(b, steps)
-        before = a.everything()
+        before = everything(a)
         for cloud, R, t in asks:
             for reach in (0, 1):
                 a.query(cloud, R, t, reach, 0.3, True, True)
                 a.query(cloud, R, t, reach, 0.3, False)
-        assert a.everything() == before == b.everything()
+        assert everything(a) == before == everything(b)
         assert a.insert(more, *E.IDENTITY, None) == b.insert(more, *E.IDENTITY, None)
-        assert a.everything() == b.everything()
+        assert everything(a) == everything(b)
         assert a.clear_rays(asks[1][0], *E.IDENTITY, np.array([0.1, -0.2, 0.3])) == b.clear_rays(asks[1][0], *E.IDENTITY, np.array([0.1, -0.2, 0.3]))
-        assert a.everything() == b.everything()
+        assert everything(a) == everything(b)
 
 
 def _raw(ctx, mid, cid, R, t, reach, max_dist, bufs, capacity, counts, handle=True):
@@ -205,9 +129,9 @@ def test_device_query_refusals_write_nothing(ctx, made):
     def refused(code, mid, cloud, R_, t_, reach, max_dist, keep, capacity=40, with_counts=True, handle=True):
         bufs, counts = fresh()
         given = [b if k else None for b, k in zip(bufs, keep)]
-        before = ev.everything() + plain.everything()
+        before = everything(ev) + everything(plain)
         assert _raw(ctx, mid, cloud, R_, t_, reach, max_dist, given, capacity, counts if with_counts else None, handle) == code
-        assert untouched(bufs, counts) and ev.everything() + plain.everything() == before
+        assert untouched(bufs, counts) and everything(ev) + everything(plain) == before
 
     try:
         all5 = (1, 1, 1, 1, 1)

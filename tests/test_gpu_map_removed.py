@@ -7,6 +7,7 @@ behind entries already there, the log's growth); the watermarks 0, 1, M/2, M - 1
 and without the column; tracking off, switched on and off; the full log; every refusal; two maps; a map far larger than any cloud
 its context has seen; a block grown from one row; the log across a growth of the map."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -15,63 +16,18 @@ import cloud_export_ref as E
 import map_prune_ref as P
 import map_removed_ref as Rm
 from mad_icp_amd import capi
-from test_gpu_map_clear import DevMap
-from test_host_map_removed import (CAPACITY, CLEAR_NAMES, INVALID, PRUNE_NAMES, WATERMARK_NAMES, Twin, logged, one_then_4097, refusable)
+from map_impls import DevImpl, maps  # noqa: F401 (maps is a fixture)
+from test_host_map_removed import (CAPACITY, CLEAR_NAMES, INVALID, PRUNE_NAMES, WATERMARK_NAMES, TWIN, logged, one_then_4097)
 
 pytestmark = pytest.mark.gpu
 
 _fp, _u64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 
 
-class Dev(DevMap):
-    """tests/test_gpu_map_clear.py's adapter with what tests/map_removed_ref.py's replay asks for besides"""
-
-    def __init__(self, ctx, *a, tracking=True, **k):
-        super().__init__(ctx, *a, **k)
-        if tracking:
-            self.track(True)
-
-    def insert(self, pts, R, t, words):
-        return refusable(super().insert, pts, R, t, words)
-
-    def prune(self, c, r, wm):
-        return refusable(self.ctx.map_prune, self.mid, c, r, wm)
-
-    def clear_rays(self, pts, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, wm=0):
-        return refusable(super().clear_rays, pts, R, t, origin, margin, wm)
-
-    def keys(self):
-        return self.ctx.map_download_keys(self.mid)
-
-    def removed_count(self):
-        return self.ctx.map_removed_count(self.mid)
-
-    def take(self):
-        return self.ctx.map_take_removed(self.mid, self.with_attr)
-
-    def track(self, on):
-        self.ctx.map_track_removed(self.mid, on)
-
-    def reset(self):
-        self.ctx.map_clear(self.mid)
-
-
 @pytest.fixture
-def made(ctx):
-    """Dev / Twin factories whose maps are released at the end of the test"""
-    alive = []
-
-    def dev(*a, **k):
-        alive.append(Dev(k.pop("on", ctx), *a, **k))
-        return alive[-1]
-
-    def twin(*a, **k):
-        alive.append(Twin(*a, **k))
-        return alive[-1]
-
-    yield dev, twin
-    for m in alive:
-        m.close()
+def made(ctx, maps):
+    """device map / host twin factories"""
+    return functools.partial(maps.dev, ctx, **TWIN), functools.partial(maps.host, **TWIN)
 
 
 @pytest.mark.parametrize("cadence", ["every", "end"])
@@ -158,7 +114,7 @@ def test_a_map_larger_than_any_cloud_its_context_has_seen(natives):
     """map_prune_ref.large's 20 480-row map in a context that has seen only 256-point clouds: the log's kernel is sized by the map"""
     c = capi.Context(0)
     try:
-        m = Dev(c, initial_rows=1)
+        m = DevImpl(c, initial_rows=1, **TWIN)
         done, want = Rm.expected("prune:large", "end", "all")
         assert logged(want) > 5000
         Rm.replay(done, want, m, tag="large")

@@ -3,6 +3,7 @@ restatement of tests/map_clear_ref.py after EVERY step of the shared sequences, 
 column — on the input sets of tests/test_host_map_prune.py as well — and every refusal with the map unchanged.  The cases whose
 outcome can be worked out by hand are spelled out here, so that the restatement itself is held to something.  No GPU."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -11,46 +12,18 @@ import cloud_export_ref as E
 import map_clear_ref as Cl
 import map_prune_ref as P
 from mad_icp_amd import capi
+from map_impls import maps  # noqa: F401 (maps is a fixture)
 
 INVALID = -1
 _dp = C.POINTER(C.c_double)
 
 
-class HostTwin:
-    def __init__(self, voxel=Cl.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True):
-        self.with_attr = with_attr
-        self.h = (capi.host_map_create_attr if with_attr else capi.host_map_create)(voxel, initial_rows, max_rows)
-
-    def insert(self, pts, R, t, words):
-        return capi.host_map_insert_attr(self.h, pts, words, R, t) if self.with_attr else capi.host_map_insert(self.h, pts, R, t)
-
-    def clear_rays(self, pts, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, wm=0):
-        return capi.host_map_clear_rays(self.h, pts, R, t, origin, margin, wm)
-
-    def prune(self, c, r, wm):
-        return capi.host_map_prune(self.h, c, r, wm)
-
-    def rows(self):
-        return capi.host_map_download_f32(self.h)
-
-    def words(self):
-        return capi.host_map_download_attr(self.h) if self.with_attr else None
-
-    def close(self):
-        capi.host_map_destroy(self.h)
+TWIN = dict(voxel=Cl.VOXEL, with_attr=True)  # what this suite's maps are unless a test says otherwise
 
 
 @pytest.fixture
-def twins(natives):
-    made = []
-
-    def make(*a, **k):
-        made.append(HostTwin(*a, **k))
-        return made[-1]
-
-    yield make
-    for m in made:
-        m.close()
+def twins(maps):
+    return functools.partial(maps.host, **TWIN)
 
 
 @pytest.mark.parametrize("name", Cl.SIZE_NAMES)

@@ -13,43 +13,16 @@ import cloud_export_ref as E
 import map_evidence_ref as Ev
 import map_removed_ref as Rm
 from mad_icp_amd import capi
-from test_host_map_removed import CAPACITY, INVALID, Twin
+from map_impls import maps  # noqa: F401 (maps is a fixture)
+from test_host_map_removed import CAPACITY, INVALID, TWIN
 
 _fp, _u64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 
 
-class EvTwin(Twin):
-    """tests/test_host_map_removed.py's adapter over a map of madicp_host_map_create_ev"""
-
-    def __init__(self, params, voxel=Ev.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True, tracking=True):
-        self.with_attr = with_attr
-        self.h = capi.host_map_create_ev(voxel, initial_rows, max_rows, *params, with_attr=with_attr)
-        if tracking:
-            self.track(True)
-
-    def evidence(self):
-        return capi.host_map_download_evidence(self.h)
-
-    def confirmed(self, min_e):
-        return capi.host_map_download_min_evidence(self.h, min_e, with_keys=True, with_attr=self.with_attr, with_ev=True)
-
-
-class PlainTwin(Twin):
-    def evidence(self):
-        return None
-
-
 @pytest.fixture
-def twins(natives):
-    made = []
-
-    def make(params, **k):
-        made.append(EvTwin(params, **k) if params is not None else PlainTwin(**k))
-        return made[-1]
-
-    yield make
-    for m in made:
-        m.close()
+def twins(maps):
+    """params None: a plain map"""
+    return lambda params, **k: maps.host(**{**TWIN, "voxel": Ev.VOXEL, "evidence": params, **k})
 
 
 def evidence_after(name, params, step=-1):

@@ -18,7 +18,8 @@ import map_evidence_ref as Ev
 import map_moments_ref as Mo
 import map_removed_ref as Rm
 from mad_icp_amd import capi
-from test_host_map_removed import CAPACITY, INVALID, Twin
+from map_impls import maps  # noqa: F401 (maps is a fixture)
+from test_host_map_removed import CAPACITY, INVALID, TWIN
 
 _fp, _u64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
 
@@ -27,36 +28,9 @@ MEASURED_NORMAL = 2.98e-8
 MEASURED_EIG_REL = 5.73e-8
 
 
-class MomTwin(Twin):
-    """tests/test_host_map_removed.py's adapter over a map of madicp_host_map_create_mom"""
-
-    def __init__(self, max_count, params=None, voxel=Mo.VOXEL, initial_rows=64, max_rows=1 << 24, with_attr=True, tracking=True):
-        self.with_attr, self.params = with_attr, params
-        self.h = capi.host_map_create_mom(voxel, initial_rows, max_rows, max_count, with_attr=with_attr, evidence=params)
-        if tracking:
-            self.track(True)
-
-    def evidence(self):
-        return capi.host_map_download_evidence(self.h) if self.params is not None else None
-
-    def moments(self):
-        return capi.host_map_download_moments(self.h)
-
-    def surfels(self):
-        return capi.host_map_download_surfels(self.h)
-
-
 @pytest.fixture
-def twins(natives):
-    made = []
-
-    def make(*a, **k):
-        made.append(MomTwin(*a, **k))
-        return made[-1]
-
-    yield make
-    for m in made:
-        m.close()
+def twins(maps):
+    return lambda max_count, params=None, **k: maps.host(**{**TWIN, "voxel": Mo.VOXEL, "max_count": max_count, "evidence": params, **k})
 
 
 @pytest.mark.parametrize("max_count", [1, 3, 1000])

@@ -9,67 +9,20 @@ import pytest
 import cloud_export_ref as E
 import map_query_ref as Q
 from mad_icp_amd import capi
+from map_impls import maps  # noqa: F401 (maps is a fixture)
 
 INVALID, CAPACITY = -1, -4
 KINDS = ["plain", "attr", "ev", "mom"]
 
 
-class Twin:
-    """a host map of one of the four kinds behind map_query_ref.build / hold's interface"""
-
-    def __init__(self, kind="plain", voxel=Q.VOXEL, initial_rows=64, max_rows=1 << 24):
-        self.kind = kind
-        if kind == "plain":
-            self.h = capi.host_map_create(voxel, initial_rows, max_rows)
-        elif kind == "attr":
-            self.h = capi.host_map_create_attr(voxel, initial_rows, max_rows)
-        elif kind == "ev":
-            self.h = capi.host_map_create_ev(voxel, initial_rows, max_rows, 2, 1, 6, with_attr=True)
-        else:
-            self.h = capi.host_map_create_mom(voxel, initial_rows, max_rows, 4, with_attr=False)
-
-    def close(self):
-        capi.host_map_destroy(self.h)
-
-    def insert(self, pts, R, t, words):
-        return capi.host_map_insert_attr(self.h, pts, words, R, t)
-
-    def prune(self, center, radius):
-        return capi.host_map_prune(self.h, center, radius)
-
-    def clear_rays(self, pts, R, t, origin):
-        return capi.host_map_clear_rays(self.h, pts, R, t, origin)
-
-    def wipe(self):
-        capi.host_map_clear(self.h)
-
-    def rows(self):
-        return capi.host_map_download_f32(self.h)
-
-    def keys(self):
-        return capi.host_map_download_keys(self.h)
-
-    def words(self):
-        return capi.host_map_download_attr(self.h) if self.kind in ("attr", "ev") else None
-
-    def evidence(self):
-        return capi.host_map_download_evidence(self.h) if self.kind == "ev" else None
-
-    def query(self, cloud, R, t, reach, max_dist, per_point=True, with_keys=False, with_attr=False, with_ev=False):
-        return capi.host_map_query(self.h, cloud, R, t, reach, max_dist, per_point, with_keys, with_attr, with_ev)
+# the four kinds of map this suite and tests/test_gpu_map_query.py query, as what the adapters of tests/map_impls.py take
+SPECS = {"plain": dict(), "attr": dict(with_attr=True), "ev": dict(with_attr=True, evidence=(2, 1, 6)), "mom": dict(max_count=4)}
 
 
 @pytest.fixture
-def twin():
-    alive = []
-
-    def make(*a, **k):
-        alive.append(Twin(*a, **k))
-        return alive[-1]
-
-    yield make
-    for m in alive:
-        m.close()
+def twin(maps):
+    """a host map of one of the four kinds; its folds always go through madicp_host_map_insert_attr"""
+    return lambda kind="plain", **k: maps.host(**{"voxel": Q.VOXEL, "insert_attr": True, **SPECS[kind], **k})
 
 
 @pytest.mark.parametrize("name", Q.SIZE_NAMES + Q.OTHER_NAMES)

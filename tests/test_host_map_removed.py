@@ -5,6 +5,7 @@ stored keys, words, the log's count and what a take returns, bit for bit — tak
 watermarks 0, 1, M/2, M - 1 and M, with and without the attribute column, tracking off, switched on and off mid-sequence, the
 full log, and every refusal with nothing changed.  No GPU."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -14,7 +15,8 @@ import map_clear_ref as Cl
 import map_prune_ref as P
 import map_removed_ref as Rm
 from mad_icp_amd import capi
-from test_host_map_clear import HostTwin
+from map_impls import maps  # noqa: F401 (maps is a fixture)
+from test_host_map_clear import TWIN
 
 INVALID, CAPACITY = -1, -4
 _fp, _u64p, _u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
@@ -24,60 +26,12 @@ CLEAR_NAMES = ["clear:" + n for n in Cl.SIZE_NAMES + ["edges", "protected", "eve
 WATERMARK_NAMES = ["prune:size-1025-alternate", "prune:size-4097-median", "prune:size-257-all", "clear:size-1025-257", "clear:but_the_endpoints"]
 
 
-def refusable(call, *a):
-    """the answer of a capi call, None where it is refused for capacity (error -4)"""
-    try:
-        return call(*a)
-    except capi.MadIcpError as e:
-        if "error -4" not in str(e):
-            raise
-        return None
-
-
-class Twin(HostTwin):
-    """tests/test_host_map_clear.py's adapter with what tests/map_removed_ref.py's replay asks for besides"""
-
-    def __init__(self, *a, tracking=True, **k):
-        super().__init__(*a, **k)
-        if tracking:
-            self.track(True)
-
-    def insert(self, pts, R, t, words):
-        return refusable(super().insert, pts, R, t, words)
-
-    def prune(self, c, r, wm):
-        return refusable(super().prune, c, r, wm)
-
-    def clear_rays(self, pts, R, t, origin=(0.0, 0.0, 0.0), margin=0.0, wm=0):
-        return refusable(super().clear_rays, pts, R, t, origin, margin, wm)
-
-    def keys(self):
-        return capi.host_map_download_keys(self.h)
-
-    def removed_count(self):
-        return capi.host_map_removed_count(self.h)
-
-    def take(self):
-        return capi.host_map_take_removed(self.h, self.with_attr)
-
-    def track(self, on):
-        capi.host_map_track_removed(self.h, on)
-
-    def reset(self):
-        capi.host_map_clear(self.h)
+TWIN = dict(TWIN, tracking=True, refusals=True)  # tests/test_host_map_clear.py's maps with what tests/map_removed_ref.py's replay asks for
 
 
 @pytest.fixture
-def twins(natives):
-    made = []
-
-    def make(*a, **k):
-        made.append(Twin(*a, **k))
-        return made[-1]
-
-    yield make
-    for m in made:
-        m.close()
+def twins(maps):
+    return functools.partial(maps.host, **TWIN)
 
 
 def logged(want):

@@ -2,6 +2,7 @@
 tests/voxel_map_ref.py, bit for bit (cloud_export_ref.same_bits) after every fold, and every refusal with the map unchanged.
 No GPU."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -9,43 +10,16 @@ import pytest
 import cloud_export_ref as E
 import voxel_map_ref as V
 from mad_icp_amd import capi
+from map_impls import maps  # noqa: F401 (maps is a fixture)
 
 INVALID, CAPACITY = -1, -4
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 
 
-class HostMap:
-    def __init__(self, voxel, initial_rows=64, max_rows=1 << 30):
-        self.h = capi.host_map_create(voxel, initial_rows, max_rows)
-
-    def insert(self, pts, R, t):
-        return capi.host_map_insert(self.h, pts, R, t)
-
-    def rows(self, first_row=0):
-        return capi.host_map_download_f32(self.h, first_row)
-
-    def size(self):
-        return capi.host_map_size(self.h)
-
-    def clear(self):
-        capi.host_map_clear(self.h)
-
-    def close(self):
-        capi.host_map_destroy(self.h)
-
-
 @pytest.fixture
-def new_map(natives):
-    made = []
-
-    def make(*a, **k):
-        made.append(HostMap(*a, **k))
-        return made[-1]
-
-    yield make
-    for m in made:
-        m.close()
+def new_map(maps):
+    return functools.partial(maps.host, max_rows=1 << 30)
 
 
 @pytest.mark.parametrize("kind", ["identity", "random"])
