@@ -699,7 +699,13 @@ int madicp_map_release(madicp_ctx* ctx, int map_id);
  * 1 516 352 (64 keyframes) at four poses each, so S has no value: no pair of those problems passes within 1e-7 m of a plane
  * and the device-built planes lie within ~1e-12 m of the reference's.  Every internal node is held to its members'
  * centroid within the float64 summation bound and to their principal axis with at most 4 x the reference's own residual
- * (measured 2.34 x); nodes of at most 32 points have the reference's centroid bit for bit. */
+ * (measured 2.34 x); nodes of at most 32 points have the reference's centroid bit for bit.
+ * Depth limit: a tree of up to 95 levels below the root is built (one launch step per level, 96 steps); a deeper one — 97 or more
+ * collinear points a constant factor apart, one point peeled per split — is refused with MADICP_ERR_INVALID, "tree build: tree
+ * deeper than the supported 96 levels", from here and from madicp_tree_build_end: no tree id is issued, nothing is left behind, the
+ * context builds on.  (The reference recurses without a limit; a 120 k-point scan at b_max 0.2 is 17 levels deep.)
+ * A build is a function of (cloud, b_max, b_min): what the context built before changes how the launches are sized, never a bit
+ * of the tree or of its records (tests/test_gpu_tree_build_history.py). */
 int madicp_tree_build(madicp_ctx* ctx, int cloud_id, double b_max, double b_min, int* out_tree_id, int32_t* out_n_leaves);
 /* The same construction as a look-ahead, for a caller that has the NEXT scan in hand while the current one registers
  * (what Pipeline::prefetch does with the device front-end on).  _begin copies the (n,3) float64 scan to the device and

@@ -13,6 +13,7 @@ buffer handed out while a stream still reads it, a slot left pending would all s
 import numpy as np
 import pytest
 
+from descent_ref import descend  # (the numpy descent in the reference's operation order: -> dict, "leaf" the getLeafs() ordinal)
 from fixtures import B_MAX, B_MIN, PARAMS
 from mad_icp_amd import capi, synth
 
@@ -21,21 +22,6 @@ pytestmark = pytest.mark.gpu
 
 DEFAULT_ROUTE = {"use_graph": 1, "eager_when_busy": 1, "seq_completion": 1, "host_feed_wait": 1, "wait_mode": 0, "nn_lds_top": 0,
                  "persistent": 0, "xcd_fold": 0}  # struct Options, launch_plan.h
-
-
-def descend(nodes, q):
-    """bestMatchingLeafFast over a linear node array, the reference's arithmetic: (q - mean) . dir with the contiguous
-    3-vector reduction order (oracle/linalg.h dotc), left when negative."""
-    right, mean, d, leaf_id = nodes["right"], nodes["mean"], nodes["dir"], nodes["leaf_id"]
-    idx = np.zeros(len(q), np.int64)
-    live = right[idx] != 0
-    while live.any():
-        ii = idx[live]
-        e = q[live] - mean[ii]
-        s = (e[:, 0] * d[ii, 0] + e[:, 1] * d[ii, 1]) + e[:, 2] * d[ii, 2]
-        idx[live] = np.where(s < 0, ii + 1, ii + right[ii])
-        live = right[idx] != 0
-    return leaf_id[idx].astype(np.uint32)
 
 
 def rigid(rng, scale=1.0):
@@ -138,7 +124,7 @@ def test_random_walk_over_the_abi(ctx, seed):
             assert got.tobytes() == m["nodes"].tobytes(), "resident tree differs from the model (step %d)" % step
             q = scans[k][:: 7] + rng.normal(size=3) * 0.05
             leaf = ctx.nn_search(tid, q, want=("leaf",))["leaf"]
-            assert np.array_equal(leaf, descend(m["nodes"], q))
+            assert np.array_equal(leaf, descend(m["nodes"], q)["leaf"])
             counts["search"] += 1
         elif op == "register" and trees and len(inflight) < 3:
             ids = [t for t in trees if rng.random() < 0.5][:6] or [next(iter(trees))]
