@@ -606,6 +606,26 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                            change) gets a transient one in the call's scratch first (fe::map_slot_rows, one lane per row).  The
  *                            scratch is the call's own, pooled: the builder's is not touched (legal while a look-ahead build is in
  *                            flight).  One host synchronisation, whatever n and M.
+ * SCORING MANY POSES.  A relocalisation, a loop-closure search or a drift check has not one pose but a cloud of hypotheses;
+ * madicp_map_score_poses gives the query's three counts at each of n_poses poses in ONE call.  The rule (one source with the host
+ * twin: csrc/common/export_point.h — map_score_refusal, score_takes_part and the query's own functions):
+ *   poses is (n_poses, 12) doubles: R row-major, then t — the first 12 entries of a row of madicp_map_register_cloud's out_trace.
+ *   Point i TAKES PART iff i % stride == 0, stride >= 1: subsampling, a hypothesis search does not need every point.
+ *   out_counts[3 k .. 3 k + 2] = {candidates, matched, within} are madicp_map_query_cloud's out_counts for the cloud of the points
+ *   that take part, at pose k: the same position rule, candidate decision, neighbourhood, (d2, row) order and d2 <= max_dist
+ *   max_dist in fp64.  Sums of integers: a function of (map, cloud, poses, reach, max_dist, stride) alone, whatever the launch
+ *   geometry — bit-equal between device, host twin, a numpy restatement and n_poses separate scoring queries.
+ *   madicp_map_score_poses   MADICP_ERR_INVALID, nothing written and nothing launched, for a null ctx, poses or out_counts, an
+ *                            unknown id, n_poses outside 1 .. 4096, a non-finite entry in ANY pose (the whole call is refused), a
+ *                            reach other than 0 and 1, a max_dist that is NaN or negative, a stride < 1.  The map is only read, as
+ *                            by the query.  Kernel (fe::map_score_poses): a workgroup stages a chunk of 64 poses in LDS (96 B
+ *                            each), a lane loads its point once and scores it at every pose of the chunk, several poses' gathers
+ *                            in flight per lane; per pose ballots and popcounts per wavefront, 64-bit integer LDS counters, one
+ *                            64-bit integer global atomic per workgroup, pose and count — no float atomics, nothing wraps.  The
+ *                            scratch is the call's own, pooled (counts, poses and, on plain and attribute maps, the transient
+ *                            slot-to-row array): the builder's is not touched.  Everything runs on the copy stream — one memset,
+ *                            the pose upload, the kernels, one copy out — and ends in ONE host synchronisation, whatever n, M and
+ *                            n_poses (profiles/map_score_time.md).
  * REGISTER.  madicp_map_register_cloud gives the pose that FITS a resident cloud to a moments map: `iterations` rounds of
  * point-to-plane Gauss-Newton against the map's surfels, all on the device.  The rule (one source with the host twin:
  * csrc/common/map_align.h), fp64 and integers only, no contraction, no library function in the linearisation:
@@ -684,6 +704,8 @@ int madicp_map_register_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const d
                               double* out_trace /* (iterations + 1) x 40: X[12] | H[21] | b[6] | chi2 */,
                               uint64_t* out_counts /* (iterations + 1) x 4 */, int32_t* out_row, double* out_e,
                               int64_t capacity_points);
+int madicp_map_score_poses(madicp_ctx* ctx, int map_id, int cloud_id, const double* poses, int64_t n_poses, int reach, double max_dist,
+                           int64_t stride, uint64_t* out_counts /* n_poses x 3 */);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

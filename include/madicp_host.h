@@ -162,6 +162,11 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  neighbourhood (reach 0: its own cell, 1: the 27 around it); out_row / out_d2 / out_keys / out_attr / out_ev
  *                  null where not wanted, out_counts = {candidates, matched, within max_dist}.  The map is only read.  The same
  *                  refusals and codes, nothing written; xyz may be null when n == 0.  Every output bit-equal to the device's.
+ *   _score         the twin of madicp_map_score_poses (madicp_hip.h has the rule): _query's three counts at each of n_poses poses —
+ *                  (n_poses, 12) doubles, R row-major then t — over the points i of xyz with i % stride == 0; out_counts is
+ *                  n_poses x 3.  The map is only read.  The same refusals (null poses or out_counts, n_poses outside 1 .. 4096, a
+ *                  non-finite entry in any pose, reach, max_dist, stride < 1), nothing written.  n == 0 is legal here (xyz may
+ *                  then be null): zeros.  Every count equal to the device's.
  *   _register      the twin of madicp_map_register_cloud (madicp_hip.h and csrc/common/map_align.h have the rule): `iterations`
  *                  rounds of point-to-plane Gauss-Newton of the n points of xyz against the map's surfels — its own map_surfel of
  *                  every row, computed once per call — the same gates, terms and adjacent-pair tree sum; the step is the host's
@@ -214,6 +219,8 @@ int madicp_host_map_download_surfels(const madicp_host_map* map, int64_t first_r
 int madicp_host_map_query(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3], int reach,
                           double max_dist, int32_t* out_row, double* out_d2, uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev,
                           int64_t capacity_points, uint64_t out_counts[3]);
+int madicp_host_map_score(const madicp_host_map* map, const double* xyz, int64_t n, const double* poses, int64_t n_poses, int reach,
+                          double max_dist, int64_t stride, uint64_t* out_counts);
 int madicp_host_map_register(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
                              const madicp_map_align_params* params, int iterations, double out_R[9], double out_t[3],
                              double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points);

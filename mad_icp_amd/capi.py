@@ -81,6 +81,7 @@ MAP_ENTRY_POINTS = [
     ("clear_rays", "clear_rays", [_SCAN, _dp, _dp, _dp, C.c_double] + _REMOVAL),
     ("query_cloud", "query", [_SCAN, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p, C.c_int64, _u64p]),
     ("register_cloud", "register", [_SCAN, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp, _u64p, _i32p, _dp, C.c_int64]),
+    ("score_poses", "score", [_SCAN, _dp, C.c_int64, C.c_int, C.c_double, C.c_int64, _u64p]),
     ("track_removed", "track_removed", [C.c_int]),
     ("removed_count", "removed_count", [_i64p]),
     ("take_removed", "take_removed", [_u64p, _fp, _u32p] + _WINDOW),
@@ -631,6 +632,16 @@ def _ptr(a):
 _XYZ, _KEYS, _WORDS, _MOMENTS = ((3,), np.float32), ((), np.uint64), ((), np.uint32), ((10,), np.uint64)
 
 
+def pose_rows(poses):
+    """K poses as the (K, 12) float64 rows the scoring entry points take — R row-major, then t — from (K, 12) or (K, 4, 4)"""
+    P = np.asarray(poses, np.float64)
+    if P.ndim == 3 and P.shape[1:] == (4, 4):
+        P = np.concatenate([P[:, :3, :3].reshape(-1, 9), P[:, :3, 3]], axis=1)
+    if P.ndim != 2 or P.shape[1] != 12:
+        raise ValueError("poses must be (K, 12) or (K, 4, 4)")
+    return np.ascontiguousarray(P)
+
+
 class _Map:
     """One voxel map, every operation once; Context.map_* (the device's) and host_map_* (the twin's) are these and the
     Context methods document them.  HostMap and DeviceMap say how a call reaches C (create, _call) and what a scan becomes as C
@@ -716,6 +727,12 @@ class _Map:
             ans["row"], ans["e"] = row[:n].copy(), e[:n].copy()
         return ans
 
+    def score(self, scan, poses, reach=1, max_dist=float("inf"), stride=1):
+        P = pose_rows(poses)
+        counts = np.zeros((max(P.shape[0], 1), 3), np.uint64)
+        self._call("score", *self._scan(scan)[0], _ptr(P), P.shape[0], int(reach), float(max_dist), int(stride), _ptr(counts))
+        return counts[:P.shape[0]]
+
     def track_removed(self, on=True):
         self._call("track_removed", 1 if on else 0)
 
@@ -787,7 +804,8 @@ class HostMap(_Map):
 
 class DeviceMap(_Map):
     """The map where it lives (madicp_map_*, include/madicp_hip.h): map `mid` of Context `ctx`; close() releases it."""
-    _NAMES = {"insert": "insert_cloud", "query": "query_cloud", "register": "register_cloud", "close": "release"}
+    _NAMES = {"insert": "insert_cloud", "query": "query_cloud", "register": "register_cloud", "score": "score_poses", "close": "release"}
+    score_poses = _Map.score  # (the entry point's name on this side: Context.map_score_poses goes through it)
 
     def __init__(self, ctx, mid):
         self._ctx, self.mid = ctx, mid
@@ -827,6 +845,7 @@ def host_map_query(h, xyz, R, t, reach=1, max_dist=float("inf"), per_point=True,
     return HostMap(h).query(xyz, R, t, reach, max_dist, per_point, with_keys, with_attr, with_ev)
 def host_map_register(h, xyz, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0, per_point=False):
     return HostMap(h).register(xyz, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
+def host_map_score(h, xyz, poses, reach=1, max_dist=float("inf"), stride=1): return HostMap(h).score(xyz, poses, reach, max_dist, stride)
 def host_map_track_removed(h, on=True): HostMap(h).track_removed(on)
 def host_map_removed_count(h): return HostMap(h).removed_count()
 def host_map_take_removed(h, with_attr=False): return HostMap(h).take_removed(with_attr)
@@ -1144,6 +1163,13 @@ class Context:
         chi2, counts) with one row per linearisation — row k at X[k], the last at the returned pose — and, with per_point (only
         with iterations == 0), row (n,) int32 and e (n,) float64.  One host synchronisation."""
         return DeviceMap(self, mid).register(cid, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
+
+    def map_score_poses(self, mid, cid, poses, reach=1, max_dist=float("inf"), stride=1):
+        """madicp_map_score_poses: map_query's three counts (candidates, matched, within max_dist) of resident cloud cid at each
+        of K poses — (K, 12) rows of R row-major then t, or (K, 4, 4) — over the points i with i % stride == 0, in one call:
+        one upload of the poses, one launch sequence, ONE host synchronisation whatever n, M and K.  Returns (K, 3) uint64, row k
+        what map_query(mid, the subsampled cloud, R_k, t_k, reach, max_dist, per_point=False) returns.  The map is only read."""
+        return DeviceMap(self, mid).score_poses(cid, poses, reach, max_dist, stride)
 
     def map_clear(self, mid):
         DeviceMap(self, mid).clear()

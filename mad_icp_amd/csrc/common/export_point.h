@@ -224,4 +224,26 @@ MADICP_HD inline bool query_before(double d2, int32_t row, double best_d2, int32
   return d2 < best_d2 || (d2 == best_d2 && static_cast<uint32_t>(row) < static_cast<uint32_t>(best_row));
 }
 
+// ---- scoring many poses (madicp_map_score_poses / madicp_host_map_score): the query's three counts at each of K poses ---------------
+// poses is (K, 12) doubles, R row-major then t (the first 12 entries of a row of the registration's trace).  Point i TAKES PART iff
+// i % stride == 0; counts[k] = {candidates, matched, within} are the query's counts, above, of the cloud of the points that take
+// part at pose k: the same export_position, export_cells, neighbourhood, (d2, row) order and d2 <= max_dist max_dist in fp64.  Sums
+// of integers: a function of (map, cloud, poses, reach, max_dist, stride) alone, equal to K scoring queries of the subsampled cloud.
+constexpr int64_t kScoreMaxPoses = 4096;
+constexpr int kScorePoseDoubles = 12;
+
+MADICP_HD inline bool score_takes_part(int64_t i, int64_t stride) { return i % stride == 0; }
+
+// what both entry points refuse (null = nothing to refuse); one non-finite entry in any pose refuses the whole call
+inline const char* map_score_refusal(const double* poses, int64_t n_poses, int reach, double max_dist, int64_t stride) {
+  if (!poses) return "null argument";
+  if (n_poses < 1 || n_poses > kScoreMaxPoses) return "n_poses: 1 .. 4096";
+  for (int64_t i = 0; i < n_poses * kScorePoseDoubles; ++i)
+    if (!(poses[i] - poses[i] == 0.0)) return "poses: finite entries";
+  if (reach != 0 && reach != 1) return "reach: 0 or 1";
+  if (!(max_dist >= 0.0)) return "max_dist: >= 0 and not NaN (+inf is legal)";
+  if (stride < 1) return "stride: at least 1";
+  return nullptr;
+}
+
 }  // namespace madicp_host

@@ -1160,5 +1160,128 @@ __global__ __launch_bounds__(64) void map_align_step(const double* __restrict__ 
   }
 }
 
+// ---- scoring many poses: the query's three counts at each of K poses (madicp_map_score_poses) ----------------------------------------
+// The rule is csrc/common/export_point.h's (score_takes_part and the query's own), shared with the host twin.  map_score_poses:
+//   grid       x: passes over the points that take part (one lane per point, grid-stride); y: chunks of kScoreChunk poses
+//   LDS        the chunk's poses (96 B each; slots past the last pose hold zeros and are never scored) and 3 64-bit counters per pose
+//   a pass     a lane loads its point ONCE and scores it at every pose of the chunk, kScorePosesPerStep<REACH> poses per step, the
+//              rest one at a time (score_step<REACH, 1>); the bounds are the workgroup's, so every lane of a wavefront walks the same
+//              steps and a lane past the last point takes part with "no candidate"
+//   a step     the gathers of its P poses run STAGE BY STAGE, not probe by probe: first every chain's table slot is loaded (P chains
+//              at reach 0; P x 9 at reach 1, one z-layer of the 27 cells at a time), then the rare collision walks, then every
+//              chain's slot row, then every chain's 12-byte row — so P or 9 P independent loads are in flight per lane where
+//              map_find's loop, called probe by probe, has one.  The walk of a chain is map_find's: the same slot, the same answer.
+//   counts     per pose three ballots and popcounts per wavefront, lane 0 adds them to the LDS counters (64-bit integer adds:
+//              nothing wraps whatever n); after the last pass one 64-bit integer global atomic per non-zero counter.  No float
+//              atomics: sums of integers, the same whatever the geometry.
+constexpr int kScoreChunk = 64;
+template <int REACH>
+struct ScoreGeometry {
+  static constexpr int kPosesPerStep = REACH ? 2 : 8;
+  static constexpr int kCellsPerStage = REACH ? 9 : 1;  // per pose: one z-layer of the neighbourhood, or the point's own cell
+  static constexpr int kStages = REACH ? 3 : 1;
+};
+template <int REACH, int P>
+__device__ inline void score_step(const QueryMap& M, const double* __restrict__ sp, unsigned long long* __restrict__ sc, bool have,
+                                  const double* p, double voxel, double md2, int lane) {
+  constexpr int C = ScoreGeometry<REACH>::kCellsPerStage, B = P * C;
+  double q[P][3], best[P];
+  int32_t cell[P][3], brow[P];
+  bool cand[P];
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    madicp_host::export_position(p, sp + madicp_host::kScorePoseDoubles * u, sp + madicp_host::kScorePoseDoubles * u + 9, q[u]);
+    cand[u] = madicp_host::export_cells(q[u], voxel, cell[u]) && have;
+    best[u] = madicp_host::kQueryNoDistance;
+    brow[u] = -1;
+  }
+#pragma unroll
+  for (int l = 0; l < ScoreGeometry<REACH>::kStages; ++l) {
+    unsigned long long seen[B];
+    uint64_t key[B];
+    uint32_t slot[B], row[B];
+    bool live[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) {  // every chain's first slot: B loads in flight
+      key[b] = 0;
+      live[b] = cand[b / C] && madicp_host::query_cell_key(cell[b / C], REACH ? C * l + b % C : madicp_host::kQueryOwnCell, &key[b]);
+      slot[b] = export_slot0(key[b], M.slots);
+      seen[b] = live[b] ? M.keys[slot[b]] : (unsigned long long)madicp_host::kExportNoKey;
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {  // (map_find's walk from where the first load left it: rare)
+      while (seen[b] != key[b] && seen[b] != madicp_host::kExportNoKey) {
+        slot[b] = (slot[b] + 1 == M.slots) ? 0u : slot[b] + 1;
+        seen[b] = M.keys[slot[b]];
+      }
+      live[b] = live[b] && seen[b] == key[b];
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      row[b] = live[b] ? M.slot_row[slot[b]] : 0xffffffffu;
+      live[b] = live[b] && (long)row[b] < M.n_rows;  // (never false for a found key: every slot that holds a key knows its row)
+    }
+    float r[B][3];
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) r[b][a] = live[b] ? M.xyz[3 * (size_t)row[b] + a] : 0.0f;
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const double d = madicp_host::query_d2(q[b / C], r[b]);
+      if (live[b] && madicp_host::query_before(d, (int32_t)row[b], best[b / C], brow[b / C])) {
+        best[b / C] = d;
+        brow[b / C] = (int32_t)row[b];
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < P; ++u) {
+    const bool matched = brow[u] >= 0;
+    const unsigned long long a = __popcll(__ballot(cand[u]));
+    const unsigned long long m = __popcll(__ballot(matched));
+    const unsigned long long w = __popcll(__ballot(matched && best[u] <= md2));
+    if (lane == 0) {
+      if (a) atomicAdd(&sc[3 * u], a);
+      if (m) atomicAdd(&sc[3 * u + 1], m);
+      if (w) atomicAdd(&sc[3 * u + 2], w);
+    }
+  }
+}
+// n_take: the points that take part, (n - 1) / stride + 1; point s of them is point s * stride of the cloud
+template <int REACH>
+__global__ __launch_bounds__(256) void map_score_poses(const double* __restrict__ xyz, long n_take, long stride,
+                                                       const double* __restrict__ poses, int n_poses, double voxel, double md2, QueryMap M,
+                                                       unsigned long long* __restrict__ counts) {
+  constexpr int P = ScoreGeometry<REACH>::kPosesPerStep, kD = madicp_host::kScorePoseDoubles;
+  static_assert(kScoreChunk % P == 0, "a chunk is whole steps");
+  __shared__ double sp[kScoreChunk * kD];
+  __shared__ unsigned long long sc[kScoreChunk * 3];
+  const int k0 = blockIdx.y * kScoreChunk;
+  const int kc = n_poses - k0 < kScoreChunk ? n_poses - k0 : kScoreChunk;  // (>= 1: gridDim.y is ceil(n_poses / kScoreChunk))
+  for (int v = threadIdx.x; v < kScoreChunk * kD; v += blockDim.x) sp[v] = v < kc * kD ? poses[(size_t)k0 * kD + v] : 0.0;
+  for (int v = threadIdx.x; v < kScoreChunk * 3; v += blockDim.x) sc[v] = 0ull;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  // (blockDim and the stride are multiples of 64: s - lane is the wavefront's, so all its lanes leave the loop together)
+  for (long s = blockIdx.x * (long)blockDim.x + threadIdx.x; s - lane < n_take; s += (long)gridDim.x * blockDim.x) {
+    const bool have = s < n_take;
+    double p[3] = {0.0, 0.0, 0.0};
+    if (have) {
+      const size_t i = (size_t)s * (size_t)stride;
+      p[0] = xyz[3 * i];
+      p[1] = xyz[3 * i + 1];
+      p[2] = xyz[3 * i + 2];
+    }
+    int k = 0;
+    for (; k + P <= kc; k += P) score_step<REACH, P>(M, sp + kD * k, sc + 3 * k, have, p, voxel, md2, lane);
+    for (; k < kc; ++k) score_step<REACH, 1>(M, sp + kD * k, sc + 3 * k, have, p, voxel, md2, lane);
+  }
+  __syncthreads();
+  for (int v = threadIdx.x; v < kc * 3; v += blockDim.x)
+    if (sc[v]) atomicAdd(&counts[(size_t)k0 * 3 + v], sc[v]);
+}
+
 }  // namespace fe
 }  // namespace madicp

@@ -1684,6 +1684,64 @@ int madicp_map_query_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const doub
   return rc;
 }
 
+// The query's three counts at each of n_poses poses (fe::map_score_poses; csrc/common/export_point.h has the rule).  The map's block
+// is only read.  The call's scratch is ONE pooled block of its own — the builder's is not touched —
+//   counts (K x 3 x 8) | poses (K x 96) | slot_row (slots x 4)
+// the last only on a map without the column (fe::map_slot_rows fills it).  Everything on the copy stream: one memset for the counts,
+// the pose upload, the kernels, one copy out, ONE wait, whatever n, M and K.
+int madicp_map_score_poses(madicp_ctx* ctx, int map_id, int cloud_id, const double* poses, int64_t n_poses, int reach, double max_dist,
+                           int64_t stride, uint64_t* out_counts) {
+  if (!ctx || !poses || !out_counts) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  DevCloud* c = find_cloud(ctx, cloud_id);
+  if (!c) return fail(MADICP_ERR_INVALID, "unknown cloud id");
+  if (const char* why = madicp_host::map_score_refusal(poses, n_poses, reach, max_dist, stride)) return fail(MADICP_ERR_INVALID, why);
+  const int64_t n = c->n;
+  const size_t K = (size_t)n_poses;
+  if (n <= 0) {  // (never: a resident cloud holds at least one point)
+    std::fill(out_counts, out_counts + 3 * K, uint64_t(0));
+    return MADICP_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t n_take = (n - 1) / stride + 1;
+  const bool own_slot_row = !m->slot_row();
+  const size_t at_poses = align_up(8 * 3 * K), at_slot_row = align_up(at_poses + 8 * madicp_host::kScorePoseDoubles * K);
+  void* p = nullptr;
+  RC_TRY(pool_alloc(ctx, own_slot_row ? at_slot_row + 4 * (size_t)m->slots : at_slot_row, ctx->copy, &p));
+  char* block = static_cast<char*>(p);
+  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(block);
+  double* d_poses = reinterpret_cast<double*>(block + at_poses);
+  uint32_t* slot_row = own_slot_row ? reinterpret_cast<uint32_t*>(block + at_slot_row) : m->slot_row();
+  const fe::QueryMap Q{m->keys(), m->slots, slot_row, m->xyz(), (long)m->rows, m->row_keys(), nullptr, nullptr};
+  hipError_t e = hipMemsetAsync(d_counts, 0, 8 * 3 * K, ctx->copy);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_poses, poses, 8 * madicp_host::kScorePoseDoubles * K, hipMemcpyHostToDevice, ctx->copy);
+  if (e == hipSuccess) {
+    if (own_slot_row && m->rows > 0)
+      hipLaunchKernelGGL(fe::map_slot_rows, dim3(grid_256(ctx, m->rows)), dim3(256), 0, ctx->copy, (const unsigned long long*)m->row_keys(),
+                         (long)m->rows, (const unsigned long long*)m->keys(), m->slots, slot_row);
+    // chunks of poses in y; in x as many workgroups as the points that take part fill, the whole grid about 8 per CU
+    const unsigned chunks = (unsigned)((n_poses + fe::kScoreChunk - 1) / fe::kScoreChunk);
+    const int64_t per_chunk = std::max<int64_t>(((int64_t)ctx->n_cus * 8 + chunks - 1) / chunks, 1);
+    const dim3 grid((unsigned)std::min<int64_t>((n_take + 255) / 256, per_chunk), chunks);
+    const double md2 = max_dist * max_dist;
+    if (reach == 0)
+      hipLaunchKernelGGL(fe::map_score_poses<0>, grid, dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n_take, (long)stride,
+                         (const double*)d_poses, (int)n_poses, m->voxel, md2, Q, d_counts);
+    else
+      hipLaunchKernelGGL(fe::map_score_poses<1>, grid, dim3(256), 0, ctx->copy, (const double*)c->xyz, (long)n_take, (long)stride,
+                         (const double*)d_poses, (int)n_poses, m->voxel, md2, Q, d_counts);
+    e = hipGetLastError();
+  }
+  std::vector<uint64_t> counts(3 * K);
+  const CopyOut outs[] = {{counts.data(), d_counts, 8 * 3 * K}};
+  const int rc = copies_then_wait(ctx, e, outs, 1, "voxel map scoring: ");
+  pool_free(ctx, block, nullptr);  // (behind the wait: nothing is in flight on it)
+  if (rc == MADICP_OK) std::memcpy(out_counts, counts.data(), 8 * 3 * K);
+  return rc;
+}
+
 // `iterations` Gauss-Newton rounds of a resident cloud against the map's surfels (csrc/common/map_align.h has the rule).  The
 // map's block is only read.  The call's scratch is ONE pooled block of its own — the builder's is not touched —
 //   counts ((K + 1) x 4 x 8) | pose (12 x 8) | trace ((K + 1) x 40 x 8) | partial rows A (ceil(n / 256) x 28 x 8) | partial rows B

@@ -76,6 +76,13 @@ class DeviceMapStore final : public MapStore {
                                     capacity_points, out_counts);
     });
   }
+  int score(const ScanRef& scan, const double* poses, int64_t n_poses, int reach, double max_dist, int64_t stride,
+            uint64_t* out_counts) override {
+    ScanBorrow b(*this, scan);
+    return call("madicp_map_score_poses", [&](madicp_ctx* ctx) {
+      return madicp_map_score_poses(ctx, id_, b.scan().cloud_id, poses, n_poses, reach, max_dist, stride, out_counts);
+    });
+  }
   int align(const ScanRef& scan, const double* R, const double* t, const AlignParams& p, int iterations, double* out_R, double* out_t,
             double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points) override {
     ScanBorrow b(*this, scan);

@@ -91,6 +91,9 @@ class MapStore {
                         int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) = 0;
   virtual int query(const ScanRef& scan, const double* R, const double* t, int reach, double max_dist, int32_t* out_row, double* out_d2,
                     uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, int64_t capacity_points, uint64_t* out_counts) = 0;
+  // madicp_map_score_poses / VoxelMap::score: poses (n_poses, 12), out_counts n_poses x 3
+  virtual int score(const ScanRef& scan, const double* poses, int64_t n_poses, int reach, double max_dist, int64_t stride,
+                    uint64_t* out_counts) = 0;
   // madicp_map_register_cloud / VoxelMap::align: out_trace (iterations + 1) x 40, out_counts (iterations + 1) x 4
   virtual int align(const ScanRef& scan, const double* R, const double* t, const AlignParams& params, int iterations, double* out_R,
                     double* out_t, double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points) = 0;
@@ -160,6 +163,11 @@ class HostMapStore final : public MapStore {
             uint64_t* out_keys, uint32_t* out_attr, uint32_t* out_ev, int64_t capacity_points, uint64_t* out_counts) override {
     ScanBorrow b(*this, scan);
     return map_.query(b.scan().xyz, b.scan().n, R, t, reach, max_dist, out_row, out_d2, out_keys, out_attr, out_ev, capacity_points, out_counts);
+  }
+  int score(const ScanRef& scan, const double* poses, int64_t n_poses, int reach, double max_dist, int64_t stride,
+            uint64_t* out_counts) override {
+    ScanBorrow b(*this, scan);
+    return map_.score(b.scan().xyz, b.scan().n, poses, n_poses, reach, max_dist, stride, out_counts);
   }
   int align(const ScanRef& scan, const double* R, const double* t, const AlignParams& p, int iterations, double* out_R, double* out_t,
             double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points) override {

@@ -488,6 +488,80 @@ void Pipeline::mapRegister(const double* xyz, size_t n, const double R[9], const
   if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapRegister: " + map.lastError());
 }
 
+void Pipeline::mapScorePoses(const double* xyz, size_t n, const double* poses, size_t n_poses, int reach, double max_dist, int64_t stride,
+                             uint64_t* counts) {
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapScorePoses: setMapAccumulation(voxel_size > 0) first");
+  if ((!xyz && n > 0) || !poses || !counts) throw std::invalid_argument("Pipeline::mapScorePoses: null argument");
+  if (n > static_cast<size_t>(kMapMaxRows)) throw std::invalid_argument("Pipeline::mapScorePoses: at most 2^30 points");
+  const int64_t k64 = n_poses > static_cast<size_t>(kScoreMaxPoses) ? kScoreMaxPoses + 1 : static_cast<int64_t>(n_poses);
+  if (const char* why = map_score_refusal(poses, k64, reach, max_dist, stride))
+    throw std::invalid_argument(std::string("Pipeline::mapScorePoses: ") + why);
+  std::unique_ptr<MapStore> empty;  // before the first fold and for no point at all: an empty host map of the same kind answers
+  if (!map_ || n == 0) {
+    MapSpec kind = map_spec_;
+    kind.first_rows = kind.max_rows = 1;
+    empty = std::make_unique<HostMapStore>(kind);
+  }
+  MapStore& map = empty ? *empty : *map_;
+  const int rc = map.score(ScanRef::host(xyz, nullptr, static_cast<int64_t>(n)), poses, k64, reach, max_dist, stride, counts);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapScorePoses: " + map.lastError());
+  if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapScorePoses: " + map.lastError());
+}
+
+size_t Pipeline::mapRelocalize(const double* xyz, size_t n, const double* poses, size_t n_poses, int reach, double max_dist, int64_t stride,
+                               int refine, const AlignParams& params, int iterations, int32_t* out_index, uint64_t* out_scores,
+                               double* out_poses, double* out_sums, uint64_t* out_counts, size_t* out_best) {
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapRelocalize: setMapAccumulation(voxel_size > 0) first");
+  if (map_spec_.mom == 0) throw std::logic_error("Pipeline::mapRelocalize: the map was made without moments (setMapAccumulation's moments)");
+  if ((!xyz && n > 0) || !poses || !out_index || !out_scores || !out_poses || !out_sums || !out_counts || !out_best)
+    throw std::invalid_argument("Pipeline::mapRelocalize: null argument");
+  if (n > static_cast<size_t>(kMapMaxRows)) throw std::invalid_argument("Pipeline::mapRelocalize: at most 2^30 points");
+  if (refine < 1 || refine > kRelocalizeMaxRefine) throw std::invalid_argument("Pipeline::mapRelocalize: refine must be 1 .. 64");
+  const int64_t k64 = n_poses > static_cast<size_t>(kScoreMaxPoses) ? kScoreMaxPoses + 1 : static_cast<int64_t>(n_poses);
+  if (const char* why = map_score_refusal(poses, k64, reach, max_dist, stride))
+    throw std::invalid_argument(std::string("Pipeline::mapRelocalize: ") + why);
+  if (const char* why = map_align_refusal(poses, poses + 9, params.reach, params.max_dist, params.rho, params.min_count, params.flat))
+    throw std::invalid_argument(std::string("Pipeline::mapRelocalize: ") + why);
+  if (iterations < 0 || iterations > kAlignMaxIterations) throw std::invalid_argument("Pipeline::mapRelocalize: iterations must be 0 .. 64");
+  std::unique_ptr<MapStore> empty;  // before the first fold and for no point at all: an empty host map of the same kind answers
+  if (!map_ || n == 0) {
+    MapSpec kind = map_spec_;
+    kind.first_rows = kind.max_rows = 1;
+    empty = std::make_unique<HostMapStore>(kind);
+  }
+  MapStore& map = empty ? *empty : *map_;
+  auto check_rc = [&](int rc) {
+    if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapRelocalize: " + map.lastError());
+    if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapRelocalize: " + map.lastError());
+  };
+  const size_t K = static_cast<size_t>(k64), m = std::min<size_t>(static_cast<size_t>(refine), K);
+  ScanBorrow scan(map, ScanRef::host(xyz, nullptr, static_cast<int64_t>(n)));  // ONE borrow: the scan goes up once
+  std::vector<uint64_t> scores(3 * K);
+  check_rc(map.score(scan.scan(), poses, k64, reach, max_dist, stride, scores.data()));
+  std::vector<int32_t> order(K);
+  for (size_t k = 0; k < K; ++k) order[k] = static_cast<int32_t>(k);
+  // (within descending, index ascending): a strict total order, the ranking is a function of the integers alone
+  std::partial_sort(order.begin(), order.begin() + m, order.end(), [&](int32_t a, int32_t b) {
+    return scores[3 * a + 2] > scores[3 * b + 2] || (scores[3 * a + 2] == scores[3 * b + 2] && a < b);
+  });
+  std::vector<double> trace(kAlignTraceRow * (static_cast<size_t>(iterations) + 1));
+  std::vector<uint64_t> counts(kAlignCounts * (static_cast<size_t>(iterations) + 1));
+  size_t best = 0;
+  for (size_t r = 0; r < m; ++r) {
+    const size_t k = static_cast<size_t>(order[r]);
+    const double* X = poses + kScorePoseDoubles * k;
+    check_rc(map.align(scan.scan(), X, X + 9, params, iterations, out_poses + 12 * r, out_poses + 12 * r + 9, trace.data(), counts.data(),
+                       nullptr, nullptr, 0));
+    out_index[r] = order[r];
+    std::copy(scores.begin() + 3 * k, scores.begin() + 3 * k + 3, out_scores + 3 * r);
+    std::copy(trace.end() - kAlignTerms, trace.end(), out_sums + kAlignTerms * r);
+    std::copy(counts.end() - kAlignCounts, counts.end(), out_counts + kAlignCounts * r);
+    if (out_counts[kAlignCounts * r + 3] > out_counts[kAlignCounts * best + 3]) best = r;  // (a tie stays with the better rank)
+  }
+  *out_best = best;
+  return m;
+}
+
 size_t Pipeline::mapNewRowCount() {
   if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapNewRows: setMapAccumulation(voxel_size > 0) first");
   return mapSize() - map_cursor_;

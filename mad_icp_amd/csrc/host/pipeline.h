@@ -294,6 +294,29 @@ class Pipeline {
   // without moments; std::invalid_argument for a null argument and for what madicp_map_register_cloud refuses.
   void mapRegister(const double* xyz, size_t n, const double R[9], const double t[3], const AlignParams& params, int iterations,
                    double out_R[9], double out_t[3], double* trace, uint64_t* counts, int32_t* row = nullptr, double* e = nullptr);
+  // additive: MANY HYPOTHESES.  mapScorePoses: mapQuery's three counts (candidates, matched, within max_dist) of the n points xyz at
+  // each of n_poses poses — (n_poses, 12) doubles, R row-major then t — over the points i with i % stride == 0, counts (n_poses x 3):
+  // row k is what the scoring form of mapQuery answers for the subsampled cloud at pose k (include/madicp_hip.h:
+  // madicp_map_score_poses has the rule).  Device front-end: ONE upload of the points, one launch sequence, ONE host
+  // synchronisation whatever n, the map's size and n_poses; host front-end: the bit-equal host twin.  Before the first fold the map
+  // is empty: every candidate is unmatched.  The map is only read.  std::logic_error while accumulation is off;
+  // std::invalid_argument for a null argument, n_poses outside 1 .. 4096, a non-finite entry in any pose, a reach other than 0 and
+  // 1, a max_dist that is NaN or negative, a stride < 1.
+  // mapRelocalize: under ONE borrow of the scan (one upload on the device front-end) it (1) scores all n_poses poses as
+  // mapScorePoses does, (2) ranks them by (within descending, index ascending) and (3) registers the first min(refine, n_poses) of
+  // them as mapRegister does — every point, no stride, `iterations` rounds from the hypothesis' own pose.  It IS that composition
+  // and equals it bit for bit.  Per refined hypothesis r, in rank order: out_index[r], out_scores (3: its score counts), out_poses
+  // (12: the registered pose), out_sums (28) and out_counts (4: candidates, matched, within, inliers) of the closing linearisation;
+  // *out_best is the r with the most closing inliers, a tie to the better rank.  Returns min(refine, n_poses).  The pipeline's own
+  // pose is never touched and the map is only read.  Host synchronisations on the device front-end: 1 + refine (the scoring call's
+  // one, then one per registration), behind the upload.  std::logic_error while accumulation is off or without moments;
+  // std::invalid_argument for refine outside 1 .. 64 and for what mapScorePoses and mapRegister refuse.
+  static constexpr int kRelocalizeMaxRefine = 64;
+  void mapScorePoses(const double* xyz, size_t n, const double* poses, size_t n_poses, int reach, double max_dist, int64_t stride,
+                     uint64_t* counts);
+  size_t mapRelocalize(const double* xyz, size_t n, const double* poses, size_t n_poses, int reach, double max_dist, int64_t stride, int refine,
+                       const AlignParams& params, int iterations, int32_t* out_index, uint64_t* out_scores, double* out_poses,
+                       double* out_sums, uint64_t* out_counts, size_t* out_best);
   // setMapAlignment(on, iterations, params) — default off: not a launch, not an allocation, the same pose and map bits — lets
   // foldFrame(), inside its one borrow of the frame's cloud and BEFORE the fold, register that cloud against the map as it stands,
   // from the frame's own pose (a drift check of the odometry against its own map).  The result is only REPORTED: mapFrameAlignment()

@@ -155,6 +155,12 @@ int madicp_host_map_query(const madicp_host_map* map, const double* xyz, int64_t
   return map->map.query(xyz, n, R, t, reach, max_dist, out_row, out_d2, out_keys, out_attr, out_ev, capacity_points, out_counts);
 }
 
+int madicp_host_map_score(const madicp_host_map* map, const double* xyz, int64_t n, const double* poses, int64_t n_poses, int reach,
+                          double max_dist, int64_t stride, uint64_t* out_counts) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.score(xyz, n, poses, n_poses, reach, max_dist, stride, out_counts);
+}
+
 int madicp_host_map_register(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
                              const madicp_map_align_params* params, int iterations, double out_R[9], double out_t[3],
                              double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points) {

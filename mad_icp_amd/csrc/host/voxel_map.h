@@ -294,6 +294,55 @@ class VoxelMap {
     return kMapOk;
   }
 
+  // include/madicp_host.h: madicp_host_map_score — query()'s three counts at each of n_poses poses (export_point.h has the rule:
+  // map_score_refusal, score_takes_part), over the points i with i % stride == 0; out_counts is n_poses x 3.  The map is only read;
+  // the transient key -> row index of a map without moments is made once per call, not once per pose.
+  int score(const double* xyz, int64_t n, const double* poses, int64_t n_poses, int reach, double max_dist, int64_t stride,
+            uint64_t* out_counts) const {
+    if (!out_counts || n < 0 || n > kMapMaxRows || (!xyz && n > 0)) return kMapInvalid;
+    if (map_score_refusal(poses, n_poses, reach, max_dist, stride)) return kMapInvalid;
+    std::unordered_map<uint64_t, int64_t> own_index;
+    if (!with_mom_ && n > 0) {
+      own_index.reserve(row_keys_.size());
+      for (int64_t j = 0; j < size(); ++j) own_index[row_keys_[j]] = j;
+    }
+    const std::unordered_map<uint64_t, int64_t>& index = with_mom_ ? row_of_ : own_index;
+    const double md2 = max_dist * max_dist;
+    for (int64_t k = 0; k < n_poses; ++k) {
+      const double* R = poses + kScorePoseDoubles * k;
+      const double* t = R + 9;
+      uint64_t candidates = 0, matched = 0, within = 0;
+      for (int64_t i = 0; i < n; i += stride) {  // (i % stride == 0: score_takes_part)
+        double q[3];
+        export_position(xyz + 3 * i, R, t, q);
+        int32_t cell[3], best = -1;
+        double best_d2 = kQueryNoDistance;
+        if (!export_cells(q, voxel_, cell)) continue;
+        ++candidates;
+        for (int c = reach ? 0 : kQueryOwnCell; c < (reach ? kQueryCells : kQueryOwnCell + 1); ++c) {
+          uint64_t key;
+          if (!query_cell_key(cell, c, &key)) continue;
+          const auto it = index.find(key);
+          if (it == index.end()) continue;
+          const int32_t j = static_cast<int32_t>(it->second);
+          const double d2 = query_d2(q, rows_.data() + 3 * it->second);
+          if (query_before(d2, j, best_d2, best)) {
+            best_d2 = d2;
+            best = j;
+          }
+        }
+        if (best >= 0) {
+          ++matched;
+          if (best_d2 <= md2) ++within;
+        }
+      }
+      out_counts[3 * k] = candidates;
+      out_counts[3 * k + 1] = matched;
+      out_counts[3 * k + 2] = within;
+    }
+    return kMapOk;
+  }
+
   // include/madicp_host.h: madicp_host_map_register — `iterations` rounds of point-to-plane Gauss-Newton against the surfels
   // (../common/map_align.h has the rule: align_inlier, align_terms, align_tree), the map only read.  The surfels are map_surfel of
   // every row, once per call; the row of a point is query()'s; the step is ldlt6_solve and exp_so3 of linalg.h.  out_trace:

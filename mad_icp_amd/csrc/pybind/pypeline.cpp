@@ -68,6 +68,27 @@ static py::tuple map_register_py(Pipeline& self, const py::array_t<double, py::a
   return py::make_tuple(out_pose, info);
 }
 
+// K poses given as (K, 4, 4) or (K, 12) -> the (K, 12) rows Pipeline::mapScorePoses takes: R row-major, then t
+static std::vector<double> pose_rows_py(const py::array_t<double, py::array::c_style | py::array::forcecast>& poses) {
+  const bool square = poses.ndim() == 3 && poses.shape(1) == 4 && poses.shape(2) == 4;
+  if (!square && !(poses.ndim() == 2 && poses.shape(1) == 12)) throw py::value_error("poses must be (K, 4, 4) or (K, 12)");
+  const size_t K = static_cast<size_t>(poses.shape(0));
+  std::vector<double> rows(12 * std::max<size_t>(K, 1));
+  const double* T = poses.data();
+  for (size_t k = 0; k < K; ++k) {
+    double* X = rows.data() + 12 * k;
+    if (!square) {
+      std::copy(T + 12 * k, T + 12 * k + 12, X);
+      continue;
+    }
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) X[3 * r + c] = T[16 * k + 4 * r + c];
+      X[9 + r] = T[16 * k + 4 * r + 3];
+    }
+  }
+  return rows;
+}
+
 PYBIND11_MODULE(pypeline, m) {
   m.doc() = "mad_icp_amd: MAD-ICP odometry pipeline with the registration on MI355X, drop-in for mad_icp.src.pybind.pypeline";
   // the reference registers the same container in pyvector and pypeline; module_local lets both be imported
@@ -425,6 +446,82 @@ PYBIND11_MODULE(pypeline, m) {
          },
          py::arg("cloud"), py::arg("pose"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance,
          py::arg("rho") = madicp_host::kQueryNoDistance, py::arg("min_count") = 3, py::arg("flat") = 1.0, py::arg("with_rows") = false)
+    // additive: many hypotheses (Pipeline::mapScorePoses / mapRelocalize).  mapScorePoses(cloud (n, 3), poses (K, 4, 4) or (K, 12),
+    // reach=1, max_dist=inf, stride=1) returns (K, 3) uint64: mapOverlap's three counts of cloud[::stride] at every pose, one call
+    // and one host synchronisation.  mapRelocalize(cloud, poses, refine=4, iterations=10, stride=8, reach=1, max_dist=inf, rho=inf,
+    // min_count=3, flat=1.0) scores all K poses (stride), ranks them by (within descending, index ascending) and registers the first
+    // min(refine, K) with every point, as mapRegister does; it returns a dict, one entry per refined hypothesis in rank order: index
+    // (m,) int32, scores (m, 3) uint64, poses (m, 4, 4), H (m, 6, 6), b (m, 6), chi2 (m,), counts (m, 4) of the closing
+    // linearisation, and best: the entry with the most closing inliers (a tie to the better rank).  reach and max_dist serve both the
+    // scoring and the registration.  ValueError for what the calls refuse and for refine outside 1 .. 64; RuntimeError
+    // (std::logic_error) while accumulation is off and, for mapRelocalize, without moments.
+    .def("mapScorePoses",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> poses, int reach, double max_dist, int64_t stride) {
+           if (cloud.ndim() != 2 || cloud.shape(1) != 3) throw py::value_error("cloud must be (n, 3)");
+           const std::vector<double> rows = pose_rows_py(poses);
+           const py::ssize_t K = poses.shape(0);
+           py::array_t<uint64_t> counts({K, static_cast<py::ssize_t>(3)});
+           std::vector<uint64_t> got(3 * std::max<size_t>(static_cast<size_t>(K), 1));
+           self.mapScorePoses(cloud.data(), static_cast<size_t>(cloud.shape(0)), rows.data(), static_cast<size_t>(K), reach, max_dist, stride,
+                              got.data());
+           std::copy(got.begin(), got.begin() + 3 * K, counts.mutable_data());
+           return counts;
+         },
+         py::arg("cloud"), py::arg("poses"), py::arg("reach") = 1, py::arg("max_dist") = madicp_host::kQueryNoDistance, py::arg("stride") = 1)
+    .def("mapRelocalize",
+         [](Pipeline& self, py::array_t<double, py::array::c_style | py::array::forcecast> cloud,
+            py::array_t<double, py::array::c_style | py::array::forcecast> poses, int refine, int iterations, int64_t stride, int reach,
+            double max_dist, double rho, uint32_t min_count, double flat) {
+           if (cloud.ndim() != 2 || cloud.shape(1) != 3) throw py::value_error("cloud must be (n, 3)");
+           if (refine < 1 || refine > Pipeline::kRelocalizeMaxRefine) throw py::value_error("refine must be 1 .. 64");
+           const std::vector<double> rows = pose_rows_py(poses);
+           const size_t K = static_cast<size_t>(poses.shape(0)), cap = static_cast<size_t>(refine);
+           std::vector<int32_t> index(cap);
+           std::vector<uint64_t> scores(3 * cap), counts(madicp_host::kAlignCounts * cap);
+           std::vector<double> X(12 * cap), sums(madicp_host::kAlignTerms * cap);
+           size_t best = 0;
+           const py::ssize_t m = static_cast<py::ssize_t>(
+               self.mapRelocalize(cloud.data(), static_cast<size_t>(cloud.shape(0)), rows.data(), K, reach, max_dist, stride, refine,
+                                  madicp_host::AlignParams{reach, max_dist, rho, min_count, flat}, iterations, index.data(), scores.data(),
+                                  X.data(), sums.data(), counts.data(), &best));
+           py::array_t<int32_t> o_index(m);
+           py::array_t<uint64_t> o_scores({m, static_cast<py::ssize_t>(3)}), o_counts({m, static_cast<py::ssize_t>(madicp_host::kAlignCounts)});
+           py::array_t<double> o_poses({m, static_cast<py::ssize_t>(4), static_cast<py::ssize_t>(4)}),
+               H({m, static_cast<py::ssize_t>(6), static_cast<py::ssize_t>(6)}), b({m, static_cast<py::ssize_t>(6)}), chi2(m);
+           std::copy(index.begin(), index.begin() + m, o_index.mutable_data());
+           std::copy(scores.begin(), scores.begin() + 3 * m, o_scores.mutable_data());
+           std::copy(counts.begin(), counts.begin() + madicp_host::kAlignCounts * m, o_counts.mutable_data());
+           for (py::ssize_t r = 0; r < m; ++r) {
+             double* P = o_poses.mutable_data() + 16 * r;
+             for (int i = 0; i < 3; ++i) {
+               for (int c = 0; c < 3; ++c) P[4 * i + c] = X[12 * r + 3 * i + c];
+               P[4 * i + 3] = X[12 * r + 9 + i];
+             }
+             P[12] = P[13] = P[14] = 0.0;
+             P[15] = 1.0;
+             const double* q = sums.data() + madicp_host::kAlignTerms * r;
+             double* Hr = H.mutable_data() + 36 * r;
+             int v = 0;
+             for (int c = 0; c < 6; ++c)
+               for (int i = c; i < 6; ++i) Hr[6 * i + c] = Hr[6 * c + i] = q[v++];
+             std::copy(q + 21, q + 27, b.mutable_data() + 6 * r);
+             chi2.mutable_data()[r] = q[27];
+           }
+           py::dict out;
+           out["index"] = o_index;
+           out["scores"] = o_scores;
+           out["poses"] = o_poses;
+           out["H"] = H;
+           out["b"] = b;
+           out["chi2"] = chi2;
+           out["counts"] = o_counts;
+           out["best"] = py::int_(best);
+           return out;
+         },
+         py::arg("cloud"), py::arg("poses"), py::arg("refine") = 4, py::arg("iterations") = 10, py::arg("stride") = 8, py::arg("reach") = 1,
+         py::arg("max_dist") = madicp_host::kQueryNoDistance, py::arg("rho") = madicp_host::kQueryNoDistance, py::arg("min_count") = 3,
+         py::arg("flat") = 1.0)
     // setMapAlignment(on, iterations=5, reach=1, max_dist=inf, rho=inf, min_count=3, flat=1.0) makes every fold register the frame
     // against the map first and only REPORT it; mapFrameAlignment() returns None for a frame without one, else (pose (4, 4), info) with
     // H, b, chi2, counts at that pose and chi2_start, counts_start at the frame's own.
