@@ -169,7 +169,11 @@ int madicp_nn_search_device_enqueue(madicp_ctx* ctx, int tree_id, const double* 
 /* ---- moving side -------------------------------------------------------------------------------- */
 /* MADicp::setMoving (mad_icp.cpp:53-55): the sensor-frame means of the current scan's leaves, (L,3). */
 int madicp_moving_upload(madicp_ctx* ctx, const double* leaf_means, int32_t L, int* out_moving_id);
-/* The next scan into the SAME buffers (grow-only: no allocation, free or synchronisation in steady state). */
+/* The next scan into the SAME buffers (grow-only: no allocation, free or synchronisation in steady state).  A set's buffers
+ * hold (L + L / 8) leaves rounded up to a multiple of 256: a scan more than one eighth larger than the largest before it
+ * re-allocates them (and the correspondence cache with them), a smaller one uses their head.  Either way a registration's
+ * outputs — X, H, b, matched flags, X_iters, visits, counts — are a function of its arguments and the resident trees alone,
+ * bit for bit, whatever the set, the stream slot or the context held before (tests/test_gpu_registration_history.py). */
 int madicp_moving_update(madicp_ctx* ctx, int moving_id, const double* leaf_means, int32_t L);
 /* The same on the library's COPY stream: the transfer runs beside the batch the compute stream is working on — one that reads
  * OTHER moving sets — instead of behind it.  Ordered by the library: the transfer waits for the last registration that read
@@ -231,7 +235,10 @@ int madicp_icp_publish_collect(madicp_ctx* ctx, int ticket, int n_scans, double*
  * flight), the results are written by the registration's last kernel straight into pinned host memory, a sequence
  * number last, and madicp_stream_collect polls that number (spinning on the calling thread until the registration has
  * finished; an event instead with option "seq_completion" = 0).  Up to 4 tickets may be outstanding; collect them in any order before
- * their slot is needed again (MADICP_ERR_CAPACITY otherwise).  Bit-identical to madicp_icp_register on the same inputs. */
+ * their slot is needed again (MADICP_ERR_CAPACITY otherwise).  Bit-identical to madicp_icp_register on the same inputs.
+ * A submission sizes its own slot AND every idle slot of the ring for its L and K (the capacity rule of
+ * madicp_moving_update): the first submission sizes the whole ring, a later one re-allocates only where a scan outgrew a
+ * slot — a slot with a ticket pending is left alone and is sized by the next submission that finds it idle. */
 int madicp_stream_submit(madicp_ctx* ctx, const double* leaf_means, int32_t L, const int* tree_ids, int K,
                          const double X0[12], const madicp_icp_params* params, int n_iters, int* out_ticket);
 /* The same with the moving set taken from a tree that is already resident: the scan's own MAD-tree, uploaded for the
