@@ -585,7 +585,11 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                                 (3 floats), and n as uint32 — computed on the device (fe::map_surfels, one lane per
  *                                 row, fp64) into a transient block: one kernel, one copy chain, ONE host synchronisation.  The same
  *                                 refusals.  Centroid and count are bit-equal to the host twin's; eigenvalues and normals go
- *                                 through atan2 / cos / sin and agree to the last bits only.
+ *                                 through atan2 / cos / sin and agree to the last bits only.  THE ZERO RULE: an eigenvalue that
+ *                                 is not above 2^-24 of the largest plus 4 x 2^-52 max(S2_aa / n) — what the solve can tell
+ *                                 from zero, measured (csrc/common/voxel_moments.h) — is delivered as +0.0: never negative, and
+ *                                 identical or collinear points have eig1 == 0 whatever their rounding noise, which is what
+ *                                 madicp_map_register_cloud's `eig1 > 0` refuses; an exact plane has eig0 == 0 < eig1.
  * QUERY.  Everything above writes the map or downloads it; madicp_map_query_cloud ASKS it, where it lives, what it holds at the
  * points of a resident cloud: per point the nearest row of its voxel neighbourhood.  The rule (one source with the host twin:
  * csrc/common/export_point.h — export_cells, query_cell_key, query_d2, query_before), fp64 and integers only, no library function,

@@ -157,6 +157,9 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  the twins of madicp_map_create_mom and its neighbours (madicp_hip.h and csrc/common/voxel_moments.h have the
  *                  rule): ten 64-bit moment words per row, max_count, the same refusals and codes.  Words, centroid and count are
  *                  bit-equal to the device's; eigenvalues and normals agree to the last bits (libm against the device library).
+ *                  The zero rule is the device's, one source: an eigenvalue not above 2^-24 of the largest plus
+ *                  4 x 2^-52 max(S2_aa / n) is delivered as +0.0, so a voxel of identical or collinear points has eig1 == 0 and
+ *                  _register's `eig1 > 0` refuses it.
  *   _query         the twin of madicp_map_query_cloud (madicp_hip.h has the rule): for each of the n points of xyz taken through
  *                  (R, t), the row with the smallest (d2, row) among the rows whose stored key is a cell of the point's
  *                  neighbourhood (reach 0: its own cell, 1: the 27 around it); out_row / out_d2 / out_keys / out_attr / out_ev

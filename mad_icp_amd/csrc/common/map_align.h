@@ -10,7 +10,9 @@
 //   2  its row j is the QUERY's answer at `reach` (export_point.h: the smallest (d2, j) from the stored float row) — the same rule,
 //      not a second one; matched iff j >= 0, within iff also d2 <= max_dist * max_dist
 //   3  an inlier iff within, count[j] >= min_count, (double)eig[j][1] > 0 and (double)eig[j][0] <= flat * (double)eig[j][1]
-//      (align_inlier)
+//      (align_inlier).  eig1 > 0 is a statement about the geometry, not about rounding: map_surfel's ZERO RULE (voxel_moments.h)
+//      delivers +0.0 for an eigenvalue the solve cannot tell from zero, so identical or collinear points — no plane — are refused,
+//      and an exact plane (eig0 == +0.0 < eig1) passes at every flat
 //   4  with c, n the float32 centroid and normal of row j taken to double (align_terms):
 //        e    = sum3s(n0 (q0 - c0), n1 (q1 - c1), n2 (q2 - c2))
 //        m[k] = sum3s(n0 R[k], n1 R[3 + k], n2 R[6 + k])                  n^T R

@@ -4,6 +4,8 @@ or integers, elementwise (numpy does not fuse).  The surfel columns — centroid
 an INPUT: the side under test hands over its own, so the last bits of its eigen-solve are no part of the comparison.
   row, d2    map_query_ref.query: the same rule as the query, not a second one
   inlier     row >= 0, d2 <= max_dist^2, count >= min_count, eig1 > 0, eig0 <= flat * eig1
+             (eig1 > 0 stands on map_surfel's ZERO RULE, restated as `zero_at`: an eigenvalue w of the covariance, in offset units
+             squared, is delivered as +0.0 unless w > 2^-24 w2 + 4 * 2^-52 max(S2_aa / n) — so a line or a point has eig1 == 0)
   e, J       e = n0 (q0 - c0) + (n1 (q1 - c1) + n2 (q2 - c2)); m = n^T R; J = [m, p x m]
   terms      s = |e| > rho ? rho / |e| : 1; H(r, c) = (s J[r]) J[c], r >= c, packed column by column | b[r] = (s J[r]) e | (s e) e
   the sum    `tree`: pad with +0.0 to the next power of two, then x = x[0::2] + x[1::2] until one vector is left — by reshapes
@@ -23,6 +25,15 @@ DEFAULT = dict(reach=1, max_dist=np.inf, rho=np.inf, min_count=3, flat=1.0)     
 GATED = dict(reach=1, max_dist=0.45, rho=0.03, min_count=40, flat=0.3)                 # every gate and the kernel at work
 SEED = 23  # the committed seed: along the five GATED rounds at n = 4 097 gate_margins stays above 1e-3 (3.9e-3 for d2, 0.42 for the
 #            eigenvalues; of the seeds 20 .. 39 tried, 20 and 22 did not) — tests/test_host_map_align.py asserts it
+
+
+ZERO_SHARE, ZERO_FLOOR = 2.0 ** -24, 4.0  # voxel_moments.h: kSurfelZeroShare, kSurfelZeroFloor
+
+
+def zero_at(mom, w2):
+    """the zero rule's threshold per row, in offset units squared: mom (M, 10) the ten words, w2 (M,) the largest eigenvalue"""
+    m = np.asarray(mom).astype(np.float64)
+    return ZERO_SHARE * np.asarray(w2, np.float64) + ZERO_FLOOR * 2.0 ** -52 * (m[:, [4, 7, 9]] / m[:, 0:1]).max(axis=1)
 
 
 def tree(x):

@@ -63,6 +63,8 @@ def numpy_surfels(mom, keys, voxel):
     for j, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
         C[:, a, b] = C[:, b, a] = m[:, 4 + j] / n[:, 0] - mean[:, a] * mean[:, b]
     w, V = np.linalg.eigh(C)
+    zero_at = 2.0 ** -24 * w[:, 2] + 4.0 * 2.0 ** -52 * (m[:, [4, 7, 9]] / n).max(axis=1)  # the zero rule
+    w = np.where(w > zero_at[:, None], w, 0.0)
     s = voxel / 65536.0
     normal = np.where(n >= 3, V[:, :, 0], 0.0).astype(np.float32)
     return centroid, normal, (w * (s * s)).astype(np.float32), mom[:, 0].astype(np.uint32)
