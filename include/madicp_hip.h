@@ -637,6 +637,29 @@ int madicp_cloud_export_f32_attr(madicp_ctx* ctx, int cloud_id, const double R[9
  *                            slot-to-row array): the builder's is not touched.  Everything runs on the copy stream — one memset,
  *                            the pose upload, the kernels, one copy out — and ends in ONE host synchronisation, whatever n, M and
  *                            n_poses (profiles/map_score_time.md).
+ * MERGING SAVED ROWS.  Every column of a map can be downloaded; madicp_map_merge_rows puts a batch of such rows back — a map
+ * restored after a restart (a merge into an empty map), a prior map loaded, two maps of one frame and voxel size joined.  The rule
+ * (one source with the host twin: csrc/common/map_merge.h — map_merge_refusal, merge_evidence, and voxel_moments.h's freeze):
+ *   a batch is n entries (keys[i], xyz[3 i .. 3 i + 2] float32, attr[i], ev[i], mom[10 i .. 10 i + 9]); attr, ev and mom are given
+ *   exactly when the map has that column and null otherwise.  A merge is ONE fold: on a moments map it takes the next fold ordinal.
+ *   Rows: the keys the map does not hold become one new row each, in ascending order of the LOWEST index that carries the key; xyz
+ *   and attr are that entry's, copied bit for bit (NaN payloads, -0.0), the stored key is the entry's; nothing checks that xyz lies
+ *   in the key's voxel.  Rows the map holds keep xyz, attr and position.  Evidence: with s the sum of ev over a key's entries, a
+ *   new row gets min(s, cap), a row that held e gets min(e + s, cap); the per-slot hit stamps of the folds are not touched.  Moments:
+ *   a row takes ALL entries of its key iff its n before the merge is < max_count (a new row: 0), else none; the ten words add; the
+ *   add that reaches max_count freezes the row with the merge's ordinal.  Integer sums and a lowest index: a function of (map,
+ *   batch) alone, bit-equal between device, host twin and a numpy restatement, whatever the launch geometry.
+ *   madicp_map_merge_rows    *out_added rows were appended, the map holds *out_rows.  MADICP_ERR_INVALID, the map untouched, nothing
+ *                            written and nothing launched, for a null ctx, out_added or out_rows, an unknown id, n < 0 or > 2^30, a
+ *                            voxel that is not == the map's, a column given that the map lacks or (n > 0) lacking that it has, a
+ *                            key with bit 63 set, an ev outside 1 .. 2^31 - 1, a mom count < 1, an S1 word > 65535 count or an S2
+ *                            word > 65535^2 count, counts that sum past 2^31 - 1.  MADICP_ERR_CAPACITY, the same, when rows + n >
+ *                            max_rows (the fold's conservative rule), on a moments map past its last fold ordinal, and while a
+ *                            look-ahead build is in flight (the builder's scratch).  n == 0 is legal and does nothing.  The batch
+ *                            goes up in one staged copy into a transient pooled block; kernels fe::rows_claim, fe::voxel_mark, the
+ *                            tile scan, fe::rows_append and, on evidence and moments maps, fe::rows_combine (a 32-bit
+ *                            compare-and-swap loop and ten 64-bit integer atomic adds per entry — no float atomics); everything
+ *                            on the copy stream, ONE host synchronisation, for the count (one more where the map grows).
  * REGISTER.  madicp_map_register_cloud gives the pose that FITS a resident cloud to a moments map: `iterations` rounds of
  * point-to-plane Gauss-Newton against the map's surfels, all on the device.  The rule (one source with the host twin:
  * csrc/common/map_align.h), fp64 and integers only, no contraction, no library function in the linearisation:
@@ -717,6 +740,8 @@ int madicp_map_register_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const d
                               int64_t capacity_points);
 int madicp_map_score_poses(madicp_ctx* ctx, int map_id, int cloud_id, const double* poses, int64_t n_poses, int reach, double max_dist,
                            int64_t stride, uint64_t* out_counts /* n_poses x 3 */);
+int madicp_map_merge_rows(madicp_ctx* ctx, int map_id, double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr,
+                          const uint32_t* ev, const uint64_t* mom, int64_t n, int64_t* out_added, int64_t* out_rows);
 int madicp_map_clear(madicp_ctx* ctx, int map_id);
 int madicp_map_release(madicp_ctx* ctx, int map_id);
 /* MADtree::build + getLeafs + the upload, all on the device (mad_tree.cpp:47-142,154-163): the tree of the cloud becomes

@@ -176,7 +176,14 @@ int madicp_host_cloud_export_f32_attr(const double* xyz, const uint32_t* attr, i
  *                  LDLT solve and exponential.  Trace, counts, out_row / out_e (iterations == 0 only) as on the device, the same
  *                  refusals and codes, nothing written.  n == 0 is legal here (xyz may then be null): zero sums, the pose as
  *                  given.  Fed the same surfel bits the sums are bit-equal to the device's; the surfels' normals and eigenvalues
- *                  agree to the last bits only, and so do poses: within the pose contract, not to the bit. */
+ *                  agree to the last bits only, and so do poses: within the pose contract, not to the bit.
+ *   _merge_rows    the twin of madicp_map_merge_rows (madicp_hip.h and csrc/common/map_merge.h have the rule): n saved entries —
+ *                  keys (n), xyz (n, 3) float32, and attr (n) / ev (n) / mom (n, 10) exactly where the map has that column, null
+ *                  otherwise — merged in as ONE fold: a key the map lacks becomes a row (the lowest index that carries it, bits
+ *                  copied), evidence adds and saturates, moments add under the freeze rule.  *out_added rows were appended, the
+ *                  map holds *out_rows.  The same refusals and codes from the same one pass (map_merge_refusal), the map
+ *                  unchanged and nothing written; n == 0 is legal (the columns may then be null) and does nothing.  Every column
+ *                  bit-equal to the device's. */
 #ifndef MADICP_MAP_ALIGN_PARAMS_DEFINED
 #define MADICP_MAP_ALIGN_PARAMS_DEFINED
 typedef struct {
@@ -227,6 +234,8 @@ int madicp_host_map_score(const madicp_host_map* map, const double* xyz, int64_t
 int madicp_host_map_register(const madicp_host_map* map, const double* xyz, int64_t n, const double R[9], const double t[3],
                              const madicp_map_align_params* params, int iterations, double out_R[9], double out_t[3],
                              double* out_trace, uint64_t* out_counts, int32_t* out_row, double* out_e, int64_t capacity_points);
+int madicp_host_map_merge_rows(madicp_host_map* map, double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr,
+                               const uint32_t* ev, const uint64_t* mom, int64_t n, int64_t* out_added, int64_t* out_rows);
 int madicp_host_map_clear(madicp_host_map* map);
 void madicp_host_map_destroy(madicp_host_map* map);
 

@@ -82,6 +82,7 @@ MAP_ENTRY_POINTS = [
     ("query_cloud", "query", [_SCAN, _dp, _dp, C.c_int, C.c_double, _i32p, _dp, _u64p, _u32p, _u32p, C.c_int64, _u64p]),
     ("register_cloud", "register", [_SCAN, _dp, _dp, C.POINTER(MapAlignParams), C.c_int, _dp, _dp, _dp, _u64p, _i32p, _dp, C.c_int64]),
     ("score_poses", "score", [_SCAN, _dp, C.c_int64, C.c_int, C.c_double, C.c_int64, _u64p]),
+    ("merge_rows", "merge_rows", [C.c_double, _u64p, _fp, _u32p, _u32p, _u64p, C.c_int64, _i64p, _i64p]),
     ("track_removed", "track_removed", [C.c_int]),
     ("removed_count", "removed_count", [_i64p]),
     ("take_removed", "take_removed", [_u64p, _fp, _u32p] + _WINDOW),
@@ -733,6 +734,20 @@ class _Map:
         self._call("score", *self._scan(scan)[0], _ptr(P), P.shape[0], int(reach), float(max_dist), int(stride), _ptr(counts))
         return counts[:P.shape[0]]
 
+    def merge_rows(self, voxel, keys, rows, words=None, ev=None, mom=None):
+        """a batch of saved rows in: keys (n,) uint64, rows (n, 3) float32 and the columns the map has (None: not given) — what
+        download_rows / download_evidence / download_moments hand out; bits are passed on as they are (no conversion of values)"""
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        n = k.shape[0]
+        x = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 3)
+        w, e = (None if a is None else _u32(a) for a in (words, ev))
+        M = None if mom is None else np.ascontiguousarray(mom, dtype=np.uint64).reshape(-1, 10)
+        if any(a is not None and a.shape[0] != n for a in (x, w, e, M)):
+            raise ValueError("one entry of every column per key")
+        added, total = C.c_int64(0), C.c_int64(0)
+        self._call("merge_rows", float(voxel), _ptr(k), _ptr(x), _ptr(w), _ptr(e), _ptr(M), n, C.byref(added), C.byref(total))
+        return added.value, total.value
+
     def track_removed(self, on=True):
         self._call("track_removed", 1 if on else 0)
 
@@ -846,6 +861,7 @@ def host_map_query(h, xyz, R, t, reach=1, max_dist=float("inf"), per_point=True,
 def host_map_register(h, xyz, R, t, iterations, reach=1, max_dist=float("inf"), rho=float("inf"), min_count=3, flat=1.0, per_point=False):
     return HostMap(h).register(xyz, R, t, iterations, reach, max_dist, rho, min_count, flat, per_point)
 def host_map_score(h, xyz, poses, reach=1, max_dist=float("inf"), stride=1): return HostMap(h).score(xyz, poses, reach, max_dist, stride)
+def host_map_merge_rows(h, voxel, keys, rows, words=None, ev=None, mom=None): return HostMap(h).merge_rows(voxel, keys, rows, words, ev, mom)
 def host_map_track_removed(h, on=True): HostMap(h).track_removed(on)
 def host_map_removed_count(h): return HostMap(h).removed_count()
 def host_map_take_removed(h, with_attr=False): return HostMap(h).take_removed(with_attr)
@@ -1170,6 +1186,14 @@ class Context:
         one upload of the poses, one launch sequence, ONE host synchronisation whatever n, M and K.  Returns (K, 3) uint64, row k
         what map_query(mid, the subsampled cloud, R_k, t_k, reach, max_dist, per_point=False) returns.  The map is only read."""
         return DeviceMap(self, mid).score_poses(cid, poses, reach, max_dist, stride)
+
+    def map_merge_rows(self, mid, voxel, keys, rows, words=None, ev=None, mom=None):
+        """madicp_map_merge_rows: a batch of saved rows merged into the map as ONE fold — keys (n,) uint64, rows (n, 3) float32, and
+        words (n,) uint32 / ev (n,) uint32 / mom (n, 10) uint64 exactly where the map has that column (what map_download_rows,
+        map_download_evidence and map_download_moments return); voxel must equal the map's.  A key the map lacks becomes a row (the
+        lowest index that carries it, bits copied), evidence adds and saturates at cap, moments add under the freeze rule.
+        Restoring a saved map is merging into an empty one.  Returns (rows added, rows the map holds).  One host synchronisation."""
+        return DeviceMap(self, mid).merge_rows(voxel, keys, rows, words, ev, mom)
 
     def map_clear(self, mid):
         DeviceMap(self, mid).clear()

@@ -24,6 +24,7 @@
 #include "../common/export_point.h"
 #include "../common/voxel_moments.h"
 #include "../common/map_align.h"
+#include "../common/map_merge.h"
 
 #pragma clang fp contract(off)
 
@@ -685,6 +686,100 @@ __global__ __launch_bounds__(256) void map_surfels(const unsigned long long* __r
       eig[3 * j + k] = e[k];
     }
     count[j] = cnt;
+  }
+}
+
+// ---- merging saved rows: a batch of downloaded rows folded back into a map (madicp_map_merge_rows) --------------------------------
+// The rule is csrc/common/map_merge.h's, shared with the host twin.  The batch lies in a transient device block of the call's own
+// (MergeRows: null where the map has no such column); the table, the owner words and the per-fold scratch are the fold's, and so is
+// the shape — claim, mark, tile scan, append — with the batch's keys in place of the keys of positions:
+//   rows_claim    one lane per entry: the entry's key found or claimed (map_find_or_claim), atomicMin(owner, i + 1) unless settled, with
+//                 voxel_claim's two relaxed loads in front of the atomics; slot_of[i] is always a slot (a key has no bit 63: every entry
+//                 is a candidate)
+//   voxel_mark / tile scan   unchanged: mark[i] = the lowest index of a key the map did not hold, S[i] = marks before i
+//   rows_append   marked entries: key, the three floats and the attribute word COPIED as 32-bit words (NaN payloads and -0.0 are bits)
+//                 to row first_row + S[i]; the evidence word starts at 0, the ten moment words at 0 and closed_at at "never" — what
+//                 rows_combine adds to; slot_row learns the row and the owner settles (one marked entry per slot)
+//   rows_combine  evidence and moments maps only, behind rows_append (every slot settled, slot_row complete), one lane per entry:
+//                 r = slot_row[slot_of[i]].  Evidence: a 32-bit compare-and-swap loop new = merge_evidence(old, e_i, cap).  Moments:
+//                 where moment_row_takes(closed_at[r], ordinal), ten 64-bit integer atomicAdds; the add on n is the one that RETURNS
+//                 and the single entry that sees old < max_count <= old + n_i stores the merge's ordinal into closed_at[r] — exactly
+//                 map_moments' mechanism, an entry's n_i in place of a run's count.
+// Determinism: rows are decided as in the fold — two integer atomics whose results commute, read behind a kernel boundary.  The
+// evidence word is a saturating sum: min(min(e + a, cap) + b, cap) == min(e + a + b, cap), so the order in which the swaps succeed
+// changes no bit; a loop that reads cap leaves at once (the word only rises within the kernel, so a stale value costs one swap).
+// The moment words are integer sums, and within a merge closed_at[r] only goes from "never" to this merge's ordinal, a lane proceeds
+// on either: what a racing load returns decides nothing.  A function of (map, batch) alone, whatever the launch geometry.  No float
+// atomics.  Contention: a saved map has ONE entry per key — ten uncontended atomics per entry; all entries on ONE key serialise on
+// one evidence word and ten moment words, one atomic per entry and word: correct, not tuned for.
+struct MergeRows {  // by value: the batch's columns on the device
+  const unsigned long long* keys;
+  const uint32_t* xyz;  // (n, 3) the floats' bits
+  const uint32_t* attr;
+  const uint32_t* ev;
+  const unsigned long long* mom;  // (n, 10)
+};
+__global__ __launch_bounds__(256) void rows_claim(const unsigned long long* __restrict__ batch_keys, long n,
+                                                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ owner, uint32_t slots,
+                                                  uint32_t* __restrict__ slot_of) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const uint32_t s = map_find_or_claim(keys, slots, batch_keys[i]);
+    // (kMapSettled is 0 and never above i + 1)
+    if (__hip_atomic_load(&owner[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)i + 1u) atomicMin(&owner[s], (uint32_t)i + 1u);
+    slot_of[i] = s;
+  }
+}
+// Null arguments (kernel arguments: the branches are wave-uniform) are the columns the map lacks: B.attr / row_attr, row_ev with
+// slot_row, row_mom with row_closed.
+__global__ __launch_bounds__(256) void rows_append(MergeRows B, long n, const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
+                                                   const uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner, long first_row,
+                                                   uint32_t* __restrict__ rows, unsigned long long* __restrict__ row_keys,
+                                                   uint32_t* __restrict__ row_attr, uint32_t* __restrict__ row_ev,
+                                                   uint32_t* __restrict__ slot_row, unsigned long long* __restrict__ row_mom,
+                                                   uint32_t* __restrict__ row_closed) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    if (!mark[i]) continue;
+    const long d = first_row + (long)pos[i];
+    rows[3 * d] = B.xyz[3 * i];
+    rows[3 * d + 1] = B.xyz[3 * i + 1];
+    rows[3 * d + 2] = B.xyz[3 * i + 2];
+    row_keys[d] = B.keys[i];
+    if (row_attr) row_attr[d] = B.attr[i];
+    if (row_ev) row_ev[d] = 0u;  // (rows_combine adds the entries' words, this one's among them)
+    if (slot_row) slot_row[slot_of[i]] = (uint32_t)d;
+    if (row_mom) {
+      for (int k = 0; k < madicp_host::kMomentWords; ++k) row_mom[madicp_host::kMomentWords * d + k] = 0ull;
+      row_closed[d] = madicp_host::kMomentsNeverClosed;
+    }
+    owner[slot_of[i]] = kMapSettled;  // (one marked entry per slot: nobody else writes it in this kernel)
+  }
+}
+__global__ __launch_bounds__(256) void rows_combine(MergeRows B, long n, const uint32_t* __restrict__ slot_of,
+                                                    const uint32_t* __restrict__ slot_row, uint32_t* __restrict__ ev, uint32_t cap,
+                                                    unsigned long long* __restrict__ mom, uint32_t* __restrict__ closed_at, uint32_t ordinal,
+                                                    uint32_t max_count) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const uint32_t r = slot_row[slot_of[i]];
+    if (ev) {
+      const uint32_t e_i = B.ev[i];
+      uint32_t old = __hip_atomic_load(&ev[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (;;) {
+        const uint32_t next = madicp_host::merge_evidence(old, e_i, cap);
+        if (next == old) break;  // (e_i >= 1: only at cap, and the word does not fall within this kernel)
+        const uint32_t seen = atomicCAS(&ev[r], old, next);
+        if (seen == old) break;
+        old = seen;
+      }
+    }
+    if (mom && madicp_host::moment_row_takes(__hip_atomic_load(&closed_at[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ordinal)) {
+      const unsigned long long* E = B.mom + (size_t)madicp_host::kMomentWords * i;
+      unsigned long long* M = mom + (size_t)madicp_host::kMomentWords * r;
+      const unsigned long long n_i = E[0];  // (1 .. 2^31 - 1: map_merge_refusal)
+      const unsigned long long old = atomicAdd(&M[0], n_i);
+      if (madicp_host::moment_closes(old, (uint32_t)n_i, max_count))
+        __hip_atomic_store(&closed_at[r], ordinal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int k = 1; k < madicp_host::kMomentWords; ++k) atomicAdd(&M[k], E[k]);
+    }
   }
 }
 

@@ -1434,6 +1434,97 @@ int madicp_map_insert_cloud(madicp_ctx* ctx, int map_id, int cloud_id, const dou
   return MADICP_OK;
 }
 
+// A batch of saved rows merged in as ONE fold (csrc/common/map_merge.h has the rule, frontend.hip.h the kernels and the determinism
+// argument).  Busy and scratch rules are the fold's: the per-fold scratch lies in the builder's (slot_of, marks, scan, total — as in
+// voxel_fold), growth keeps the table at most half full.  The batch itself goes through the pinned staging in ONE copy into a
+// transient pooled block of the call's own —
+//   keys (n x 8) | mom (n x 80) | xyz (n x 12) | attr (n x 4) | ev (n x 4)
+// of which only the columns the map has are there — and that block goes back behind the wait.  Claim, mark, scan, the count's copy,
+// append and (evidence and moments maps) combine are enqueued before the host knows the count: ONE synchronisation for the result —
+// in the sense of every staged upload: acquiring the staging slot waits for the copy that last used it, and a growth adds its own wait.
+int madicp_map_merge_rows(madicp_ctx* ctx, int map_id, double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr,
+                          const uint32_t* ev, const uint64_t* mom, int64_t n, int64_t* out_added, int64_t* out_rows) {
+  if (!ctx || !out_added || !out_rows) return fail(MADICP_ERR_INVALID, "null argument");
+  DevMap* m = find_map(ctx, map_id);
+  if (!m) return fail(MADICP_ERR_INVALID, "unknown map id");
+  RC_TRY(busy_with_lookahead(ctx));  // (in front of the O(n) pass, as the fold asks first)
+  bool capacity = false;
+  if (const char* why = madicp_host::map_merge_refusal(
+          madicp_host::MergeBatch{keys, xyz, attr, ev, mom, n}, voxel,
+          madicp_host::MergeTarget{m->voxel, m->with_attr, m->with_ev, m->with_mom, m->rows, m->max_rows, m->ordinal}, &capacity))
+    return fail(capacity ? MADICP_ERR_CAPACITY : MADICP_ERR_INVALID, why);
+  if (n == 0) {
+    *out_added = 0;
+    *out_rows = m->rows;
+    return MADICP_OK;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  FrontScratch* fs = nullptr;
+  RC_TRY(ensure_scratch(ctx, n, &fs));
+  const size_t N = (size_t)n;
+  size_t off = 0;
+  auto place = [&](bool wanted, size_t bytes) {
+    const size_t at = off;
+    if (wanted) off = align_up(off + bytes);
+    return at;
+  };
+  const size_t at_keys = place(true, 8 * N), at_mom = place(m->with_mom, 8 * madicp_host::kMomentWords * N), at_xyz = place(true, 12 * N);
+  const size_t at_attr = place(m->with_attr, 4 * N), at_ev = place(m->with_ev, 4 * N);
+  int hb = 0;
+  char* stage = nullptr;
+  RC_TRY(ctx->staging.acquire(off, &hb, &stage));
+  std::memcpy(stage + at_keys, keys, 8 * N);
+  if (m->with_mom) std::memcpy(stage + at_mom, mom, 8 * madicp_host::kMomentWords * N);
+  std::memcpy(stage + at_xyz, xyz, 12 * N);
+  if (m->with_attr) std::memcpy(stage + at_attr, attr, 4 * N);
+  if (m->with_ev) std::memcpy(stage + at_ev, ev, 4 * N);
+  void* p = nullptr;
+  RC_TRY(pool_alloc(ctx, off, ctx->copy, &p));
+  char* block = static_cast<char*>(p);
+  // growth last of what can fail in front of the launches: a call that cannot get its staging or its block has not touched the map's
+  if (m->rows + n > m->cap) {
+    const int rc = map_grow(ctx, m, m->rows + n);
+    if (rc != MADICP_OK) {
+      pool_free(ctx, block, nullptr);  // (nothing was enqueued on it)
+      return rc;
+    }
+  }
+  const fe::MergeRows B{reinterpret_cast<const unsigned long long*>(block + at_keys), reinterpret_cast<const uint32_t*>(block + at_xyz),
+                        m->with_attr ? reinterpret_cast<const uint32_t*>(block + at_attr) : nullptr,
+                        m->with_ev ? reinterpret_cast<const uint32_t*>(block + at_ev) : nullptr,
+                        m->with_mom ? reinterpret_cast<const unsigned long long*>(block + at_mom) : nullptr};
+  uint32_t* slot_of = fs->idx[0];
+  uint32_t* mark = fs->P.leaf_start;
+  const int blocks = grid_256(ctx, n);
+  hipError_t e = hipMemcpyAsync(block, stage, off, hipMemcpyHostToDevice, ctx->copy);
+  if (e == hipSuccess) e = ctx->staging.sent(hb, ctx->copy);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fe::rows_claim, dim3(blocks), dim3(256), 0, ctx->copy, B.keys, (long)n, m->keys(), m->owner(), m->slots, slot_of);
+    hipLaunchKernelGGL(fe::voxel_mark, dim3(blocks), dim3(256), 0, ctx->copy, (const uint32_t*)slot_of, (const uint32_t*)m->owner(), (long)n, mark);
+    e = scan_marks(ctx->copy, mark, n, fs->S, fs->tile_sums, &fs->rec_res->r.kept);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&fs->h_rec_res->r.kept, &fs->rec_res->r.kept, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->copy);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fe::rows_append, dim3(blocks), dim3(256), 0, ctx->copy, B, (long)n, (const uint32_t*)mark, (const uint32_t*)fs->S,
+                       (const uint32_t*)slot_of, m->owner(), (long)m->rows, reinterpret_cast<uint32_t*>(m->xyz()), m->row_keys(), m->attr(),
+                       m->ev(), m->slot_row(), m->mom(), m->closed_at());
+    if (m->with_ev || m->with_mom)
+      hipLaunchKernelGGL(fe::rows_combine, dim3(blocks), dim3(256), 0, ctx->copy, B, (long)n, (const uint32_t*)slot_of,
+                         (const uint32_t*)m->slot_row(), m->ev(), m->ev_cap, m->mom(), m->closed_at(), m->ordinal, m->mom_max_count);
+    e = hipGetLastError();
+  }
+  const hipError_t w = hipStreamSynchronize(ctx->copy);  // the count
+  if (e == hipSuccess) e = w;
+  pool_free(ctx, block, nullptr);  // (behind the wait: nothing is in flight on it)
+  if (e != hipSuccess) return fail(MADICP_ERR_DEVICE, std::string("voxel map merge: ") + hipGetErrorString(e));
+  const int64_t added = fs->h_rec_res->r.kept;
+  if (m->with_mom) ++m->ordinal;
+  m->rows += added;
+  *out_added = added;
+  *out_rows = m->rows;
+  return MADICP_OK;
+}
+
 int madicp_map_size(madicp_ctx* ctx, int map_id, int64_t* out_rows) {
   if (!ctx || !out_rows) return fail(MADICP_ERR_INVALID, "null argument");
   DevMap* m = find_map(ctx, map_id);

@@ -52,6 +52,11 @@ class DeviceMapStore final : public MapStore {
     return call("madicp_map_insert_cloud",
                 [&](madicp_ctx* ctx) { return madicp_map_insert_cloud(ctx, id_, b.scan().cloud_id, R, t, out_added, out_rows); });
   }
+  int merge(double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr, const uint32_t* ev, const uint64_t* mom, int64_t n,
+            int64_t* out_added, int64_t* out_rows) override {
+    return call("madicp_map_merge_rows",
+                [&](madicp_ctx* ctx) { return madicp_map_merge_rows(ctx, id_, voxel, keys, xyz, attr, ev, mom, n, out_added, out_rows); });
+  }
   int prune(const double* center, double radius, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) override {
     return call("madicp_map_prune",
                 [&](madicp_ctx* ctx) { return madicp_map_prune(ctx, id_, center, radius, watermark, out_removed, out_rows, out_watermark); });

@@ -86,6 +86,9 @@ class MapStore {
 
   virtual int size(int64_t* out_rows) = 0;
   virtual int insert(const ScanRef& scan, const double* R, const double* t, int64_t* out_added, int64_t* out_rows) = 0;
+  // madicp_map_merge_rows / VoxelMap::merge_rows: n saved entries, the columns null where the map has none
+  virtual int merge(double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr, const uint32_t* ev, const uint64_t* mom,
+                    int64_t n, int64_t* out_added, int64_t* out_rows) = 0;
   virtual int prune(const double* center, double radius, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) = 0;
   virtual int clearRays(const ScanRef& scan, const double* R, const double* t, const double* origin, double margin, int64_t watermark,
                         int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) = 0;
@@ -150,6 +153,10 @@ class HostMapStore final : public MapStore {
   int insert(const ScanRef& scan, const double* R, const double* t, int64_t* out_added, int64_t* out_rows) override {
     ScanBorrow b(*this, scan);
     return map_.insert(b.scan().xyz, b.scan().n, R, t, out_added, out_rows, b.scan().attr);
+  }
+  int merge(double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr, const uint32_t* ev, const uint64_t* mom, int64_t n,
+            int64_t* out_added, int64_t* out_rows) override {
+    return map_.merge_rows(voxel, keys, xyz, attr, ev, mom, n, out_added, out_rows);
   }
   int prune(const double* center, double radius, int64_t watermark, int64_t* out_removed, int64_t* out_rows, int64_t* out_watermark) override {
     return map_.prune(center, radius, watermark, out_removed, out_rows, out_watermark);

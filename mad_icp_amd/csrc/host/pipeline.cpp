@@ -562,6 +562,34 @@ size_t Pipeline::mapRelocalize(const double* xyz, size_t n, const double* poses,
   return m;
 }
 
+size_t Pipeline::mapMergeRows(const uint64_t* keys, const float* rows, const uint32_t* attribute, const uint32_t* evidence,
+                              const uint64_t* moments, size_t n, size_t* out_added) {
+  if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapMergeRows: setMapAccumulation(voxel_size > 0) first");
+  if (!out_added) throw std::invalid_argument("Pipeline::mapMergeRows: null argument");
+  if (n > static_cast<size_t>(kMapMaxRows)) throw std::invalid_argument("Pipeline::mapMergeRows: at most 2^30 entries");
+  // a fresh map goes where the front-end's scans will live; a device map's merge holds the device lock like a fold
+  const bool device = map_ ? map_->onDevice() : device_frontend_;
+  std::unique_lock<std::recursive_mutex> lock(Device::mutex(), std::defer_lock);
+  if (device) lock.lock();
+  std::unique_ptr<MapStore> fresh;  // (kept only if the merge succeeds: a refusal leaves everything as it was)
+  if (!map_) {
+    if (device)
+      fresh = make_device_map_store(map_spec_);
+    else
+      fresh = std::make_unique<HostMapStore>(map_spec_, fetch_resident_scan);
+    if (map_track_removed_ && fresh->trackRemoved(true) != MADICP_OK) throw std::runtime_error("Pipeline::mapMergeRows: " + fresh->lastError());
+  }
+  MapStore& map = fresh ? *fresh : *map_;
+  if (device) MADtree::cancelDeviceBuild(0);  // the merge needs the builder's scratch: a look-ahead of another Pipeline gives way
+  int64_t added = 0, size = 0;
+  const int rc = map.merge(map_spec_.voxel, keys, rows, attribute, evidence, moments, static_cast<int64_t>(n), &added, &size);
+  if (rc == MADICP_ERR_INVALID) throw std::invalid_argument("Pipeline::mapMergeRows: " + map.lastError());
+  if (rc != MADICP_OK) throw std::runtime_error("Pipeline::mapMergeRows: " + map.lastError());
+  if (fresh) map_ = std::move(fresh);
+  *out_added = static_cast<size_t>(added);
+  return static_cast<size_t>(size);
+}
+
 size_t Pipeline::mapNewRowCount() {
   if (map_spec_.voxel == 0.0) throw std::logic_error("Pipeline::mapNewRows: setMapAccumulation(voxel_size > 0) first");
   return mapSize() - map_cursor_;

@@ -317,6 +317,21 @@ class Pipeline {
   size_t mapRelocalize(const double* xyz, size_t n, const double* poses, size_t n_poses, int reach, double max_dist, int64_t stride, int refine,
                        const AlignParams& params, int iterations, int32_t* out_index, uint64_t* out_scores, double* out_poses,
                        double* out_sums, uint64_t* out_counts, size_t* out_best);
+  // additive: SAVED ROWS BACK IN.  mapMergeRows merges a batch of n saved rows into the map as ONE fold (include/madicp_hip.h:
+  // madicp_map_merge_rows and csrc/common/map_merge.h have the rule): keys (n), rows (n, 3) float32 and attribute (n) / evidence (n) /
+  // moments (n, 10) exactly where the map has that column, null otherwise — what mapKeys, mapCloud, mapAttribute, mapEvidence and
+  // mapMoments hand out, of this pipeline or of another with the same voxel size and columns.  A map restored after a restart is a
+  // merge before the first frame: where no map exists yet the call makes one — on the device iff deviceFrontEnd(), else the host
+  // twin — under foldFrame's lock and look-ahead cancellation, and the first fold then finds that map.  The merged rows are NEW rows
+  // to mapNewRows() (the cursor does not move), so a mirror fed across a merge still equals the map.  *out_added: the rows
+  // appended; returns the rows the map holds.  Nothing runs unless called: poses and map bits without a call are unchanged.
+  // std::logic_error while accumulation is off; std::invalid_argument for what madicp_map_merge_rows refuses as invalid;
+  // std::runtime_error for a capacity refusal (rows + n > max_points, the last fold ordinal) — the map, the cursor and the overflow
+  // flag are as they were, and a map the call would have made is not kept.
+  size_t mapMergeRows(const uint64_t* keys, const float* rows, const uint32_t* attribute, const uint32_t* evidence, const uint64_t* moments,
+                      size_t n, size_t* out_added);
+  const uint32_t* mapEvidenceParams() const { return map_spec_.ev; }  // hit, miss, cap ({1, 1, 1} without evidence)
+  uint32_t mapMomentsMaxCount() const { return map_spec_.mom; }        // 0: no moments
   // setMapAlignment(on, iterations, params) — default off: not a launch, not an allocation, the same pose and map bits — lets
   // foldFrame(), inside its one borrow of the frame's cloud and BEFORE the fold, register that cloud against the map as it stands,
   // from the frame's own pose (a drift check of the odometry against its own map).  The result is only REPORTED: mapFrameAlignment()

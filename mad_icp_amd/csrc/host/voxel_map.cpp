@@ -90,6 +90,12 @@ int madicp_host_map_insert_attr(madicp_host_map* map, const double* xyz, const u
   return map->map.insert(xyz, n, R, t, out_added, out_rows, attr);
 }
 
+int madicp_host_map_merge_rows(madicp_host_map* map, double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr,
+                               const uint32_t* ev, const uint64_t* mom, int64_t n, int64_t* out_added, int64_t* out_rows) {
+  if (!map) return MADICP_ERR_INVALID;
+  return map->map.merge_rows(voxel, keys, xyz, attr, ev, mom, n, out_added, out_rows);
+}
+
 int madicp_host_map_download_attr(const madicp_host_map* map, int64_t first_row, uint32_t* out_attr, int64_t capacity_rows, int64_t* out_n) {
   if (!map) return MADICP_ERR_INVALID;
   return map->map.download_attr(first_row, out_attr, capacity_rows, out_n);

@@ -24,6 +24,7 @@
 
 #include "../common/export_point.h"
 #include "../common/map_align.h"
+#include "../common/map_merge.h"
 #include "../common/voxel_moments.h"
 #include "linalg.h"  // ldlt6_solve, exp_so3: the host's update step (align)
 
@@ -89,6 +90,56 @@ class VoxelMap {
     if (with_ev_ && !met.empty())  // the rows that were there before the fold: once per fold
       for (int64_t j = 0; j < before; ++j)
         if (met.count(row_keys_[j])) ev_[j] = map_evidence_hit(ev_[j], hit_, cap_);
+    *out_added = size() - before;
+    *out_rows = size();
+    return kMapOk;
+  }
+
+  // include/madicp_host.h: madicp_host_map_merge_rows — a batch of saved rows merged in (../common/map_merge.h has the rule): one
+  // sequential pass, which IS "the lowest index that carries a new key, in ascending order".  A map without moments has no key -> row
+  // index; an evidence map then makes a transient one of its own — over ALL its rows, O(rows) per call whatever n: fine for a
+  // restore and for a twin, not for many small batches — a plain map needs none (a key it holds changes nothing).
+  int merge_rows(double voxel, const uint64_t* keys, const float* xyz, const uint32_t* attr, const uint32_t* ev, const uint64_t* mom,
+                 int64_t n, int64_t* out_added, int64_t* out_rows) {
+    if (!out_added || !out_rows) return kMapInvalid;
+    bool capacity = false;
+    if (map_merge_refusal(MergeBatch{keys, xyz, attr, ev, mom, n}, voxel,
+                          MergeTarget{voxel_, with_attr_, with_ev_, with_mom_, size(), max_rows_, ordinal_}, &capacity))
+      return capacity ? kMapCapacity : kMapInvalid;
+    const int64_t before = size();
+    std::unordered_map<uint64_t, int64_t> own_index;
+    if (with_ev_ && !with_mom_ && n > 0) {
+      own_index.reserve(row_keys_.size() + static_cast<size_t>(n));
+      for (int64_t j = 0; j < before; ++j) own_index[row_keys_[j]] = j;
+    }
+    std::unordered_map<uint64_t, int64_t>* index = with_mom_ ? &row_of_ : with_ev_ ? &own_index : nullptr;
+    for (int64_t i = 0; i < n; ++i) {
+      const uint64_t key = keys[i];
+      int64_t r = -1;
+      if (keys_.insert(key).second) {
+        r = size();
+        rows_.resize(rows_.size() + 3);
+        std::memcpy(rows_.data() + 3 * r, xyz + 3 * i, 3 * sizeof(float));  // (bits, not values: a NaN keeps its payload)
+        row_keys_.push_back(key);
+        if (with_attr_) attr_.push_back(attr[i]);
+        if (with_ev_) ev_.push_back(0u);
+        if (with_mom_) {
+          mom_.insert(mom_.end(), kMomentWords, uint64_t(0));
+          closed_at_.push_back(kMomentsNeverClosed);
+        }
+        if (index) (*index)[key] = r;
+      } else if (index) {
+        r = index->find(key)->second;
+      }
+      if (with_ev_) ev_[r] = merge_evidence(ev_[r], ev[i], cap_);
+      if (with_mom_ && moment_row_takes(closed_at_[r], ordinal_)) {
+        const uint64_t* E = mom + kMomentWords * i;
+        uint64_t* M = mom_.data() + kMomentWords * r;
+        if (moment_closes(M[0], static_cast<uint32_t>(E[0]), max_count_)) closed_at_[r] = ordinal_;
+        for (int k = 0; k < kMomentWords; ++k) M[k] += E[k];
+      }
+    }
+    if (with_mom_ && n > 0) ++ordinal_;
     *out_added = size() - before;
     *out_rows = size();
     return kMapOk;

@@ -522,6 +522,90 @@ PYBIND11_MODULE(pypeline, m) {
          py::arg("cloud"), py::arg("poses"), py::arg("refine") = 4, py::arg("iterations") = 10, py::arg("stride") = 8, py::arg("reach") = 1,
          py::arg("max_dist") = madicp_host::kQueryNoDistance, py::arg("rho") = madicp_host::kQueryNoDistance, py::arg("min_count") = 3,
          py::arg("flat") = 1.0)
+    // additive: saved rows back in (Pipeline::mapMergeRows).  mapState() returns a dict: what the map was made from — voxel,
+    // with_attribute, evidence ((hit, miss, cap) or None), moments (max_count or None) — and its columns through the window downloads:
+    // keys (M,) uint64, rows (M, 3) float32, attribute (M,) uint32 or None, evidence_words (M,) uint32 or None, moment_words (M, 10)
+    // uint64 or None.  mapMergeRows(keys, rows, attribute=None, evidence=None, moments=None) merges such columns into this pipeline's
+    // map as ONE fold — before the first frame too: the map is then made — and returns (added, size); a column is given exactly
+    // where the map has it.  Attribute words travel as uint32: an array of another 4-byte dtype is taken by its bits, never
+    // converted.  mad_icp_amd.map_io has save_map / load_map over the two.  ValueError for what madicp_map_merge_rows refuses as
+    // invalid and for columns of unequal length; RuntimeError for a capacity refusal and while accumulation is off.
+    .def("mapState",
+         [](Pipeline& self) {
+           if (self.mapVoxelSize() == 0.0) throw std::logic_error("Pipeline::mapState: setMapAccumulation(voxel_size > 0) first");
+           const size_t m = self.mapSize();
+           const py::ssize_t rows = static_cast<py::ssize_t>(m);
+           py::dict out;
+           out["voxel"] = self.mapVoxelSize();
+           out["with_attribute"] = self.mapWithAttribute();
+           const uint32_t* e = self.mapEvidenceParams();
+           out["evidence"] = self.mapWithEvidence() ? py::object(py::make_tuple(e[0], e[1], e[2])) : py::object(py::none());
+           out["moments"] = self.mapWithMoments() ? py::object(py::int_(self.mapMomentsMaxCount())) : py::object(py::none());
+           auto took = [&](size_t got) {
+             if (got != m) throw std::runtime_error("Pipeline::mapState: the map changed during the call");
+           };
+           py::array_t<uint64_t> keys(rows);
+           py::array_t<float> xyz({rows, static_cast<py::ssize_t>(3)});
+           uint64_t no_key[10];
+           float none[3];
+           uint32_t no_word[1];
+           took(self.mapKeys(m ? keys.mutable_data() : no_key, m, 0));
+           took(self.mapCloud(m ? xyz.mutable_data() : none, m, 0));
+           out["keys"] = keys;
+           out["rows"] = xyz;
+           out["attribute"] = py::none();
+           out["evidence_words"] = py::none();
+           out["moment_words"] = py::none();
+           if (self.mapWithAttribute()) {
+             py::array_t<uint32_t> w(rows);
+             took(self.mapAttribute(m ? w.mutable_data() : no_word, m, 0));
+             out["attribute"] = w;
+           }
+           if (self.mapWithEvidence()) {
+             py::array_t<uint32_t> w(rows);
+             took(self.mapEvidence(m ? w.mutable_data() : no_word, m, 0));
+             out["evidence_words"] = w;
+           }
+           if (self.mapWithMoments()) {
+             py::array_t<uint64_t> w({rows, static_cast<py::ssize_t>(10)});
+             took(self.mapMoments(m ? w.mutable_data() : no_key, m, 0));
+             out["moment_words"] = w;
+           }
+           return out;
+         })
+    .def("mapMergeRows",
+         [](Pipeline& self, py::array_t<uint64_t, py::array::c_style> keys, py::array_t<float, py::array::c_style> rows, py::object attribute,
+            py::object evidence_words, py::object moment_words) {
+           if (keys.ndim() != 1) throw py::value_error("keys must be (n,) uint64");
+           const py::ssize_t n = keys.shape(0);
+           if (rows.ndim() != 2 || rows.shape(0) != n || rows.shape(1) != 3) throw py::value_error("rows must be (n, 3) float32");
+           py::array_t<uint32_t, py::array::c_style> words;
+           const bool with_attr = !attribute.is_none(), with_ev = !evidence_words.is_none(), with_mom = !moment_words.is_none();
+           py::array_t<uint32_t, py::array::c_style> evidence;
+           py::array_t<uint64_t, py::array::c_style> moments;
+           if (with_ev) evidence = evidence_words.cast<py::array_t<uint32_t, py::array::c_style>>();
+           if (with_mom) moments = moment_words.cast<py::array_t<uint64_t, py::array::c_style>>();
+           if (with_attr) {  // (the bits of a 4-byte dtype, whatever it is: a float32 attribute is not converted to integers)
+             py::array a = py::module_::import("numpy").attr("ascontiguousarray")(attribute);
+             if (a.itemsize() != 4) throw py::value_error("attribute must have a 4-byte dtype (its words travel as uint32)");
+             words = a.attr("view")("uint32");
+             if (words.ndim() != 1 || words.shape(0) != n) throw py::value_error("attribute must be (n,)");
+           }
+           if (with_ev && (evidence.ndim() != 1 || evidence.shape(0) != n)) throw py::value_error("evidence must be (n,) uint32");
+           if (with_mom && (moments.ndim() != 2 || moments.shape(0) != n || moments.shape(1) != 10))
+             throw py::value_error("moments must be (n, 10) uint64");
+           size_t added = 0;
+           try {
+             const size_t size = self.mapMergeRows(keys.data(), rows.data(), with_attr ? words.data() : nullptr,
+                                                   with_ev ? evidence.data() : nullptr, with_mom ? moments.data() : nullptr,
+                                                   static_cast<size_t>(n), &added);
+             return py::make_tuple(added, size);
+           } catch (const std::invalid_argument& e) {
+             throw py::value_error(e.what());
+           }
+         },
+         py::arg("keys"), py::arg("rows"), py::arg("attribute") = py::none(), py::arg("evidence") = py::none(),
+         py::arg("moments") = py::none())
     // setMapAlignment(on, iterations=5, reach=1, max_dist=inf, rho=inf, min_count=3, flat=1.0) makes every fold register the frame
     // against the map first and only REPORT it; mapFrameAlignment() returns None for a frame without one, else (pose (4, 4), info) with
     // H, b, chi2, counts at that pose and chi2_start, counts_start at the frame's own.
